@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- decoded cimbar frames/s (1024x1024 mode B) on N MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--config 2|4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--config 2|4] [--dump-outputs DIR]
 
 One "step" = one pass of the whole decode path (threshold -> symbols -> RS -> CCM -> colours -> RS -> chunks) over one
 device-resident batch of F synthetic clean mode-B frames (BASELINE.json configs[1]: F = 1024). Consecutive steps decode
@@ -717,6 +717,26 @@ def launch_check(rank, local_rank, world):
     return 0 if ok else 4
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6 - 4096          # 64 MB, less room for the .npy headers
+
+
+def dump_outputs(out_dir, **arrays):
+    """--dump-outputs: each (frames, ...) device tensor -> out_dir/<name>.npy in float32 (exact for u8 chunks and 12-bit masks). Beyond
+    DUMP_LIMIT_BYTES in all, the same fixed, seeded sample of frames is taken from every array and its frame indices are written as
+    sampled_frames.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    frames = next(iter(arrays.values())).shape[0]
+    per_frame = sum(4 * (a.numel() // frames) for a in arrays.values())
+    rows = None
+    if per_frame * frames > DUMP_LIMIT_BYTES:
+        keep = DUMP_LIMIT_BYTES // (per_frame + 8)
+        rows = np.sort(np.random.default_rng(0).choice(frames, keep, replace=False))
+        np.save(os.path.join(out_dir, "sampled_frames.npy"), rows.astype(np.float64))
+    for name, a in arrays.items():
+        host = a.cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), (host if rows is None else host[rows]).astype(np.float32))
+
+
 def claim_stdout():
     """The JSON line must be the only thing on stdout: libraries print there too (RCCL's version banner lands in the C runtime's buffer and is flushed
     at exit, BEHIND the line). File descriptor 1 is pointed at stderr for everything else; Python's sys.stdout keeps the real one."""
@@ -739,7 +759,11 @@ def main():
     ap.add_argument("--allow-fallback", action="store_true",
                     help="N > 1: if the library's own exchange (cimbar_hip_gather_chunks) cannot be set up, fall back to torch.distributed.gather "
                          "instead of failing -- the line then says so in config.exchange, and is NOT a measurement of this library's exchange")
-    ap.add_argument("--reps", type=int, default=0, help="repeat the timed region this many times and report the median (0: 5 when --steps < 100, else 1)")
+    ap.add_argument("--reps", type=int, default=1,
+                    help="repeat the timed region this many times and report the median (default 1: exactly --steps timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (chunks, masks) as DIR/<name>.npy in float32, at most "
+                         "64 MB in all (a fixed, seeded sample of frames beyond that): two builds run with the same arguments compare output for output")
     ap.add_argument("--no-pipeline", action="store_true",
                     help="one ordinary call per step instead of the pipelined entry point (kernels of different steps never overlap: "
                          "what tools/gpu_profile.sh uses so that every traced dispatch is one kernel running alone)")
@@ -759,6 +783,10 @@ def main():
                     help="launcher self-test, touches no GPU: start the --gpus ranks exactly as a measurement would, rendezvous them over gloo on "
                          "127.0.0.1, and print one JSON line with every rank's RANK / LOCAL_RANK / WORLD_SIZE")
     args = ap.parse_args()
+    if args.steps < 1 or args.reps < 1 or args.warmup < 0:
+        ap.error("--steps and --reps must be at least 1, --warmup at least 0")
+    if args.dump_outputs is not None and args.config != 2:
+        ap.error("--dump-outputs: only the default workload (--config 2) writes its outputs")
     if os.environ.get("CIMBAR_HIP_DEBUG_SKIP", "0") not in ("", "0") and not args.probe_run:
         # (the product library ignores the variable -- the switch only exists in a -DCIMBAR_PROBES build -- but a line printed while it is set would
         # invite exactly the doubt it is easiest to avoid)
@@ -908,8 +936,8 @@ def main():
     drain()
     barrier()
     # The timed region: EXACTLY --steps steps between two barriers (max over ranks). With few steps it lasts a few milliseconds, and boxes /
-    # clocks wander by 5-10 % over such a span: the region is then repeated and the MEDIAN repetition is the one reported (all of them listed).
-    nreps = args.reps if args.reps > 0 else (5 if args.steps < 100 else 1)
+    # clocks wander by 5-10 % over such a span: --reps R repeats the region and reports the MEDIAN repetition (all of them listed).
+    nreps = args.reps
     rep_s = []
     for _ in range(nreps):
         t0 = time.perf_counter()
@@ -925,6 +953,9 @@ def main():
         rep_s.append(e)
     elapsed = sorted(rep_s)[len(rep_s) // 2]
     all_chunks, all_masks = pipe.last if pipe.last is not None else outs[(pipe.steps - 1) % NB]
+    if args.dump_outputs is not None and rank == 0:
+        # before the correctness check, so that a build that decodes wrongly still leaves its outputs to compare
+        dump_outputs(args.dump_outputs, chunks=all_chunks, masks=all_masks)
 
     # correctness of what was just timed (outside the timed region): bit-exact payload, every chunk delivered, every buffer set
     ok = True

@@ -67,3 +67,28 @@ def test_summary_is_the_last_key_and_names_every_secondary_row():
     assert s["configs2_ms_per_step"] == 0.85 and s["configs3_n1_without_solve"] == 6e5 and s["configs4_captures_per_s"]["4096"] == 45000.0
     assert s["single_frame_ms"] == 0.19 and s["mode_k1_frac"]["66"] == 0.52 and s["mode_k1_frac"]["67"] is None
     assert len(json.dumps(s)) < 1500, "must fit the tail of the line the driver records"
+
+
+def test_bad_step_counts_and_dump_outside_the_default_workload_are_refused():
+    for args in (["--steps", "0"], ["--reps", "0"], ["--warmup", "-1"], ["--config", "4", "--dump-outputs", "out"]):
+        r = run(args)
+        assert r.returncode != 0 and "error:" in r.stderr and '"n_gpus"' not in r.stdout, args
+
+
+@pytest.mark.gpu
+def test_steps_is_the_timed_region_and_the_dump_holds_the_last_step(tmp_path):
+    import numpy as np
+    from libcimbar_amd import framegen, modeb
+    if gpu_count() == 0:
+        pytest.skip("no GPU")
+    n = 64
+    r = run(["--steps", "3", "--warmup", "1", "--frames", str(n), "--no-cpu-baseline", "--no-extras", "--dump-outputs", str(tmp_path)], timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 3 and line["timed_region"]["repetitions"] == 1 and line["ms_per_step"] > 0
+    assert sorted(os.listdir(tmp_path)) == ["chunks.npy", "masks.npy"]
+    chunks, masks = np.load(tmp_path / "chunks.npy"), np.load(tmp_path / "masks.npy")
+    assert chunks.dtype == masks.dtype == np.float32 and chunks.shape == (n, modeb.FRAME_BYTES) and masks.shape == (n,)
+    assert (masks == 0xFFF).all()
+    # the last timed step decoded one of the rotated input batches (rank 0: seed 1234 + 7919 b), bit for bit
+    assert any((chunks == framegen.synth_payload(n, seed=1234 + 7919 * b).numpy()).all() for b in range(16))

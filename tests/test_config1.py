@@ -40,11 +40,12 @@ def test_fixture_frame_is_the_reference_encoders_frame(ref, synth):
     """pins the fixture: the frame rendered from its payload is byte for byte what Encoder::encode_next made of LICENSE"""
     frame = synth.frames_from_payload(torch.from_numpy(PAYLOAD.reshape(1, 7500).copy())).numpy()[0]
     assert hashlib.sha256(frame.tobytes()).hexdigest() == FIX["frame_sha256"]
-    if os.path.exists("/root/reference/LICENSE"):
-        data = np.frombuffer(open("/root/reference/LICENSE", "rb").read(), np.uint8)
-        rgb = np.zeros((1024, 1024, 3), np.uint8)
-        assert ref.ref_encode_fountain_z(P(data), len(data), 109, 16, b"LICENSE", 0, 1, P(rgb)) == 1
-        assert (rgb == frame).all()
+    # LICENSE itself, recovered from the fixture's chunks by the reference's sink + zstd and pinned by its SHA-256, encoded once more
+    data = sink_to_file(ref, PAYLOAD, 0xFFF)
+    assert data.size == FIX["file_size"] and hashlib.sha256(data.tobytes()).hexdigest() == FIX["file_sha256"]
+    rgb = np.zeros((1024, 1024, 3), np.uint8)
+    assert ref.ref_encode_fountain_z(P(data), len(data), 109, 16, b"LICENSE", 0, 1, P(rgb)) == 1
+    assert (rgb == frame).all()
 
 
 def test_oracle_decodes_config1_to_the_file(ref, synth):
