@@ -254,6 +254,42 @@ int64_t cimbar_hip_scan_extract_decode_batch_fmt(cimbar_hip_ctx* ctx, const uint
                                                  int img_mem, int preprocess, int color_correction, uint8_t* chunks, uint32_t* masks, int* status,
                                                  int out_mem, void* hip_stream);
 
+/* ---- lens undistortion: `cimbar --undistort` (src/exe/cimbar/cimbar.cpp:135-145) -----------------------------------------------------------
+ * Undistort<SimpleCameraCalibration> (src/lib/extractor/Undistort.h:11-62) in front of Extractor::extract, on the device. Captures as for the _fmt
+ * entry points above (`format`, img_mem, out_mem, hip_stream, ctx->err via cimbar_hip_last_error on failure).
+ *
+ * cimbar_hip_undistort_calibrate_fmt: SimpleCameraCalibration::scan (SimpleCameraCalibration.h:30-58, .cpp:1-75) per capture -- Scanner's anchor
+ *   search, Scanner::scan_edges (Scanner.cpp:204-276) and calculate_distortion_factor. ok[f] = 1 with k1[f] = the distortion factor where the
+ *   reference returns parameters (no edge found at all still counts: k1 = 0), ok[f] = 0 and k1[f] = 0 where it returns {} (fewer than 4 anchors;
+ *   opposite sides parallel, which an axis-aligned capture without perspective has). The camera is naive_radial_undistort's
+ *   [w/4, 0, w/2; 0, h/4, h/2; 0, 0, 1] (integer division), the distortion (k1, 0, 0, 0). ok and k1 are host arrays of n; complete on return.
+ *   Where Scanner::chase_edge would read outside the image (undefined behaviour upstream), the pixel counts as inactive.
+ *
+ * cimbar_hip_undistort_batch_fmt: Undistort::undistort(img, out) with a fresh object per capture (what cimbar.cpp:139 does), i.e.
+ *   cv::initUndistortRectifyMap(camera, dist, Mat(), camera, size, CV_32FC1) + cv::remap(INTER_LINEAR, BORDER_CONSTANT 0):
+ *   out_rgb = n undistorted RGB8 captures of width x height (any width), whatever the input format.
+ *   params == NULL: calibrate each capture as above; a capture whose calibration fails gets ok = 0 and its plain RGB conversion (the CLI's img
+ *                   stays as it was).
+ *   params != NULL: 14 doubles, camera[9] (row-major) + distortion[5] (k1 k2 p1 p2 k3), applied to all n captures (set_distortion_params): ok = 1,
+ *                   k1_out = params[9]. Only zero-skew cameras [fx, 0, cx; 0, fy, cy; 0, 0, 1] (finite, non-singular): anything else is
+ *                   CIMBAR_HIP_EINVAL.
+ *   ok / k1_out (n each, may be NULL) follow out_mem. Host outputs: complete on return; device outputs: enqueued.
+ *
+ * cimbar_hip_scan_undistort_extract_decode_batch_fmt: cimbar_hip_scan_extract_decode_batch_fmt with `--undistort` -- the body of cimbar.cpp:124-162:
+ *   calibrate, remap, extract, decode, nothing crossing PCIe in between. undistort_ok (n, may be NULL; follows out_mem) = the calibration's ok.
+ *   Everything else as for cimbar_hip_scan_extract_decode_batch_fmt.
+ *
+ * Bounds: the undistorted captures live in a context-owned scratch allocated on the first call of these entry points (none of the others touch
+ * it) and holding at most 256 MiB (CIMBAR_HIP_UNDISTORT_SCRATCH_MB): a batch goes through in groups of that many captures (43 at 1920x1080), at least
+ * one. Staged host input, the scan state and the deskewed frames of the composite are as large as for the entry points above. */
+int cimbar_hip_undistort_calibrate_fmt(cimbar_hip_ctx* ctx, const uint8_t* img, unsigned width, unsigned height, int format, int n, int img_mem,
+                                       int* ok, double* k1, void* hip_stream);
+int cimbar_hip_undistort_batch_fmt(cimbar_hip_ctx* ctx, const uint8_t* img, unsigned width, unsigned height, int format, int n, int img_mem,
+                                   const double* params, uint8_t* out_rgb, int out_mem, int* ok, double* k1_out, void* hip_stream);
+int64_t cimbar_hip_scan_undistort_extract_decode_batch_fmt(cimbar_hip_ctx* ctx, const uint8_t* img, unsigned width, unsigned height, int format, int n,
+                                                           int img_mem, int preprocess, int color_correction, uint8_t* chunks, uint32_t* masks,
+                                                           int* status, int* undistort_ok, int out_mem, void* hip_stream);
+
 /* ---- multi-GPU: the one exchange step ------------------------------------------------------------------------------------
  * Frames are independent, so each GPU decodes its own slab with its own context; afterwards every rank's n x (7500 chunk bytes + 1 mask
  * word) are gathered on `root` in rank order (== frame order for contiguous slabs), where the host feeds the single fountain_decoder_sink

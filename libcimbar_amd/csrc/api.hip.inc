@@ -221,6 +221,24 @@ int64_t cimbar_hip_scan_extract_decode_batch_fmt(cimbar_hip_ctx* ctx, const uint
 	return CIMBAR_FWD(cimbar_hip_scan_extract_decode_batch_fmt, img, width, height, format, n, img_mem, preprocess, color_correction, chunks, masks, status, out_mem, hip_stream);
 }
 
+int cimbar_hip_undistort_calibrate_fmt(cimbar_hip_ctx* ctx, const uint8_t* img, unsigned width, unsigned height, int format, int n, int img_mem, int* ok, double* k1, void* hip_stream)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return CIMBAR_FWD(cimbar_hip_undistort_calibrate_fmt, img, width, height, format, n, img_mem, ok, k1, hip_stream);
+}
+
+int cimbar_hip_undistort_batch_fmt(cimbar_hip_ctx* ctx, const uint8_t* img, unsigned width, unsigned height, int format, int n, int img_mem, const double* params, uint8_t* out_rgb, int out_mem, int* ok, double* k1_out, void* hip_stream)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return CIMBAR_FWD(cimbar_hip_undistort_batch_fmt, img, width, height, format, n, img_mem, params, out_rgb, out_mem, ok, k1_out, hip_stream);
+}
+
+int64_t cimbar_hip_scan_undistort_extract_decode_batch_fmt(cimbar_hip_ctx* ctx, const uint8_t* img, unsigned width, unsigned height, int format, int n, int img_mem, int preprocess, int color_correction, uint8_t* chunks, uint32_t* masks, int* status, int* undistort_ok, int out_mem, void* hip_stream)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return CIMBAR_FWD(cimbar_hip_scan_undistort_extract_decode_batch_fmt, img, width, height, format, n, img_mem, preprocess, color_correction, chunks, masks, status, undistort_ok, out_mem, hip_stream);
+}
+
 int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_bytes)
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;

@@ -431,22 +431,72 @@ __device__ __forceinline__ void capture_pair(const uint8_t* __restrict__ src, in
 	}
 }
 constexpr int WARP_ROWS = 4;
+// Which tile of its frame a workgroup takes (round 6). The hardware deals consecutive workgroups round-robin to the eight XCDs, each with an L2 of its
+// own, and a tile's 64 destination columns read ~183 source bytes per row -- 2.4 cache lines of 128 bytes for 1.4 lines' worth of pixels, the rest
+// shared with the tiles to its left and right. In launch order (x fastest) those neighbours sit on OTHER XCDs and every shared line is fetched from
+// HBM twice (profiles/r04zb: 10.7 GB fetched for 6.1 GB of source pixels, 77 % L2 misses). So the frame's tiles are dealt in eight contiguous runs:
+// workgroup b of the frame (b = x + gridDim.x * y; its XCD is b % 8 when the tiles per frame are a multiple of eight) takes tile
+// (b % 8) * (tiles / 8) + b / 8 -- one XCD walks a band of the frame left to right, row of tiles after row of tiles, and finds its neighbours' lines
+// in its own L2. Shared by k_warp and k_undistort (undistort.hip.inc), whose gathers are near-identity as well.
+__device__ __forceinline__ void xcd_tile(int xcd_order, int& bx, int& by)
+{
+	const unsigned tiles = gridDim.x * gridDim.y, b = blockIdx.x + gridDim.x * blockIdx.y;
+	const unsigned t = (xcd_order && tiles % 8u == 0u) ? (b % 8u) * (tiles / 8u) + b / 8u : b;      // (xcd_order 0: launch order, CIMBAR_HIP_WARP_ORDER=0 -- for A/B runs)
+	bx = (int)(t % gridDim.x); by = (int)(t / gridDim.x);
+}
+// remap's fixed-point INTER_LINEAR / BORDER_CONSTANT 0 tap (imgwarp.cpp remapBilinear) at the source position (X, Y) in 1/32 pixel, X = cvRound(32 x):
+// one output pixel as R | G << 8 | B << 16, the source in capture format FMT converted as it is loaded. Shared by k_warp and k_undistort.
+template <int FMT>
+__device__ __forceinline__ uint32_t remap_bilinear(const uint8_t* __restrict__ src, int sw, int sh, int X, int Y)
+{
+	int sx = X >> 5, sy = Y >> 5;
+	sx = sx < -32768 ? -32768 : (sx > 32767 ? 32767 : sx);
+	sy = sy < -32768 ? -32768 : (sy > 32767 ? 32767 : sy);
+	const int fx = X & 31, fy = Y & 31;
+	uint32_t v = 0;
+	if ((unsigned)sx < (unsigned)(sw - 2) && (unsigned)sy < (unsigned)(sh - 1)) {
+		// all four taps inside the capture (every pixel but those on its border; column sw-2 goes the other way so that the wide loads of
+		// capture_pair never leave the frame). The weights (32-fx)(32-fy)*32 ... factor,
+		// sum = 32 * ((32-fy) * ((32-fx)*a0 + fx*a1) + fy * ((32-fx)*b0 + fx*b1)) exactly, so the reference's (sum + 2^14) >> 15 is (S + 512) >> 10.
+		uint32_t a0p, a1p, b0p, b1p;
+		capture_pair<FMT>(src, sw, sh, sx, sy, a0p, a1p);
+		capture_pair<FMT>(src, sw, sh, sx, sy + 1, b0p, b1p);
+		// per channel: the two taps of a row as bytes 0 / 1 of a dword (one v_perm_b32), times (32-fx, fx) with one v_dot4_u32_u8; the two row
+		// sums (<= 8160) as the halves of a dword, times (32-fy, fy) with one v_dot2_u32_u16 that also adds the rounding term
+		typedef unsigned short us2w __attribute__((ext_vector_type(2)));
+		const uint32_t wx = (32u - (uint32_t)fx) | ((uint32_t)fx << 8);
+		const us2w wy = us2w{(unsigned short)(32 - fy), (unsigned short)fy};
+#pragma unroll
+		for (int c = 0; c < 3; ++c) {
+			const uint32_t sel = 0x0C0C0400u + (uint32_t)c * 0x0101u;       // byte 0 <- a0p[c], byte 1 <- a1p[c], bytes 2 / 3 <- 0
+			const uint32_t ra = __builtin_amdgcn_udot4(__builtin_amdgcn_perm(a1p, a0p, sel), wx, 0u, false);
+			const uint32_t rb = __builtin_amdgcn_udot4(__builtin_amdgcn_perm(b1p, b0p, sel), wx, 0u, false);
+			const uint32_t S = __builtin_amdgcn_udot2(us2w{(unsigned short)ra, (unsigned short)rb}, wy, 512u, false);
+			v |= (S >> 10) << (8 * c);
+		}
+	} else if (sx >= -1 && sx < sw && sy >= -1 && sy < sh) {   // border: taps outside read as 0 (BORDER_CONSTANT)
+		const int w00 = (32 - fx) * (32 - fy) * 32, w01 = fx * (32 - fy) * 32, w10 = (32 - fx) * fy * 32, w11 = fx * fy * 32;
+		const bool in_x0 = sx >= 0, in_x1 = sx + 1 < sw, in_y0 = sy >= 0, in_y1 = sy + 1 < sh;
+		const uint32_t p00 = capture_px(src, sw, sh, FMT, in_x0 ? sx : 0, in_y0 ? sy : 0), p01 = capture_px(src, sw, sh, FMT, in_x1 ? sx + 1 : 0, in_y0 ? sy : 0);
+		const uint32_t p10 = capture_px(src, sw, sh, FMT, in_x0 ? sx : 0, in_y1 ? sy + 1 : 0), p11 = capture_px(src, sw, sh, FMT, in_x1 ? sx + 1 : 0, in_y1 ? sy + 1 : 0);
+		const int m00 = (in_y0 && in_x0) ? w00 : 0, m01 = (in_y0 && in_x1) ? w01 : 0, m10 = (in_y1 && in_x0) ? w10 : 0, m11 = (in_y1 && in_x1) ? w11 : 0;
+#pragma unroll
+		for (int c = 0; c < 3; ++c) {
+			const int s00 = (int)((p00 >> (8 * c)) & 0xFFu), s01 = (int)((p01 >> (8 * c)) & 0xFFu), s10 = (int)((p10 >> (8 * c)) & 0xFFu), s11 = (int)((p11 >> (8 * c)) & 0xFFu);
+			v |= (uint32_t)(((s00 * m00 + s01 * m01 + s10 * m10 + s11 * m11) + (1 << 14)) >> 15) << (8 * c);
+		}
+	}
+	return v;
+}
 template <int FMT>
 __global__ __launch_bounds__(256) void k_warp(const uint8_t* __restrict__ rgb, int sw, int sh, const double* __restrict__ minv,
                                               uint8_t* __restrict__ out, int width, int height, int xcd_order)
 {
 	// A workgroup covers 64 columns x (16 x WARP_ROWS) rows, sixteen rows at a time: with one row group per workgroup the two million
 	// short-lived workgroups of a 2 048-capture batch spent their time starting up (kernel arguments, the matrix, one dependent gather, done).
-	// Which tile of its frame a workgroup takes (round 6). The hardware deals consecutive workgroups round-robin to the eight XCDs, each with an L2 of its
-	// own, and a tile's 64 destination columns read ~183 source bytes per row -- 2.4 cache lines of 128 bytes for 1.4 lines' worth of pixels, the rest
-	// shared with the tiles to its left and right. In launch order (x fastest) those neighbours sit on OTHER XCDs and every shared line is fetched from
-	// HBM twice (profiles/r04zb: 10.7 GB fetched for 6.1 GB of source pixels, 77 % L2 misses). So the frame's tiles are dealt in eight contiguous runs:
-	// workgroup b of the frame (b = x + gridDim.x * y; its XCD is b % 8 when the tiles per frame are a multiple of eight) takes tile
-	// (b % 8) * (tiles / 8) + b / 8 -- one XCD walks a band of the frame left to right, row of tiles after row of tiles, and finds its neighbours' lines
-	// in its own L2.
-	const unsigned tiles = gridDim.x * gridDim.y, b = blockIdx.x + gridDim.x * blockIdx.y;
-	const unsigned t = (xcd_order && tiles % 8u == 0u) ? (b % 8u) * (tiles / 8u) + b / 8u : b;      // (xcd_order 0: launch order, CIMBAR_HIP_WARP_ORDER=0 -- for A/B runs)
-	const int bx = (int)(t % gridDim.x), by = (int)(t / gridDim.x);
+	// The tile order: xcd_tile above.
+	int bx, by;
+	xcd_tile(xcd_order, bx, by);
 	const int f = blockIdx.z, xb = bx * 64, xq = (threadIdx.x & 15) * 4;
 	if (xb + xq >= width) return;   // (width is a multiple of 4)
 	const double* Mg = minv + (size_t)f * 9;
@@ -469,44 +519,7 @@ __global__ __launch_bounds__(256) void k_warp(const uint8_t* __restrict__ rgb, i
 		fX = fX < (double)INT_MAX ? fX : (double)INT_MAX; fX = fX > (double)INT_MIN ? fX : (double)INT_MIN;
 		fY = fY < (double)INT_MAX ? fY : (double)INT_MAX; fY = fY > (double)INT_MIN ? fY : (double)INT_MIN;
 		const int X = (int)rint(fX), Y = (int)rint(fY);          // cvRound: round half to even
-		int sx = X >> 5, sy = Y >> 5;
-		sx = sx < -32768 ? -32768 : (sx > 32767 ? 32767 : sx);
-		sy = sy < -32768 ? -32768 : (sy > 32767 ? 32767 : sy);
-		const int fx = X & 31, fy = Y & 31;
-		uint32_t v = 0;
-		if ((unsigned)sx < (unsigned)(sw - 2) && (unsigned)sy < (unsigned)(sh - 1)) {
-			// all four taps inside the capture (every pixel but those on its border; column sw-2 goes the other way so that the wide loads of
-			// capture_pair never leave the frame). The weights (32-fx)(32-fy)*32 ... factor,
-			// sum = 32 * ((32-fy) * ((32-fx)*a0 + fx*a1) + fy * ((32-fx)*b0 + fx*b1)) exactly, so the reference's (sum + 2^14) >> 15 is (S + 512) >> 10.
-			uint32_t a0p, a1p, b0p, b1p;
-			capture_pair<FMT>(src, sw, sh, sx, sy, a0p, a1p);
-			capture_pair<FMT>(src, sw, sh, sx, sy + 1, b0p, b1p);
-			// per channel: the two taps of a row as bytes 0 / 1 of a dword (one v_perm_b32), times (32-fx, fx) with one v_dot4_u32_u8; the two row
-			// sums (<= 8160) as the halves of a dword, times (32-fy, fy) with one v_dot2_u32_u16 that also adds the rounding term
-			typedef unsigned short us2w __attribute__((ext_vector_type(2)));
-			const uint32_t wx = (32u - (uint32_t)fx) | ((uint32_t)fx << 8);
-			const us2w wy = us2w{(unsigned short)(32 - fy), (unsigned short)fy};
-#pragma unroll
-			for (int c = 0; c < 3; ++c) {
-				const uint32_t sel = 0x0C0C0400u + (uint32_t)c * 0x0101u;       // byte 0 <- a0p[c], byte 1 <- a1p[c], bytes 2 / 3 <- 0
-				const uint32_t ra = __builtin_amdgcn_udot4(__builtin_amdgcn_perm(a1p, a0p, sel), wx, 0u, false);
-				const uint32_t rb = __builtin_amdgcn_udot4(__builtin_amdgcn_perm(b1p, b0p, sel), wx, 0u, false);
-				const uint32_t S = __builtin_amdgcn_udot2(us2w{(unsigned short)ra, (unsigned short)rb}, wy, 512u, false);
-				v |= (S >> 10) << (8 * c);
-			}
-		} else if (sx >= -1 && sx < sw && sy >= -1 && sy < sh) {   // border: taps outside read as 0 (BORDER_CONSTANT)
-			const int w00 = (32 - fx) * (32 - fy) * 32, w01 = fx * (32 - fy) * 32, w10 = (32 - fx) * fy * 32, w11 = fx * fy * 32;
-			const bool in_x0 = sx >= 0, in_x1 = sx + 1 < sw, in_y0 = sy >= 0, in_y1 = sy + 1 < sh;
-			const uint32_t p00 = capture_px(src, sw, sh, FMT, in_x0 ? sx : 0, in_y0 ? sy : 0), p01 = capture_px(src, sw, sh, FMT, in_x1 ? sx + 1 : 0, in_y0 ? sy : 0);
-			const uint32_t p10 = capture_px(src, sw, sh, FMT, in_x0 ? sx : 0, in_y1 ? sy + 1 : 0), p11 = capture_px(src, sw, sh, FMT, in_x1 ? sx + 1 : 0, in_y1 ? sy + 1 : 0);
-			const int m00 = (in_y0 && in_x0) ? w00 : 0, m01 = (in_y0 && in_x1) ? w01 : 0, m10 = (in_y1 && in_x0) ? w10 : 0, m11 = (in_y1 && in_x1) ? w11 : 0;
-#pragma unroll
-			for (int c = 0; c < 3; ++c) {
-				const int s00 = (int)((p00 >> (8 * c)) & 0xFFu), s01 = (int)((p01 >> (8 * c)) & 0xFFu), s10 = (int)((p10 >> (8 * c)) & 0xFFu), s11 = (int)((p11 >> (8 * c)) & 0xFFu);
-				v |= (uint32_t)(((s00 * m00 + s01 * m01 + s10 * m10 + s11 * m11) + (1 << 14)) >> 15) << (8 * c);
-			}
-		}
-		px[k] = v;                                               // R | G << 8 | B << 16
+		px[k] = remap_bilinear<FMT>(src, sw, sh, X, Y);            // R | G << 8 | B << 16
 	}
 	uint32_t* o = reinterpret_cast<uint32_t*>(out + ((size_t)f * width * height + (size_t)y * width + xb + xq) * 3);
 	o[0] = px[0] | (px[1] << 24);

@@ -100,6 +100,12 @@ struct cimbar_hip_ctx {
 	int* d_scan_offs = nullptr; int* d_scan_ovf = nullptr; ScanConf* d_scan_conf = nullptr; ScanStage* d_scan_stage = nullptr;   // stage[0..n) primary, [n..2n) bottom-right
 	double* h_ex_minv = nullptr;      // pinned staging for the warp matrices (an async copy must not read a pageable temporary)
 	hipEvent_t ev_ex_minv = nullptr;  // the last copy out of h_ex_minv
+	// lens undistortion (cimbar_hip_undistort_* / cimbar_hip_scan_undistort_extract_decode_batch_fmt): nothing of it exists until one of those is called
+	uint8_t* d_ud_img = nullptr; size_t d_ud_img_cap = 0;    // the undistorted RGB8 captures of one group (at most ud_scratch bytes, see undistort_group)
+	int* d_ud_ok = nullptr; double* d_ud_k1 = nullptr; int* d_ud_status = nullptr; int d_ud_n = 0;   // per capture of a call
+	double* d_ud_xt = nullptr; double* h_ud_xt = nullptr; int ud_xt_cap = 0;   // the column table of U2 (device + pinned staging)
+	hipEvent_t ev_ud_xt = nullptr;    // the last copy out of h_ud_xt
+	size_t ud_scratch = (size_t)256 << 20;   // CIMBAR_HIP_UNDISTORT_SCRATCH_MB
 	FloodScratch flood{};
 	int flood_cap = 0;                // spill areas allocated in flood.heap (grown to what the launches use: one frame -> 0.6 MB, a full batch -> 610 MB)
 	uint32_t* d_fw_queue = nullptr;   // k_flood_wave: one work queue of NCELLS entries per resident workgroup
@@ -393,6 +399,9 @@ void destroy_ctx(cimbar_hip_ctx* ctx)
 	fr(ctx->d_masks); fr(ctx->flood.heap); fr(ctx->flood.prio); fr(ctx->flood.next); fr(ctx->d_fw_queue); fr(ctx->d_vsym); fr(ctx->d_vdrift); fr(ctx->d_vflag); fr(ctx->d_vtotals);
 	fr(ctx->d_ex_rgb); fr(ctx->d_ex_box); fr(ctx->d_ex_in); fr(ctx->d_ex_out); fr(ctx->d_ex_hist); fr(ctx->d_ex_thr); fr(ctx->d_ex_minv);
 	fr(ctx->d_ex_gray); fr(ctx->d_ex_frames); fr(ctx->d_scan_hits); fr(ctx->d_scan_nhits); fr(ctx->d_scan_res); fr(ctx->d_scan_offs); fr(ctx->d_scan_ovf); fr(ctx->d_scan_serial); fr(ctx->d_scan_conf); fr(ctx->d_scan_stage);
+	fr(ctx->d_ud_img); fr(ctx->d_ud_ok); fr(ctx->d_ud_k1); fr(ctx->d_ud_status); fr(ctx->d_ud_xt);
+	if (ctx->h_ud_xt) (void)hipHostFree(ctx->h_ud_xt);
+	if (ctx->ev_ud_xt) (void)hipEventDestroy(ctx->ev_ud_xt);
 	if (ctx->h_ex_minv) (void)hipHostFree(ctx->h_ex_minv);
 	if (ctx->h_flagged) (void)hipHostFree(ctx->h_flagged);
 	if (ctx->ev_ex_minv) (void)hipEventDestroy(ctx->ev_ex_minv);
@@ -728,6 +737,7 @@ int cimbar_hip_create(int device, int mode_val, cimbar_hip_ctx** out)
 	if (const char* v = std::getenv("CIMBAR_HIP_FRAME_STAGE")) ctx->frame_stage = std::atoi(v);
 	if (const char* v = std::getenv("CIMBAR_HIP_WARP_TWOPASS")) ctx->warp_twopass = std::atoi(v);
 	if (const char* v = std::getenv("CIMBAR_HIP_WARP_SCRATCH_MB")) { long k = std::atol(v); if (k >= 1 && k <= (1 << 20)) ctx->warp_scratch = (size_t)k << 20; }
+	if (const char* v = std::getenv("CIMBAR_HIP_UNDISTORT_SCRATCH_MB")) { long k = std::atol(v); if (k >= 1 && k <= (1 << 20)) ctx->ud_scratch = (size_t)k << 20; }
 	if (const char* v = std::getenv("CIMBAR_HIP_K1_STRIPS")) ctx->k1_tall = !std::strcmp(v, "tall") ? 1 : (!std::strcmp(v, "short") ? 0 : -1);
 	if (const char* v = std::getenv("CIMBAR_HIP_K1_LDS_PAD")) { int k = std::atoi(v); if (k >= 0 && k <= 100000) ctx->k1_lds_pad = k; }
 	if (const char* v = std::getenv("CIMBAR_HIP_FRAME_ZEROCOPY")) ctx->frame_zerocopy = std::atoi(v);
@@ -1580,3 +1590,248 @@ int cimbar_hip_stage_times(cimbar_hip_ctx* ctx, const char** names, float* ms, i
 	return k;
 }
 
+
+// ---- lens undistortion (undistort.hip.inc) --------------------------------------------------------------------------------------------
+namespace {
+
+#pragma clang fp contract(off)
+// [assumed-OpenCV] The column table of U2: initUndistortRectifyMap (undistort.simd.hpp) walks each row with running sums, _x = i*ir[1] + ir[2]
+// then _x += ir[0] per column, and divides by _w = i*ir[7] + ir[8] (+= ir[6]). For a zero-skew camera ir[1] = ir[3] = ir[6] = ir[7] = 0, so
+// _x depends on the column alone and _w is ir[8] everywhere: x_j = _x_j * (1 / ir[8]), summed serially here, once per batch. This restates the
+// scalar loop; OpenCV's 64-bit SIMD body instead restarts the sum at every 2 * vlanes columns from lane offsets k * ir[0] -- where its
+// dispatch puts those restarts changes the last bit of some x_j, which the float cast of the map hides almost always. A pin against a real
+// OpenCV would change this function and nothing else.
+void undistort_column_table(const double ir[9], int w, double* xt)
+{
+	const double winv = 1. / ir[8];
+	double _x = 0 * ir[1] + ir[2];
+	for (int j = 0; j < w; ++j, _x += ir[0]) xt[j] = _x * winv;
+}
+
+// [assumed-OpenCV] lapack.cpp invert() for 3x3 CV_64F with DECOMP_LU: det3, d = 1 / det, cofactors * d -- what Mat::inv() gives
+// initUndistortRectifyMap for iR = (newCameraMatrix * R).inv(), R = identity. false: singular.
+bool undistort_invert3x3(const double* S, double* t)
+{
+	double d = S[0] * (S[4] * S[8] - S[5] * S[7]) - S[1] * (S[3] * S[8] - S[5] * S[6]) + S[2] * (S[3] * S[7] - S[4] * S[6]);
+	if (d == 0.) return false;
+	d = 1. / d;
+	t[0] = (S[4] * S[8] - S[5] * S[7]) * d; t[1] = (S[2] * S[7] - S[1] * S[8]) * d; t[2] = (S[1] * S[5] - S[2] * S[4]) * d;
+	t[3] = (S[5] * S[6] - S[3] * S[8]) * d; t[4] = (S[0] * S[8] - S[2] * S[6]) * d; t[5] = (S[2] * S[3] - S[0] * S[5]) * d;
+	t[6] = (S[3] * S[7] - S[4] * S[6]) * d; t[7] = (S[1] * S[6] - S[0] * S[7]) * d; t[8] = (S[0] * S[4] - S[1] * S[3]) * d;
+	return true;
+}
+
+// SimpleCameraCalibration's _targetRatio = edge_to_anchor_ratio(1024, 30, 3) (SimpleCameraCalibration.cpp:14-21,38-41): |(512,3)-(512,30)| / |(30,30)-(994,30)|
+double undistort_target_ratio() { return std::sqrt(729.0) / std::sqrt(929296.0); }
+#pragma clang fp contract(fast)
+
+// The camera of a call: `params` = camera[9] + distortion[5] (k1 k2 p1 p2 k3), or NULL = SimpleCameraCalibration::naive_radial_undistort
+// (SimpleCameraCalibration.h:50-58: [w/4, 0, w/2; 0, h/4, h/2; 0, 0, 1] in INTEGER division, distortion (k1, 0, 0, 0), k1 per capture).
+// Cameras with skew (camera[1] or camera[3] != 0, or a bottom row other than [0, 0, 1]) and singular ones: EINVAL.
+int undistort_setup(cimbar_hip_ctx* ctx, const char* who, const double* params, unsigned width, unsigned height, UndistortParams* P, double ir[9])
+{
+	double cam[9] = {(double)(int)(width / 4), 0, (double)(int)(width / 2), 0, (double)(int)(height / 4), (double)(int)(height / 2), 0, 0, 1};
+	double dist[5] = {0, 0, 0, 0, 0};
+	if (params) {
+		for (int k = 0; k < 9; ++k) cam[k] = params[k];
+		for (int k = 0; k < 5; ++k) dist[k] = params[9 + k];
+		for (int k = 0; k < 14; ++k)
+			if (!std::isfinite(params[k])) { ctx->err = std::string(who) + ": camera / distortion parameters must be finite"; return CIMBAR_HIP_EINVAL; }
+		if (cam[1] != 0. || cam[3] != 0. || cam[6] != 0. || cam[7] != 0. || cam[8] != 1.) {
+			ctx->err = std::string(who) + ": only zero-skew cameras [fx, 0, cx; 0, fy, cy; 0, 0, 1] are supported";
+			return CIMBAR_HIP_EINVAL;
+		}
+	}
+	if (!undistort_invert3x3(cam, ir)) { ctx->err = std::string(who) + ": the camera matrix is singular"; return CIMBAR_HIP_EINVAL; }
+	*P = UndistortParams{cam[0], cam[4], cam[2], cam[5], dist[0], dist[1], dist[2], dist[3], dist[4], ir[4], ir[5], 1. / ir[8]};
+	return 0;
+}
+
+// captures per group: as many undistorted RGB8 captures as ud_scratch holds (256 MiB: 43 at 1080p), at least one
+int undistort_group(const cimbar_hip_ctx* ctx, unsigned width, unsigned height, int n)
+{
+	const size_t per = (size_t)width * height * 3, fit = ctx->ud_scratch / per;
+	return fit < 1 ? 1 : (fit < (size_t)n ? (int)fit : n);
+}
+
+// per-capture state of a call of n captures, the column table for `width` columns (the table goes through pinned staging: an async copy must not
+// read a pageable temporary), and -- with `group` > 0 -- the image scratch of one group
+int undistort_state(cimbar_hip_ctx* ctx, hipStream_t st, int n, const double ir[9], unsigned width, unsigned height, int group)
+{
+	if (n > ctx->d_ud_n) {
+		HIPCHK(hipStreamSynchronize(st));
+		ctx->d_ud_n = 0;
+		HIPCHK(regrow(ctx->d_ud_ok, (size_t)n));
+		HIPCHK(regrow(ctx->d_ud_k1, (size_t)n));
+		HIPCHK(regrow(ctx->d_ud_status, (size_t)n));
+		ctx->d_ud_n = n;
+	}
+	if (!ctx->ev_ud_xt) HIPCHK(hipEventCreateWithFlags(&ctx->ev_ud_xt, hipEventDisableTiming));
+	HIPCHK(hipEventSynchronize(ctx->ev_ud_xt));
+	if ((int)width > ctx->ud_xt_cap) {
+		HIPCHK(hipStreamSynchronize(st));
+		ctx->ud_xt_cap = 0;
+		HIPCHK(regrow(ctx->d_ud_xt, (size_t)width));
+		if (ctx->h_ud_xt) { HIPCHK(hipHostFree(ctx->h_ud_xt)); ctx->h_ud_xt = nullptr; }
+		HIPCHK(hipHostMalloc(&ctx->h_ud_xt, sizeof(double) * width, hipHostMallocDefault));
+		ctx->ud_xt_cap = (int)width;
+	}
+	undistort_column_table(ir, (int)width, ctx->h_ud_xt);
+	HIPCHK(hipMemcpyAsync(ctx->d_ud_xt, ctx->h_ud_xt, sizeof(double) * width, hipMemcpyHostToDevice, st));
+	HIPCHK(hipEventRecord(ctx->ev_ud_xt, st));
+	const size_t need = (size_t)width * height * 3 * (size_t)group;
+	if (need > ctx->d_ud_img_cap) {
+		HIPCHK(hipStreamSynchronize(st));
+		ctx->d_ud_img_cap = 0;
+		HIPCHK(regrow(ctx->d_ud_img, need));
+		ctx->d_ud_img_cap = need;
+	}
+	return 0;
+}
+
+// U1 for m device-resident captures: X1 + X2 + S1-S3 (enqueue_scan), then k_undistort_calibrate -> d_ok[m], d_k1[m]
+int enqueue_undistort_calibrate(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_in, unsigned width, unsigned height, int fmt, int m, int* d_ok, double* d_k1)
+{
+	if (int r = extract_state(ctx, m)) return r;
+	if (int r = enqueue_scan(ctx, st, d_in, width, height, fmt, m)) return r;
+	hipLaunchKernelGGL(k_undistort_calibrate, dim3((m + 63) / 64), dim3(64), 0, st, ctx->d_ex_gray, (int)width, (int)height, ctx->d_ex_thr,
+	                   &ctx->d_scan_res[0].status, (int)(sizeof(ScanResult) / sizeof(int)), ctx->d_scan_res[0].corners, (int)(sizeof(ScanResult) / sizeof(float)),
+	                   m, undistort_target_ratio(), d_ok, d_k1);
+	HIPCHK(hipGetLastError());
+	return 0;
+}
+
+// U2 for m captures in `fmt` -> m undistorted RGB8 captures at d_out
+void launch_undistort(hipStream_t st, int fmt, const uint8_t* d_in, unsigned width, unsigned height, int m, const double* d_xt, const UndistortParams& P,
+                      const double* d_k1, const int* d_ok, uint8_t* d_out)
+{
+	static const int xcd_order = [] { const char* v = std::getenv("CIMBAR_HIP_WARP_ORDER"); return v ? std::atoi(v) : 1; }();
+	const dim3 g((width + 63) / 64, (height + 16 * UD_ROWS - 1) / (16 * UD_ROWS), m);
+	const int W = (int)width, H = (int)height;
+	if (fmt == FMT_RGBA) hipLaunchKernelGGL((k_undistort<FMT_RGBA>), g, dim3(256), 0, st, d_in, W, H, d_xt, P, d_k1, d_ok, d_out, xcd_order);
+	else if (fmt == FMT_NV12) hipLaunchKernelGGL((k_undistort<FMT_NV12>), g, dim3(256), 0, st, d_in, W, H, d_xt, P, d_k1, d_ok, d_out, xcd_order);
+	else if (fmt == FMT_I420) hipLaunchKernelGGL((k_undistort<FMT_I420>), g, dim3(256), 0, st, d_in, W, H, d_xt, P, d_k1, d_ok, d_out, xcd_order);
+	else hipLaunchKernelGGL((k_undistort<FMT_RGB>), g, dim3(256), 0, st, d_in, W, H, d_xt, P, d_k1, d_ok, d_out, xcd_order);
+}
+
+// the argument checks the three entry points share; *st = the stream the call runs on
+int undistort_args(cimbar_hip_ctx* ctx, const char* who, const uint8_t* img, unsigned width, unsigned height, int format, int n, int img_mem, int out_mem,
+                   void* hip_stream, int* fmt, size_t* cbytes, hipStream_t* st)
+{
+	if (!img || n <= 0 || width < 8 || height < 8) { ctx->err = std::string(who) + ": null buffer, n <= 0 or a capture smaller than 8x8"; return CIMBAR_HIP_EINVAL; }
+	if ((img_mem != CIMBAR_HIP_MEM_HOST && img_mem != CIMBAR_HIP_MEM_DEVICE) || (out_mem != CIMBAR_HIP_MEM_HOST && out_mem != CIMBAR_HIP_MEM_DEVICE)) {
+		ctx->err = std::string(who) + ": img_mem / out_mem must be CIMBAR_HIP_MEM_HOST or CIMBAR_HIP_MEM_DEVICE";
+		return CIMBAR_HIP_EINVAL;
+	}
+	if (int r = check_capture(ctx, who, width, height, format, fmt, cbytes)) return r;
+	HIPCHK(hipSetDevice(ctx->device));
+	const bool any_device = img_mem == CIMBAR_HIP_MEM_DEVICE || out_mem == CIMBAR_HIP_MEM_DEVICE;
+	*st = hip_stream ? (hipStream_t)hip_stream : (any_device ? (hipStream_t)nullptr : ctx->stream);
+	return drain_pipeline_into(ctx, *st);
+}
+
+}  // namespace
+
+int cimbar_hip_undistort_calibrate_fmt(cimbar_hip_ctx* ctx, const uint8_t* img, unsigned width, unsigned height, int format, int n, int img_mem,
+                                       int* ok, double* k1, void* hip_stream)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	if (!ok || !k1) { ctx->err = "undistort_calibrate: null ok / k1"; return CIMBAR_HIP_EINVAL; }
+	int fmt; size_t cbytes; hipStream_t st;
+	if (int r = undistort_args(ctx, "undistort_calibrate", img, width, height, format, n, img_mem, CIMBAR_HIP_MEM_HOST, hip_stream, &fmt, &cbytes, &st)) return r;
+	UndistortParams P; double ir[9];
+	if (int r = undistort_setup(ctx, "undistort_calibrate", nullptr, width, height, &P, ir)) return r;
+	const int group = undistort_group(ctx, width, height, n);
+	if (int r = undistort_state(ctx, st, n, ir, width, height, 0)) return r;
+	const uint8_t* d_in = nullptr;
+	if (int r = stage_captures(ctx, st, img, cbytes * n, img_mem, &d_in)) return r;
+	for (int lo = 0; lo < n; lo += group) {
+		const int m = n - lo < group ? n - lo : group;
+		if (int r = enqueue_undistort_calibrate(ctx, st, d_in + (size_t)lo * cbytes, width, height, fmt, m, ctx->d_ud_ok + lo, ctx->d_ud_k1 + lo)) return r;
+	}
+	HIPCHK(hipMemcpyAsync(ok, ctx->d_ud_ok, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipMemcpyAsync(k1, ctx->d_ud_k1, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipStreamSynchronize(st));
+	return 0;
+}
+
+int cimbar_hip_undistort_batch_fmt(cimbar_hip_ctx* ctx, const uint8_t* img, unsigned width, unsigned height, int format, int n, int img_mem,
+                                   const double* params, uint8_t* out_rgb, int out_mem, int* ok, double* k1_out, void* hip_stream)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	if (!out_rgb) { ctx->err = "undistort_batch: null out_rgb"; return CIMBAR_HIP_EINVAL; }
+	int fmt; size_t cbytes; hipStream_t st;
+	if (int r = undistort_args(ctx, "undistort_batch", img, width, height, format, n, img_mem, out_mem, hip_stream, &fmt, &cbytes, &st)) return r;
+	UndistortParams P; double ir[9];
+	if (int r = undistort_setup(ctx, "undistort_batch", params, width, height, &P, ir)) return r;
+	const int group = undistort_group(ctx, width, height, n);
+	if (int r = undistort_state(ctx, st, n, ir, width, height, out_mem == CIMBAR_HIP_MEM_HOST ? group : 0)) return r;
+	const uint8_t* d_in = nullptr;
+	if (int r = stage_captures(ctx, st, img, cbytes * n, img_mem, &d_in)) return r;
+	const size_t per = (size_t)width * height * 3;
+	if (params) hipLaunchKernelGGL(k_undistort_fill, dim3((n + 63) / 64), dim3(64), 0, st, n, P.k1, ctx->d_ud_ok, ctx->d_ud_k1);
+	for (int lo = 0; lo < n; lo += group) {
+		const int m = n - lo < group ? n - lo : group;
+		if (!params)
+			if (int r = enqueue_undistort_calibrate(ctx, st, d_in + (size_t)lo * cbytes, width, height, fmt, m, ctx->d_ud_ok + lo, ctx->d_ud_k1 + lo)) return r;
+		uint8_t* d_out = out_mem == CIMBAR_HIP_MEM_DEVICE ? out_rgb + (size_t)lo * per : ctx->d_ud_img;
+		launch_undistort(st, fmt, d_in + (size_t)lo * cbytes, width, height, m, ctx->d_ud_xt, P, params ? nullptr : ctx->d_ud_k1 + lo,
+		                 params ? nullptr : ctx->d_ud_ok + lo, d_out);
+		HIPCHK(hipGetLastError());
+		// (the next group's kernels overwrite the scratch only after this copy: same stream)
+		if (out_mem == CIMBAR_HIP_MEM_HOST) HIPCHK(hipMemcpyAsync(out_rgb + (size_t)lo * per, d_out, per * m, hipMemcpyDeviceToHost, st));
+	}
+	const hipMemcpyKind kind = out_mem == CIMBAR_HIP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+	if (ok) HIPCHK(hipMemcpyAsync(ok, ctx->d_ud_ok, sizeof(int) * (size_t)n, kind, st));
+	if (k1_out) HIPCHK(hipMemcpyAsync(k1_out, ctx->d_ud_k1, sizeof(double) * (size_t)n, kind, st));
+	if (out_mem == CIMBAR_HIP_MEM_DEVICE) return 0;
+	HIPCHK(hipStreamSynchronize(st));
+	return 0;
+}
+
+int64_t cimbar_hip_scan_undistort_extract_decode_batch_fmt(cimbar_hip_ctx* ctx, const uint8_t* img, unsigned width, unsigned height, int format, int n,
+                                                           int img_mem, int preprocess, int color_correction, uint8_t* chunks, uint32_t* masks, int* status,
+                                                           int* undistort_ok, int out_mem, void* hip_stream)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	if (!chunks || !masks) { ctx->err = "scan_undistort_extract_decode_batch: null chunks / masks"; return CIMBAR_HIP_EINVAL; }
+	int fmt; size_t cbytes; hipStream_t st;
+	if (int r = undistort_args(ctx, "scan_undistort_extract_decode_batch", img, width, height, format, n, img_mem, out_mem, hip_stream, &fmt, &cbytes, &st)) return r;
+	UndistortParams P; double ir[9];
+	if (int r = undistort_setup(ctx, "scan_undistort_extract_decode_batch", nullptr, width, height, &P, ir)) return r;
+	if (int r = ensure_capacity(ctx, n)) return r;
+	const int group = undistort_group(ctx, width, height, n);
+	if (int r = undistort_state(ctx, st, n, ir, width, height, group)) return r;
+	const uint8_t* d_in = nullptr;
+	if (int r = stage_captures(ctx, st, img, cbytes * n, img_mem, &d_in)) return r;
+	if ((size_t)n * FRAME_RGB > ctx->d_ex_frames_cap) { HIPCHK(regrow(ctx->d_ex_frames, (size_t)n * FRAME_RGB)); ctx->d_ex_frames_cap = (size_t)n * FRAME_RGB; }
+	// cimbar.cpp:135-146 per capture, a group at a time: calibrate on the raw capture, remap (a failed calibration leaves the image as it was), then
+	// Extractor::extract on the result; the deskewed frames of the whole batch then go through ONE decode, as in scan_extract_decode_batch
+	for (int lo = 0; lo < n; lo += group) {
+		const int m = n - lo < group ? n - lo : group;
+		if (int r = enqueue_undistort_calibrate(ctx, st, d_in + (size_t)lo * cbytes, width, height, fmt, m, ctx->d_ud_ok + lo, ctx->d_ud_k1 + lo)) return r;
+		launch_undistort(st, fmt, d_in + (size_t)lo * cbytes, width, height, m, ctx->d_ud_xt, P, ctx->d_ud_k1 + lo, ctx->d_ud_ok + lo, ctx->d_ud_img);
+		if (int r = enqueue_scan(ctx, st, ctx->d_ud_img, width, height, FMT_RGB, m)) return r;
+		if (int r = launch_warp_ctx(ctx, st, FMT_RGB, ctx->d_ud_img, width, height, m, ctx->d_ex_minv, ctx->d_ex_frames + (size_t)lo * FRAME_RGB)) return r;
+		HIPCHK(hipMemcpy2DAsync(ctx->d_ud_status + lo, sizeof(int), &ctx->d_scan_res[0].status, sizeof(ScanResult), sizeof(int), (size_t)m, hipMemcpyDeviceToDevice, st));
+	}
+	uint8_t* d_chunks = out_mem == CIMBAR_HIP_MEM_DEVICE ? chunks : ctx->d_chunks;
+	uint32_t* d_masks = out_mem == CIMBAR_HIP_MEM_DEVICE ? masks : ctx->d_masks;
+	const bool guess = preprocess != 0 && preprocess != 1;
+	ctx->no_split_once = true;
+	const int er = enqueue(ctx, st, ctx->d_ex_frames, n, preprocess == 1 ? 1 : 0, color_correction, d_chunks, d_masks, 0, false, guess ? ctx->d_ud_status : nullptr, 1);
+	ctx->no_split_once = false;
+	if (er) return er;
+	hipLaunchKernelGGL(k_mask_failed, dim3(n), dim3(256), 0, st, ctx->d_ud_status, 1, n, d_masks, d_chunks);
+	HIPCHK(hipGetLastError());
+	const hipMemcpyKind kind = out_mem == CIMBAR_HIP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+	if (status) HIPCHK(hipMemcpyAsync(status, ctx->d_ud_status, sizeof(int) * (size_t)n, kind, st));
+	if (undistort_ok) HIPCHK(hipMemcpyAsync(undistort_ok, ctx->d_ud_ok, sizeof(int) * (size_t)n, kind, st));
+	if (out_mem == CIMBAR_HIP_MEM_DEVICE) return 0;
+	HIPCHK(hipMemcpyAsync(chunks, d_chunks, (size_t)n * FRAME_BYTES, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipMemcpyAsync(masks, d_masks, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipStreamSynchronize(st));
+	unsigned long long total = 0;
+	for (int f = 0; f < n; ++f) total += (unsigned long long)CHUNK * (unsigned)__builtin_popcount(masks[f] & ((1u << CHUNKS) - 1u));
+	return (int64_t)total;
+}

@@ -108,6 +108,7 @@ struct Tables {
 #include "encode.hip.inc"
 #include "extract.hip.inc"
 #include "scan.hip.inc"
+#include "undistort.hip.inc"
 
 }  // namespace
 

@@ -33,6 +33,7 @@ EXPORTS = (
     "cimbar_hip_ctx_bufsize", "cimbar_hip_mode_bufsize", "cimbar_hip_set_ccm",
     "cimbar_hip_capture_bytes", "cimbar_hip_scan_preprocess_fmt", "cimbar_hip_deskew_batch_fmt", "cimbar_hip_extract_batch_fmt",
     "cimbar_hip_scan_extract_decode_batch_fmt",
+    "cimbar_hip_undistort_calibrate_fmt", "cimbar_hip_undistort_batch_fmt", "cimbar_hip_scan_undistort_extract_decode_batch_fmt",
 )
 PNG_EHEADER, PNG_ESTREAM, PNG_ECODES, PNG_ESIZE, PNG_ECHECK = -30, -31, -32, -33, -34
 
@@ -107,6 +108,12 @@ def load_library(path=None):
     lib.cimbar_hip_extract_batch_fmt.restype = i32
     lib.cimbar_hip_scan_extract_decode_batch_fmt.argtypes = [vp, vp, u32, u32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp]
     lib.cimbar_hip_scan_extract_decode_batch_fmt.restype = i64
+    lib.cimbar_hip_undistort_calibrate_fmt.argtypes = [vp, vp, u32, u32, i32, i32, i32, vp, vp, vp]
+    lib.cimbar_hip_undistort_calibrate_fmt.restype = i32
+    lib.cimbar_hip_undistort_batch_fmt.argtypes = [vp, vp, u32, u32, i32, i32, i32, vp, vp, i32, vp, vp, vp]
+    lib.cimbar_hip_undistort_batch_fmt.restype = i32
+    lib.cimbar_hip_scan_undistort_extract_decode_batch_fmt.argtypes = [vp, vp, u32, u32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp]
+    lib.cimbar_hip_scan_undistort_extract_decode_batch_fmt.restype = i64
     lib.cimbar_hip_comm_init_all.argtypes = [i32, vp, ctypes.POINTER(vp)]
     lib.cimbar_hip_comm_init_all.restype = i32
     lib.cimbar_hip_comm_unique_id.argtypes = [vp]
@@ -455,6 +462,45 @@ class HipDecoder:
                                                                              int(color_correction), chunks.ctypes.data, masks.ctypes.data,
                                                                              status.ctypes.data, MEM_HOST, None), "cimbar_hip_scan_extract_decode_batch_fmt")
         return int(rc), chunks, masks, status
+
+    # ------------------------------------------------------------------ lens undistortion (`cimbar --undistort`, Undistort<SimpleCameraCalibration>)
+    def undistort_calibrate(self, captures, size=None, fmt=3):
+        """SimpleCameraCalibration::scan per capture -> (ok (n,) int32, k1 (n,) float64); camera = [w/4, 0, w/2; 0, h/4, h/2; 0, 0, 1]"""
+        captures, n, w, h, fmt = self._captures(captures, size, fmt)
+        ok = np.zeros(n, dtype=np.int32)
+        k1 = np.zeros(n, dtype=np.float64)
+        self._check(self._lib.cimbar_hip_undistort_calibrate_fmt(self._ctx, captures.ctypes.data, w, h, fmt, n, MEM_HOST, ok.ctypes.data, k1.ctypes.data,
+                                                                 None), "cimbar_hip_undistort_calibrate_fmt")
+        return ok, k1
+
+    def undistort_batch(self, captures, params=None, size=None, fmt=3):
+        """Undistort::undistort per capture -> (images (n,h,w,3) uint8, ok (n,) int32, k1 (n,) float64). params: None (calibrate each capture) or
+        14 floats, camera[9] + distortion[5] (k1 k2 p1 p2 k3), for all of them (set_distortion_params)."""
+        captures, n, w, h, fmt = self._captures(captures, size, fmt)
+        out = np.zeros((n, h, w, 3), dtype=np.uint8)
+        ok = np.zeros(n, dtype=np.int32)
+        k1 = np.zeros(n, dtype=np.float64)
+        p = None
+        if params is not None:
+            p = np.ascontiguousarray(params, dtype=np.float64).reshape(-1)
+            if p.size != 14:
+                raise CimbarHipError(f"params: camera[9] + distortion[5], got {p.size} values")
+        self._check(self._lib.cimbar_hip_undistort_batch_fmt(self._ctx, captures.ctypes.data, w, h, fmt, n, MEM_HOST, p.ctypes.data if p is not None else None,
+                                                             out.ctypes.data, MEM_HOST, ok.ctypes.data, k1.ctypes.data, None), "cimbar_hip_undistort_batch_fmt")
+        return out, ok, k1
+
+    def scan_undistort_extract_decode_batch(self, captures, preprocess=-1, color_correction=2, size=None, fmt=3):
+        """the decode loop of `cimbar --undistort` for n captures -> (good_bytes, chunks (n,12,625), masks (n,), status (n,), undistort_ok (n,))"""
+        captures, n, w, h, fmt = self._captures(captures, size, fmt)
+        chunks = np.zeros((n, self.geo.CHUNKS_PER_FRAME, self.geo.CHUNK), dtype=np.uint8)
+        masks = np.zeros(n, dtype=np.uint32)
+        status = np.zeros(n, dtype=np.int32)
+        ok = np.zeros(n, dtype=np.int32)
+        rc = self._check(self._lib.cimbar_hip_scan_undistort_extract_decode_batch_fmt(self._ctx, captures.ctypes.data, w, h, fmt, n, MEM_HOST, int(preprocess),
+                                                                                       int(color_correction), chunks.ctypes.data, masks.ctypes.data,
+                                                                                       status.ctypes.data, ok.ctypes.data, MEM_HOST, None),
+                         "cimbar_hip_scan_undistort_extract_decode_batch_fmt")
+        return int(rc), chunks, masks, status, ok
 
     def scan_extract_decode_device(self, captures_ptr, w, h, n, chunks_ptr, masks_ptr, status_ptr=None, preprocess=-1, color_correction=2, stream=None, fmt=3):
         """device captures in, device chunks / masks / status out; asynchronous on `stream`"""
