@@ -15,6 +15,7 @@ from oracle import pyref
 from oracle.make_golden_modes import cases
 from oracle.pyref import P
 from tests import frames as F
+from tests import rs_cases
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # by hand from GridConf.h: total_cells, RS blocks (symbol + colour), chunk size = capacity(6) * (block - ecc) / block / chunks per frame
@@ -39,6 +40,17 @@ def synth67(MODE):
 @pytest.fixture(scope="module")
 def FIX(MODE):
     return json.load(open(os.path.join(HERE, "golden", "mode%d.json" % MODE)))
+
+
+@pytest.mark.parametrize("mode", [68, 67, 66, 4, 8])
+def test_rs_cases_renderer_is_the_mode_encoder(mode):
+    """tests/rs_cases.py blocks_to_tiles (stream bytes -> cells, what tests/test_gpu_rs_fuzz.py renders its hand-made blocks with) == FrameSynth's
+    cell_tiles, which test_framegen_matches_the_reference_encoder (and tests/test_framegen_vs_ref.py for mode 68) pins to the reference's encoder"""
+    synth = framegen.FrameSynth("cpu", mode)
+    g = synth.geo
+    payload = framegen.synth_payload(3, seed=60 + mode, mode=mode)
+    blocks = rs_cases.encode(payload.numpy().reshape(3 * g.BLOCKS, g.RS_DATA), g.RS_PARITY).reshape(3, g.BLOCKS * g.RS_BLOCK)
+    assert (rs_cases.blocks_to_tiles(synth, blocks) == synth.cell_tiles(payload)).all()
 
 
 def test_geometry_tables(MODE):

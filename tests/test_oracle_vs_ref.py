@@ -8,6 +8,7 @@ from libcimbar_amd import modeb
 from oracle import pyref
 from oracle.pyref import P
 from tests import frames as F
+from tests import rs_cases
 
 
 def test_tile_hashes_and_tiles(ref, synth):
@@ -36,25 +37,41 @@ def test_interleave_and_rs_encode(ref, oracle):
         assert (e1 == e2).all()
 
 
-def test_rs_decode_fuzz_including_failure_regime(ref, oracle):
+@pytest.mark.parametrize("n,parity", [(155, 30), (179, 36), (168, 33)])      # modes 68 / 4 / 8, 67, 66
+def test_rs_decode_fuzz_including_failure_regime(ref, oracle, n, parity):
+    k, t_max = n - parity, parity // 2
     g = np.random.default_rng(6)
     succ = 0
     for t in range(1500):
-        msg = g.integers(0, 256, 125, dtype=np.uint8)
-        enc = np.zeros(155, np.uint8)
-        ref.ref_rs_encode(P(msg), 125, 30, P(enc))
-        ne = int(g.integers(0, 30))
-        pos = g.choice(155, ne, replace=False)
+        msg = g.integers(0, 256, k, dtype=np.uint8)
+        enc = np.zeros(n, np.uint8)
+        ref.ref_rs_encode(P(msg), k, parity, P(enc))
+        ne = int(g.integers(0, parity))
+        pos = g.choice(n, ne, replace=False)
         bad = enc.copy()
         bad[pos] ^= g.integers(1, 256, ne, dtype=np.uint8)
-        o1, o2 = np.zeros(125, np.uint8), np.zeros(125, np.uint8)
-        r1 = ref.ref_rs_decode(P(bad), 155, 30, P(o1))
-        r2 = oracle.co_rs_decode(P(bad), 155, 30, P(o2))
+        o1, o2 = np.zeros(k, np.uint8), np.zeros(k, np.uint8)
+        r1 = ref.ref_rs_decode(P(bad), n, parity, P(o1))
+        r2 = oracle.co_rs_decode(P(bad), n, parity, P(o2))
         assert r1 == r2, (t, ne)
         if r1 > 0:
             assert (o1 == o2).all(), (t, ne)
             succ += 1
-    assert 700 < succ < 1000
+    # about (t + 1) / parity of the trials carry <= t errors (at (155, 30): 800 of 1500, held to 700 < succ < 1000)
+    expect = 1500 * (t_max + 1) / parity
+    assert 0.875 * expect < succ < 1.25 * expect
+    # ... and the blocks at the correction limit (tests/rs_cases.py), each also held to what it was built to produce
+    cases = rs_cases.edge_cases(np.random.default_rng(1000 + parity), n, parity)
+    assert {c[1] for c in cases} == set(rs_cases.FAMILIES) - {"random"}
+    for i, case in enumerate(cases):
+        bad = np.ascontiguousarray(case[0])
+        o1, o2 = np.zeros(k, np.uint8), np.zeros(k, np.uint8)
+        r1 = ref.ref_rs_decode(P(bad), n, parity, P(o1))
+        r2 = oracle.co_rs_decode(P(bad), n, parity, P(o2))
+        assert r1 == r2, (i, case[1], r1, r2)
+        if r1 > 0:
+            assert (o1 == o2).all(), (i, case[1])
+        rs_cases.check_promise(case, parity, r1, o1)
 
 
 def test_color_classifier_fuzz(ref, oracle):
