@@ -611,6 +611,12 @@ unsigned co_best_color(float r, float g, float b, const co_ccm* ccm)
 	return best_fit;
 }
 
+/* co_best_color over n (r, g, b) float triples (rgb3n) -> out[n]: the exhaustive classifier tests go through this, not one ctypes call per input */
+void co_best_color_batch(const float* rgb3n, unsigned n, const co_ccm* ccm, uint8_t* out)
+{
+	for (unsigned i = 0; i < n; ++i) out[i] = (uint8_t)co_best_color(rgb3n[3 * i], rgb3n[3 * i + 1], rgb3n[3 * i + 2], ccm);
+}
+
 /* lib/cimb_translator/CimbReader.cpp:55-86 calculateWhite (dark): max over three 4x4 anchor-centre means, floor (1,1,1) */
 static void calculate_white(const uint8_t* rgb, float white[3])
 {

@@ -54,6 +54,9 @@ def oracle_lib(mode=68):
         L.co_last_positions.restype = ctypes.POINTER(ctypes.c_int32)
         L.co_best_color.argtypes = [ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_void_p]
         L.co_best_color.restype = ctypes.c_uint
+        if hasattr(L, "co_best_color_batch"):
+            L.co_best_color_batch.argtypes = [ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p]
+            L.co_best_color_batch.restype = None
         _oracle[mode] = L
     return _oracle[mode]
 
@@ -65,9 +68,19 @@ def ref_lib():
         L = ctypes.CDLL(REF_SO)
         L.ref_sink_decode_frame.restype = ctypes.c_int64
         L.ref_best_color.argtypes = [ctypes.c_float, ctypes.c_float, ctypes.c_float]
+        if ref_has_colour_batch(L):          # (oracle/ref/ref_colour.cpp: a reference build that predates it still serves everything else)
+            L.ref_set_ccm.argtypes = [ctypes.c_void_p, ctypes.c_int]
+            L.ref_set_ccm.restype = None
+            L.ref_best_color_batch.argtypes = [ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p]
         L.ref_configure(68)
         _ref = L
     return _ref
+
+
+def ref_has_colour_batch(L=None):
+    """whether the reference build carries ref_set_ccm / ref_best_color_batch (oracle/ref/ref_colour.cpp)"""
+    L = L if L is not None else ref_lib()
+    return L is not None and hasattr(L, "ref_set_ccm") and hasattr(L, "ref_best_color_batch")
 
 
 class ref_mode:
