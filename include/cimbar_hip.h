@@ -172,6 +172,36 @@ int cimbar_hip_get_ccm(cimbar_hip_ctx* ctx, float out9[9]);
  * derives its own (color_correction 2 with a decoded header) or cimbar_hip_reset_ccm. Waits for batches in flight. */
 int cimbar_hip_set_ccm(cimbar_hip_ctx* ctx, const float m9[9]);
 
+/* Erasure decoding (off after cimbar_hip_create). With sym_distance > 0, every decode entry point that reports chunks (decode_frame, _async,
+ * decode_batch, _pipelined, scan_extract_decode_batch(_fmt), scan_undistort_extract_decode_batch_fmt) retries the symbol chunks its mask
+ * lacks: a cell whose 8x8 hash at its final position is sym_distance or more bits from its decoded symbol's tile makes the stream bytes it
+ * supplies erasures (at most max_erasures per block, the most distant first), the blocks errors-only decoding failed are decoded again with
+ * them (cimbar_hip_rs_decode_erasures below), and a chunk whose blocks are then all accepted joins the mask with its bytes. Chunks already in
+ * the mask, colour chunks, the per-block flags and the colour-correction state are never changed; the mask only gains bits.
+ *   sym_distance  : <= 0 turns it off (nothing extra is launched); 1 .. 64 the threshold
+ *   colour_margin : kept and reported; colour blocks are not retried
+ *   max_erasures  : < 0 = the default, parity - 8 (22 / 28 / 25 in modes 68 / 67 / 66); at most the parity bytes
+ * Modes 4 and 8 (one coupled stream) refuse it (EINVAL); cimbar_hip_decode_plain_batch returns EINVAL while it is on. Takes effect for
+ * batches issued after the call. get: writes the three values in force (max_erasures resolved), returns 1 if on, 0 if off. */
+int cimbar_hip_set_erasure_decode(cimbar_hip_ctx* ctx, int sym_distance, int colour_margin, int max_erasures);
+int cimbar_hip_get_erasure_decode(cimbar_hip_ctx* ctx, int* sym_distance, int* colour_margin, int* max_erasures);
+
+/* Errors-and-erasures Reed-Solomon decode of n caller-given blocks of the context's code (RS(155,125) in modes 68 / 4 / 8, RS(179,143) in
+ * 67, RS(168,135) in 66): libcorrect's correct_reed_solomon_decode_with_erasures, bit-exact, plus an acceptance check libcorrect does not
+ * make. With e erasures a block decodes whenever 2 * (errors outside them) + e <= parity.
+ *   blocks    : n * block_length bytes, transmit order
+ *   erasures  : n * block_length bytes; the first counts[b] bytes of row b are byte positions (< block_length) in block b
+ *   counts    : n bytes, the erasure count per block; a count above the parity bytes fails the block (libcorrect returns -1)
+ *   msgs      : n * message_length bytes: libcorrect's output where status >= 0, the received message bytes where status is -1
+ *   status    : n bytes, -1 = libcorrect returns -1; 0 = libcorrect returns the message but the corrected block is not a codeword, or a root
+ *               of the locator lies in the shortened code's zero padding (a miscorrection); 1 = decoded and accepted
+ *   mem       : CIMBAR_HIP_MEM_HOST (every buffer in host memory: staged through a buffer the context keeps, on hip_stream or the
+ *               context's stream if NULL; synchronises) or CIMBAR_HIP_MEM_DEVICE (all on the device: enqueues on hip_stream, the null stream if
+ *               NULL, and returns 0) -- the stream convention of cimbar_hip_encode_batch
+ * Touches no decode state of the context. */
+int cimbar_hip_rs_decode_erasures(cimbar_hip_ctx* ctx, const uint8_t* blocks, int n, const uint8_t* erasures, const uint8_t* counts, int mem,
+                                  uint8_t* msgs, int8_t* status, void* hip_stream);
+
 /* ---- the encode half ("next" row of the scope table: on-device frame synthesiser) --------------------------------------------
  * Encoder::encode_next (src/lib/encoder/Encoder.h:69-129) for n frames at once: each frame takes 7500 payload bytes (the 60
  * reads of 125 bytes a fountain_encoder_stream / ifstream would have served), RS(155,125)-encodes them (libcorrect encode.c:3-34),

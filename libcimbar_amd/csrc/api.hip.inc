@@ -159,6 +159,25 @@ int cimbar_hip_set_template(cimbar_hip_ctx* ctx, const uint8_t* rgb_template, in
 	return CIMBAR_FWD(cimbar_hip_set_template, rgb_template, mem);
 }
 
+int cimbar_hip_set_erasure_decode(cimbar_hip_ctx* ctx, int sym_distance, int colour_margin, int max_erasures)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return CIMBAR_FWD(cimbar_hip_set_erasure_decode, sym_distance, colour_margin, max_erasures);
+}
+
+int cimbar_hip_get_erasure_decode(cimbar_hip_ctx* ctx, int* sym_distance, int* colour_margin, int* max_erasures)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return CIMBAR_FWD(cimbar_hip_get_erasure_decode, sym_distance, colour_margin, max_erasures);
+}
+
+int cimbar_hip_rs_decode_erasures(cimbar_hip_ctx* ctx, const uint8_t* blocks, int n, const uint8_t* erasures, const uint8_t* counts, int mem,
+                                  uint8_t* msgs, int8_t* status, void* hip_stream)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return CIMBAR_FWD(cimbar_hip_rs_decode_erasures, blocks, n, erasures, counts, mem, msgs, status, hip_stream);
+}
+
 int cimbar_hip_encode_batch(cimbar_hip_ctx* ctx, const uint8_t* payload, int n, int payload_mem, uint8_t* rgb_out, int rgb_mem, void* hip_stream)
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;

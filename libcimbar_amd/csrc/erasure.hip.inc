@@ -1,0 +1,371 @@
+// erasure.hip.inc -- part of cimbar_hip.hip (one translation unit; included inside its anonymous namespace, after k3_rs.hip.inc).
+// E3: Reed-Solomon errors-and-erasures decode of the mode's RS(RS_BLOCK, RS_DATA)
+// ------------------------------------------------------------------------------------------------ E3 errors-and-erasures
+// libcorrect's correct_reed_solomon_decode_with_erasures (decode.c:381-508) restated, one block per wavefront, for blocks whose erasure
+// positions are given. Its quirks are kept: the location remap block_length - (pos + pad + 1) in 8-bit arithmetic (decode.c:424), the
+// erasure locator prod (x + 1/X_i) (polynomial.c:161-197), the modified syndromes (erasure locator * S mod x^p, decode.c:247-257,445-452),
+// Berlekamp-Massey over the remaining p - e of them (decode.c:32-118), Chien over the error locator alone with the erasure roots kept in
+// front (decode.c:122-145), Forney over erasure locator * error locator with the ORIGINAL syndromes (decode.c:165-196, fcr = 1:
+// field_pow(root, 0) == 1) and field_div(x, 0) == 0. e == 0 is libcorrect's errors-only decode, which the same arithmetic gives with an
+// erasure locator of 1. e > p returns -1 (decode.c:392).
+//
+// The syndromes (of the received block and of the corrected one) and the Chien search run across the wavefront; the short serial parts
+// (erasure locator, modified syndromes, Berlekamp-Massey, the polynomial products) run on lane 0, the Forney step one root per lane. The
+// kernel is meant for the few blocks errors-only decoding could not correct, so it trades the last bit of speed for a line-by-line match.
+//
+// Where libcorrect's own behaviour is undefined -- a Berlekamp-Massey locator of order >= p, whose Chien search would read past the
+// element_exp rows (decode.c:136), or erasure + error roots above p, whose Forney step would do the same (decode.c:194) -- the block is
+// reported as a failure (-1).
+//
+// Per block: status -1 = libcorrect returns -1 (the message bytes written are the received ones, uncorrected); 0 = libcorrect returns the
+// message length but the result fails the acceptance check; 1 = accepted. Acceptance: the corrected RS_BLOCK-byte word has all-zero
+// syndromes, and no root of the combined locator lies in the shortened code's zero padding (location >= RS_BLOCK). libcorrect checks
+// neither: it drops a correction in the padding and returns whatever the Forney step produced.
+constexpr int ER_POLY = 2 * RS_PARITY + 12;   // locator / previous-locator scratch (as RS_POLY: libcorrect's min_distance + 1 and the shift slack)
+struct RsEraShared {
+	uint8_t exp[768];                          // exp[512..767] = 0, as in k_rs
+	uint8_t log[256];
+	uint8_t enc[4][192];                       // the block, transmit order; corrected in place
+	uint8_t synd[4][64];                       // S_0 .. S_{p-1} of the received block
+	uint8_t tsyn[4][64];                       // Berlekamp-Massey's input: modified syndromes e .. p-1
+	uint8_t eloc[4][64];                       // erasure locator, order e
+	uint8_t loc[4][ER_POLY];                   // Berlekamp-Massey's error locator
+	uint8_t last[4][ER_POLY];                  // ... and its previous locator
+	uint8_t full[4][2 * 64];                   // erasure locator * error locator
+	uint8_t ev[4][64];                         // error evaluator = full * S mod x^p
+	uint8_t roots[4][256];                     // erasure roots, then the Chien roots in increasing element order
+	uint8_t val[4][64];                        // Forney values, one per root
+	uint8_t where[4][64];                      // the roots' locations (power of x)
+};
+static_assert(RS_PARITY <= 64 && RS_BLOCK <= 192, "one lane per parity byte; a lane owns three bytes of the block");
+
+// the block's p syndromes, S_j = r(alpha^(j+1)), r(x) = sum_k enc[RS_BLOCK-1-k] x^k, term-parallel over the lanes' three bytes; lane 0 writes
+// them to `out` when it is not null. Returns whether all are zero (wave-uniform).
+__device__ bool er_syndromes(RsEraShared& s, const uint8_t* enc, uint8_t* out, int lane)
+{
+	uint32_t lg[3], pw[3];
+#pragma unroll
+	for (int r = 0; r < 3; ++r) {
+		const int k = lane + 64 * r;
+		const uint32_t v = k < RS_BLOCK ? enc[k] : 0u;
+		lg[r] = v ? (uint32_t)s.log[v] % 255u : 512u;
+		pw[r] = k < RS_BLOCK ? (uint32_t)(RS_BLOCK - 1 - k) : 0u;
+	}
+	uint32_t any = 0;
+	for (int j = 0; j < RS_PARITY; ++j) {
+		uint32_t part = 0;
+#pragma unroll
+		for (int r = 0; r < 3; ++r) part ^= s.exp[lg[r] >= 512u ? 512u : lg[r] + (pw[r] * (uint32_t)(j + 1)) % 255u];
+		const uint32_t sj = wave_xor(part) & 0xFFu;
+		any |= sj;
+		if (out && lane == 0) out[j] = (uint8_t)sj;
+	}
+	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+	__builtin_amdgcn_wave_barrier();
+	return any == 0;
+}
+
+// the decode of the block in s.enc[wv] with erasures at byte positions pos[0 .. e) (global or LDS); corrected in place. Returns the
+// block's status (-1 / 0 / 1, see above); wave-uniform, all 64 lanes active. The enc bytes are visible to the whole wave on return.
+__device__ int er_decode(RsEraShared& s, int wv, int lane, int e, const uint8_t* pos, int* nerr = nullptr)
+{
+	if (nerr) *nerr = 0;   // errors located beside the erasures (Berlekamp-Massey's locator order) where the decode gets that far
+	uint8_t* enc = s.enc[wv];
+	auto finish = [&](int st) {
+		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+		__builtin_amdgcn_wave_barrier();
+		return st;
+	};
+	if (e > RS_PARITY) return finish(-1);                  // decode.c:392
+
+	uint8_t* synd = s.synd[wv];
+	if (er_syndromes(s, enc, synd, lane)) return finish(1);  // decode.c:436-443: a codeword; nothing corrected
+
+	uint8_t* eloc = s.eloc[wv];
+	uint8_t* tsyn = s.tsyn[wv];
+	uint8_t* loc = s.loc[wv];
+	uint8_t* last = s.last[wv];
+	uint8_t* full = s.full[wv];
+	uint8_t* roots = s.roots[wv];
+	int order = 0;
+	bool bad = false;
+	if (lane == 0) {
+		// erasure roots (decode.c:422-428, 226-235): location L = block_length - (pos + pad + 1) as a field_logarithm_t, root = 1 / alpha^L
+		const uint8_t* er = pos;
+		for (int i = 0; i < e; ++i) {
+			const uint8_t L = (uint8_t)(RS_BLOCK - 1 - (int)er[i]);
+			roots[i] = gf_div(s, 1, s.exp[L]);
+		}
+		// erasure locator prod_i (x + root_i) (polynomial.c:161-197); e == 0: the constant 1 (the errors-only decode, decode.c:384-386)
+		for (int k = 0; k <= RS_PARITY; ++k) eloc[k] = 0;
+		if (e == 0) eloc[0] = 1;
+		else {
+			eloc[0] = roots[0]; eloc[1] = 1;
+			for (int i = 1; i < e; ++i) {          // (x + root_i) * eloc, full product of order i + 1, from the top down in place
+				for (int k = i + 1; k >= 0; --k) eloc[k] = (uint8_t)((k >= 1 ? eloc[k - 1] : 0) ^ gf_mul(s, roots[i], eloc[k]));
+			}
+		}
+		// modified syndromes eloc * S mod x^p; Berlekamp-Massey reads entries e .. p-1 (decode.c:445-452)
+		for (int k = 0; k < RS_PARITY; ++k) {
+			uint32_t acc = 0;
+			for (int i = 0; i <= e && i <= k; ++i) acc ^= gf_mul(s, eloc[i], synd[k - i]);
+			if (k >= e) tsyn[k - e] = (uint8_t)acc;
+		}
+		// Berlekamp-Massey over p - e syndromes, statement for statement (decode.c:32-118)
+		for (int k = 0; k < ER_POLY; ++k) { loc[k] = (k == 0); last[k] = (k == 0); }
+		unsigned loc_order = 0, last_order = 0, numerrors = 0, delay = 1;
+		uint32_t last_disc = 1;
+		for (unsigned i = 0; i < (unsigned)(RS_PARITY - e); ++i) {
+			uint32_t disc = tsyn[i];
+			for (unsigned j = 1; j <= numerrors; ++j) disc ^= gf_mul(s, loc[j], tsyn[i - j]);
+			if (!disc) { delay++; continue; }
+			if (2 * numerrors <= i) {
+				for (int j = (int)last_order; j >= 0; --j)
+					if ((unsigned)j + delay < (unsigned)ER_POLY) last[j + delay] = gf_div(s, gf_mul(s, last[j], disc), last_disc);
+				for (int j = (int)delay - 1; j >= 0; --j) if (j < ER_POLY) last[j] = 0;
+				for (unsigned j = 0; j <= last_order + delay && j < (unsigned)ER_POLY; ++j) {
+					const uint8_t t = loc[j];
+					loc[j] ^= last[j];
+					last[j] = t;
+				}
+				const unsigned t_order = loc_order;
+				loc_order = last_order + delay;
+				last_order = t_order;
+				numerrors = i + 1 - numerrors;
+				last_disc = disc;
+				delay = 1;
+				continue;
+			}
+			for (int j = (int)last_order; j >= 0; --j)
+				if ((unsigned)j + delay < (unsigned)ER_POLY) loc[j + delay] ^= gf_div(s, gf_mul(s, last[j], disc), last_disc);
+			loc_order = (last_order + delay > loc_order) ? last_order + delay : loc_order;
+			delay++;
+		}
+		order = (int)loc_order;
+		bad = order >= RS_PARITY || order + e > RS_PARITY;   // libcorrect's look-up rows end there (see above)
+	}
+	order = __builtin_amdgcn_readfirstlane(order);
+	bad = __builtin_amdgcn_readfirstlane((int)bad) != 0;
+	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+	__builtin_amdgcn_wave_barrier();
+	if (nerr) *nerr = order;
+	if (bad) return finish(-1);
+
+	// Chien over all 256 field elements with the error locator alone (decode.c:122-145); element 0 evaluates to loc[0] = 1, never a root.
+	// Lane l tests elements l, l+64, l+128, l+192; the roots land in increasing element order behind the e erasure roots.
+	unsigned long long rootm[4];
+#pragma unroll
+	for (int r = 0; r < 4; ++r) {
+		const int x = lane + 64 * r;
+		rootm[r] = __builtin_amdgcn_ballot_w64(x != 0 && gf_eval(s, loc, order, (uint8_t)x) == 0);
+	}
+	const int n0 = (int)__popcll(rootm[0]), n1 = n0 + (int)__popcll(rootm[1]), n2 = n1 + (int)__popcll(rootm[2]), nroots = n2 + (int)__popcll(rootm[3]);
+	if (nroots != order) return finish(-1);           // decode.c:474-479: too many errors
+	{
+		const unsigned long long below = (1ull << lane) - 1ull;
+		const int base4[4] = {0, n0, n1, n2};
+#pragma unroll
+		for (int r = 0; r < 4; ++r)
+			if ((rootm[r] >> lane) & 1ull) roots[e + base4[r] + (int)__popcll(rootm[r] & below)] = (uint8_t)(lane + 64 * r);
+	}
+	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+	__builtin_amdgcn_wave_barrier();
+
+	// combined locator = erasure locator * error locator (decode.c:481-484) and the error evaluator = combined * S mod x^p (decode.c:175-179)
+	const int total = e + order;
+	uint8_t* ev = s.ev[wv];
+	if (lane == 0) {
+		for (int k = 0; k <= total; ++k) {
+			uint32_t acc = 0;
+			for (int i = 0; i <= e && i <= k; ++i) if (k - i <= order) acc ^= gf_mul(s, eloc[i], loc[k - i]);
+			full[k] = (uint8_t)acc;
+		}
+		for (int k = 0; k < RS_PARITY; ++k) {
+			uint32_t acc = 0;
+			for (int i = 0; i <= total && i <= k; ++i) acc ^= gf_mul(s, full[i], synd[k - i]);
+			ev[k] = (uint8_t)acc;
+		}
+	}
+	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+	__builtin_amdgcn_wave_barrier();
+
+	// Forney (decode.c:165-196) and the locations (decode.c:198-222), one root per lane. The formal derivative's coefficient i is
+	// full[i + 1] for even i, 0 for odd i (polynomial.c:74-87).
+	uint8_t* val = s.val[wv];
+	uint8_t* where = s.where[wv];
+	if (lane < total) {
+		const uint8_t x = roots[lane];
+		const uint8_t num = gf_eval(s, ev, RS_PARITY - 1, x);
+		uint32_t den = 0;
+		{
+			const unsigned lx = s.log[x] % 255u;
+			unsigned acc = 0;
+			for (int i = 0; i <= total - 1; ++i) {
+				if (!(i & 1) && full[i + 1]) den ^= s.exp[(unsigned)s.log[full[i + 1]] % 255u + acc];
+				acc += lx; if (acc >= 255u) acc -= 255u;
+			}
+		}
+		val[lane] = gf_div(s, num, den);
+		const uint8_t X = gf_div(s, 1, x);                     // the location is log(1 / root); 1 is found at j = 0 first: location 0
+		where[lane] = X == 1 ? (uint8_t)0 : s.log[X];
+	}
+	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+	__builtin_amdgcn_wave_barrier();
+	// the corrections in libcorrect's order (two roots may share a location); a location >= RS_BLOCK is the zero padding: not emitted
+	int in_pad = 0;
+	if (lane == 0) {
+		for (int i = 0; i < total; ++i) {
+			const int w = where[i];
+			if (w < RS_BLOCK) enc[RS_BLOCK - 1 - w] ^= val[i];
+			else in_pad = 1;
+		}
+	}
+	in_pad = __builtin_amdgcn_readfirstlane(in_pad);
+	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+	__builtin_amdgcn_wave_barrier();
+	const bool clean = er_syndromes(s, enc, nullptr, lane);
+	return finish(clean && !in_pad ? 1 : 0);
+}
+
+__device__ __forceinline__ void er_tables(RsEraShared& s)
+{
+	for (int k = threadIdx.x; k < 768; k += 256) s.exp[k] = k < 512 ? c_gf_exp[k] : (uint8_t)0;
+	s.log[threadIdx.x] = c_gf_log[threadIdx.x];
+	__syncthreads();
+}
+
+// cimbar_hip_rs_decode_erasures. blocks: [n][RS_BLOCK]; erasures: [n][RS_BLOCK], row b's first counts[b] bytes are byte positions in the
+// block; msgs: [n][RS_DATA] (libcorrect's output, the received bytes where it fails)
+__global__ __launch_bounds__(256) void k_rs_erasures(const uint8_t* __restrict__ blocks, int n, const uint8_t* __restrict__ erasures,
+                                                     const uint8_t* __restrict__ counts, uint8_t* __restrict__ msgs, int8_t* __restrict__ status)
+{
+	__shared__ RsEraShared s;
+	er_tables(s);
+	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+	const int b = blockIdx.x * 4 + wv;
+	if (b >= n) return;
+	uint8_t* enc = s.enc[wv];
+	for (int k = lane; k < RS_BLOCK; k += 64) enc[k] = blocks[(size_t)b * RS_BLOCK + k];
+	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+	__builtin_amdgcn_wave_barrier();
+	const int st = er_decode(s, wv, lane, counts[b], erasures + (size_t)b * RS_BLOCK);
+	for (int k = lane; k < RS_DATA; k += 64) msgs[(size_t)b * RS_DATA + k] = enc[k];
+	if (lane == 0) status[b] = (int8_t)st;
+}
+
+// ------------------------------------------------------------------------------------------------ erasure retry of a decoded frame
+constexpr int ERASURE_SLACK = 6;
+// Opt-in (cimbar_hip_set_erasure_decode), launched after k_frame_end on the same stream, one workgroup per frame, modes 68 / 67 / 66.
+// A frame whose symbol chunks are all in the mask returns at once (a clean batch costs one launch). Otherwise the four waves walk the symbol
+// blocks of the chunks the mask lacks:
+//  * confidence: d_sym(c) = popcount(ahash8 at the cell's final position ^ tile hash of its decoded symbol), from the bit plane, the drift and
+//    the symbol the decode produced (the position is the cell's grid position plus its drift where the frame went through the flood pass --
+//    the window k_colors reads -- and the grid position otherwise). Where the +-7 drift clamp moved the final position off the matched
+//    window this definition wins.
+//  * selection: a stream byte comes from two cells (nibbles); its score is max over them of d_sym - T_sym + 1, and it is flagged when the
+//    score is > 0. The max_erasures highest scores are kept, ties to the lower byte position.
+//  * a block errors-only decoding failed is retried with those erasures (none flagged: not retried -- it would be errors-only again); a
+//    block it decoded is decoded again with none (libcorrect's errors-only result, because k_frame_end has zeroed the slots of the chunks the
+//    mask lacks). Then a chunk whose blocks are now all accepted (status 1) gets its bytes and its mask bit; the slots of chunks still
+//    missing are zeroed again. Chunks already in the mask, the colour chunks, rs_ok, the frame state and the colour-correction carry are
+//    not touched.
+__global__ __launch_bounds__(256) void k_erasure_frame(const uint32_t* __restrict__ plane, Tables tb, const uint8_t* __restrict__ symbols,
+                                                       const int8_t* __restrict__ drift, const uint32_t* __restrict__ flood_flag,
+                                                       const uint8_t* __restrict__ rs_ok, uint8_t* __restrict__ chunks, uint32_t* __restrict__ masks,
+                                                       int f0, int t_sym, int e_max)
+{
+	if constexpr (LEGACY) return;                          // (one coupled stream: no symbol-only blocks; the host never launches it there)
+	constexpr uint32_t SYM_MASK = (1u << SYM_CHUNKS) - 1u;
+	const int f = f0 + blockIdx.x;
+	const uint32_t mask = masks[f];
+	if ((mask & SYM_MASK) == SYM_MASK) return;             // (uniform over the workgroup)
+	__shared__ RsEraShared s;
+	__shared__ int16_t s_score[4][192];
+	__shared__ uint8_t s_pos[4][64];
+	__shared__ int8_t s_st[SYM_BLOCKS];
+	er_tables(s);
+	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+	const uint8_t* sym = symbols + (size_t)f * NCELLS;
+	const uint32_t* pl = plane + (size_t)f * PLANE_WORDS;
+	const bool flooded = flood_flag[f] != 0;
+	uint8_t* fc = chunks + (size_t)f * FRAME_BYTES;
+	for (int b = wv; b < SYM_BLOCKS; b += 4) {
+		const int j = b / BLOCKS_PER_CHUNK;
+		if (mask & (1u << j)) { if (lane == 0) s_st[b] = 2; continue; }
+		const bool ok = rs_ok[(size_t)f * ALL_BLOCKS + b] != 0;
+		uint8_t* enc = s.enc[wv];
+		int16_t* score = s_score[wv];
+		for (int k = lane; k < RS_BLOCK; k += 64) {
+			const int sidx = (RS_BLOCK * b + k) * 2;
+			int best = -32768;
+			uint32_t v = 0;
+#pragma unroll
+			for (int q = 0; q < 2; ++q) {
+				const int cell = tb.stream_cell[sidx + q];
+				const uint32_t sy = sym[cell] & 15u;
+				v = (v << 4) | sy;
+				if (!ok) {
+					const ushort2 xy = tb.cell_xy[cell];
+					const int dx = flooded ? drift[((size_t)f * NCELLS + cell) * 2] : 0, dy = flooded ? drift[((size_t)f * NCELLS + cell) * 2 + 1] : 0;
+					uint32_t rows[10];
+					window_rows(pl, (int)xy.x + dx - 1, (int)xy.y + dy - 1, rows);
+					const int d = (int)__popcll(window_hash(rows, 4) ^ c_tile[sy]);
+					best = d - t_sym + 1 > best ? d - t_sym + 1 : best;
+				}
+			}
+			enc[k] = (uint8_t)v;
+			score[k] = (int16_t)best;
+		}
+		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+		__builtin_amdgcn_wave_barrier();
+		int e = 0;
+		if (!ok) {
+			// rank of each flagged byte among the flagged ones (higher score first, then lower position); the e_max best become erasures
+			int mine = 0;
+			for (int k = lane; k < RS_BLOCK; k += 64) {
+				const int sk = score[k];
+				if (sk <= 0) continue;
+				int rank = 0;
+				for (int q = 0; q < RS_BLOCK; ++q) {
+					const int sq = score[q];
+					rank += (sq > sk || (sq == sk && q < k)) ? 1 : 0;
+				}
+				if (rank < e_max) { s_pos[wv][rank] = (uint8_t)k; ++mine; }
+			}
+			for (int o = 32; o >= 1; o >>= 1) mine += __shfl_xor(mine, o);
+			e = mine;
+			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+			__builtin_amdgcn_wave_barrier();
+			if (e == 0) { if (lane == 0) s_st[b] = -2; continue; }   // nothing to erase: errors-only already failed it
+		}
+		int nerr = 0;
+		int st = er_decode(s, wv, lane, e, s_pos[wv], &nerr);
+		// a retried block must also leave ERASURE_SLACK syndromes unused: a damaged block lies within s errors of SOME codeword on its n - e
+		// unerased bytes with probability ~ C(n - e, s) 255^s / 256^(p - e), which the codeword check cannot see (1 in 200 blocks at
+		// p - e = 8, s = 4); with 2 s <= p - e - 6 it is below 1e-14
+		if (st == 1 && e > 0 && 2 * nerr > RS_PARITY - e - ERASURE_SLACK) st = 0;
+		if (st == 1) {
+			uint8_t* dst = fc + (size_t)j * CHUNK + (size_t)(b % BLOCKS_PER_CHUNK) * RS_DATA;
+			for (int k = lane; k < RS_DATA; k += 64) dst[k] = enc[k];
+		}
+		if (lane == 0) s_st[b] = (int8_t)st;
+	}
+	__syncthreads();
+	__shared__ uint32_t s_new;
+	if (threadIdx.x == 0) {
+		uint32_t m = mask;
+		for (int j = 0; j < SYM_CHUNKS; ++j) {
+			if (mask & (1u << j)) continue;
+			bool all = true;
+			for (int q = 0; q < BLOCKS_PER_CHUNK; ++q) all = all && s_st[j * BLOCKS_PER_CHUNK + q] == 1;
+			if (all) m |= 1u << j;
+		}
+		s_new = m;
+		masks[f] = m;
+	}
+	__syncthreads();
+	const uint32_t m = s_new;
+	for (int j = 0; j < SYM_CHUNKS; ++j)
+		if (!(m & (1u << j)))
+			for (int k = threadIdx.x; k < CHUNK; k += 256) fc[(size_t)j * CHUNK + k] = 0;
+}

@@ -10,6 +10,9 @@ struct cimbar_hip_ctx {
 	int tail_split = 1, tail_parts = 2;
 	uint32_t* h_flagged = nullptr;    // pinned, written by k_count_flagged at the end of every ordinary batch: [0] frames that left the parallel path, [1] frames of that batch,
 	                                  // [2] frames the exact replay had to take.
+	int er_sym = 0, er_col = -1, er_max = -1;   // cimbar_hip_set_erasure_decode: off while er_sym <= 0 (k_erasure_frame is then never launched)
+	uint8_t* d_er_buf = nullptr;                // cimbar_hip_rs_decode_erasures' staging for host-memory calls (grown on demand)
+	size_t d_er_cap = 0;
 	int wave_adapt = 1;               // CIMBAR_HIP_FLOOD_WAVE_ADAPT=0: run k_flood_wave in front of every exact replay, whatever it achieved before
 	bool wave_ran = false;            // k_flood_wave ran in the batch h_flagged describes
 	int wave_skip_left = 0;           // batches that still go straight to the exact replay (see enqueue)
@@ -394,7 +397,7 @@ void destroy_ctx(cimbar_hip_ctx* ctx)
 	}
 	auto fr = [](void* p) { if (p) (void)hipFree(p); };
 	fr(ctx->tb.cell_xy); fr(ctx->tb.stream_cell); fr(ctx->tb.cand); fr(ctx->tb.ccm_grid); fr(ctx->tb.cell_grid); fr(ctx->tb.grid_cell);
-	fr(ctx->d_template); fr(ctx->d_gen_log); fr(ctx->d_payload); fr(ctx->d_rgb); fr(ctx->d_plane); fr(ctx->d_cellmean); fr(ctx->d_symbols); fr(ctx->d_colors); fr(ctx->d_drift); fr(ctx->d_flood);
+	fr(ctx->d_template); fr(ctx->d_gen_log); fr(ctx->d_er_buf); fr(ctx->d_payload); fr(ctx->d_rgb); fr(ctx->d_plane); fr(ctx->d_cellmean); fr(ctx->d_symbols); fr(ctx->d_colors); fr(ctx->d_drift); fr(ctx->d_flood);
 	fr(ctx->d_rs_ok); fr(ctx->d_states); fr(ctx->d_ccm_frames); fr(ctx->d_ccm_used); fr(ctx->d_carry); fr(ctx->d_chunks);
 	fr(ctx->d_masks); fr(ctx->flood.heap); fr(ctx->flood.prio); fr(ctx->flood.next); fr(ctx->d_fw_queue); fr(ctx->d_vsym); fr(ctx->d_vdrift); fr(ctx->d_vflag); fr(ctx->d_vtotals);
 	fr(ctx->d_ex_rgb); fr(ctx->d_ex_box); fr(ctx->d_ex_in); fr(ctx->d_ex_out); fr(ctx->d_ex_hist); fr(ctx->d_ex_thr); fr(ctx->d_ex_minv);
@@ -468,6 +471,11 @@ int ensure_flood_areas(cimbar_hip_ctx* ctx, int count)
 }
 
 constexpr int K1_TALL_MIN = 256;   // frames: 16 tall strips x 256 = 4 096 wavefronts, more than the 3 072 the chip holds
+// erasures per retried block: the setting, or the default RS_PARITY - 8 (at most 4 errors beside them; DESIGN_WIDENING.md "Erasure decoding":
+// with 2 the decoder accepts a wrong codeword for about one garbage block in eight)
+constexpr int ERASURE_MAX_DEFAULT = RS_PARITY - 8;
+inline int erasure_max(const cimbar_hip_ctx* ctx) { return ctx->er_max < 0 ? ERASURE_MAX_DEFAULT : ctx->er_max; }
+
 int enqueue(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_rgb, int n, int pre, int cc, uint8_t* d_chunks, uint32_t* d_masks, int plain = 0,
             bool pipe = false, const int* d_sel = nullptr, int sel_stride = 0)
 {
@@ -611,6 +619,11 @@ int enqueue(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_rgb, int n, in
 		// (split chain: the carry is written by k_carry_out after the join -- an earlier part's colour pass may still be reading the old one)
 		if (!(ctx->dbg_skip & 64)) hipLaunchKernelGGL(k_frame_end, dim3(m), dim3(64), 0, s, ctx->d_rs_ok, ctx->d_states, d_chunks, d_masks, ctx->d_ccm_used, ctx->d_carry, fa,
 		                   (!split && fa + m == n) ? 1 : 0, plain);
+		// opt-in erasure retry of the symbol chunks the mask lacks (erasure.hip.inc); reads the frame's own intermediates only, writes its
+		// chunks and mask: the same stream, after k_frame_end, in every chain shape (split halves, pipelined sets)
+		if (!LEGACY && !plain && ctx->er_sym > 0)
+			hipLaunchKernelGGL(k_erasure_frame, dim3(m), dim3(256), 0, s, ctx->d_plane, ctx->tb, ctx->d_symbols, ctx->d_drift, ctx->d_flood, ctx->d_rs_ok,
+			                   d_chunks, d_masks, fa, ctx->er_sym, erasure_max(ctx));
 		return s == st ? mark() : hipSuccess;
 	};
 	if (pipe) {
@@ -878,6 +891,7 @@ int64_t cimbar_hip_decode_plain_batch(cimbar_hip_ctx* ctx, const uint8_t* rgb, i
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;
 	if (!rgb || !bytes || n <= 0) { ctx->err = "decode_plain_batch: null buffer or n <= 0"; return CIMBAR_HIP_EINVAL; }
+	if (ctx->er_sym > 0) { ctx->err = "decode_plain_batch: erasure decoding is on (cimbar_hip_set_erasure_decode); the plain stream has no chunk mask to extend"; return CIMBAR_HIP_EINVAL; }
 	if ((rgb_mem != CIMBAR_HIP_MEM_HOST && rgb_mem != CIMBAR_HIP_MEM_DEVICE) || (out_mem != CIMBAR_HIP_MEM_HOST && out_mem != CIMBAR_HIP_MEM_DEVICE)) {
 		ctx->err = "decode_plain_batch: rgb_mem / out_mem must be CIMBAR_HIP_MEM_HOST or CIMBAR_HIP_MEM_DEVICE";
 		return CIMBAR_HIP_EINVAL;
@@ -1479,6 +1493,66 @@ int cimbar_hip_encode_batch(cimbar_hip_ctx* ctx, const uint8_t* payload, int n, 
 		HIPCHK(hipMemcpyAsync(rgb_out, d_out, (size_t)n * FRAME_RGB, hipMemcpyDeviceToHost, st));
 		HIPCHK(hipStreamSynchronize(st));
 	}
+	return 0;
+}
+
+int cimbar_hip_set_erasure_decode(cimbar_hip_ctx* ctx, int sym_distance, int colour_margin, int max_erasures)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	if (LEGACY && sym_distance > 0) { ctx->err = "set_erasure_decode: modes 4 and 8 carry one coupled stream; erasure decoding covers the symbol blocks of modes 68 / 67 / 66"; return CIMBAR_HIP_EINVAL; }
+	if (sym_distance > 64 || max_erasures > RS_PARITY) { ctx->err = "set_erasure_decode: sym_distance <= 64, max_erasures <= the parity bytes"; return CIMBAR_HIP_EINVAL; }
+	// (read when a batch is enqueued: batches already issued keep the setting they were issued with)
+	ctx->er_sym = sym_distance > 0 ? sym_distance : 0;
+	ctx->er_col = colour_margin < 0 ? -1 : colour_margin;
+	ctx->er_max = max_erasures < 0 ? -1 : max_erasures;
+	return 0;
+}
+
+int cimbar_hip_get_erasure_decode(cimbar_hip_ctx* ctx, int* sym_distance, int* colour_margin, int* max_erasures)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	if (sym_distance) *sym_distance = ctx->er_sym;
+	if (colour_margin) *colour_margin = ctx->er_col;
+	if (max_erasures) *max_erasures = erasure_max(ctx);
+	return ctx->er_sym > 0 ? 1 : 0;
+}
+
+int cimbar_hip_rs_decode_erasures(cimbar_hip_ctx* ctx, const uint8_t* blocks, int n, const uint8_t* erasures, const uint8_t* counts, int mem,
+                                  uint8_t* msgs, int8_t* status, void* hip_stream)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	if (!blocks || !erasures || !counts || !msgs || !status || n <= 0) { ctx->err = "rs_decode_erasures: null buffer or n <= 0"; return CIMBAR_HIP_EINVAL; }
+	if (mem != CIMBAR_HIP_MEM_HOST && mem != CIMBAR_HIP_MEM_DEVICE) { ctx->err = "rs_decode_erasures: mem must be CIMBAR_HIP_MEM_HOST or CIMBAR_HIP_MEM_DEVICE"; return CIMBAR_HIP_EINVAL; }
+	HIPCHK(hipSetDevice(ctx->device));
+	const unsigned grid = (unsigned)((n + 3) / 4);
+	if (mem == CIMBAR_HIP_MEM_DEVICE) {   // stream-ordered on the caller's stream (the null stream by default); nothing waits
+		hipLaunchKernelGGL(k_rs_erasures, dim3(grid), dim3(256), 0, (hipStream_t)hip_stream, blocks, n, erasures, counts, msgs, status);
+		HIPCHK(hipGetLastError());
+		return 0;
+	}
+	// host memory: staged through a context-owned device buffer (grown on demand, kept), synchronous. A NULL stream is the context's own
+	// stream here, the null stream for device memory: the convention of cimbar_hip_encode_batch / cimbar_hip_decode_batch.
+	hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+	const size_t nb = (size_t)n * RS_BLOCK, nm = (size_t)n * RS_DATA, need = 2 * nb + 2 * (size_t)n + nm;
+	if (need > ctx->d_er_cap) {
+		HIPCHK(hipStreamSynchronize(st));   // (a previous call's copies on another stream are complete: every host-memory call synchronises)
+		HIPCHK(regrow(ctx->d_er_buf, need));
+		ctx->d_er_cap = need;
+	}
+	uint8_t* d = ctx->d_er_buf;
+	uint8_t *d_blocks = d, *d_er = d + nb, *d_counts = d + 2 * nb, *d_msgs = d_counts + n;
+	int8_t* d_status = reinterpret_cast<int8_t*>(d_msgs + nm);
+	hipError_t e = hipMemcpyAsync(d_blocks, blocks, nb, hipMemcpyHostToDevice, st);
+	if (e == hipSuccess) e = hipMemcpyAsync(d_er, erasures, nb, hipMemcpyHostToDevice, st);
+	if (e == hipSuccess) e = hipMemcpyAsync(d_counts, counts, (size_t)n, hipMemcpyHostToDevice, st);
+	if (e == hipSuccess) {
+		hipLaunchKernelGGL(k_rs_erasures, dim3(grid), dim3(256), 0, st, d_blocks, n, d_er, d_counts, d_msgs, d_status);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = hipMemcpyAsync(msgs, d_msgs, nm, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipMemcpyAsync(status, d_status, (size_t)n, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipStreamSynchronize(st);
+	HIPCHK(e);
 	return 0;
 }
 

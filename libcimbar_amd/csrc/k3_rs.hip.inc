@@ -37,10 +37,11 @@ struct RsShared {
 	uint8_t last[4][RS_POLY];
 };
 
-__device__ __forceinline__ uint8_t gf_mul(const RsShared& s, uint8_t l, uint8_t r) { return (!l || !r) ? 0 : s.exp[(unsigned)s.log[l] + s.log[r]]; }
-__device__ __forceinline__ uint8_t gf_div(const RsShared& s, uint8_t l, uint8_t r) { return (!l || !r) ? 0 : s.exp[255u + s.log[l] - s.log[r]]; }
+// (templates over the LDS layout: k_rs_erasures' RsEraShared holds the same exp / log tables -- erasure.hip.inc)
+template <class S> __device__ __forceinline__ uint8_t gf_mul(const S& s, uint8_t l, uint8_t r) { return (!l || !r) ? 0 : s.exp[(unsigned)s.log[l] + s.log[r]]; }
+template <class S> __device__ __forceinline__ uint8_t gf_div(const S& s, uint8_t l, uint8_t r) { return (!l || !r) ? 0 : s.exp[255u + s.log[l] - s.log[r]]; }
 // value of sum_i coef[i] * e^i for i <= order (polynomial.c:113-131 with element_exp rows = successive powers of e), e != 0
-__device__ __forceinline__ uint8_t gf_eval(const RsShared& s, const uint8_t* coef, int order, uint8_t e)
+template <class S> __device__ __forceinline__ uint8_t gf_eval(const S& s, const uint8_t* coef, int order, uint8_t e)
 {
 	unsigned le = s.log[e] % 255u, acc = 0;   // log[1] == 255 -> 0
 	uint8_t res = 0;

@@ -34,6 +34,7 @@ EXPORTS = (
     "cimbar_hip_capture_bytes", "cimbar_hip_scan_preprocess_fmt", "cimbar_hip_deskew_batch_fmt", "cimbar_hip_extract_batch_fmt",
     "cimbar_hip_scan_extract_decode_batch_fmt",
     "cimbar_hip_undistort_calibrate_fmt", "cimbar_hip_undistort_batch_fmt", "cimbar_hip_scan_undistort_extract_decode_batch_fmt",
+    "cimbar_hip_rs_decode_erasures", "cimbar_hip_set_erasure_decode", "cimbar_hip_get_erasure_decode",
 )
 PNG_EHEADER, PNG_ESTREAM, PNG_ECODES, PNG_ESIZE, PNG_ECHECK = -30, -31, -32, -33, -34
 
@@ -136,6 +137,12 @@ def load_library(path=None):
     lib.cimbar_hip_get_ccm.restype = i32
     lib.cimbar_hip_set_ccm.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
     lib.cimbar_hip_set_ccm.restype = i32
+    lib.cimbar_hip_rs_decode_erasures.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp]
+    lib.cimbar_hip_rs_decode_erasures.restype = i32
+    lib.cimbar_hip_set_erasure_decode.argtypes = [vp, i32, i32, i32]
+    lib.cimbar_hip_set_erasure_decode.restype = i32
+    lib.cimbar_hip_get_erasure_decode.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    lib.cimbar_hip_get_erasure_decode.restype = i32
     lib.cimbar_hip_mode_bufsize.argtypes = [i32]
     lib.cimbar_hip_mode_bufsize.restype = i32
     lib.cimbar_hip_ctx_bufsize.argtypes = [vp]
@@ -585,6 +592,48 @@ class HipDecoder:
         """CimbDecoder::update_color_correction: the carried matrix becomes `m` (3x3) and is active from the next frame on"""
         arr = (ctypes.c_float * 9)(*[float(x) for x in np.asarray(m, dtype=np.float32).reshape(-1)])
         self._check(self._lib.cimbar_hip_set_ccm(self._ctx, arr), "cimbar_hip_set_ccm")
+
+    def set_erasure_decode(self, sym_distance, colour_margin=-1, max_erasures=-1):
+        """cimbar_hip_set_erasure_decode: sym_distance <= 0 turns erasure decoding off; max_erasures < 0 = parity - 8"""
+        self._check(self._lib.cimbar_hip_set_erasure_decode(self._ctx, int(sym_distance), int(colour_margin), int(max_erasures)),
+                    "cimbar_hip_set_erasure_decode")
+
+    def get_erasure_decode(self):
+        """(on, sym_distance, colour_margin, max_erasures)"""
+        a, b, c = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        rc = self._check(self._lib.cimbar_hip_get_erasure_decode(self._ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)),
+                         "cimbar_hip_get_erasure_decode")
+        return bool(rc), a.value, b.value, c.value
+
+    def rs_decode_erasures(self, blocks, erasures):
+        """Errors-and-erasures Reed-Solomon decode of caller-given blocks of this mode's code (cimbar_hip_rs_decode_erasures).
+        blocks: (n, RS_BLOCK) uint8; erasures: a list of n sequences of byte positions (at most RS_BLOCK each, any count: more than
+        RS_PARITY fails the block). Returns (msgs (n, RS_DATA) uint8, status (n,) int8: -1 libcorrect fails, 0 rejected, 1 accepted)."""
+        g = self.geo
+        blocks = np.ascontiguousarray(blocks, dtype=np.uint8).reshape(-1, g.RS_BLOCK)
+        n = blocks.shape[0]
+        if len(erasures) != n:
+            raise ValueError("one erasure list per block")
+        er = np.zeros((n, g.RS_BLOCK), np.uint8)
+        counts = np.zeros(n, np.uint8)
+        for b, pos in enumerate(erasures):
+            pos = np.asarray(pos, dtype=np.int64).reshape(-1)
+            if len(pos) > g.RS_BLOCK or (len(pos) and (pos.min() < 0 or pos.max() >= g.RS_BLOCK)):
+                raise ValueError(f"block {b}: at most {g.RS_BLOCK} erasure positions, each < {g.RS_BLOCK}")
+            er[b, :len(pos)] = pos
+            counts[b] = len(pos)
+        msgs = np.zeros((n, g.RS_DATA), np.uint8)
+        status = np.zeros(n, np.int8)
+        self._check(self._lib.cimbar_hip_rs_decode_erasures(self._ctx, blocks.ctypes.data, n, er.ctypes.data, counts.ctypes.data, MEM_HOST,
+                                                            msgs.ctypes.data, status.ctypes.data, None), "cimbar_hip_rs_decode_erasures")
+        return msgs, status
+
+    def rs_decode_erasures_device(self, blocks_ptr, n, erasures_ptr, counts_ptr, msgs_ptr, status_ptr, stream=None):
+        """Device pointers in and out (layouts as in include/cimbar_hip.h); asynchronous on `stream` (None / 0 = the null stream)."""
+        self._check(self._lib.cimbar_hip_rs_decode_erasures(self._ctx, ctypes.c_void_p(blocks_ptr), int(n), ctypes.c_void_p(erasures_ptr),
+                                                            ctypes.c_void_p(counts_ptr), MEM_DEVICE, ctypes.c_void_p(msgs_ptr),
+                                                            ctypes.c_void_p(status_ptr), ctypes.c_void_p(stream) if stream else None),
+                    "cimbar_hip_rs_decode_erasures(device)")
 
     def bufsize(self):
         """cimbard_get_bufsize() of this context's configuration"""
