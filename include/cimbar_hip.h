@@ -202,6 +202,44 @@ int cimbar_hip_get_erasure_decode(cimbar_hip_ctx* ctx, int* sym_distance, int* c
 int cimbar_hip_rs_decode_erasures(cimbar_hip_ctx* ctx, const uint8_t* blocks, int n, const uint8_t* erasures, const uint8_t* counts, int mem,
                                   uint8_t* msgs, int8_t* status, void* hip_stream);
 
+/* Multi-capture decoding. A camera captures each displayed frame several times; glare, blur and focus hit different cells in each capture.
+ * These calls decode a batch capture by capture exactly as cimbar_hip_decode_batch / cimbar_hip_scan_extract_decode_batch_fmt do (chunks,
+ * masks and status equal theirs for the same input and context settings, the colour-correction carry included), then decode every run of
+ * captures of one frame (a "group") once more from the cells of all its members together.
+ *   grouping     groups_in == NULL: agree(k, k+1) = the cells whose symbol and colour are both equal in captures k and k+1. Walking left to
+ *                right, capture k starts a new group when it is the first, when agree(k-1, k) * 1000 < min_agree_permille * cells, when the
+ *                previous group already has max_group members, or when capture k-1 or k is unusable (capture path: its extraction failed).
+ *                Unusable captures are in no group (-1); groups are numbered 0, 1, ... in capture order; groups never span two calls.
+ *                groups_in != NULL (host memory, n ints): the caller's groups -- each -1 or an id, ids starting at 0 and rising by one, each
+ *                id's captures contiguous and at most max_group; anything else is CIMBAR_HIP_EINVAL. On the capture path a capture whose
+ *                extraction failed is left out of its group (and reported -1); a group left without members delivers nothing.
+ *   min_agree_permille <= 0: 750 (a torn capture, half one frame and half the next, joins neither neighbour; two different frames agree on
+ *                about 1/64 of the cells in mode 68). max_group <= 0: 4; above 8: CIMBAR_HIP_EINVAL.
+ *   combined cells  per cell, over the members c with decisions s_c / col_c and d_c(t) = popcount(H_c ^ tile t), H_c the cell's 8x8 hash in
+ *                member c's bit plane at its final position: the symbol is kept where all s_c agree, else argmin_t sum_c (2 d_c(t) - [t == s_c])
+ *                (ties: lowest t; margin = second-lowest score - lowest); the colour is the plurality of col_c, a tie going to the colour of the
+ *                tied member with the smallest d_c(symbol), then the lowest member index. A group of one capture, or of identical ones,
+ *                reproduces that capture's cells.
+ *   group decode the combined cells go through the same Reed-Solomon decode and chunk delivery as one frame (modes 4 / 8: the coupled
+ *                stream); no colour-correction matrix is derived, read or carried. Group chunk j = the combined decode's chunk j where it
+ *                delivered it, else chunk j of the lowest-index member that delivered it; gmask = the combined mask | the members' masks.
+ *                With erasure decoding on (cimbar_hip_set_erasure_decode, modes 68 / 67 / 66) the symbol chunks still missing are retried
+ *                with the stream bytes of symbol-disputed cells as erasures (smallest margin first, then stream position, at most
+ *                max_erasures per block), accepted as in the per-capture retry; colour chunks are not retried.
+ *   chunks / masks / status  per capture, as for the plain call; groups_out: n ints (may be NULL)
+ *   gchunks / gmasks         n slots of 12 * 625 bytes / one mask; slots at or above the group count are zero
+ *   n_groups                 the group count (may be NULL)
+ * Every output follows out_mem. Host outputs: synchronises and returns the group count. Device outputs: enqueues only (the grouping runs on
+ * the device; nothing waits), writes the count to device memory and returns 0. Buffers, stream and errors as for cimbar_hip_decode_batch. */
+int64_t cimbar_hip_decode_batch_combined(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rgb_mem, int should_preprocess, int color_correction,
+                                         const int* groups_in, int min_agree_permille, int max_group, uint8_t* chunks, uint32_t* masks,
+                                         int* groups_out, uint8_t* gchunks, uint32_t* gmasks, int* n_groups, int out_mem, void* hip_stream);
+int64_t cimbar_hip_scan_extract_decode_batch_combined_fmt(cimbar_hip_ctx* ctx, const uint8_t* img, unsigned width, unsigned height, int format, int n,
+                                                          int img_mem, int preprocess, int color_correction, const int* groups_in,
+                                                          int min_agree_permille, int max_group, uint8_t* chunks, uint32_t* masks, int* status,
+                                                          int* groups_out, uint8_t* gchunks, uint32_t* gmasks, int* n_groups, int out_mem,
+                                                          void* hip_stream);
+
 /* ---- the encode half ("next" row of the scope table: on-device frame synthesiser) --------------------------------------------
  * Encoder::encode_next (src/lib/encoder/Encoder.h:69-129) for n frames at once: each frame takes 7500 payload bytes (the 60
  * reads of 125 bytes a fountain_encoder_stream / ifstream would have served), RS(155,125)-encodes them (libcorrect encode.c:3-34),
@@ -403,10 +441,15 @@ enum {
 	                                  run: after a batch where it certified fewer than one in sixteen of the frames it was given, the next fifteen
 	                                  batches go straight to the exact replay (CIMBAR_HIP_FLOOD_WAVE_ADAPT=0 at cimbar_hip_create: never skip).
 	                                  Which pass produced a frame's symbols never changes them */
-	CIMBAR_HIP_TAP_FLOOD_VERIFY = 9 /* n u32          : with CIMBAR_HIP_FLOOD_VERIFY=1 in the environment at cimbar_hip_create, every frame the batch-parallel
+	CIMBAR_HIP_TAP_FLOOD_VERIFY = 9, /* n u32         : with CIMBAR_HIP_FLOOD_VERIFY=1 in the environment at cimbar_hip_create, every frame the batch-parallel
 	                                  flood certified is ALSO replayed exactly and compared: cells whose symbol or drifted position differed
 	                                  (0 = the certificate held; the exact result is what the decode used either way); 0xFFFFFFFF for frames
 	                                  that were not certified, or when the mode is off. The context prints the totals to stderr at destroy. */
+	/* the group decode of the last batch, when it was a combined one (cimbar_hip_decode_batch_combined / _scan_extract_decode_batch_combined_fmt;
+	 * CIMBAR_HIP_EINVAL after any other batch). The taps above keep describing that batch's per-capture decode. */
+	CIMBAR_HIP_TAP_GROUP_CELLS = 10,  /* n_groups * cells bytes: the group's combined cell, colour << 4 | symbol */
+	CIMBAR_HIP_TAP_GROUP_MARGIN = 11, /* n_groups * cells u16  : the symbol's margin, 0xFFFF where the members' symbols agree */
+	CIMBAR_HIP_TAP_GROUPS = 12        /* n int32               : the group of every capture, -1 for none */
 };
 int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_bytes);
 

@@ -1,0 +1,394 @@
+// combine.hip.inc -- part of cimbar_hip.hip (one translation unit; included inside its anonymous namespace, after k4_frame.hip.inc).
+// G1-G4: multi-capture decoding -- consecutive captures of one displayed frame decoded once more from the cells of all of them
+// ------------------------------------------------------------------------------------------------ grouping and combined cells
+// A batch is decoded capture by capture first (enqueue(), unchanged). Then:
+//   G1 k_group_agree   agree(k, k+1) = cells whose symbol AND colour are equal in captures k and k+1, one workgroup per pair
+//   G2 k_group_walk    one wavefront walks the captures left to right and numbers the runs ("groups"), or takes the caller's numbering; it
+//                      writes every group's members (capture indices, ascending, at most GMAX) and the group count to device memory
+//   G3 k_group_cells   per group and cell: the combined symbol, colour and margin (the rule below); unanimous cells cost one compare
+//   K3 k_rs            the same Reed-Solomon kernels as a capture's decode, over the groups' cells (LIVE: workgroups past the count return,
+//                      and so does every wavefront of a group whose members agree on every cell -- see k_group_end)
+//   G4 k_group_end     the aligned_stream bookkeeping of k_frame_mid + k_frame_end over the group's blocks, the members' chunks for what the
+//                      combined decode did not deliver, and (erasure decoding on) the erasure retry of the symbol chunks still missing
+// Every kernel after G2 is launched for n captures' worth of groups and returns at once at or above the device-side group count, so nothing
+// here waits for the host.
+constexpr int GMAX = 8;                    // captures per group at most (the max_group argument is <= this)
+constexpr int GROUP_MAX_DEFAULT = 4, GROUP_AGREE_DEFAULT = 750;
+constexpr uint16_t MARGIN_NONE = 0xFFFFu;  // the symbol of the cell is not disputed
+static_assert(NCELLS % 4 == 0, "a frame's cells are whole dwords");
+
+// G1: one workgroup per pair (k, k+1), k < n - 1
+__global__ __launch_bounds__(256) void k_group_agree(const uint8_t* __restrict__ symbols, const uint8_t* __restrict__ colors, int n,
+                                                     uint32_t* __restrict__ agree)
+{
+	const int k = blockIdx.x;
+	if (k + 1 >= n) return;
+	const uint32_t* s0 = reinterpret_cast<const uint32_t*>(symbols + (size_t)k * NCELLS);
+	const uint32_t* c0 = reinterpret_cast<const uint32_t*>(colors + (size_t)k * NCELLS);
+	constexpr int W = NCELLS / 4;
+	constexpr uint32_t CM = 0x01010101u * (uint32_t)(NCOLORS - 1);
+	uint32_t cnt = 0;
+	for (int w = threadIdx.x; w < W; w += 256) {
+		const uint32_t x = ((s0[w] ^ s0[W + w]) & 0x0F0F0F0Fu) | ((c0[w] ^ c0[W + w]) & CM);
+		cnt += ((x & 0xFFu) == 0u) + ((x & 0xFF00u) == 0u) + ((x & 0xFF0000u) == 0u) + ((x >> 24) == 0u);
+	}
+	for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o);
+	__shared__ uint32_t s_part[4];
+	if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = cnt;
+	__syncthreads();
+	if (threadIdx.x == 0) agree[k] = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+}
+
+// G2: one wavefront, 64 captures per step, everything carried in registers from step to step.
+//  * usable: status == nullptr, or the capture's extraction status > 0
+//  * groups_in == nullptr: capture k starts a group when it is usable and it is the first capture, or capture k - 1 is unusable, or
+//    agree(k - 1, k) * 1000 < min_agree * NCELLS, or the group before already has max_group members; an unusable capture is in no group
+//  * groups_in != nullptr (validated by the host: -1 or ids from 0 rising by one, each id contiguous, at most max_group captures each): the
+//    ids as given, except that an unusable capture is left out of its group
+// groups[k] = the group of capture k or -1; gmem[g * GMAX + r] = the r-th member of group g; gcount[g] (zeroed by the host) = its members;
+// *ngroups = the highest id + 1.
+__global__ __launch_bounds__(64) void k_group_walk(const uint32_t* __restrict__ agree, int n, const int* __restrict__ status, int stride,
+                                                   const int* __restrict__ groups_in, int min_agree, int max_group, int* __restrict__ groups,
+                                                   int* __restrict__ gmem, int* __restrict__ gcount, int* __restrict__ ngroups)
+{
+	const int lane = threadIdx.x;
+	const unsigned long long below = (1ull << lane) - 1ull, upto = below | (1ull << lane);
+	int run_carry = 0, starts_carry = 0, mem_carry = 0, base_carry = 0, prev_id = -1, top = -1;
+	bool prev_u = false;
+	// (each step's loads are issued one step ahead: the walk is otherwise one dependent global load per 64 captures)
+	auto fetch = [&](int k, uint32_t& a, int& st, int& gi) {
+		a = (!groups_in && k > 0 && k < n) ? agree[k - 1] : 0u;
+		st = (status && k < n) ? status[(size_t)k * stride] : 1;
+		gi = (groups_in && k < n) ? groups_in[k] : -1;
+	};
+	uint32_t a_cur; int st_cur, gi_cur;
+	fetch(lane, a_cur, st_cur, gi_cur);
+	for (int k0 = 0; k0 < n; k0 += 64) {
+		const int k = k0 + lane;
+		uint32_t a_nxt; int st_nxt, gi_nxt;
+		fetch(k + 64, a_nxt, st_nxt, gi_nxt);
+		const bool in = k < n;
+		const bool u = in && st_cur > 0;
+		const unsigned long long ub = __ballot(u);
+		const bool u_prev = lane == 0 ? prev_u : ((ub >> (lane - 1)) & 1ull) != 0;
+		int id;
+		if (groups_in) id = in ? gi_cur : -1;
+		else {
+			const bool brk = in && (k == 0 || !u_prev || (unsigned long long)a_cur * 1000ull < (unsigned long long)min_agree * NCELLS);
+			const unsigned long long bb = __ballot(brk) & upto;
+			const int run = bb ? k0 + 63 - __clzll(bb) : run_carry;          // the latest break at or before k
+			const bool start = u && (k - run) % max_group == 0;
+			const unsigned long long sb = __ballot(start);
+			id = u ? starts_carry + (int)__popcll(sb & upto) - 1 : -1;
+			run_carry = __shfl(run, 63);
+			starts_carry += (int)__popcll(sb);
+		}
+		const int id_prev_lane = __shfl(id, lane > 0 ? lane - 1 : 0);
+		const int id_prev = lane == 0 ? prev_id : id_prev_lane;
+		const bool head = id >= 0 && (k == 0 || id_prev != id);
+		const bool member = id >= 0 && u;
+		const unsigned long long mb = __ballot(member), hb = __ballot(head) & upto;
+		const int before = mem_carry + (int)__popcll(mb & below);           // members of the batch in front of capture k
+		const int hl = hb ? 63 - __clzll(hb) : lane;
+		const int at_head = __shfl(before, hl);
+		const int base = hb ? at_head : base_carry;                          // members in front of k's group
+		if (in) groups[k] = member ? id : -1;
+		if (member) {
+			gmem[(size_t)id * GMAX + (before - base)] = k;
+			atomicAdd(&gcount[id], 1);
+		}
+		top = id > top ? id : top;
+		prev_id = __shfl(id, 63);
+		prev_u = __shfl((int)u, 63) != 0;
+		mem_carry += (int)__popcll(mb);
+		base_carry = __shfl(base, 63);
+		a_cur = a_nxt; st_cur = st_nxt; gi_cur = gi_nxt;
+	}
+	for (int o = 32; o >= 1; o >>= 1) { const int t = __shfl_xor(top, o); top = t > top ? t : top; }
+	if (lane == 0) *ngroups = top + 1;
+}
+
+// G3: the combined cells of group blockIdx.y, GC_CELLS cells per workgroup. For cell i with members c (decisions s_c, col_c) and
+// d_c(t) = popcount(H_c(i) ^ tile t), H_c(i) = the 8x8 hash of member c's bit plane at its final position (k_erasure_frame's window):
+//   symbol  all s_c equal: kept, margin MARGIN_NONE. Otherwise argmin_t sum_c (2 d_c(t) - [t == s_c]), ties to the lowest t; margin = the
+//           second-lowest score minus the lowest
+//   colour  the plurality of col_c; on a tie, the colour of the member whose colour is among the tied ones and whose d_c(symbol) is smallest,
+//           then the lowest member index
+// Phase 1 settles every cell whose symbols agree and whose colour vote has one winner (no hash needed); the rest are queued per wavefront
+// and phase 2 gives each of them a lane of its own: the cost grows with the disputed cells only.
+constexpr int GC_CELLS = 1024, GC_BLOCKS = (NCELLS + GC_CELLS - 1) / GC_CELLS;
+__global__ __launch_bounds__(256) void k_group_cells(const uint32_t* __restrict__ plane, Tables tb, const uint8_t* __restrict__ symbols,
+                                                     const uint8_t* __restrict__ colors, const int8_t* __restrict__ drift,
+                                                     const uint32_t* __restrict__ flood_flag, const int* __restrict__ gmem,
+                                                     const int* __restrict__ gcount, const int* __restrict__ ngroups, uint8_t* __restrict__ gsym,
+                                                     uint8_t* __restrict__ gcol, uint16_t* __restrict__ gmargin, uint32_t* __restrict__ gdisp)
+{
+	const int g = blockIdx.y;
+	if (g >= *ngroups) return;
+	__shared__ int s_mem[GMAX];
+	__shared__ uint32_t s_flood[GMAX];
+	__shared__ uint16_t s_q[4][GC_CELLS / 4];
+	const int m = gcount[g];
+	if (threadIdx.x < GMAX) {
+		const int f = (int)threadIdx.x < m ? gmem[(size_t)g * GMAX + threadIdx.x] : 0;
+		s_mem[threadIdx.x] = f;
+		s_flood[threadIdx.x] = (int)threadIdx.x < m ? flood_flag[f] : 0u;
+	}
+	__syncthreads();
+	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+	uint8_t* os = gsym + (size_t)g * NCELLS;
+	uint8_t* oc = gcol + (size_t)g * NCELLS;
+	uint16_t* om = gmargin + (size_t)g * NCELLS;
+	// phase 1
+	int qn = 0;
+	bool differ = false;
+#pragma unroll
+	for (int r = 0; r < GC_CELLS / 256; ++r) {
+		const int i = blockIdx.x * GC_CELLS + r * 256 + (int)threadIdx.x;
+		bool need = false;
+		if (i < NCELLS) {
+			uint32_t sy[GMAX], co[GMAX];
+			bool sym_eq = true;
+#pragma unroll
+			for (int c = 0; c < GMAX; ++c) {
+				sy[c] = c < m ? symbols[(size_t)s_mem[c] * NCELLS + i] & 15u : 0u;
+				co[c] = c < m ? colors[(size_t)s_mem[c] * NCELLS + i] : 0u;
+				sym_eq = sym_eq && (c >= m || sy[c] == sy[0]);
+			}
+			// plurality: the first member's colour among those with the most votes, and whether another colour has as many
+			int best = 0;
+			uint32_t win = co[0];
+			bool tie = false;
+#pragma unroll
+			for (int c = 0; c < GMAX; ++c) {
+				int v = 0;
+#pragma unroll
+				for (int q = 0; q < GMAX; ++q) v += (c < m && q < m && co[q] == co[c]) ? 1 : 0;
+				if (c < m) {
+					if (v > best) { best = v; win = co[c]; tie = false; }
+					else if (v == best && co[c] != win) tie = true;
+				}
+			}
+			need = m > 1 && (!sym_eq || tie);
+			differ = differ || !sym_eq || best != m;
+			if (!need) {
+				os[i] = (uint8_t)sy[0];
+				oc[i] = (uint8_t)win;
+				om[i] = MARGIN_NONE;
+			}
+		}
+		const unsigned long long qb = __ballot(need);
+		if (need) s_q[wv][qn + (int)__popcll(qb & ((1ull << lane) - 1ull))] = (uint16_t)i;
+		qn += (int)__popcll(qb);
+	}
+	if (__ballot(differ) && lane == 0) gdisp[g] = 1u;   // (zeroed by the host; every writer writes 1)
+	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+	__builtin_amdgcn_wave_barrier();
+	// phase 2: one disputed cell per lane
+	for (int q = lane; q < qn; q += 64) {
+		const int i = s_q[wv][q];
+		const ushort2 xy = tb.cell_xy[i];
+		uint64_t H[GMAX];
+		uint32_t sy[GMAX], co[GMAX];
+		int score[16];
+#pragma unroll
+		for (int t = 0; t < 16; ++t) score[t] = 0;
+		bool sym_eq = true;
+#pragma unroll
+		for (int c = 0; c < GMAX; ++c) {
+			H[c] = 0;
+			sy[c] = co[c] = 0;
+			if (c < m) {
+				const int f = s_mem[c];
+				sy[c] = symbols[(size_t)f * NCELLS + i] & 15u;
+				co[c] = colors[(size_t)f * NCELLS + i];
+				const bool flooded = s_flood[c] != 0;
+				const int dx = flooded ? drift[((size_t)f * NCELLS + i) * 2] : 0, dy = flooded ? drift[((size_t)f * NCELLS + i) * 2 + 1] : 0;
+				uint32_t rows[10];
+				window_rows(plane + (size_t)f * PLANE_WORDS, (int)xy.x + dx - 1, (int)xy.y + dy - 1, rows);
+				H[c] = window_hash(rows, 4);
+#pragma unroll
+				for (int t = 0; t < 16; ++t) score[t] += 2 * (int)__popcll(H[c] ^ c_tile[t]) - (sy[c] == (uint32_t)t ? 1 : 0);
+				sym_eq = sym_eq && sy[c] == sy[0];
+			}
+		}
+		uint32_t s_hat = sy[0];
+		uint16_t margin = MARGIN_NONE;
+		if (!sym_eq) {
+			int lo = score[0], second = 0x7FFFFFFF;
+			s_hat = 0;
+#pragma unroll
+			for (int t = 1; t < 16; ++t) {
+				if (score[t] < lo) { second = lo; lo = score[t]; s_hat = (uint32_t)t; }
+				else if (score[t] < second) second = score[t];
+			}
+			margin = (uint16_t)(second - lo);
+		}
+		int best = 0, bd = 0x7FFFFFFF;
+		uint32_t win = co[0];
+		bool tie = false;
+		int votes[GMAX];
+#pragma unroll
+		for (int c = 0; c < GMAX; ++c) {
+			int v = 0;
+#pragma unroll
+			for (int q2 = 0; q2 < GMAX; ++q2) v += (c < m && q2 < m && co[q2] == co[c]) ? 1 : 0;
+			votes[c] = v;
+			if (c < m) {
+				if (v > best) { best = v; win = co[c]; tie = false; }
+				else if (v == best && co[c] != win) tie = true;
+			}
+		}
+		if (tie) {
+#pragma unroll
+			for (int c = 0; c < GMAX; ++c) {
+				const int d = (int)__popcll(H[c] ^ c_tile[s_hat]);
+				if (c < m && votes[c] == best && d < bd) { bd = d; win = co[c]; }
+			}
+		}
+		os[i] = (uint8_t)s_hat;
+		oc[i] = (uint8_t)win;
+		om[i] = margin;
+	}
+}
+
+// G4: one workgroup per group slot (n of them). A slot at or above the group count, or a group left without members, gets zero chunks and
+// mask 0. Otherwise:
+//   cmask  the aligned_stream bookkeeping over the combined decode's block flags, the symbol blocks then the colour blocks with one state
+//          (what k_frame_mid and k_frame_end do for one frame; legacy modes: the one coupled stream)
+//   chunk j of the group = the combined decode's chunk j where cmask has it, else member chunk j of the lowest-index member that delivered it
+//   e_on   (erasure decoding, modes 68 / 67 / 66): every block of a symbol chunk still missing is decoded again -- a block errors-only decoding
+//          accepted with no erasures, a failed block with the stream bytes of the symbol-disputed cells as erasures (smallest margin first,
+//          then stream position, at most e_max) -- and accepted as in k_erasure_frame (a codeword, nothing in the padding, and with erasures
+//          2 errors <= p - e - ERASURE_SLACK). A chunk whose blocks are all accepted joins the mask with its bytes.
+// gmask = cmask | the members' masks | the chunks the retry added; slots of chunks outside it are zero.
+__global__ __launch_bounds__(256) void k_group_end(const uint8_t* __restrict__ gsym, const uint16_t* __restrict__ gmargin, Tables tb,
+                                                   const int* __restrict__ gmem, const int* __restrict__ gcount, const int* __restrict__ ngroups,
+                                                   const uint8_t* __restrict__ grs_ok, const uint8_t* __restrict__ chunks,
+                                                   const uint32_t* __restrict__ masks, const uint32_t* __restrict__ gdisp, uint8_t* __restrict__ gchunks,
+                                                   uint32_t* __restrict__ gmasks, int e_on, int e_max)
+{
+	const int g = blockIdx.x;
+	uint8_t* gc = gchunks + (size_t)g * FRAME_BYTES;
+	const int m = g < *ngroups ? gcount[g] : 0;
+	if (m == 0) {
+		for (int k = threadIdx.x; k < FRAME_BYTES; k += 256) gc[k] = 0;
+		if (threadIdx.x == 0) gmasks[g] = 0;
+		return;
+	}
+	constexpr uint32_t FULL = (1u << CHUNKS) - 1u, SYM_MASK = LEGACY ? 0u : (1u << SYM_CHUNKS) - 1u;
+	__shared__ int s_mem[GMAX];
+	__shared__ uint32_t s_mmask[GMAX];
+	__shared__ uint32_t s_cmask, s_emask;
+	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+	if (threadIdx.x < GMAX) {
+		const int f = (int)threadIdx.x < m ? gmem[(size_t)g * GMAX + threadIdx.x] : 0;
+		s_mem[threadIdx.x] = f;
+		s_mmask[threadIdx.x] = (int)threadIdx.x < m ? masks[f] : 0u;
+	}
+	// a group whose members agree on every cell has each member's cells, so its combined decode is each member's errors-only decode (a
+	// subset of the member's mask, the same bytes) and the retry finds no disputed cell: the members' chunks are the whole answer, and the
+	// Reed-Solomon pass skipped it (k_rs LIVE)
+	const bool disp = gdisp[g] != 0;
+	if (threadIdx.x == 0) { s_cmask = 0; s_emask = 0; }
+	if (wv == 0 && disp) {
+		const uint8_t* ok = grs_ok + (size_t)g * ALL_BLOCKS;
+		static_assert(ALL_BLOCKS <= 128, "block flags fit two ballots");
+		const unsigned long long lo = __ballot(lane < ALL_BLOCKS && ok[lane < ALL_BLOCKS ? lane : 0] != 0);
+		const unsigned long long hi = ALL_BLOCKS > 64 ? __ballot(64 + lane < ALL_BLOCKS && ok[64 + lane < ALL_BLOCKS ? 64 + lane : 0] != 0) : 0ull;
+		if (lane == 0) {
+			FrameState st = {0, 0, 0, 0};
+			uint8_t hdr[6] = {0, 0, 0, 0, 0, 0};
+			unsigned radio = 0;
+			for (int b = 0; b < ALL_BLOCKS; ++b) aligner_block(st, b, (int)(((b < 64 ? lo : hi) >> (b & 63)) & 1ull), nullptr, false, hdr, radio);
+			s_cmask = st.mask;
+		}
+	}
+	__syncthreads();
+	const uint32_t cmask = s_cmask;
+	uint32_t mmask = 0;
+	for (int c = 0; c < m; ++c) mmask |= s_mmask[c];
+	if constexpr (!LEGACY) {
+		const uint32_t missing = SYM_MASK & ~(cmask | mmask);
+		if (e_on && disp && missing) {
+			__shared__ RsEraShared s;
+			__shared__ uint16_t s_key[4][192];
+			__shared__ uint8_t s_pos[4][64];
+			__shared__ int8_t s_st[SYM_BLOCKS];
+			er_tables(s);
+			const uint8_t* sym = gsym + (size_t)g * NCELLS;
+			const uint16_t* mg = gmargin + (size_t)g * NCELLS;
+			for (int b = wv; b < SYM_BLOCKS; b += 4) {
+				const int j = b / BLOCKS_PER_CHUNK;
+				if (!(missing & (1u << j))) continue;
+				const bool ok = grs_ok[(size_t)g * ALL_BLOCKS + b] != 0;
+				uint8_t* enc = s.enc[wv];
+				uint16_t* key = s_key[wv];
+				for (int k = lane; k < RS_BLOCK; k += 64) {
+					const int sidx = (RS_BLOCK * b + k) * 2;
+					const int c0 = tb.stream_cell[sidx], c1 = tb.stream_cell[sidx + 1];
+					enc[k] = (uint8_t)(((sym[c0] & 15u) << 4) | (sym[c1] & 15u));
+					const uint16_t m0 = mg[c0], m1 = mg[c1];
+					key[k] = m0 < m1 ? m0 : m1;
+				}
+				__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+				__builtin_amdgcn_wave_barrier();
+				int e = 0;
+				if (!ok) {
+					// rank of each flagged byte (a disputed cell) among the flagged ones: smaller margin first, then lower position
+					int mine = 0;
+					for (int k = lane; k < RS_BLOCK; k += 64) {
+						const int kk = key[k];
+						if (kk == MARGIN_NONE) continue;
+						int rank = 0;
+						for (int q = 0; q < RS_BLOCK; ++q) {
+							const int kq = key[q];
+							rank += (kq < kk || (kq == kk && q < k)) ? 1 : 0;
+						}
+						if (rank < e_max) { s_pos[wv][rank] = (uint8_t)k; ++mine; }
+					}
+					for (int o = 32; o >= 1; o >>= 1) mine += __shfl_xor(mine, o);
+					e = mine;
+					__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+					__builtin_amdgcn_wave_barrier();
+					if (e == 0) { if (lane == 0) s_st[b] = -2; continue; }
+				}
+				int nerr = 0;
+				int st = er_decode(s, wv, lane, e, s_pos[wv], &nerr);
+				if (st == 1 && e > 0 && 2 * nerr > RS_PARITY - e - ERASURE_SLACK) st = 0;
+				if (st == 1) {
+					uint8_t* dst = gc + (size_t)j * CHUNK + (size_t)(b % BLOCKS_PER_CHUNK) * RS_DATA;
+					for (int k = lane; k < RS_DATA; k += 64) dst[k] = enc[k];
+				}
+				if (lane == 0) s_st[b] = (int8_t)st;
+			}
+			__syncthreads();
+			if (threadIdx.x == 0) {
+				uint32_t em = 0;
+				for (int j = 0; j < SYM_CHUNKS; ++j) {
+					if (!(missing & (1u << j))) continue;
+					bool all = true;
+					for (int q = 0; q < BLOCKS_PER_CHUNK; ++q) all = all && s_st[j * BLOCKS_PER_CHUNK + q] == 1;
+					if (all) em |= 1u << j;
+				}
+				s_emask = em;
+			}
+			__syncthreads();
+		}
+	}
+	const uint32_t emask = s_emask;
+	for (int j = 0; j < CHUNKS; ++j) {
+		const uint32_t bit = 1u << j;
+		if (cmask & bit) continue;
+		uint8_t* dst = gc + (size_t)j * CHUNK;
+		if (mmask & bit) {
+			int c = 0;
+			while (!(s_mmask[c] & bit)) ++c;
+			const uint8_t* src = chunks + (size_t)s_mem[c] * FRAME_BYTES + (size_t)j * CHUNK;
+			for (int k = threadIdx.x; k < CHUNK; k += 256) dst[k] = src[k];
+		} else if (!(emask & bit)) {
+			for (int k = threadIdx.x; k < CHUNK; k += 256) dst[k] = 0;
+		}
+	}
+	if (threadIdx.x == 0) gmasks[g] = (cmask | mmask | emask) & FULL;
+}

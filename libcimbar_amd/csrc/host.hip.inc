@@ -13,6 +13,13 @@ struct cimbar_hip_ctx {
 	int er_sym = 0, er_col = -1, er_max = -1;   // cimbar_hip_set_erasure_decode: off while er_sym <= 0 (k_erasure_frame is then never launched)
 	uint8_t* d_er_buf = nullptr;                // cimbar_hip_rs_decode_erasures' staging for host-memory calls (grown on demand)
 	size_t d_er_cap = 0;
+	// the group decode (cimbar_hip_decode_batch_combined / _scan_extract_decode_batch_combined_fmt, combine.hip.inc): per capture slot, grown on demand
+	int grp_cap = 0;
+	bool grp_valid = false;                     // the last batch was a combined one (the group taps describe it)
+	uint8_t* d_gsym = nullptr; uint8_t* d_gcol = nullptr; uint16_t* d_gmargin = nullptr; uint8_t* d_grs_ok = nullptr;   // [n][NCELLS], [n][ALL_BLOCKS]
+	uint32_t* d_gagree = nullptr; uint32_t* d_gdisp = nullptr; int* d_groups = nullptr; int* d_gmem = nullptr; int* d_gcount = nullptr; int* d_groups_in = nullptr;
+	int* d_ngroups = nullptr;                   // 1 int
+	uint8_t* d_gchunks = nullptr; uint32_t* d_gmasks = nullptr;   // staging for host-memory group outputs
 	int wave_adapt = 1;               // CIMBAR_HIP_FLOOD_WAVE_ADAPT=0: run k_flood_wave in front of every exact replay, whatever it achieved before
 	bool wave_ran = false;            // k_flood_wave ran in the batch h_flagged describes
 	int wave_skip_left = 0;           // batches that still go straight to the exact replay (see enqueue)
@@ -397,6 +404,8 @@ void destroy_ctx(cimbar_hip_ctx* ctx)
 	}
 	auto fr = [](void* p) { if (p) (void)hipFree(p); };
 	fr(ctx->tb.cell_xy); fr(ctx->tb.stream_cell); fr(ctx->tb.cand); fr(ctx->tb.ccm_grid); fr(ctx->tb.cell_grid); fr(ctx->tb.grid_cell);
+	fr(ctx->d_gsym); fr(ctx->d_gcol); fr(ctx->d_gmargin); fr(ctx->d_grs_ok); fr(ctx->d_gagree); fr(ctx->d_gdisp); fr(ctx->d_groups); fr(ctx->d_gmem); fr(ctx->d_gcount);
+	fr(ctx->d_groups_in); fr(ctx->d_ngroups); fr(ctx->d_gchunks); fr(ctx->d_gmasks);
 	fr(ctx->d_template); fr(ctx->d_gen_log); fr(ctx->d_er_buf); fr(ctx->d_payload); fr(ctx->d_rgb); fr(ctx->d_plane); fr(ctx->d_cellmean); fr(ctx->d_symbols); fr(ctx->d_colors); fr(ctx->d_drift); fr(ctx->d_flood);
 	fr(ctx->d_rs_ok); fr(ctx->d_states); fr(ctx->d_ccm_frames); fr(ctx->d_ccm_used); fr(ctx->d_carry); fr(ctx->d_chunks);
 	fr(ctx->d_masks); fr(ctx->flood.heap); fr(ctx->flood.prio); fr(ctx->flood.next); fr(ctx->d_fw_queue); fr(ctx->d_vsym); fr(ctx->d_vdrift); fr(ctx->d_vflag); fr(ctx->d_vtotals);
@@ -479,6 +488,7 @@ inline int erasure_max(const cimbar_hip_ctx* ctx) { return ctx->er_max < 0 ? ERA
 int enqueue(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_rgb, int n, int pre, int cc, uint8_t* d_chunks, uint32_t* d_masks, int plain = 0,
             bool pipe = false, const int* d_sel = nullptr, int sel_stride = 0)
 {
+	ctx->grp_valid = false;   // (the group taps describe a combined batch only until the next batch of any kind)
 	const bool tm = ctx->timing && !pipe;
 	int evi = 0;
 	auto mark = [&]() -> hipError_t { return tm ? hipEventRecord(ctx->ev[evi++], st) : hipSuccess; };
@@ -806,15 +816,136 @@ int cimbar_hip_set_ccm(cimbar_hip_ctx* ctx, const float m9[9])
 	return 0;
 }
 
-int64_t cimbar_hip_decode_batch(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rgb_mem, int should_preprocess,
-                                int color_correction, uint8_t* chunks, uint32_t* masks, int out_mem, void* hip_stream)
+namespace {
+
+// what the combined entry points add to a batch decode (combine.hip.inc); the plain entry points pass none
+struct CombineArgs {
+	const int* groups_in;     // host memory, n ints, or nullptr: the device groups the captures
+	int min_agree, max_group; // resolved (750 / 4 for <= 0)
+	int* groups_out; uint8_t* gchunks; uint32_t* gmasks; int* n_groups;
+};
+
+// the argument checks of the combined entry points, before anything is enqueued
+int check_combine(cimbar_hip_ctx* ctx, const char* who, int n, CombineArgs& cb)
 {
-	if (!ctx) return CIMBAR_HIP_EINVAL;
-	if (!rgb || !chunks || !masks || n <= 0) { ctx->err = "decode_batch: null buffer or n <= 0"; return CIMBAR_HIP_EINVAL; }
+	if (!cb.gchunks || !cb.gmasks) { ctx->err = std::string(who) + ": null gchunks / gmasks"; return CIMBAR_HIP_EINVAL; }
+	if (cb.max_group > GMAX) { ctx->err = std::string(who) + ": max_group above 8"; return CIMBAR_HIP_EINVAL; }
+	if (cb.max_group <= 0) cb.max_group = GROUP_MAX_DEFAULT;
+	if (cb.min_agree <= 0) cb.min_agree = GROUP_AGREE_DEFAULT;
+	if (cb.groups_in) {
+		// -1 or an id; ids start at 0 and rise by one; each id's captures contiguous and at most max_group
+		int next = 0, cur = -1, cnt = 0;
+		for (int k = 0; k < n; ++k) {
+			const int v = cb.groups_in[k];
+			if (v == -1) { cur = -1; continue; }
+			if (v == cur) { if (++cnt > cb.max_group) { ctx->err = std::string(who) + ": groups_in: a group of more than max_group captures"; return CIMBAR_HIP_EINVAL; } continue; }
+			if (v != next) { ctx->err = std::string(who) + ": groups_in: ids must be -1 or start at 0, rise by one and be contiguous"; return CIMBAR_HIP_EINVAL; }
+			cur = v; cnt = 1; ++next;
+		}
+	}
+	return 0;
+}
+
+int ensure_group_capacity(cimbar_hip_ctx* ctx, int n)
+{
+	if (n <= ctx->grp_cap) return 0;
+	const size_t N = (size_t)n;
+	ctx->grp_cap = 0;
+	HIPCHK(regrow(ctx->d_gsym, N * NCELLS));
+	HIPCHK(regrow(ctx->d_gcol, N * NCELLS));
+	HIPCHK(regrow(ctx->d_gmargin, N * NCELLS));
+	HIPCHK(regrow(ctx->d_grs_ok, N * ALL_BLOCKS));
+	HIPCHK(regrow(ctx->d_gagree, N));
+	HIPCHK(regrow(ctx->d_gdisp, N));
+	HIPCHK(regrow(ctx->d_groups, N));
+	HIPCHK(regrow(ctx->d_gmem, N * GMAX));
+	HIPCHK(regrow(ctx->d_gcount, N));
+	HIPCHK(regrow(ctx->d_groups_in, N));
+	if (!ctx->d_ngroups) HIPCHK(regrow(ctx->d_ngroups, (size_t)1));
+	HIPCHK(regrow(ctx->d_gchunks, N * FRAME_BYTES));
+	HIPCHK(regrow(ctx->d_gmasks, N));
+	ctx->grp_cap = n;
+	return 0;
+}
+
+// G1-G4 behind a batch's per-capture decode, on the same stream; reads that decode's intermediates and outputs (d_chunks / d_masks), writes
+// the group outputs (d_gchunks / d_gmasks, n slots) and the context's group scratch. d_status: the capture path's extraction status (stride
+// ints apart), nullptr: every capture usable.
+int enqueue_combine(cimbar_hip_ctx* ctx, hipStream_t st, int n, const uint8_t* d_chunks, const uint32_t* d_masks, const int* d_status, int stride,
+                    const CombineArgs& cb, int out_mem)
+{
+	if (int r = ensure_group_capacity(ctx, n)) return r;
+	// (device outputs: the caller's buffers; host outputs: the context's staging, which exists from here on)
+	uint8_t* d_gchunks = out_mem == CIMBAR_HIP_MEM_DEVICE ? cb.gchunks : ctx->d_gchunks;
+	uint32_t* d_gmasks = out_mem == CIMBAR_HIP_MEM_DEVICE ? cb.gmasks : ctx->d_gmasks;
+	if (cb.groups_in) HIPCHK(hipMemcpyAsync(ctx->d_groups_in, cb.groups_in, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, st));
+	HIPCHK(hipMemsetAsync(ctx->d_gcount, 0, sizeof(int) * (size_t)n, st));
+	HIPCHK(hipMemsetAsync(ctx->d_gdisp, 0, sizeof(uint32_t) * (size_t)n, st));
+	if (!cb.groups_in && n > 1)
+		hipLaunchKernelGGL(k_group_agree, dim3(n - 1), dim3(256), 0, st, ctx->d_symbols, ctx->d_colors, n, ctx->d_gagree);
+	hipLaunchKernelGGL(k_group_walk, dim3(1), dim3(64), 0, st, ctx->d_gagree, n, d_status, stride, cb.groups_in ? ctx->d_groups_in : (const int*)nullptr,
+	                   cb.min_agree, cb.max_group, ctx->d_groups, ctx->d_gmem, ctx->d_gcount, ctx->d_ngroups);
+	hipLaunchKernelGGL(k_group_cells, dim3(GC_BLOCKS, n), dim3(256), 0, st, ctx->d_plane, ctx->tb, ctx->d_symbols, ctx->d_colors, ctx->d_drift, ctx->d_flood,
+	                   ctx->d_gmem, ctx->d_gcount, ctx->d_ngroups, ctx->d_gsym, ctx->d_gcol, ctx->d_gmargin, ctx->d_gdisp);
+	if constexpr (LEGACY) {
+		hipLaunchKernelGGL((k_rs<CELL_BITS, false, true>), dim3((n * ALL_BLOCKS + 3) / 4), dim3(256), 0, st, ctx->d_gsym, ctx->tb, 0, n, 0, d_gchunks, ctx->d_grs_ok, 0,
+		                   (const uint8_t*)ctx->d_gcol, (const int*)ctx->d_ngroups, (const uint32_t*)ctx->d_gdisp);
+	} else {
+		hipLaunchKernelGGL((k_rs<4, false, true>), dim3((n * SYM_BLOCKS + 3) / 4), dim3(256), 0, st, ctx->d_gsym, ctx->tb, 0, n, 0, d_gchunks, ctx->d_grs_ok, 0,
+		                   (const uint8_t*)nullptr, (const int*)ctx->d_ngroups, (const uint32_t*)ctx->d_gdisp);
+		hipLaunchKernelGGL((k_rs<2, false, true>), dim3((n * COL_BLOCKS + 3) / 4), dim3(256), 0, st, ctx->d_gcol, ctx->tb, 0, n, SYM_CHUNKS, d_gchunks, ctx->d_grs_ok,
+		                   SYM_BLOCKS, (const uint8_t*)nullptr, (const int*)ctx->d_ngroups, (const uint32_t*)ctx->d_gdisp);
+	}
+	hipLaunchKernelGGL(k_group_end, dim3(n), dim3(256), 0, st, ctx->d_gsym, ctx->d_gmargin, ctx->tb, ctx->d_gmem, ctx->d_gcount, ctx->d_ngroups, ctx->d_grs_ok,
+	                   d_chunks, d_masks, ctx->d_gdisp, d_gchunks, d_gmasks, (!LEGACY && ctx->er_sym > 0) ? 1 : 0, erasure_max(ctx));
+	HIPCHK(hipGetLastError());
+	return 0;
+}
+
+// the end of a batch call: device outputs are enqueued (group ids and count included) and 0 returned; host outputs are copied back, then
+// the call synchronises and returns the good bytes over the batch, or with `cb` the group count
+int64_t finish_batch(cimbar_hip_ctx* ctx, hipStream_t st, int n, uint8_t* chunks, uint32_t* masks, const uint8_t* d_chunks, const uint32_t* d_masks,
+                     int out_mem, const CombineArgs* cb)
+{
+	const hipMemcpyKind kind = out_mem == CIMBAR_HIP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+	if (cb && cb->groups_out) HIPCHK(hipMemcpyAsync(cb->groups_out, ctx->d_groups, sizeof(int) * (size_t)n, kind, st));
+	if (out_mem == CIMBAR_HIP_MEM_DEVICE) {
+		if (cb && cb->n_groups) HIPCHK(hipMemcpyAsync(cb->n_groups, ctx->d_ngroups, sizeof(int), kind, st));
+		if (cb) ctx->grp_valid = true;
+		return 0;
+	}
+	int ng = 0;
+	HIPCHK(hipMemcpyAsync(chunks, d_chunks, (size_t)n * FRAME_BYTES, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipMemcpyAsync(masks, d_masks, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
+	if (cb) {
+		HIPCHK(hipMemcpyAsync(cb->gchunks, ctx->d_gchunks, (size_t)n * FRAME_BYTES, hipMemcpyDeviceToHost, st));
+		HIPCHK(hipMemcpyAsync(cb->gmasks, ctx->d_gmasks, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
+		HIPCHK(hipMemcpyAsync(&ng, ctx->d_ngroups, sizeof(int), hipMemcpyDeviceToHost, st));
+	}
+	HIPCHK(hipStreamSynchronize(st));
+	if (cb) {
+		ctx->grp_valid = true;
+		if (cb->n_groups) *cb->n_groups = ng;
+		return ng;
+	}
+	if (ctx->timing)
+		for (int k = 0; k < cimbar_hip_ctx::NSTAGE; ++k) HIPCHK(hipEventElapsedTime(&ctx->stage_ms[k], ctx->ev[k], ctx->ev[k + 1]));
+	// aligned_stream::tellp() summed over the batch: 625 bytes per delivered chunk (aligned_stream.h:29-32)
+	unsigned long long total = 0;
+	for (int f = 0; f < n; ++f) total += (unsigned long long)CHUNK * (unsigned)__builtin_popcount(masks[f] & ((1u << CHUNKS) - 1u));
+	return (int64_t)total;
+}
+
+int64_t decode_batch_impl(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rgb_mem, int should_preprocess, int color_correction, uint8_t* chunks,
+                          uint32_t* masks, int out_mem, void* hip_stream, CombineArgs* cb)
+{
+	const char* who = cb ? "decode_batch_combined" : "decode_batch";
+	if (!rgb || !chunks || !masks || n <= 0) { ctx->err = std::string(who) + ": null buffer or n <= 0"; return CIMBAR_HIP_EINVAL; }
 	if ((rgb_mem != CIMBAR_HIP_MEM_HOST && rgb_mem != CIMBAR_HIP_MEM_DEVICE) || (out_mem != CIMBAR_HIP_MEM_HOST && out_mem != CIMBAR_HIP_MEM_DEVICE)) {
-		ctx->err = "decode_batch: rgb_mem / out_mem must be CIMBAR_HIP_MEM_HOST or CIMBAR_HIP_MEM_DEVICE";
+		ctx->err = std::string(who) + ": rgb_mem / out_mem must be CIMBAR_HIP_MEM_HOST or CIMBAR_HIP_MEM_DEVICE";
 		return CIMBAR_HIP_EINVAL;
 	}
+	if (cb) if (int r = check_combine(ctx, who, n, *cb)) return r;
 	HIPCHK(hipSetDevice(ctx->device));
 	// NULL means what it means for any HIP launch -- the (legacy) null stream -- whenever a device buffer is involved, so the
 	// work is ordered after whatever produced the frames there; the all-host path synchronises anyway and uses its own stream
@@ -834,17 +965,27 @@ int64_t cimbar_hip_decode_batch(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, 
 	uint32_t* d_masks = out_mem == CIMBAR_HIP_MEM_DEVICE ? masks : ctx->d_masks;
 
 	if (int r = enqueue(ctx, st, d_rgb, n, should_preprocess, color_correction, d_chunks, d_masks)) return r;
+	if (cb)
+		if (int r = enqueue_combine(ctx, st, n, d_chunks, d_masks, nullptr, 0, *cb, out_mem)) return r;
+	return finish_batch(ctx, st, n, chunks, masks, d_chunks, d_masks, out_mem, cb);
+}
 
-	if (out_mem == CIMBAR_HIP_MEM_DEVICE) return 0;
-	unsigned long long total = 0;
-	HIPCHK(hipMemcpyAsync(chunks, d_chunks, (size_t)n * FRAME_BYTES, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipMemcpyAsync(masks, d_masks, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipStreamSynchronize(st));
-	if (ctx->timing)
-		for (int k = 0; k < cimbar_hip_ctx::NSTAGE; ++k) HIPCHK(hipEventElapsedTime(&ctx->stage_ms[k], ctx->ev[k], ctx->ev[k + 1]));
-	// aligned_stream::tellp() summed over the batch: 625 bytes per delivered chunk (aligned_stream.h:29-32)
-	for (int f = 0; f < n; ++f) total += (unsigned long long)CHUNK * (unsigned)__builtin_popcount(masks[f] & ((1u << CHUNKS) - 1u));
-	return (int64_t)total;
+}  // namespace
+
+int64_t cimbar_hip_decode_batch(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rgb_mem, int should_preprocess,
+                                int color_correction, uint8_t* chunks, uint32_t* masks, int out_mem, void* hip_stream)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return decode_batch_impl(ctx, rgb, n, rgb_mem, should_preprocess, color_correction, chunks, masks, out_mem, hip_stream, nullptr);
+}
+
+int64_t cimbar_hip_decode_batch_combined(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rgb_mem, int should_preprocess, int color_correction,
+                                         const int* groups_in, int min_agree_permille, int max_group, uint8_t* chunks, uint32_t* masks,
+                                         int* groups_out, uint8_t* gchunks, uint32_t* gmasks, int* n_groups, int out_mem, void* hip_stream)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	CombineArgs cb{groups_in, min_agree_permille, max_group, groups_out, gchunks, gmasks, n_groups};
+	return decode_batch_impl(ctx, rgb, n, rgb_mem, should_preprocess, color_correction, chunks, masks, out_mem, hip_stream, &cb);
 }
 
 int cimbar_hip_decode_batch_pipelined(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int should_preprocess, int color_correction,
@@ -1390,18 +1531,21 @@ int cimbar_hip_extract_batch(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsigned w
 	return cimbar_hip_extract_batch_fmt(ctx, rgb, width, height, FMT_RGB, n, rgb_mem, frames, status, corners, out_mem, hip_stream);
 }
 
-int64_t cimbar_hip_scan_extract_decode_batch_fmt(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsigned width, unsigned height, int format, int n, int rgb_mem,
-                                                 int preprocess, int color_correction, uint8_t* chunks, uint32_t* masks, int* status, int out_mem,
-                                                 void* hip_stream)
+namespace {
+
+int64_t scan_extract_decode_impl(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsigned width, unsigned height, int format, int n, int rgb_mem,
+                                 int preprocess, int color_correction, uint8_t* chunks, uint32_t* masks, int* status, int out_mem,
+                                 void* hip_stream, CombineArgs* cb)
 {
-	if (!ctx) return CIMBAR_HIP_EINVAL;
-	if (!rgb || !chunks || !masks || n <= 0 || width < 8 || height < 8) { ctx->err = "scan_extract_decode_batch: null buffer, n <= 0 or a capture smaller than 8x8"; return CIMBAR_HIP_EINVAL; }
+	const char* who = cb ? "scan_extract_decode_batch_combined" : "scan_extract_decode_batch";
+	if (!rgb || !chunks || !masks || n <= 0 || width < 8 || height < 8) { ctx->err = std::string(who) + ": null buffer, n <= 0 or a capture smaller than 8x8"; return CIMBAR_HIP_EINVAL; }
 	if ((rgb_mem != CIMBAR_HIP_MEM_HOST && rgb_mem != CIMBAR_HIP_MEM_DEVICE) || (out_mem != CIMBAR_HIP_MEM_HOST && out_mem != CIMBAR_HIP_MEM_DEVICE)) {
-		ctx->err = "scan_extract_decode_batch: rgb_mem / out_mem must be CIMBAR_HIP_MEM_HOST or CIMBAR_HIP_MEM_DEVICE";
+		ctx->err = std::string(who) + ": rgb_mem / out_mem must be CIMBAR_HIP_MEM_HOST or CIMBAR_HIP_MEM_DEVICE";
 		return CIMBAR_HIP_EINVAL;
 	}
 	int fmt; size_t cbytes;
-	if (int r = check_capture(ctx, "scan_extract_decode_batch", width, height, format, &fmt, &cbytes)) return r;
+	if (int r = check_capture(ctx, who, width, height, format, &fmt, &cbytes)) return r;
+	if (cb) if (int r = check_combine(ctx, who, n, *cb)) return r;
 	HIPCHK(hipSetDevice(ctx->device));
 	const bool any_device = rgb_mem == CIMBAR_HIP_MEM_DEVICE || out_mem == CIMBAR_HIP_MEM_DEVICE;
 	hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (any_device ? (hipStream_t)nullptr : ctx->stream);
@@ -1417,23 +1561,41 @@ int64_t cimbar_hip_scan_extract_decode_batch_fmt(cimbar_hip_ctx* ctx, const uint
 	uint32_t* d_masks = out_mem == CIMBAR_HIP_MEM_DEVICE ? masks : ctx->d_masks;
 	// cimbar.cpp:131,147-154: preprocess 1 = sharpen every frame, 0 = none, anything else = where the extractor said NEEDS_SHARPEN
 	const bool guess = preprocess != 0 && preprocess != 1;
+	const int stride = (int)(sizeof(ScanResult) / sizeof(int));
 	ctx->no_split_once = true;
 	const int er = enqueue(ctx, st, ctx->d_ex_frames, n, preprocess == 1 ? 1 : 0, color_correction, d_chunks, d_masks, 0, false,
-	                       guess ? &ctx->d_scan_res[0].status : nullptr, (int)(sizeof(ScanResult) / sizeof(int)));
+	                       guess ? &ctx->d_scan_res[0].status : nullptr, stride);
 	ctx->no_split_once = false;
 	if (er) return er;
 	// a capture the extractor gave up on is skipped by the reference (cimbar.cpp:141-146): nothing of it reaches the sink
-	hipLaunchKernelGGL(k_mask_failed, dim3(n), dim3(256), 0, st, &ctx->d_scan_res[0].status, (int)(sizeof(ScanResult) / sizeof(int)), n, d_masks, d_chunks);
+	hipLaunchKernelGGL(k_mask_failed, dim3(n), dim3(256), 0, st, &ctx->d_scan_res[0].status, stride, n, d_masks, d_chunks);
 	HIPCHK(hipGetLastError());
+	// ... nor any group (it is in none)
+	if (cb)
+		if (int r = enqueue_combine(ctx, st, n, d_chunks, d_masks, &ctx->d_scan_res[0].status, stride, *cb, out_mem)) return r;
 	const hipMemcpyKind kind = out_mem == CIMBAR_HIP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
 	if (status) HIPCHK(hipMemcpy2DAsync(status, sizeof(int), &ctx->d_scan_res[0].status, sizeof(ScanResult), sizeof(int), (size_t)n, kind, st));
-	if (out_mem == CIMBAR_HIP_MEM_DEVICE) return 0;
-	HIPCHK(hipMemcpyAsync(chunks, d_chunks, (size_t)n * FRAME_BYTES, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipMemcpyAsync(masks, d_masks, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipStreamSynchronize(st));
-	unsigned long long total = 0;
-	for (int f = 0; f < n; ++f) total += (unsigned long long)CHUNK * (unsigned)__builtin_popcount(masks[f] & ((1u << CHUNKS) - 1u));
-	return (int64_t)total;
+	return finish_batch(ctx, st, n, chunks, masks, d_chunks, d_masks, out_mem, cb);
+}
+
+}  // namespace
+
+int64_t cimbar_hip_scan_extract_decode_batch_fmt(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsigned width, unsigned height, int format, int n, int rgb_mem,
+                                                 int preprocess, int color_correction, uint8_t* chunks, uint32_t* masks, int* status, int out_mem,
+                                                 void* hip_stream)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return scan_extract_decode_impl(ctx, rgb, width, height, format, n, rgb_mem, preprocess, color_correction, chunks, masks, status, out_mem, hip_stream, nullptr);
+}
+
+int64_t cimbar_hip_scan_extract_decode_batch_combined_fmt(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsigned width, unsigned height, int format, int n,
+                                                          int rgb_mem, int preprocess, int color_correction, const int* groups_in, int min_agree_permille,
+                                                          int max_group, uint8_t* chunks, uint32_t* masks, int* status, int* groups_out,
+                                                          uint8_t* gchunks, uint32_t* gmasks, int* n_groups, int out_mem, void* hip_stream)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	CombineArgs cb{groups_in, min_agree_permille, max_group, groups_out, gchunks, gmasks, n_groups};
+	return scan_extract_decode_impl(ctx, rgb, width, height, format, n, rgb_mem, preprocess, color_correction, chunks, masks, status, out_mem, hip_stream, &cb);
 }
 
 int64_t cimbar_hip_scan_extract_decode_batch(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsigned width, unsigned height, int n, int rgb_mem,
@@ -1615,6 +1777,25 @@ int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_byte
 			if (!ctx->flood_verify || !ctx->d_vflag || (size_t)ctx->vcap < n) { std::memset(out, 0xFF, bytes); return (int64_t)bytes; }
 			HIPCHK(hipDeviceSynchronize());
 			HIPCHK(hipMemcpy(out, ctx->d_vflag + ctx->vcap, bytes, hipMemcpyDeviceToHost));
+			return (int64_t)bytes;
+		}
+		case CIMBAR_HIP_TAP_GROUP_CELLS:
+		case CIMBAR_HIP_TAP_GROUP_MARGIN:
+		case CIMBAR_HIP_TAP_GROUPS: {
+			if (!ctx->grp_valid) { ctx->err = "tap: the last batch was not a combined one (cimbar_hip_decode_batch_combined / _scan_extract_decode_batch_combined_fmt)"; return CIMBAR_HIP_EINVAL; }
+			int ng = 0;
+			HIPCHK(hipMemcpy(&ng, ctx->d_ngroups, sizeof(int), hipMemcpyDeviceToHost));
+			const size_t G = (size_t)ng;
+			bytes = what == CIMBAR_HIP_TAP_GROUPS ? n * sizeof(int32_t) : G * NCELLS * (what == CIMBAR_HIP_TAP_GROUP_MARGIN ? 2 : 1);
+			if (out_bytes < bytes) { ctx->err = "tap: buffer too small"; return CIMBAR_HIP_EINVAL; }
+			if (what == CIMBAR_HIP_TAP_GROUPS) HIPCHK(hipMemcpy(out, ctx->d_groups, bytes, hipMemcpyDeviceToHost));
+			else if (what == CIMBAR_HIP_TAP_GROUP_MARGIN) { if (bytes) HIPCHK(hipMemcpy(out, ctx->d_gmargin, bytes, hipMemcpyDeviceToHost)); }
+			else if (bytes) {
+				std::vector<uint8_t> col(bytes);
+				HIPCHK(hipMemcpy(out, ctx->d_gsym, bytes, hipMemcpyDeviceToHost));
+				HIPCHK(hipMemcpy(col.data(), ctx->d_gcol, bytes, hipMemcpyDeviceToHost));
+				for (size_t k = 0; k < bytes; ++k) ((uint8_t*)out)[k] = (uint8_t)((col[k] << 4) | (((uint8_t*)out)[k] & 15u));
+			}
 			return (int64_t)bytes;
 		}
 #ifdef FLOOD_PROF

@@ -67,12 +67,20 @@ __device__ __forceinline__ uint8_t gf_eval_log(const RsShared& s, uint32_t lcoef
 
 // NOSYND (timing probe only, CIMBAR_HIP_DEBUG_SKIP bit 128): the syndrome pass is left out and every block taken as a codeword -- right for clean
 // frames, wrong otherwise; it bounds what ANY cheaper syndrome computation (bit-sliced, matrix cores, ...) could give the pipelined step.
-template <int BITS, bool NOSYND = false>   // 4: symbol stream, 2: colour stream, 6 | 7: the legacy modes' coupled stream (cells = symbols, cells2 = colours)
+// LIVE (the group decode, combine.hip.inc): *n_live frames of the nframes the grid covers are decoded, the workgroups past them return at once,
+// and so do the wavefronts of a frame whose live_flag is 0.
+template <int BITS, bool NOSYND = false, bool LIVE = false>   // 4: symbol stream, 2: colour stream, 6 | 7: the legacy modes' coupled stream (cells = symbols, cells2 = colours)
 __global__ __launch_bounds__(256) void k_rs(const uint8_t* __restrict__ cells, Tables tb, int f0, int nframes, int first_chunk,
-                                            uint8_t* __restrict__ chunks, uint8_t* __restrict__ rs_ok, int ok_offset, const uint8_t* __restrict__ cells2 = nullptr)
+                                            uint8_t* __restrict__ chunks, uint8_t* __restrict__ rs_ok, int ok_offset, const uint8_t* __restrict__ cells2 = nullptr,
+                                            const int* __restrict__ n_live = nullptr, const uint32_t* __restrict__ live_flag = nullptr)
 {
 	constexpr int NBLK0 = (BITS == 4) ? SYM_BLOCKS : (BITS == 2 ? COL_BLOCKS : ALL_BLOCKS), NBLK = NBLK0 > 0 ? NBLK0 : 1;
 	constexpr int PER_BYTE = BITS >= 6 ? 1 : 8 / BITS;
+	if constexpr (LIVE) {
+		const int live = *n_live < nframes ? *n_live : nframes;
+		if ((int)blockIdx.x * 4 >= live * NBLK) return;       // (uniform over the workgroup: before the barrier below)
+		nframes = live;
+	}
 	__shared__ RsShared s;
 	for (int k = threadIdx.x; k < 768; k += 256) s.exp[k] = k < 512 ? c_gf_exp[k] : (uint8_t)0;
 	s.log[threadIdx.x] = c_gf_log[threadIdx.x];
@@ -83,6 +91,7 @@ __global__ __launch_bounds__(256) void k_rs(const uint8_t* __restrict__ cells, T
 	const int b = gb % NBLK;
 	if (gb / NBLK >= nframes) return;
 	const int f = f0 + gb / NBLK;
+	if constexpr (LIVE) { if (!live_flag[f]) return; }
 	const uint8_t* cf = cells + (size_t)f * NCELLS;
 	uint8_t* enc = s.enc[wv];
 

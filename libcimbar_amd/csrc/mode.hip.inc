@@ -105,6 +105,7 @@ struct Tables {
 #include "k3_rs.hip.inc"
 #include "erasure.hip.inc"
 #include "k4_frame.hip.inc"
+#include "combine.hip.inc"
 #include "k1_padded.hip.inc"
 #include "encode.hip.inc"
 #include "extract.hip.inc"

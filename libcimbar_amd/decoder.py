@@ -18,6 +18,7 @@ LIB_PATH = os.path.join(_HERE, "libcimbar_hip.so")
 
 MEM_HOST, MEM_DEVICE = 0, 1
 TAP_BITPLANE, TAP_SYMBOLS, TAP_COLORS, TAP_DRIFT, TAP_RS_OK, TAP_FLOOD, TAP_CCM, TAP_FLOOD_PATH, TAP_FLOOD_INFO, TAP_FLOOD_VERIFY = range(10)
+TAP_GROUP_CELLS, TAP_GROUP_MARGIN, TAP_GROUPS = 10, 11, 12
 
 # every symbol include/cimbar_hip.h declares (tests/test_capi_symbols.py checks the header against this list and the .so)
 EXPORTS = (
@@ -35,6 +36,7 @@ EXPORTS = (
     "cimbar_hip_scan_extract_decode_batch_fmt",
     "cimbar_hip_undistort_calibrate_fmt", "cimbar_hip_undistort_batch_fmt", "cimbar_hip_scan_undistort_extract_decode_batch_fmt",
     "cimbar_hip_rs_decode_erasures", "cimbar_hip_set_erasure_decode", "cimbar_hip_get_erasure_decode",
+    "cimbar_hip_decode_batch_combined", "cimbar_hip_scan_extract_decode_batch_combined_fmt",
 )
 PNG_EHEADER, PNG_ESTREAM, PNG_ECODES, PNG_ESIZE, PNG_ECHECK = -30, -31, -32, -33, -34
 
@@ -139,6 +141,11 @@ def load_library(path=None):
     lib.cimbar_hip_set_ccm.restype = i32
     lib.cimbar_hip_rs_decode_erasures.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp]
     lib.cimbar_hip_rs_decode_erasures.restype = i32
+    lib.cimbar_hip_decode_batch_combined.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp]
+    lib.cimbar_hip_decode_batch_combined.restype = i64
+    lib.cimbar_hip_scan_extract_decode_batch_combined_fmt.argtypes = [vp, vp, u32, u32, i32, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp,
+                                                                      vp, i32, vp]
+    lib.cimbar_hip_scan_extract_decode_batch_combined_fmt.restype = i64
     lib.cimbar_hip_set_erasure_decode.argtypes = [vp, i32, i32, i32]
     lib.cimbar_hip_set_erasure_decode.restype = i32
     lib.cimbar_hip_get_erasure_decode.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32)]
@@ -358,6 +365,65 @@ class HipDecoder:
                                                int(color_correction), chunks.ctypes.data, masks.ctypes.data, MEM_HOST, None)
         self._check(rc, "cimbar_hip_decode_batch")
         return int(rc), chunks, masks
+
+    def _groups_in(self, groups, n):
+        if groups is None:
+            return None, None
+        g = np.ascontiguousarray(groups, dtype=np.int32).reshape(-1)
+        if len(g) != n:
+            raise CimbarHipError(f"groups: one entry per capture ({n}), got {len(g)}")
+        return g, g.ctypes.data
+
+    def _group_outputs(self, n):
+        geo = self.geo
+        return (np.zeros((n, geo.CHUNKS_PER_FRAME, geo.CHUNK), dtype=np.uint8), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.int32),
+                np.zeros((n, geo.CHUNKS_PER_FRAME, geo.CHUNK), dtype=np.uint8), np.zeros(n, dtype=np.uint32))
+
+    def decode_batch_combined(self, frames, groups=None, min_agree_permille=0, max_group=0, should_preprocess=False, color_correction=2):
+        """Multi-capture decoding (cimbar_hip_decode_batch_combined): frames as for decode_batch; groups = None (the device groups runs of
+        captures of one frame) or n ids (-1 / 0, 1, ... contiguous). Returns (n_groups, chunks, masks, groups, gchunks, gmasks): the
+        per-capture results of decode_batch, the group of every capture, and n slots of group chunks / masks (zero from n_groups on)."""
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        n = frames.shape[0]
+        if frames.shape[1:] != self.geo.FRAME_SHAPE:
+            raise CimbarHipError(f"decode_batch_combined: frames must be (n,{self.geo.IMG_H},{self.geo.IMG_W},3) uint8")
+        _keep, gin = self._groups_in(groups, n)
+        chunks, masks, gout, gchunks, gmasks = self._group_outputs(n)
+        ng = ctypes.c_int(0)
+        rc = self._check(self._lib.cimbar_hip_decode_batch_combined(self._ctx, frames.ctypes.data, n, MEM_HOST, int(bool(should_preprocess)),
+                                                                    int(color_correction), gin, int(min_agree_permille), int(max_group),
+                                                                    chunks.ctypes.data, masks.ctypes.data, gout.ctypes.data, gchunks.ctypes.data,
+                                                                    gmasks.ctypes.data, ctypes.byref(ng), MEM_HOST, None),
+                         "cimbar_hip_decode_batch_combined")
+        assert rc == ng.value
+        return int(rc), chunks, masks, gout, gchunks, gmasks
+
+    def decode_batch_combined_device(self, frames_ptr, n, chunks_ptr, masks_ptr, groups_out_ptr, gchunks_ptr, gmasks_ptr, n_groups_ptr,
+                                     groups=None, min_agree_permille=0, max_group=0, should_preprocess=False, color_correction=2, stream=None):
+        """Device pointers in and out (layouts as in include/cimbar_hip.h; groups_out_ptr / n_groups_ptr may be 0); enqueues on `stream`
+        (None / 0 = the null stream) and returns at once -- the group count is written to n_groups_ptr (one int32) on the device."""
+        _keep, gin = self._groups_in(groups, n)
+        vp = ctypes.c_void_p
+        self._check(self._lib.cimbar_hip_decode_batch_combined(self._ctx, vp(frames_ptr), int(n), MEM_DEVICE, int(bool(should_preprocess)),
+                                                               int(color_correction), gin, int(min_agree_permille), int(max_group), vp(chunks_ptr),
+                                                               vp(masks_ptr), vp(groups_out_ptr or None), vp(gchunks_ptr), vp(gmasks_ptr),
+                                                               vp(n_groups_ptr or None), MEM_DEVICE, vp(stream) if stream else None),
+                    "cimbar_hip_decode_batch_combined(device)")
+
+    def scan_extract_decode_batch_combined(self, captures, groups=None, min_agree_permille=0, max_group=0, preprocess=-1, color_correction=2,
+                                           size=None, fmt=3):
+        """The capture path with multi-capture decoding (cimbar_hip_scan_extract_decode_batch_combined_fmt). Returns
+        (n_groups, chunks, masks, status, groups, gchunks, gmasks); a capture whose extraction failed is in no group."""
+        captures, n, w, h, fmt = self._captures(captures, size, fmt)
+        _keep, gin = self._groups_in(groups, n)
+        chunks, masks, gout, gchunks, gmasks = self._group_outputs(n)
+        status = np.zeros(n, dtype=np.int32)
+        ng = ctypes.c_int(0)
+        rc = self._check(self._lib.cimbar_hip_scan_extract_decode_batch_combined_fmt(
+            self._ctx, captures.ctypes.data, w, h, fmt, n, MEM_HOST, int(preprocess), int(color_correction), gin, int(min_agree_permille),
+            int(max_group), chunks.ctypes.data, masks.ctypes.data, status.ctypes.data, gout.ctypes.data, gchunks.ctypes.data, gmasks.ctypes.data,
+            ctypes.byref(ng), MEM_HOST, None), "cimbar_hip_scan_extract_decode_batch_combined_fmt")
+        return int(rc), chunks, masks, status, gout, gchunks, gmasks
 
     def decode_plain_batch(self, frames, should_preprocess=False, color_correction=2):
         """Decoder::decode (the --no-fountain path) for frames (n,1024,1024,3) uint8 numpy. Returns (bytes_written,
@@ -644,6 +710,7 @@ class HipDecoder:
             TAP_BITPLANE: ((n, self.geo.IMG_W * self.geo.IMG_H // 8), np.uint8), TAP_SYMBOLS: ((n, self.geo.NCELLS), np.uint8),
             TAP_COLORS: ((n, self.geo.NCELLS), np.uint8), TAP_DRIFT: ((n, self.geo.NCELLS, 2), np.int8),
             TAP_RS_OK: ((n, self.geo.BLOCKS), np.uint8), TAP_FLOOD: ((n,), np.uint8), TAP_CCM: ((n, 10), np.float32), TAP_FLOOD_PATH: ((n,), np.uint8), TAP_FLOOD_INFO: ((n,), np.uint32), TAP_FLOOD_VERIFY: ((n,), np.uint32),
+            TAP_GROUP_CELLS: ((n, self.geo.NCELLS), np.uint8), TAP_GROUP_MARGIN: ((n, self.geo.NCELLS), np.uint16), TAP_GROUPS: ((n,), np.int32),
         }
         shape, dt = shapes[what]
         out = np.zeros(shape, dtype=dt)
