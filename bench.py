@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- decoded cimbar frames/s (1024x1024 mode B) on N MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--config 2|4] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--config 2|4] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the whole decode path (threshold -> symbols -> RS -> CCM -> colours -> RS -> chunks) over one
 device-resident batch of F synthetic clean mode-B frames (BASELINE.json configs[1]: F = 1024). Consecutive steps decode
@@ -9,7 +9,11 @@ DIFFERENT batches (D = pipeline depth distinct inputs are rotated), so that step
 For N > 1 (launched by torch.distributed.run, one rank per GPU) every rank decodes its own F frames (weak scaling) and the
 step ends with the gather of the decoded chunks to rank 0 over RCCL. Rank 0 prints ONE JSON line.
 
-Extra objects in that line:
+A plain run does what the headline needs and nothing more: set-up, warm-up, the timed steps, --dump-outputs, the check that
+the timed steps decoded every payload bit-exact, and the line (metric, value, ms_per_step, timed_region, config).
+
+With --full the line also carries:
+  stage_ms      per-kernel ms of one un-split decode, HIP events on the launch stream inside the library
   roofline      dominant kernel's ALGORITHMIC bytes/s (3 153 232 B per frame) vs 8 TB/s HBM, timed live
                 with HIP events on the launch stream inside the library
   cpu_baseline  the CPU decoder timed on this host on a bounded sample of the same frames ("reference" = the
@@ -18,6 +22,8 @@ Extra objects in that line:
   no_pipeline   the same steps through the ordinary (un-pipelined) entry point
   extra         N = 1 only: BASELINE configs[2] (99 substituted cells per frame), host-fed decode (pinned host frames in,
                 H2D inside the timed region), the extractor chain of configs[4] (1080p captures -> scan -> deskew -> decode)
+  summary       the secondary rows' figures in one small object, the line's last key
+and the first input batch is checked against the torch restatement of the encoder before it is used.
 --config 4 runs BASELINE configs[3] instead (strong scaling: an 8192-frame fountain stream of a 16 MiB file split over the
 ranks, gather, rank-0 wirehair sink fed inside the timed region): see bench_config4.py.
 """
@@ -272,6 +278,47 @@ def stage_times(dec, frames, outs, stream, dev, reps=5, pre=False):
             acc[k] = acc.get(k, 0.0) + v / reps
     dec.enable_timing(False)
     return acc
+
+
+def kernel_figures(dec, local_rank, frames, outs, stream, dev, n, world, frames_per_s, pipelined):
+    """--full: the line's `roofline` and `stage_ms` objects, from timing runs of their own after the timed region."""
+    stage_acc = stage_times(dec, frames, outs, stream, dev)
+    dom = max(stage_acc, key=stage_acc.get)
+    dom_ms = stage_acc[dom]
+    # The pipelined loop launches the threshold kernel's TALL-strip instance for batches of 256 frames and more (fewer row steps and halo rows per
+    # frame: better for the loop, a little slower as a launch of its own -- DESIGN.md K1); a call that runs alone, like the stage timing above,
+    # takes the short-strip one. The roofline object describes the kernel the TIMED REGION ran: the tall instance, timed alone here through
+    # a context that is told to use it everywhere; the short instance's figure stays next to it.
+    short_ms, tall_used = dom_ms, False
+    if dom == "threshold" and pipelined and n >= 256 and os.environ.get("CIMBAR_HIP_K1_STRIPS", "auto") in ("auto", "tall"):
+        prev_env = os.environ.get("CIMBAR_HIP_K1_STRIPS")
+        try:
+            os.environ["CIMBAR_HIP_K1_STRIPS"] = "tall"
+            dec_t = HipDecoder(local_rank)
+            tall_acc = stage_times(dec_t, frames, outs, stream, dev)
+            dec_t.close()
+            stage_acc["threshold_tall_strips"] = tall_acc["threshold"]
+            dom_ms, tall_used = tall_acc["threshold"], True
+        finally:
+            if prev_env is None:
+                os.environ.pop("CIMBAR_HIP_K1_STRIPS", None)
+            else:
+                os.environ["CIMBAR_HIP_K1_STRIPS"] = prev_env
+    achieved = ALGO_BYTES_PER_FRAME * n / (dom_ms * 1e-3) / 1e9
+    traffic, traffic_src = measured_traffic(dom, n, tall=tall_used)
+    trace_us, trace_src = trace_average(dom, tall=tall_used)
+    return {
+        "roofline": {"bound": "hbm", "kernel": dom + (" (k_threshold<2, false, 7>: the tall-strip instance the timed loop launches, timed as a launch of its own)" if tall_used else ""),
+                     "short_strip_instance_alone": {"ms": round(short_ms, 4), "frac": round(ALGO_BYTES_PER_FRAME * n / (short_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+                                                    "note": "k_threshold<2, false, 2>: what a call that runs alone launches"} if tall_used else None,
+                     "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": round(achieved / HBM_PEAK_GBS, 5), "algorithmic_bytes": ALGO_BYTES_PER_FRAME * n,
+                     "traffic": None if traffic is None else round(traffic), "traffic_source": traffic_src,
+                     # the same kernel's average duration in the committed rocprofv3 kernel trace (another machine, another day: machines differ by 5-10 %)
+                     "kernel_avg_us": round(dom_ms * 1e3, 2), "kernel_avg_us_trace": trace_us, "kernel_avg_us_trace_source": trace_src,
+                     "whole_path_frac": round(frames_per_s / world * ALGO_BYTES_PER_FRAME / 1e9 / HBM_PEAK_GBS, 5)},
+        "stage_ms": {k: round(v, 4) for k, v in stage_acc.items()},
+    }
 
 
 def extras(dec, dev, stream, n, outs, steps):
@@ -754,8 +801,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--frames", type=int, default=1024, help="frames per GPU per step (BASELINE configs[1]: 1024)")
     ap.add_argument("--config", type=int, default=2, choices=(2, 4), help="2: BASELINE configs[1] (default); 4: configs[3], the sharded fountain stream")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure and check everything else: stage_ms and roofline, no_pipeline, cpu_baseline, the extra rows "
+                         "(other workloads, modes, sizes and ingest paths) and the summary object, plus the input batch's check against the torch "
+                         "restatement of the encoder; a plain run only sets up, warms up, times --steps steps, dumps and prints the headline line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: leave out the extra rows")
     ap.add_argument("--allow-fallback", action="store_true",
                     help="N > 1: if the library's own exchange (cimbar_hip_gather_chunks) cannot be set up, fall back to torch.distributed.gather "
                          "instead of failing -- the line then says so in config.exchange, and is NOT a measurement of this library's exchange")
@@ -772,8 +823,8 @@ def main():
                          "tools/skip_probe.sh): prints the timing fields only -- no metric / value, such a line is not a result")
     ap.add_argument("--no-solo-exchange", dest="solo_exchange", action="store_false",
                     help="N = 1 only: do NOT run every step's outputs through the library's exchange with a one-rank RCCL communicator inside the timed loop "
-                         "(the default does what each rank of an N-GPU job does: +0.4 ... 1.6 % on the step, profiles/r06m_bench_exchange_*); the line then "
-                         "checks the exchange once outside the timed region instead (config.exchange_selfcheck)")
+                         "(the default does what each rank of an N-GPU job does: +0.4 ... 1.6 % on the step, profiles/r06m_bench_exchange_*); with --full the "
+                         "line then checks the exchange once outside the timed region instead (config.exchange_selfcheck)")
     ap.add_argument("--solo-exchange", dest="solo_exchange", action="store_true", help="(the default)")
     ap.set_defaults(solo_exchange=True)
     ap.add_argument("--exchange-side-stream", action="store_true",
@@ -839,7 +890,7 @@ def main():
     # R distinct input batches, decoded in rotation: steps in flight at the same time never read the same frames (two threshold passes
     # walking the same addresses a few frames apart would share lines through L2 / the Infinity Cache, which a real stream cannot)
     R = max(dec.pipeline_depth, 4)          # (12 GB per rotation: nothing survives in the 256 MiB Infinity Cache from one use to the next)
-    batches = [make_frames(n, dev, seed=1234 + 97 * rank + 7919 * b, dec=dec, check=(b == 0)) for b in range(R)]
+    batches = [make_frames(n, dev, seed=1234 + 97 * rank + 7919 * b, dec=dec, check=(b == 0 and args.full)) for b in range(R)]
     payloads = [p for p, _ in batches]
     inputs = [f for _, f in batches]
     outs = [(torch.zeros((n, modeb.FRAME_BYTES), dtype=torch.uint8, device=dev), torch.zeros((n,), dtype=torch.int32, device=dev))
@@ -987,31 +1038,6 @@ def main():
     line = None
     if rank == 0:
         frames_per_s = world * n * args.steps / elapsed
-        stage_acc = stage_times(dec, inputs[0], outs[0], stream, dev)
-        dom = max(stage_acc, key=stage_acc.get)
-        dom_ms = stage_acc[dom]
-        # The pipelined loop launches the threshold kernel's TALL-strip instance for batches of 256 frames and more (fewer row steps and halo rows per
-        # frame: better for the loop, a little slower as a launch of its own -- DESIGN.md K1); a call that runs alone, like the stage timing above,
-        # takes the short-strip one. The roofline object describes the kernel the TIMED REGION ran: the tall instance, timed alone here through
-        # a context that is told to use it everywhere; the short instance's figure stays next to it.
-        short_ms, tall_used = dom_ms, False
-        if dom == "threshold" and not args.no_pipeline and n >= 256 and os.environ.get("CIMBAR_HIP_K1_STRIPS", "auto") in ("auto", "tall"):
-            prev_env = os.environ.get("CIMBAR_HIP_K1_STRIPS")
-            try:
-                os.environ["CIMBAR_HIP_K1_STRIPS"] = "tall"
-                dec_t = HipDecoder(local_rank)
-                tall_acc = stage_times(dec_t, inputs[0], outs[0], stream, dev)
-                dec_t.close()
-                stage_acc["threshold_tall_strips"] = tall_acc["threshold"]
-                dom_ms, tall_used = tall_acc["threshold"], True
-            finally:
-                if prev_env is None:
-                    os.environ.pop("CIMBAR_HIP_K1_STRIPS", None)
-                else:
-                    os.environ["CIMBAR_HIP_K1_STRIPS"] = prev_env
-        achieved = ALGO_BYTES_PER_FRAME * n / (dom_ms * 1e-3) / 1e9
-        traffic, traffic_src = measured_traffic(dom, n, tall=tall_used)
-        trace_us, trace_src = trace_average(dom, tall=tall_used)
         line = {
             "metric": "decoded cimbar frames/s (1024x1024 mode-B)", "value": round(frames_per_s, 1), "unit": "frames/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
@@ -1026,18 +1052,10 @@ def main():
                        "exchanges_in_timed_run": pipe.gathers, "exchange_selfcheck": None,
                        "parallelism": f"frame-sharded x{world}" + (", RCCL gather to rank 0" if world > 1 else "") +
                                       ("" if args.no_pipeline else f"; {D} steps in flight (pipelined entry point)")},
-            "roofline": {"bound": "hbm", "kernel": dom + (" (k_threshold<2, false, 7>: the tall-strip instance the timed loop launches, timed as a launch of its own)" if tall_used else ""),
-                         "short_strip_instance_alone": {"ms": round(short_ms, 4), "frac": round(ALGO_BYTES_PER_FRAME * n / (short_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-                                                        "note": "k_threshold<2, false, 2>: what a call that runs alone launches"} if tall_used else None,
-                         "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 5), "algorithmic_bytes": ALGO_BYTES_PER_FRAME * n,
-                         "traffic": None if traffic is None else round(traffic), "traffic_source": traffic_src,
-                         # the same kernel's average duration in the committed rocprofv3 kernel trace (another box of the pool, another day: boxes differ by 5-10 %)
-                         "kernel_avg_us": round(dom_ms * 1e3, 2), "kernel_avg_us_trace": trace_us, "kernel_avg_us_trace_source": trace_src,
-                         "whole_path_frac": round(frames_per_s / world * ALGO_BYTES_PER_FRAME / 1e9 / HBM_PEAK_GBS, 5)},
-            "stage_ms": {k: round(v, 4) for k, v in stage_acc.items()},
         }
-    if world == 1:
+        if args.full:
+            line.update(kernel_figures(dec, local_rank, inputs[0], outs[0], stream, dev, n, world, frames_per_s, pipelined=not args.no_pipeline))
+    if world == 1 and args.full:
         if not args.no_pipeline:
             ms_u = stream_ms(dec, inputs, outs, args.steps, min(args.warmup, 4), False, stream, dev)
             line["no_pipeline"] = {"ms_per_step": round(ms_u, 4), "frames_per_s": round(n / ms_u * 1e3, 1),
@@ -1055,16 +1073,17 @@ def main():
             inputs[1:] = []
             torch.cuda.empty_cache()
             line["extra"] = extras(dec, dev, stream, n, outs, max(20, args.steps // 4))
-    if world == 1 and exchange is None and not args.solo_exchange and not args.probe_run:
+    if world == 1 and args.full and exchange is None and not args.solo_exchange and not args.probe_run:
         # (--no-solo-exchange; if the in-loop exchange was wanted and could not be set up, config.exchange says why and nothing is tried again. Last of all: creating and destroying an RCCL communicator leaves the process with slower host-side event waits -- measured, the
         # synchronous one-frame call went from 0.149 to 0.649 ms when this ran ahead of the extra rows, profiles/r06k_bench.json)
         line["config"]["exchange_selfcheck"] = exchange_selfcheck()
     if rank == 0 and args.probe_run:
         # a probe line carries timings only: nothing in it can be mistaken for the metric
         print(json.dumps({"probe_run": True, "debug_skip": os.environ.get("CIMBAR_HIP_DEBUG_SKIP", "0"), "payload_ok": ok,
-                          "ms_per_step": line["ms_per_step"], "stage_ms": line["stage_ms"], "no_pipeline": line.get("no_pipeline")}), flush=True)
+                          "ms_per_step": line["ms_per_step"], "stage_ms": line.get("stage_ms"), "no_pipeline": line.get("no_pipeline")}), flush=True)
     elif rank == 0:
-        line["summary"] = summary(line)          # last key: the driver keeps the tail of the line
+        if args.full:
+            line["summary"] = summary(line)          # last key: whoever keeps only the tail of a long line still has the secondary rows
         print(json.dumps(line), flush=True)
     if exchange is not None:
         exchange.close()

@@ -92,3 +92,23 @@ def test_steps_is_the_timed_region_and_the_dump_holds_the_last_step(tmp_path):
     assert (masks == 0xFFF).all()
     # the last timed step decoded one of the rotated input batches (rank 0: seed 1234 + 7919 b), bit for bit
     assert any((chunks == framegen.synth_payload(n, seed=1234 + 7919 * b).numpy()).all() for b in range(16))
+
+
+@pytest.mark.gpu
+def test_a_plain_run_prints_the_headline_alone_and_full_adds_the_rest():
+    """a plain run sets up, warms up, times its steps and prints the headline; per-kernel figures and secondary rows come with --full"""
+    if gpu_count() == 0:
+        pytest.skip("no GPU")
+    moved = ("roofline", "stage_ms", "no_pipeline", "cpu_baseline", "payload_sha_match", "extra", "summary")
+    r = run(["--steps", "3", "--warmup", "1", "--frames", "64"], timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["metric"] == "decoded cimbar frames/s (1024x1024 mode-B)" and line["unit"] == "frames/s" and line["dtype"] == "u8"
+    assert line["higher_is_better"] is True and line["steps"] == 3 and line["ms_per_step"] > 0
+    assert abs(line["value"] - 64 * 1e3 / line["ms_per_step"]) <= 1e-2 * line["value"]
+    assert not [k for k in moved if k in line], "a plain run measures the headline alone"
+    r = run(["--steps", "3", "--warmup", "1", "--frames", "64", "--full", "--no-cpu-baseline", "--no-extras"], timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["stage_ms"]["threshold"] > 0 and line["roofline"]["bound"] == "hbm" and line["no_pipeline"]["ms_per_step"] > 0
+    assert "cpu_baseline" not in line and "extra" not in line and list(line)[-1] == "summary"

@@ -4,7 +4,7 @@ A=${A:-libcimbar_amd/libcimbar_hip.so}
 B=${B:-libcimbar_amd/libcimbar_hip_nofuse.so}
 for k in 1 2 3; do
   for lib in $A $B; do
-    CIMBAR_HIP_LIB=$PWD/$lib python bench.py --no-cpu-baseline --no-extras > /tmp/ab_$$.json 2> /tmp/ab_$$.err
+    CIMBAR_HIP_LIB=$PWD/$lib python bench.py --full --no-cpu-baseline --no-extras > /tmp/ab_$$.json 2> /tmp/ab_$$.err
     python - "$lib" /tmp/ab_$$.json <<'PY'
 import json, sys
 try:

@@ -6,7 +6,7 @@ LIB=$PWD/libcimbar_amd/variants/libcimbar_hip_probes.so
 [ -f $LIB ] || { echo "build the probe library first: python -m libcimbar_amd.build --probes"; exit 1; }
 export CIMBAR_HIP_LIB=$LIB
 for m in ${MASKS:-0 127 1 2 4 8 16 32 64 0}; do
-  CIMBAR_HIP_DEBUG_SKIP=$m python bench.py --probe-run --no-cpu-baseline --no-extras --steps 100 > /tmp/s_$$.json 2> /tmp/s_$$.err
+  CIMBAR_HIP_DEBUG_SKIP=$m python bench.py --probe-run --full --no-cpu-baseline --no-extras --steps 100 > /tmp/s_$$.json 2> /tmp/s_$$.err
   python - "$m" /tmp/s_$$.json <<'PY'
 import json, sys
 try:
