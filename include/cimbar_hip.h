@@ -322,6 +322,42 @@ int64_t cimbar_hip_scan_extract_decode_batch_fmt(cimbar_hip_ctx* ctx, const uint
                                                  int img_mem, int preprocess, int color_correction, uint8_t* chunks, uint32_t* masks, int* status,
                                                  int out_mem, void* hip_stream);
 
+/* ---- mode auto-detection: captures whose mode is not known ----------------------------------------------------------------------------
+ * The reference's web receiver in its default auto mode (web/recv.js:112,346,378) tries the modes [66, 68, 67, 4] in turn, each try being
+ * cimbard_configure_decode(mode) + cimbard_scan_extract_decode, and locks onto the first mode that returns bytes. An auto-detection object holds
+ * one decoder per candidate mode and ONE carried colour-correction matrix, shared by every mode -- as the reference's thread_local one is
+ * (CimbDecoder.cpp:69-73; cimbard_configure_decode leaves it alone, cimbar_recv_js.cpp:272-288).
+ *
+ * cimbar_hip_auto_create: `modes` = n_modes distinct values of 68 67 66 4 8 (anything else, a repeat or n_modes outside 1..5: CIMBAR_HIP_EINVAL).
+ *   The carried matrix starts inactive. cimbar_hip_auto_bufsize = the per-capture slot stride = the largest cimbar_hip_mode_bufsize of the modes.
+ * cimbar_hip_auto_scan_extract_decode_batch_fmt: for each capture IN BATCH ORDER the result is that of this loop on one thread of the reference:
+ *       for m in candidates: Config::update(m); r = extract + Decoder::decode_fountain in mode m (preprocess, color_correction as given);
+ *                            if r > 0: accept m, stop
+ *   with the matrix carried across captures, candidates and calls. Candidates: `order` (n_order distinct modes the object was created with, tried
+ *   in that order; a caller that has locked onto a mode passes just that one), or NULL = the creation order. Per capture f:
+ *     modes_out[f] = the accepted mode, 0 if no candidate delivered a chunk (or the extractor found no frame);
+ *     chunks[f * cimbar_hip_auto_bufsize + j * chunk_size(modes_out[f]) ..] = slot j of the accepted attempt, masks[f] its delivered slots, the
+ *       rest of the capture's slot zero (a capture with mode 0: all zero, mask 0);
+ *     status[f] = the extraction status (0 FAILURE, 1 SUCCESS, 2 NEEDS_SHARPEN) of the accepted attempt, or of the first candidate where none was
+ *       accepted (it only differs between modes in NEEDS_SHARPEN, which depends on the target size: Corners::is_granular_scale).
+ *   `format`, `preprocess` (1 / 0 / -1), img_mem / out_mem and hip_stream as for cimbar_hip_scan_extract_decode_batch_fmt. Returns the good bytes
+ *   over the batch, for device outputs too: the call reads back one count per candidate and one flag per settling round (the acceptance is
+ *   guessed from the symbol halves and checked after the colour halves; DESIGN_WIDENING.md "Mode detection"), so it always returns complete.
+ *   Erasure decoding, multi-capture combining and undistortion are not offered here. CIMBAR_HIP_EINVAL / _EDIM / _EHIP as the neighbouring
+ *   entry points, the message in cimbar_hip_auto_last_error.
+ * cimbar_hip_auto_reset_ccm / _get_ccm / _set_ccm: the ONE carried matrix, as cimbar_hip_reset_ccm / _get_ccm / _set_ccm for a context. */
+typedef struct cimbar_hip_auto cimbar_hip_auto;
+int cimbar_hip_auto_create(int device, const int* modes, int n_modes, cimbar_hip_auto** out);
+void cimbar_hip_auto_destroy(cimbar_hip_auto* a);
+int cimbar_hip_auto_bufsize(const cimbar_hip_auto* a);
+const char* cimbar_hip_auto_last_error(const cimbar_hip_auto* a);
+int cimbar_hip_auto_reset_ccm(cimbar_hip_auto* a);
+int cimbar_hip_auto_get_ccm(cimbar_hip_auto* a, float out9[9]);
+int cimbar_hip_auto_set_ccm(cimbar_hip_auto* a, const float m9[9]);
+int64_t cimbar_hip_auto_scan_extract_decode_batch_fmt(cimbar_hip_auto* a, const int* order, int n_order, const uint8_t* img, unsigned width,
+                                                      unsigned height, int format, int n, int img_mem, int preprocess, int color_correction,
+                                                      uint8_t* chunks, uint32_t* masks, int* modes_out, int* status, int out_mem, void* hip_stream);
+
 /* ---- lens undistortion: `cimbar --undistort` (src/exe/cimbar/cimbar.cpp:135-145) -----------------------------------------------------------
  * Undistort<SimpleCameraCalibration> (src/lib/extractor/Undistort.h:11-62) in front of Extractor::extract, on the device. Captures as for the _fmt
  * entry points above (`format`, img_mem, out_mem, hip_stream, ctx->err via cimbar_hip_last_error on failure).

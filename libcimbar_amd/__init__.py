@@ -4,5 +4,5 @@ The product is the C-ABI shared library (include/cimbar_hip.h, libcimbar_amd/csr
 adapter in libcimbar_amd/host/. This Python package is plumbing: a ctypes binding used by tests, bench.py and the
 multi-GPU driver, plus the synthetic-frame generator. There is no CPU decode path in here.
 """
-from .decoder import HipDecoder, CimbarHipError, load_library  # noqa: F401
+from .decoder import HipDecoder, AutoDecoder, CimbarHipError, load_library  # noqa: F401
 from . import modeb  # noqa: F401

@@ -78,7 +78,7 @@ RECV_HEADER = os.path.join(os.path.dirname(HERE), "include", "cimbar_recv_hip.h"
 def build_recv(force=False, verbose=False):
     """libcimbar_recv_hip.so: the reference's own receive-side C symbols for the decode step (cimbard_configure_decode / _get_bufsize /
     _scan_extract_decode, cimbar_recv_js.h:16-17,36) over libcimbar_hip.so -- plain C++ (g++), include/cimbar_recv_hip.h."""
-    deps = [RECV_SRC, RECV_HEADER, HEADER]
+    deps = [RECV_SRC, RECV_HEADER, os.path.join(os.path.dirname(HERE), "include", "cimbar_recv_hip_auto.h"), HEADER]
     if not force and os.path.exists(RECV_OUT) and os.path.getmtime(RECV_OUT) >= max(os.path.getmtime(p) for p in deps) \
             and os.path.getmtime(RECV_OUT) >= os.path.getmtime(OUT):
         return RECV_OUT

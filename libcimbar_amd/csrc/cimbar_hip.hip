@@ -64,5 +64,6 @@
 #undef CIMBAR_NS
 
 #include "api.hip.inc"
+#include "automode.hip.inc"
 #include "comm.hip.inc"
 #include "png.hip.inc"

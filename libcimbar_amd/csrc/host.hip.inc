@@ -486,7 +486,7 @@ constexpr int ERASURE_MAX_DEFAULT = RS_PARITY - 8;
 inline int erasure_max(const cimbar_hip_ctx* ctx) { return ctx->er_max < 0 ? ERASURE_MAX_DEFAULT : ctx->er_max; }
 
 int enqueue(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_rgb, int n, int pre, int cc, uint8_t* d_chunks, uint32_t* d_masks, int plain = 0,
-            bool pipe = false, const int* d_sel = nullptr, int sel_stride = 0)
+            bool pipe = false, const int* d_sel = nullptr, int sel_stride = 0, bool symbols_only = false)
 {
 	ctx->grp_valid = false;   // (the group taps describe a combined batch only until the next batch of any kind)
 	const bool tm = ctx->timing && !pipe;
@@ -617,7 +617,7 @@ int enqueue(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_rgb, int n, in
 			if (!(ctx->dbg_skip & 8)) hipLaunchKernelGGL(k_frame_mid, dim3(m), dim3(64), 0, s, d_rgb, ctx->d_cellmean, ctx->tb, d_chunks, ctx->d_rs_ok, cc, ctx->d_states, ctx->d_ccm_frames, fa, plain);
 			return s == st ? mark() : hipSuccess;
 		}
-		if (!(ctx->dbg_skip & 16)) hipLaunchKernelGGL(k_colors, dim3(K5_BLOCKS, m), dim3(256), 0, s, d_rgb, ctx->d_cellmean, ctx->tb, ctx->d_ccm_frames,
+		if (!(ctx->dbg_skip & 16)) hipLaunchKernelGGL((k_colors<false>), dim3(K5_BLOCKS, m), dim3(256), 0, s, d_rgb, ctx->d_cellmean, ctx->tb, ctx->d_ccm_frames,
 		                   ctx->d_carry, ctx->d_flood, ctx->d_drift, ctx->d_colors, ctx->d_ccm_used, fa);
 		if (hipError_t e = (s == st ? mark() : hipSuccess)) return e;
 		if (LEGACY) hipLaunchKernelGGL((k_rs<(LEGACY ? CELL_BITS : 6)>), dim3((m * ALL_BLOCKS + 3) / 4), dim3(256), 0, s, ctx->d_symbols, ctx->tb, fa, m, 0, d_chunks, ctx->d_rs_ok, 0, ctx->d_colors);
@@ -649,7 +649,8 @@ int enqueue(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_rgb, int n, in
 		ctx->pipe_gathered[set] = false;
 	} else if (!split) {
 		HIPCHK(tail(st, f0, n, 0));
-		HIPCHK(tail(st, f0, n, 1));
+		// (symbols_only: the mode auto-detection runs the colour half itself, once the matrix in force is known per frame: automode_mode.hip.inc)
+		if (!symbols_only) HIPCHK(tail(st, f0, n, 1));
 	} else {
 		// parts alternate between the caller's stream and stream2; pairs are issued together so that both streams always have work
 		const int P = ctx->tail_parts;

@@ -421,6 +421,9 @@ constexpr int K5_BLOCKS = (GRID_CELLS + 256 * K5_CELLS - 1) / (256 * K5_CELLS);
 // requested at the top, in one go -- the frame's flag, the cells' colour means (walked in GRID order, where K1 left them: contiguous dwords,
 // the cell index follows from the slot arithmetically -- no look-up of a slot table first), the probe for the newest matrix and, speculatively,
 // the frame's own matrix (the one the probe finds whenever the frame carried a header, i.e. nearly always).
+// CARRY_IN (the mode auto-detection, automode_mode.hip.inc): `carry` is [n][10], the matrix in force for each frame that has none of its own --
+// the frame before it in the reference's order may be an attempt in another mode, so there is no probe over the batch.
+template <bool CARRY_IN>
 __global__ __launch_bounds__(256) void k_colors(const uint8_t* __restrict__ rgb, const uint32_t* __restrict__ cellmean, Tables tb,
                                                 const float* __restrict__ ccm_frames,
                                                 const float* __restrict__ carry, const uint32_t* __restrict__ flood_flag,
@@ -443,7 +446,8 @@ __global__ __launch_bounds__(256) void k_colors(const uint8_t* __restrict__ rgb,
 	// newest frame g <= f of the batch that produced a matrix of its own: the workgroup probes 256 frames per round (thread t looks
 	// at frame base - t), so a batch without any matrix costs n/256 rounds per workgroup instead of n dependent loads on one lane
 	int g = -1;
-	for (int base = f; base >= 0 && g < 0; base -= 256) {
+	if constexpr (CARRY_IN) g = ccm_frames[(size_t)f * 10 + 9] != 0.0f ? f : -1;
+	else for (int base = f; base >= 0 && g < 0; base -= 256) {
 		const int cand = base - (int)threadIdx.x;
 		const bool valid = cand >= 0 && ccm_frames[(size_t)cand * 10 + 9] != 0.0f;
 		const unsigned long long m = __ballot(valid);
@@ -453,7 +457,7 @@ __global__ __launch_bounds__(256) void k_colors(const uint8_t* __restrict__ rgb,
 		__syncthreads();
 	}
 	if (threadIdx.x < 10) {
-		const float v = g == f ? own : (g >= 0 ? ccm_frames[(size_t)g * 10 + threadIdx.x] : carry[threadIdx.x]);
+		const float v = g == f ? own : (g >= 0 ? ccm_frames[(size_t)g * 10 + threadIdx.x] : carry[(CARRY_IN ? (size_t)f * 10 : 0) + threadIdx.x]);
 		s_m[threadIdx.x] = v;
 		if (blockIdx.x == 0) ccm_used[(size_t)f * 10 + threadIdx.x] = v;
 	}

@@ -115,5 +115,6 @@ struct Tables {
 }  // namespace
 
 #include "host.hip.inc"
+#include "automode_mode.hip.inc"
 
 }  // namespace CIMBAR_NS

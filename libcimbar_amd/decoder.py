@@ -37,6 +37,8 @@ EXPORTS = (
     "cimbar_hip_undistort_calibrate_fmt", "cimbar_hip_undistort_batch_fmt", "cimbar_hip_scan_undistort_extract_decode_batch_fmt",
     "cimbar_hip_rs_decode_erasures", "cimbar_hip_set_erasure_decode", "cimbar_hip_get_erasure_decode",
     "cimbar_hip_decode_batch_combined", "cimbar_hip_scan_extract_decode_batch_combined_fmt",
+    "cimbar_hip_auto_create", "cimbar_hip_auto_destroy", "cimbar_hip_auto_bufsize", "cimbar_hip_auto_last_error", "cimbar_hip_auto_reset_ccm",
+    "cimbar_hip_auto_get_ccm", "cimbar_hip_auto_set_ccm", "cimbar_hip_auto_scan_extract_decode_batch_fmt",
 )
 PNG_EHEADER, PNG_ESTREAM, PNG_ECODES, PNG_ESIZE, PNG_ECHECK = -30, -31, -32, -33, -34
 
@@ -146,6 +148,22 @@ def load_library(path=None):
     lib.cimbar_hip_scan_extract_decode_batch_combined_fmt.argtypes = [vp, vp, u32, u32, i32, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp,
                                                                       vp, i32, vp]
     lib.cimbar_hip_scan_extract_decode_batch_combined_fmt.restype = i64
+    lib.cimbar_hip_auto_create.argtypes = [i32, vp, i32, ctypes.POINTER(vp)]
+    lib.cimbar_hip_auto_create.restype = i32
+    lib.cimbar_hip_auto_destroy.argtypes = [vp]
+    lib.cimbar_hip_auto_destroy.restype = None
+    lib.cimbar_hip_auto_bufsize.argtypes = [vp]
+    lib.cimbar_hip_auto_bufsize.restype = i32
+    lib.cimbar_hip_auto_last_error.argtypes = [vp]
+    lib.cimbar_hip_auto_last_error.restype = ctypes.c_char_p
+    lib.cimbar_hip_auto_reset_ccm.argtypes = [vp]
+    lib.cimbar_hip_auto_reset_ccm.restype = i32
+    lib.cimbar_hip_auto_get_ccm.argtypes = [vp, vp]
+    lib.cimbar_hip_auto_get_ccm.restype = i32
+    lib.cimbar_hip_auto_set_ccm.argtypes = [vp, vp]
+    lib.cimbar_hip_auto_set_ccm.restype = i32
+    lib.cimbar_hip_auto_scan_extract_decode_batch_fmt.argtypes = [vp, vp, i32, vp, u32, u32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp]
+    lib.cimbar_hip_auto_scan_extract_decode_batch_fmt.restype = i64
     lib.cimbar_hip_set_erasure_decode.argtypes = [vp, i32, i32, i32]
     lib.cimbar_hip_set_erasure_decode.restype = i32
     lib.cimbar_hip_get_erasure_decode.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32)]
@@ -275,6 +293,28 @@ def comm_destroy(comm):
 
 
 _ERR = {-1: "EINVAL", -2: "EDIM", -3: "ENODEVICE", -4: "EHIP", -5: "ENOMEM"}
+
+
+def _captures(lib, captures, size, fmt):
+    """RGB8 captures as an (n,h,w,3) array, or -- with size=(w,h) and the C ABI's `fmt` (3 RGB, 4 RGBA, 12 NV12, 420) -- n captures of
+    cimbar_hip_capture_bytes(w, h, fmt) bytes each as an (n, bytes) array. Returns (array, n, w, h, fmt)."""
+    captures = np.ascontiguousarray(captures, dtype=np.uint8)
+    if size is None:
+        fmt = int(fmt) if int(fmt) > 0 else 3          # (<= 0 means RGB to the C ABI as well, cimbar_recv_js.cpp:150-151)
+        if fmt == 4 and captures.ndim == 4 and captures.shape[3] == 4:
+            n, h, w = captures.shape[:3]
+            return captures, n, w, h, 4
+        if fmt != 3:
+            raise CimbarHipError(f"captures in format {fmt} need size=(w, h): the array's shape does not say what the frame is")
+        if captures.ndim != 4 or captures.shape[3] != 3:
+            raise CimbarHipError(f"RGB captures are an (n, h, w, 3) array, got {captures.shape}")
+        n, h, w = captures.shape[:3]
+        return captures, n, w, h, 3
+    w, h = size
+    per = int(lib.cimbar_hip_capture_bytes(w, h, int(fmt)))
+    if per == 0 or captures.size % per:
+        raise CimbarHipError(f"captures of {w}x{h} in format {fmt}: {captures.size} bytes is no multiple of {per}")
+    return captures, captures.size // per, w, h, int(fmt)
 
 
 class HipDecoder:
@@ -470,25 +510,7 @@ class HipDecoder:
 
     # ------------------------------------------------------------------ the stage in front: Scanner's image preparation, Deskewer
     def _captures(self, captures, size, fmt):
-        """RGB8 captures as an (n,h,w,3) array, or -- with size=(w,h) and the C ABI's `fmt` (3 RGB, 4 RGBA, 12 NV12, 420) -- n captures of
-        cimbar_hip_capture_bytes(w, h, fmt) bytes each as an (n, bytes) array. Returns (array, n, w, h, fmt)."""
-        captures = np.ascontiguousarray(captures, dtype=np.uint8)
-        if size is None:
-            fmt = int(fmt) if int(fmt) > 0 else 3          # (<= 0 means RGB to the C ABI as well, cimbar_recv_js.cpp:150-151)
-            if fmt == 4 and captures.ndim == 4 and captures.shape[3] == 4:
-                n, h, w = captures.shape[:3]
-                return captures, n, w, h, 4
-            if fmt != 3:
-                raise CimbarHipError(f"captures in format {fmt} need size=(w, h): the array's shape does not say what the frame is")
-            if captures.ndim != 4 or captures.shape[3] != 3:
-                raise CimbarHipError(f"RGB captures are an (n, h, w, 3) array, got {captures.shape}")
-            n, h, w = captures.shape[:3]
-            return captures, n, w, h, 3
-        w, h = size
-        per = int(self._lib.cimbar_hip_capture_bytes(w, h, int(fmt)))
-        if per == 0 or captures.size % per:
-            raise CimbarHipError(f"captures of {w}x{h} in format {fmt}: {captures.size} bytes is no multiple of {per}")
-        return captures, captures.size // per, w, h, int(fmt)
+        return _captures(getattr(self, "_lib", None), captures, size, fmt)
 
     def scan_preprocess(self, captures, size=None, fmt=3):
         """captures -> (binary (n,h,w) uint8 of 0/255, thresholds (n,) int32): Scanner::preprocess_image."""
@@ -725,3 +747,95 @@ class HipDecoder:
         ms = (ctypes.c_float * 16)()
         k = self._check(self._lib.cimbar_hip_stage_times(self._ctx, names, ms, 16), "cimbar_hip_stage_times")
         return {names[i].decode(): float(ms[i]) for i in range(k)}
+
+
+class AutoDecoder:
+    """Mode auto-detection (cimbar_hip_auto_*): one decoder per candidate mode and ONE carried colour-correction matrix, shared by all of
+    them -- the reference's receiver in auto mode (web/recv.js), batched. See include/cimbar_hip.h."""
+
+    def __init__(self, device=0, modes=(66, 68, 67, 4), lib_path=None):
+        self._lib = load_library(lib_path)
+        self._a = ctypes.c_void_p()
+        self.modes = tuple(int(m) for m in modes)
+        arr = (ctypes.c_int32 * len(self.modes))(*self.modes)
+        rc = self._lib.cimbar_hip_auto_create(int(device), arr, len(self.modes), ctypes.byref(self._a))
+        if rc != 0:
+            self._a = ctypes.c_void_p()
+            raise CimbarHipError(f"cimbar_hip_auto_create(device={device}, modes={self.modes}) failed: {_ERR.get(rc, rc)} "
+                                 "(a gfx950 GPU is required; there is no CPU fallback)")
+        self.device = device
+        self.slot = self._lib.cimbar_hip_auto_bufsize(self._a)
+
+    def close(self):
+        if getattr(self, "_a", None) and self._a.value:
+            self._lib.cimbar_hip_auto_destroy(self._a)
+            self._a = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc, what):
+        if rc < 0:
+            msg = self._lib.cimbar_hip_auto_last_error(self._a).decode("utf-8", "replace")
+            raise CimbarHipError(f"{what}: {_ERR.get(int(rc), rc)} {msg}")
+        return rc
+
+    def bufsize(self):
+        return self._check(self._lib.cimbar_hip_auto_bufsize(self._a), "cimbar_hip_auto_bufsize")
+
+    def reset_ccm(self):
+        self._check(self._lib.cimbar_hip_auto_reset_ccm(self._a), "cimbar_hip_auto_reset_ccm")
+
+    def get_ccm(self):
+        out = (ctypes.c_float * 9)()
+        rc = self._check(self._lib.cimbar_hip_auto_get_ccm(self._a, out), "cimbar_hip_auto_get_ccm")
+        return bool(rc), np.array(list(out), dtype=np.float32).reshape(3, 3)
+
+    def set_ccm(self, m):
+        arr = (ctypes.c_float * 9)(*[float(x) for x in np.asarray(m, dtype=np.float32).reshape(-1)])
+        self._check(self._lib.cimbar_hip_auto_set_ccm(self._a, arr), "cimbar_hip_auto_set_ccm")
+
+    def _order(self, order):
+        if order is None:
+            return None, 0
+        o = np.ascontiguousarray(order, dtype=np.int32)
+        return o, o.size
+
+    def scan_extract_decode_batch_raw(self, captures, preprocess=-1, color_correction=2, size=None, fmt=3, order=None):
+        """-> (good_bytes, slots (n, bufsize) uint8, masks (n,), modes (n,), status (n,)): the C ABI's outputs as they are"""
+        captures, n, w, h, fmt = _captures(self._lib, captures, size, fmt)
+        slots = np.zeros((n, self.slot), dtype=np.uint8)
+        masks = np.zeros(n, dtype=np.uint32)
+        modes = np.zeros(n, dtype=np.int32)
+        status = np.zeros(n, dtype=np.int32)
+        o, no = self._order(order)
+        rc = self._check(self._lib.cimbar_hip_auto_scan_extract_decode_batch_fmt(
+            self._a, o.ctypes.data if o is not None else None, no, captures.ctypes.data, w, h, fmt, n, MEM_HOST, int(preprocess),
+            int(color_correction), slots.ctypes.data, masks.ctypes.data, modes.ctypes.data, status.ctypes.data, MEM_HOST, None),
+            "cimbar_hip_auto_scan_extract_decode_batch_fmt")
+        return int(rc), slots, masks, modes, status
+
+    def scan_extract_decode_batch(self, captures, preprocess=-1, color_correction=2, size=None, fmt=3, order=None):
+        """-> (good_bytes, chunks, masks (n,), modes (n,), status (n,)); chunks[f] = (chunks per frame, chunk size) of the accepted mode,
+        an empty (0, 0) array for a capture no candidate delivered for"""
+        total, slots, masks, modes, status = self.scan_extract_decode_batch_raw(captures, preprocess, color_correction, size, fmt, order)
+        chunks = []
+        for f in range(len(modes)):
+            if modes[f] == 0:
+                chunks.append(np.zeros((0, 0), np.uint8))
+                continue
+            g = geometry.for_mode(int(modes[f]))
+            chunks.append(slots[f, : g.CHUNKS_PER_FRAME * g.CHUNK].reshape(g.CHUNKS_PER_FRAME, g.CHUNK))
+        return total, chunks, masks, modes, status
+
+    def scan_extract_decode_device(self, d_captures, w, h, n, d_slots, d_masks, d_modes, d_status, preprocess=-1, color_correction=2, fmt=3,
+                                   order=None, stream=None):
+        """device-memory captures and outputs (raw pointers) on `stream` (a HIP stream handle, or None)"""
+        o, no = self._order(order)
+        return self._check(self._lib.cimbar_hip_auto_scan_extract_decode_batch_fmt(
+            self._a, o.ctypes.data if o is not None else None, no, ctypes.c_void_p(d_captures), w, h, int(fmt), n, MEM_DEVICE, int(preprocess),
+            int(color_correction), ctypes.c_void_p(d_slots), ctypes.c_void_p(d_masks), ctypes.c_void_p(d_modes), ctypes.c_void_p(d_status),
+            MEM_DEVICE, ctypes.c_void_p(stream) if stream else None), "cimbar_hip_auto_scan_extract_decode_batch_fmt(device)")

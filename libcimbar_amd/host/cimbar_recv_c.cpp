@@ -3,6 +3,7 @@
 //     cimbard_get_bufsize            /root/reference/src/lib/cimbar_js/cimbar_recv_js.cpp:143-146
 //     cimbard_scan_extract_decode    cimbar_recv_js.cpp:148-189 (get_rgb :94-120, Extractor::extract, Decoder::decode_fountain, escrow_buffer_writer)
 //     cimbard_configure_decode       cimbar_recv_js.cpp:272-288
+// and, not in the reference, cimbard_hip_scan_extract_decode_auto (include/cimbar_recv_hip_auto.h): web/recv.js's auto mode in one call
 #include <atomic>
 #include <cstdint>
 #include <cstdio>
@@ -12,6 +13,7 @@
 
 #include "../../include/cimbar_hip.h"
 #include "../../include/cimbar_recv_hip.h"
+#include "../../include/cimbar_recv_hip_auto.h"
 
 #ifdef CIMBARD_HOST_REST
 // A build of the reference that keeps the rest of its cimbar_recv_js.cpp (sink, zstd: host code) beside this file: its own configure -- renamed
@@ -57,6 +59,28 @@ struct ThreadDecoder {
 	}
 };
 thread_local ThreadDecoder t_dec;
+
+// the auto mode's decoder: one auto-detection object per calling thread over the web receiver's candidates (recv.js:346,378)
+constexpr int AUTO_MODES[4] = {66, 68, 67, 4};
+struct ThreadAuto {
+	cimbar_hip_auto* a = nullptr;
+	int device = -1;
+	~ThreadAuto() { if (a) cimbar_hip_auto_destroy(a); }
+	int ensure(int want_device)
+	{
+		if (a && device == want_device) return 0;
+		if (a) { cimbar_hip_auto_destroy(a); a = nullptr; }
+		const int rc = cimbar_hip_auto_create(want_device, AUTO_MODES, 4, &a);
+		if (rc != 0 || !a) {
+			t_dec.report = "cimbar_hip_auto_create failed (" + std::to_string(rc) + "): no gfx950 device for the decode path";
+			a = nullptr;
+			return rc ? rc : CIMBAR_HIP_EHIP;
+		}
+		device = want_device;
+		return 0;
+	}
+};
+thread_local ThreadAuto t_auto;
 
 }  // namespace
 
@@ -122,6 +146,37 @@ int cimbard_scan_extract_decode(const unsigned char* imgdata, unsigned imgw, uns
 	for (unsigned j = 0; j < per; ++j)
 		if (mask & (1u << j)) std::memcpy(bufspace + (size_t)cs * used++, chunks + (size_t)cs * j, cs);
 	t_dec.report = "decoded " + std::to_string(used * cs) + " bytes" + (status == 2 ? " (needs sharpen)" : "");
+	return (int)(used * cs);
+}
+
+int cimbard_hip_scan_extract_decode_auto(const unsigned char* imgdata, unsigned imgw, unsigned imgh, int format, unsigned char* bufspace,
+                                         unsigned bufsize, int* mode_out)
+{
+	if (mode_out) *mode_out = 0;
+	if (format <= 0) format = 3;
+	if (imgw == 0 || imgh == 0) return -1;
+	if (bufsize < (unsigned)cimbar_hip_mode_bufsize(68)) return -2;   // 7500: the largest cimbard_get_bufsize of 66 68 67 4
+	if (!imgdata || !bufspace) { t_dec.report = "null buffer"; return -4; }
+	if (t_auto.ensure(device_ordinal()) != 0) return -4;
+	uint8_t slot[CIMBAR_HIP_MAX_FRAME_BYTES];
+	uint32_t mask = 0;
+	int mode = 0, status = 0;
+	const int64_t rc = cimbar_hip_auto_scan_extract_decode_batch_fmt(t_auto.a, nullptr, 0, imgdata, imgw, imgh, format, 1, CIMBAR_HIP_MEM_HOST,
+	                                                                 /*preprocess*/ 1, /*color_correction*/ 2, slot, &mask, &mode, &status,
+	                                                                 CIMBAR_HIP_MEM_HOST, nullptr);
+	if (rc < 0) {
+		t_dec.report = std::string("cimbar_hip_auto_scan_extract_decode_batch_fmt failed (") + std::to_string((long long)rc) + "): " +
+		               cimbar_hip_auto_last_error(t_auto.a);
+		return -4;
+	}
+	if (status <= 0) { t_dec.report = "no frame found"; return -3; }
+	if (mode_out) *mode_out = mode;
+	if (mode == 0) { t_dec.report = "no mode delivered a chunk"; return 0; }
+	const int per = mode == 66 ? 6 : (mode == 4 || mode == 8 ? 10 : 12), cs = cimbar_hip_mode_bufsize(mode) / per;
+	unsigned used = 0;
+	for (int j = 0; j < per; ++j)
+		if (mask & (1u << j)) std::memcpy(bufspace + (size_t)cs * used++, slot + (size_t)cs * j, cs);
+	t_dec.report = "mode " + std::to_string(mode) + ": decoded " + std::to_string(used * cs) + " bytes";
 	return (int)(used * cs);
 }
 
