@@ -179,12 +179,31 @@ int cimbar_hip_set_ccm(cimbar_hip_ctx* ctx, const float m9[9]);
  * them (cimbar_hip_rs_decode_erasures below), and a chunk whose blocks are then all accepted joins the mask with its bytes. Chunks already in
  * the mask, colour chunks, the per-block flags and the colour-correction state are never changed; the mask only gains bits.
  *   sym_distance  : <= 0 turns it off (nothing extra is launched); 1 .. 64 the threshold
- *   colour_margin : kept and reported; colour blocks are not retried
+ *   colour_margin : kept and reported, not used: the colour blocks have a retry and a setting of their own,
+ *                   cimbar_hip_set_colour_erasure_decode below
  *   max_erasures  : < 0 = the default, parity - 8 (22 / 28 / 25 in modes 68 / 67 / 66); at most the parity bytes
  * Modes 4 and 8 (one coupled stream) refuse it (EINVAL); cimbar_hip_decode_plain_batch returns EINVAL while it is on. Takes effect for
  * batches issued after the call. get: writes the three values in force (max_erasures resolved), returns 1 if on, 0 if off. */
 int cimbar_hip_set_erasure_decode(cimbar_hip_ctx* ctx, int sym_distance, int colour_margin, int max_erasures);
 int cimbar_hip_get_erasure_decode(cimbar_hip_ctx* ctx, int* sym_distance, int* colour_margin, int* max_erasures);
+
+/* Colour erasure decoding (off after cimbar_hip_create; independent of cimbar_hip_set_erasure_decode: either, both or neither may be on). With
+ * colour_margin > 0 the same entry points retry the COLOUR chunks a frame's mask lacks, after the symbol retry where that runs. A cell's
+ * confidence is the classifier's margin: (second-smallest) - (smallest) squared distance of CimbDecoder::get_best_color, computed from the
+ * mean and the matrix the colour pass classified the cell from (130 050 for pure green, cyan and yellow, 390 150 for pure magenta, 0 for
+ * white, black, grey and every tie).
+ * A colour-stream byte comes from four cells; it is flagged when one of them has a margin below colour_margin, the flagged bytes with the
+ * smallest margins become erasures (at most max_erasures per block, ties to the lower byte position), and retry and acceptance are those of
+ * the symbol retry. Chunks already in the mask, symbol chunks, the per-block flags, the colours and the colour-correction state are never
+ * changed; the mask only gains bits. In the combined calls the group outputs pick up what the members' retry delivered.
+ *   colour_margin : <= 0 turns it off (nothing extra is launched); CIMBAR_HIP_COLOUR_MARGIN_SUGGESTED is the value the tests use, chosen on
+ *                   rendered frames (DESIGN_WIDENING.md "Colour erasure decoding"); camera captures are unmeasured
+ *   max_erasures  : < 0 = the default, parity - 8; at most the parity bytes (else EINVAL)
+ * Modes 4 and 8 refuse a positive margin (EINVAL); cimbar_hip_decode_plain_batch returns EINVAL while it is on. Takes effect for batches
+ * issued after the call. get: writes the values in force (max_erasures resolved), returns 1 if on, 0 if off. */
+#define CIMBAR_HIP_COLOUR_MARGIN_SUGGESTED 32512
+int cimbar_hip_set_colour_erasure_decode(cimbar_hip_ctx* ctx, int colour_margin, int max_erasures);
+int cimbar_hip_get_colour_erasure_decode(cimbar_hip_ctx* ctx, int* colour_margin, int* max_erasures);
 
 /* Errors-and-erasures Reed-Solomon decode of n caller-given blocks of the context's code (RS(155,125) in modes 68 / 4 / 8, RS(179,143) in
  * 67, RS(168,135) in 66): libcorrect's correct_reed_solomon_decode_with_erasures, bit-exact, plus an acceptance check libcorrect does not
@@ -225,7 +244,8 @@ int cimbar_hip_rs_decode_erasures(cimbar_hip_ctx* ctx, const uint8_t* blocks, in
  *                delivered it, else chunk j of the lowest-index member that delivered it; gmask = the combined mask | the members' masks.
  *                With erasure decoding on (cimbar_hip_set_erasure_decode, modes 68 / 67 / 66) the symbol chunks still missing are retried
  *                with the stream bytes of symbol-disputed cells as erasures (smallest margin first, then stream position, at most
- *                max_erasures per block), accepted as in the per-capture retry; colour chunks are not retried.
+ *                max_erasures per block), accepted as in the per-capture retry; colour chunks are not retried in the group decode (with
+ *                cimbar_hip_set_colour_erasure_decode on, the members' own colour retry runs before the group fill, which takes its chunks).
  *   chunks / masks / status  per capture, as for the plain call; groups_out: n ints (may be NULL)
  *   gchunks / gmasks         n slots of 12 * 625 bytes / one mask; slots at or above the group count are zero
  *   n_groups                 the group count (may be NULL)
@@ -485,7 +505,10 @@ enum {
 	 * CIMBAR_HIP_EINVAL after any other batch). The taps above keep describing that batch's per-capture decode. */
 	CIMBAR_HIP_TAP_GROUP_CELLS = 10,  /* n_groups * cells bytes: the group's combined cell, colour << 4 | symbol */
 	CIMBAR_HIP_TAP_GROUP_MARGIN = 11, /* n_groups * cells u16  : the symbol's margin, 0xFFFF where the members' symbols agree */
-	CIMBAR_HIP_TAP_GROUPS = 12        /* n int32               : the group of every capture, -1 for none */
+	CIMBAR_HIP_TAP_GROUPS = 12,       /* n int32               : the group of every capture, -1 for none */
+	/* the colour retry of the last batch (cimbar_hip_set_colour_erasure_decode; CIMBAR_HIP_EINVAL when that batch ran with the setting off) */
+	CIMBAR_HIP_TAP_COLOUR_MARGIN = 13 /* n * cells u32         : the classifier's margin of every cell, by linear cell index, of the frames the retry
+	                                     worked on; 0xFFFFFFFF for all cells of a frame it skipped (all colour chunks in the mask) */
 };
 int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_bytes);
 

@@ -1,4 +1,4 @@
-// erasure.hip.inc -- part of cimbar_hip.hip (one translation unit; included inside its anonymous namespace, after k3_rs.hip.inc).
+// erasure.hip.inc -- part of cimbar_hip.hip (one translation unit; included inside its anonymous namespace, after k3_rs.hip.inc and k4_frame.hip.inc).
 // E3: Reed-Solomon errors-and-erasures decode of the mode's RS(RS_BLOCK, RS_DATA)
 // ------------------------------------------------------------------------------------------------ E3 errors-and-erasures
 // libcorrect's correct_reed_solomon_decode_with_erasures (decode.c:381-508) restated, one block per wavefront, for blocks whose erasure
@@ -255,6 +255,28 @@ __global__ __launch_bounds__(256) void k_rs_erasures(const uint8_t* __restrict__
 
 // ------------------------------------------------------------------------------------------------ erasure retry of a decoded frame
 constexpr int ERASURE_SLACK = 6;
+// the selection both retries share: the rank of each flagged byte (score > 0) among the flagged ones, higher score first, then lower position;
+// the e_max best become erasures, pos[rank] = byte position. One wavefront per block; returns the erasure count (wave-uniform), pos visible
+// to the wave.
+template <class T>
+__device__ __forceinline__ int er_select(const T* score, int lane, int e_max, uint8_t* pos)
+{
+	int mine = 0;
+	for (int k = lane; k < RS_BLOCK; k += 64) {
+		const int sk = score[k];
+		if (sk <= 0) continue;
+		int rank = 0;
+		for (int q = 0; q < RS_BLOCK; ++q) {
+			const int sq = score[q];
+			rank += (sq > sk || (sq == sk && q < k)) ? 1 : 0;
+		}
+		if (rank < e_max) { pos[rank] = (uint8_t)k; ++mine; }
+	}
+	for (int o = 32; o >= 1; o >>= 1) mine += __shfl_xor(mine, o);
+	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+	__builtin_amdgcn_wave_barrier();
+	return mine;
+}
 // Opt-in (cimbar_hip_set_erasure_decode), launched after k_frame_end on the same stream, one workgroup per frame, modes 68 / 67 / 66.
 // A frame whose symbol chunks are all in the mask returns at once (a clean batch costs one launch). Otherwise the four waves walk the symbol
 // blocks of the chunks the mask lacks:
@@ -268,7 +290,7 @@ constexpr int ERASURE_SLACK = 6;
 //    block it decoded is decoded again with none (libcorrect's errors-only result, because k_frame_end has zeroed the slots of the chunks the
 //    mask lacks). Then a chunk whose blocks are now all accepted (status 1) gets its bytes and its mask bit; the slots of chunks still
 //    missing are zeroed again. Chunks already in the mask, the colour chunks, rs_ok, the frame state and the colour-correction carry are
-//    not touched.
+//    not touched. (The colour chunks have a retry of their own: k_colour_erasure_frame below.)
 __global__ __launch_bounds__(256) void k_erasure_frame(const uint32_t* __restrict__ plane, Tables tb, const uint8_t* __restrict__ symbols,
                                                        const int8_t* __restrict__ drift, const uint32_t* __restrict__ flood_flag,
                                                        const uint8_t* __restrict__ rs_ok, uint8_t* __restrict__ chunks, uint32_t* __restrict__ masks,
@@ -320,22 +342,7 @@ __global__ __launch_bounds__(256) void k_erasure_frame(const uint32_t* __restric
 		__builtin_amdgcn_wave_barrier();
 		int e = 0;
 		if (!ok) {
-			// rank of each flagged byte among the flagged ones (higher score first, then lower position); the e_max best become erasures
-			int mine = 0;
-			for (int k = lane; k < RS_BLOCK; k += 64) {
-				const int sk = score[k];
-				if (sk <= 0) continue;
-				int rank = 0;
-				for (int q = 0; q < RS_BLOCK; ++q) {
-					const int sq = score[q];
-					rank += (sq > sk || (sq == sk && q < k)) ? 1 : 0;
-				}
-				if (rank < e_max) { s_pos[wv][rank] = (uint8_t)k; ++mine; }
-			}
-			for (int o = 32; o >= 1; o >>= 1) mine += __shfl_xor(mine, o);
-			e = mine;
-			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-			__builtin_amdgcn_wave_barrier();
+			e = er_select(score, lane, e_max, s_pos[wv]);
 			if (e == 0) { if (lane == 0) s_st[b] = -2; continue; }   // nothing to erase: errors-only already failed it
 		}
 		int nerr = 0;
@@ -366,6 +373,122 @@ __global__ __launch_bounds__(256) void k_erasure_frame(const uint32_t* __restric
 	__syncthreads();
 	const uint32_t m = s_new;
 	for (int j = 0; j < SYM_CHUNKS; ++j)
+		if (!(m & (1u << j)))
+			for (int k = threadIdx.x; k < CHUNK; k += 256) fc[(size_t)j * CHUNK + k] = 0;
+}
+
+// ------------------------------------------------------------------------------------------------ colour erasure retry of a decoded frame
+// Opt-in (cimbar_hip_set_colour_erasure_decode), launched after k_frame_end (and after k_erasure_frame where that runs) on the same stream, one
+// workgroup of four wavefronts per frame, modes 68 / 67 / 66. A frame whose colour chunks are all in the mask returns at once (worked[f] = 0:
+// CIMBAR_HIP_TAP_COLOUR_MARGIN reports 0xFFFFFFFF for its cells). Otherwise:
+//  * confidence: margin(c) = (second-smallest) - (smallest) squared distance of get_best_color (color_fit<true>), from exactly what k_colors
+//    classified the cell from -- the K1 cell mean where the frame did not go through the flood pass, mean6x6 at the drifted position where it
+//    did, and the matrix in force (ccm_used[f], active flag included). The workgroup computes it for every cell of the frame once, into
+//    margins[f] (the tap).
+//  * selection: a colour-stream byte comes from four cells (2 bits each); its score is max over them of c_margin - margin(c), flagged when the
+//    score is > 0. The e_max highest scores are kept, ties to the lower byte position (er_select, as k_erasure_frame).
+//  * retry and acceptance as in k_erasure_frame, block for block: a block errors-only decoding failed is decoded again with those erasures (none
+//    flagged: not retried), a block it decoded is decoded again with none; accepted = status 1 and, with erasures, 2 errors <= p - e -
+//    ERASURE_SLACK. A colour chunk whose blocks are all accepted gets its bytes and its mask bit; the slots of colour chunks still missing
+//    are zeroed again. Chunks already in the mask, the symbol chunks, rs_ok, the frame state, the colours and the colour-correction carry are
+//    not touched.
+__global__ __launch_bounds__(256) void k_colour_erasure_frame(const uint8_t* __restrict__ rgb, const uint32_t* __restrict__ cellmean, Tables tb,
+                                                              const uint8_t* __restrict__ colors, const int8_t* __restrict__ drift,
+                                                              const uint32_t* __restrict__ flood_flag, const float* __restrict__ ccm_used,
+                                                              const uint8_t* __restrict__ rs_ok, uint8_t* __restrict__ chunks, uint32_t* __restrict__ masks,
+                                                              uint32_t* margins, uint32_t* __restrict__ worked, int f0, int c_margin, int e_max)
+{
+	if constexpr (LEGACY) return;                          // (one coupled stream: no colour-only blocks; the host never launches it there)
+	constexpr uint32_t COL_MASK = ((1u << COL_CHUNKS) - 1u) << SYM_CHUNKS;
+	constexpr int NB = COL_BLOCKS > 0 ? COL_BLOCKS : 1;
+	const int f = f0 + blockIdx.x;
+	const uint32_t mask = masks[f];
+	if ((mask & COL_MASK) == COL_MASK) {                   // (uniform over the workgroup)
+		if (threadIdx.x == 0) worked[f] = 0;
+		return;
+	}
+	__shared__ RsEraShared s;
+	__shared__ int32_t s_score[4][192];
+	__shared__ uint8_t s_pos[4][64];
+	__shared__ int8_t s_st[NB];
+	__shared__ float s_m[10];
+	er_tables(s);
+	if (threadIdx.x < 10) s_m[threadIdx.x] = ccm_used[(size_t)f * 10 + threadIdx.x];
+	__syncthreads();
+	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+	const bool flooded = flood_flag[f] != 0;
+	const bool active = s_m[9] != 0.0f;
+	uint32_t* mg = margins + (size_t)f * NCELLS;
+	for (int i = threadIdx.x; i < NCELLS; i += 256) {
+		uint32_t col[3];
+		if (flooded) {
+			const ushort2 xy = tb.cell_xy[i];
+			const int x = (int)xy.x + drift[((size_t)f * NCELLS + i) * 2], y = (int)xy.y + drift[((size_t)f * NCELLS + i) * 2 + 1];
+			mean6x6(rgb + (size_t)f * FRAME_RGB, x + 1, y + 1, col);
+		} else {
+			const uint32_t mv = cellmean[(size_t)f * GRID_CELLS + tb.cell_grid[i]];
+			col[0] = mv & 0xFFu; col[1] = (mv >> 8) & 0xFFu; col[2] = (mv >> 16) & 0xFFu;
+		}
+		mg[i] = color_fit<true>((float)col[0], (float)col[1], (float)col[2], s_m, active).margin;
+	}
+	if (threadIdx.x == 0) worked[f] = 1;
+	__syncthreads();                                       // (the margins are read back below by other lanes of this workgroup)
+	const uint8_t* cf = colors + (size_t)f * NCELLS;
+	uint8_t* fc = chunks + (size_t)f * FRAME_BYTES;
+	for (int b = SYM_BLOCKS + wv; b < ALL_BLOCKS; b += 4) {
+		const int j = b / BLOCKS_PER_CHUNK, cb = b - SYM_BLOCKS;
+		if (mask & (1u << j)) { if (lane == 0) s_st[cb] = 2; continue; }
+		const bool ok = rs_ok[(size_t)f * ALL_BLOCKS + b] != 0;
+		uint8_t* enc = s.enc[wv];
+		int32_t* score = s_score[wv];
+		for (int k = lane; k < RS_BLOCK; k += 64) {
+			const int sidx = (RS_BLOCK * cb + k) * 4;
+			int best = INT_MIN;
+			uint32_t v = 0;
+#pragma unroll
+			for (int q = 0; q < 4; ++q) {
+				const int cell = tb.stream_cell[sidx + q];
+				v = (v << 2) | (cf[cell] & 3u);
+				if (!ok) {
+					const int sc = c_margin - (int)mg[cell];
+					best = sc > best ? sc : best;
+				}
+			}
+			enc[k] = (uint8_t)v;
+			score[k] = best;
+		}
+		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+		__builtin_amdgcn_wave_barrier();
+		int e = 0;
+		if (!ok) {
+			e = er_select(score, lane, e_max, s_pos[wv]);
+			if (e == 0) { if (lane == 0) s_st[cb] = -2; continue; }   // nothing to erase: errors-only already failed it
+		}
+		int nerr = 0;
+		int st = er_decode(s, wv, lane, e, s_pos[wv], &nerr);
+		if (st == 1 && e > 0 && 2 * nerr > RS_PARITY - e - ERASURE_SLACK) st = 0;   // (the slack rule of k_erasure_frame)
+		if (st == 1) {
+			uint8_t* dst = fc + (size_t)j * CHUNK + (size_t)(b % BLOCKS_PER_CHUNK) * RS_DATA;
+			for (int k = lane; k < RS_DATA; k += 64) dst[k] = enc[k];
+		}
+		if (lane == 0) s_st[cb] = (int8_t)st;
+	}
+	__syncthreads();
+	__shared__ uint32_t s_new;
+	if (threadIdx.x == 0) {
+		uint32_t m = mask;
+		for (int j = SYM_CHUNKS; j < CHUNKS; ++j) {
+			if (mask & (1u << j)) continue;
+			bool all = true;
+			for (int q = 0; q < BLOCKS_PER_CHUNK; ++q) all = all && s_st[j * BLOCKS_PER_CHUNK + q - SYM_BLOCKS] == 1;
+			if (all) m |= 1u << j;
+		}
+		s_new = m;
+		masks[f] = m;
+	}
+	__syncthreads();
+	const uint32_t m = s_new;
+	for (int j = SYM_CHUNKS; j < CHUNKS; ++j)
 		if (!(m & (1u << j)))
 			for (int k = threadIdx.x; k < CHUNK; k += 256) fc[(size_t)j * CHUNK + k] = 0;
 }

@@ -11,6 +11,8 @@ struct cimbar_hip_ctx {
 	uint32_t* h_flagged = nullptr;    // pinned, written by k_count_flagged at the end of every ordinary batch: [0] frames that left the parallel path, [1] frames of that batch,
 	                                  // [2] frames the exact replay had to take.
 	int er_sym = 0, er_col = -1, er_max = -1;   // cimbar_hip_set_erasure_decode: off while er_sym <= 0 (k_erasure_frame is then never launched)
+	int ec_margin = 0, ec_max = -1;             // cimbar_hip_set_colour_erasure_decode: off while ec_margin <= 0 (k_colour_erasure_frame is then never launched)
+	bool cm_valid = false;                      // the last batch ran the colour retry (CIMBAR_HIP_TAP_COLOUR_MARGIN describes it)
 	uint8_t* d_er_buf = nullptr;                // cimbar_hip_rs_decode_erasures' staging for host-memory calls (grown on demand)
 	size_t d_er_cap = 0;
 	// the group decode (cimbar_hip_decode_batch_combined / _scan_extract_decode_batch_combined_fmt, combine.hip.inc): per capture slot, grown on demand
@@ -44,6 +46,8 @@ struct cimbar_hip_ctx {
 	FrameState* d_states = nullptr;
 	float* d_ccm_frames = nullptr;
 	float* d_ccm_used = nullptr;
+	uint32_t* d_cmargin = nullptr;    // the colour retry's margins [cm_cap][NCELLS], then its per-frame "worked on" words [cm_cap]; allocated once the setting is on
+	int cm_cap = 0;
 	// the pipelined entry point rotates through `pipe_depth` sets of the intermediates above (the members are always the set in
 	// use by the newest batch; the others are parked here) and as many streams, so that several batches are in flight at once
 	static constexpr int MAXP = 4;
@@ -52,6 +56,7 @@ struct cimbar_hip_ctx {
 		uint32_t* d_plane = nullptr; uint32_t* d_cellmean = nullptr; uint8_t* d_symbols = nullptr; uint8_t* d_colors = nullptr;
 		int8_t* d_drift = nullptr; uint32_t* d_flood = nullptr; uint8_t* d_rs_ok = nullptr; FrameState* d_states = nullptr;
 		float* d_ccm_frames = nullptr; float* d_ccm_used = nullptr;
+		uint32_t* d_cmargin = nullptr; int cm_cap = 0;
 	} parked[MAXP];
 	int pipe_depth = 3;               // batches in flight (CIMBAR_HIP_PIPE_DEPTH): 3 measured best once every step reads HBM (4 distinct input batches): 0.81 vs 0.85 ms at 4
 #ifdef CIMBAR_PROBES
@@ -350,6 +355,16 @@ hipError_t regrow(T*& p, size_t count)
 	return hipMalloc(&p, sizeof(T) * count);
 }
 
+// the colour retry's margin buffer follows the scratch set in use: as many frames as the set holds, grown where the setting is on
+int ensure_margin_capacity(cimbar_hip_ctx* ctx)
+{
+	if (ctx->ec_margin <= 0 || ctx->cm_cap >= ctx->cap) return 0;
+	ctx->cm_cap = 0;
+	HIPCHK(regrow(ctx->d_cmargin, (size_t)ctx->cap * (NCELLS + 1)));
+	ctx->cm_cap = ctx->cap;
+	return 0;
+}
+
 int ensure_capacity(cimbar_hip_ctx* ctx, int n)
 {
 	size_t N = (size_t)n;
@@ -360,7 +375,7 @@ int ensure_capacity(cimbar_hip_ctx* ctx, int n)
 		HIPCHK(regrow(ctx->d_masks, N));
 		ctx->out_cap = n;
 	}
-	if (n <= ctx->cap) return 0;
+	if (n <= ctx->cap) return ensure_margin_capacity(ctx);
 	ctx->cap = 0;   // a failed regrow below must not leave a stale capacity behind
 	HIPCHK(regrow(ctx->d_plane, N * PLANE_WORDS));
 	HIPCHK(regrow(ctx->d_cellmean, N * GRID_CELLS));
@@ -375,7 +390,7 @@ int ensure_capacity(cimbar_hip_ctx* ctx, int n)
 	HIPCHK(regrow(ctx->d_ccm_used, N * 10));
 	if (!ctx->d_fw_queue) HIPCHK(regrow(ctx->d_fw_queue, (size_t)FW_GRID * NCELLS));
 	ctx->cap = n;
-	return 0;
+	return ensure_margin_capacity(ctx);
 }
 
 int ensure_verify_capacity(cimbar_hip_ctx* ctx, int n)
@@ -407,7 +422,7 @@ void destroy_ctx(cimbar_hip_ctx* ctx)
 	fr(ctx->d_gsym); fr(ctx->d_gcol); fr(ctx->d_gmargin); fr(ctx->d_grs_ok); fr(ctx->d_gagree); fr(ctx->d_gdisp); fr(ctx->d_groups); fr(ctx->d_gmem); fr(ctx->d_gcount);
 	fr(ctx->d_groups_in); fr(ctx->d_ngroups); fr(ctx->d_gchunks); fr(ctx->d_gmasks);
 	fr(ctx->d_template); fr(ctx->d_gen_log); fr(ctx->d_er_buf); fr(ctx->d_payload); fr(ctx->d_rgb); fr(ctx->d_plane); fr(ctx->d_cellmean); fr(ctx->d_symbols); fr(ctx->d_colors); fr(ctx->d_drift); fr(ctx->d_flood);
-	fr(ctx->d_rs_ok); fr(ctx->d_states); fr(ctx->d_ccm_frames); fr(ctx->d_ccm_used); fr(ctx->d_carry); fr(ctx->d_chunks);
+	fr(ctx->d_rs_ok); fr(ctx->d_states); fr(ctx->d_ccm_frames); fr(ctx->d_ccm_used); fr(ctx->d_cmargin); fr(ctx->d_carry); fr(ctx->d_chunks);
 	fr(ctx->d_masks); fr(ctx->flood.heap); fr(ctx->flood.prio); fr(ctx->flood.next); fr(ctx->d_fw_queue); fr(ctx->d_vsym); fr(ctx->d_vdrift); fr(ctx->d_vflag); fr(ctx->d_vtotals);
 	fr(ctx->d_ex_rgb); fr(ctx->d_ex_box); fr(ctx->d_ex_in); fr(ctx->d_ex_out); fr(ctx->d_ex_hist); fr(ctx->d_ex_thr); fr(ctx->d_ex_minv);
 	fr(ctx->d_ex_gray); fr(ctx->d_ex_frames); fr(ctx->d_scan_hits); fr(ctx->d_scan_nhits); fr(ctx->d_scan_res); fr(ctx->d_scan_offs); fr(ctx->d_scan_ovf); fr(ctx->d_scan_serial); fr(ctx->d_scan_conf); fr(ctx->d_scan_stage);
@@ -436,7 +451,7 @@ void destroy_ctx(cimbar_hip_ctx* ctx)
 	}
 	for (auto& a : ctx->parked) {
 		fr(a.d_plane); fr(a.d_cellmean); fr(a.d_symbols); fr(a.d_colors); fr(a.d_drift); fr(a.d_flood);
-		fr(a.d_rs_ok); fr(a.d_states); fr(a.d_ccm_frames); fr(a.d_ccm_used);
+		fr(a.d_rs_ok); fr(a.d_states); fr(a.d_ccm_frames); fr(a.d_ccm_used); fr(a.d_cmargin);
 	}
 	delete ctx;
 }
@@ -458,6 +473,7 @@ void rotate_scratch_sets(cimbar_hip_ctx* ctx)
 		std::swap(ctx->d_colors, a.d_colors); std::swap(ctx->d_drift, a.d_drift); std::swap(ctx->d_flood, a.d_flood);
 		std::swap(ctx->d_rs_ok, a.d_rs_ok); std::swap(ctx->d_states, a.d_states); std::swap(ctx->d_ccm_frames, a.d_ccm_frames);
 		std::swap(ctx->d_ccm_used, a.d_ccm_used);
+		std::swap(ctx->d_cmargin, a.d_cmargin); std::swap(ctx->cm_cap, a.cm_cap);
 	};
 	exchange(ctx->parked[ctx->pipe_set]);                       // members (set pipe_set) -> its slot; members now empty
 	ctx->pipe_set = (ctx->pipe_set + 1) % ctx->pipe_depth;
@@ -484,11 +500,16 @@ constexpr int K1_TALL_MIN = 256;   // frames: 16 tall strips x 256 = 4 096 wavef
 // with 2 the decoder accepts a wrong codeword for about one garbage block in eight)
 constexpr int ERASURE_MAX_DEFAULT = RS_PARITY - 8;
 inline int erasure_max(const cimbar_hip_ctx* ctx) { return ctx->er_max < 0 ? ERASURE_MAX_DEFAULT : ctx->er_max; }
+inline int colour_erasure_max(const cimbar_hip_ctx* ctx) { return ctx->ec_max < 0 ? ERASURE_MAX_DEFAULT : ctx->ec_max; }
 
 int enqueue(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_rgb, int n, int pre, int cc, uint8_t* d_chunks, uint32_t* d_masks, int plain = 0,
             bool pipe = false, const int* d_sel = nullptr, int sel_stride = 0, bool symbols_only = false)
 {
 	ctx->grp_valid = false;   // (the group taps describe a combined batch only until the next batch of any kind)
+	// the colour retry (erasure.hip.inc) runs behind every chain that reports chunks; the set in use holds its margins
+	const bool colour_retry = !LEGACY && !plain && !symbols_only && ctx->ec_margin > 0;
+	if (colour_retry) { if (int r = ensure_margin_capacity(ctx)) return r; }
+	ctx->cm_valid = colour_retry;
 	const bool tm = ctx->timing && !pipe;
 	int evi = 0;
 	auto mark = [&]() -> hipError_t { return tm ? hipEventRecord(ctx->ev[evi++], st) : hipSuccess; };
@@ -634,6 +655,11 @@ int enqueue(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_rgb, int n, in
 		if (!LEGACY && !plain && ctx->er_sym > 0)
 			hipLaunchKernelGGL(k_erasure_frame, dim3(m), dim3(256), 0, s, ctx->d_plane, ctx->tb, ctx->d_symbols, ctx->d_drift, ctx->d_flood, ctx->d_rs_ok,
 			                   d_chunks, d_masks, fa, ctx->er_sym, erasure_max(ctx));
+		// ... and of the colour chunks it lacks (cimbar_hip_set_colour_erasure_decode), independent of the symbol retry and behind it
+		if (colour_retry)
+			hipLaunchKernelGGL(k_colour_erasure_frame, dim3(m), dim3(256), 0, s, d_rgb, ctx->d_cellmean, ctx->tb, ctx->d_colors, ctx->d_drift, ctx->d_flood,
+			                   ctx->d_ccm_used, ctx->d_rs_ok, d_chunks, d_masks, ctx->d_cmargin, ctx->d_cmargin + (size_t)ctx->cm_cap * NCELLS, fa,
+			                   ctx->ec_margin, colour_erasure_max(ctx));
 		return s == st ? mark() : hipSuccess;
 	};
 	if (pipe) {
@@ -1034,6 +1060,7 @@ int64_t cimbar_hip_decode_plain_batch(cimbar_hip_ctx* ctx, const uint8_t* rgb, i
 	if (!ctx) return CIMBAR_HIP_EINVAL;
 	if (!rgb || !bytes || n <= 0) { ctx->err = "decode_plain_batch: null buffer or n <= 0"; return CIMBAR_HIP_EINVAL; }
 	if (ctx->er_sym > 0) { ctx->err = "decode_plain_batch: erasure decoding is on (cimbar_hip_set_erasure_decode); the plain stream has no chunk mask to extend"; return CIMBAR_HIP_EINVAL; }
+	if (ctx->ec_margin > 0) { ctx->err = "decode_plain_batch: colour erasure decoding is on (cimbar_hip_set_colour_erasure_decode); the plain stream has no chunk mask to extend"; return CIMBAR_HIP_EINVAL; }
 	if ((rgb_mem != CIMBAR_HIP_MEM_HOST && rgb_mem != CIMBAR_HIP_MEM_DEVICE) || (out_mem != CIMBAR_HIP_MEM_HOST && out_mem != CIMBAR_HIP_MEM_DEVICE)) {
 		ctx->err = "decode_plain_batch: rgb_mem / out_mem must be CIMBAR_HIP_MEM_HOST or CIMBAR_HIP_MEM_DEVICE";
 		return CIMBAR_HIP_EINVAL;
@@ -1680,6 +1707,30 @@ int cimbar_hip_get_erasure_decode(cimbar_hip_ctx* ctx, int* sym_distance, int* c
 	return ctx->er_sym > 0 ? 1 : 0;
 }
 
+int cimbar_hip_set_colour_erasure_decode(cimbar_hip_ctx* ctx, int colour_margin, int max_erasures)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	if (LEGACY && colour_margin > 0) { ctx->err = "set_colour_erasure_decode: modes 4 and 8 carry one coupled stream; colour erasure decoding covers the colour blocks of modes 68 / 67 / 66"; return CIMBAR_HIP_EINVAL; }
+	if (max_erasures > RS_PARITY) { ctx->err = "set_colour_erasure_decode: max_erasures <= the parity bytes"; return CIMBAR_HIP_EINVAL; }
+	// (read when a batch is enqueued: batches already issued keep the setting they were issued with)
+	ctx->ec_margin = colour_margin > 0 ? colour_margin : 0;
+	ctx->ec_max = max_erasures < 0 ? -1 : max_erasures;
+	if (ctx->ec_margin > 0 && ctx->cap > 0) {
+		// the margin buffer (CIMBAR_HIP_TAP_COLOUR_MARGIN) exists from the first time the setting is on; a context that has not decoded yet gets it with its scratch
+		HIPCHK(hipSetDevice(ctx->device));
+		if (int r = ensure_margin_capacity(ctx)) return r;
+	}
+	return 0;
+}
+
+int cimbar_hip_get_colour_erasure_decode(cimbar_hip_ctx* ctx, int* colour_margin, int* max_erasures)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	if (colour_margin) *colour_margin = ctx->ec_margin;
+	if (max_erasures) *max_erasures = colour_erasure_max(ctx);
+	return ctx->ec_margin > 0 ? 1 : 0;
+}
+
 int cimbar_hip_rs_decode_erasures(cimbar_hip_ctx* ctx, const uint8_t* blocks, int n, const uint8_t* erasures, const uint8_t* counts, int mem,
                                   uint8_t* msgs, int8_t* status, void* hip_stream)
 {
@@ -1778,6 +1829,17 @@ int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_byte
 			if (!ctx->flood_verify || !ctx->d_vflag || (size_t)ctx->vcap < n) { std::memset(out, 0xFF, bytes); return (int64_t)bytes; }
 			HIPCHK(hipDeviceSynchronize());
 			HIPCHK(hipMemcpy(out, ctx->d_vflag + ctx->vcap, bytes, hipMemcpyDeviceToHost));
+			return (int64_t)bytes;
+		}
+		case CIMBAR_HIP_TAP_COLOUR_MARGIN: {
+			if (!ctx->cm_valid || !ctx->d_cmargin || (size_t)ctx->cm_cap < n) { ctx->err = "tap: the last batch ran without colour erasure decoding (cimbar_hip_set_colour_erasure_decode)"; return CIMBAR_HIP_EINVAL; }
+			bytes = n * NCELLS * sizeof(uint32_t);
+			if (out_bytes < bytes) { ctx->err = "tap: buffer too small"; return CIMBAR_HIP_EINVAL; }
+			std::vector<uint32_t> worked(n);
+			HIPCHK(hipMemcpy(out, ctx->d_cmargin, bytes, hipMemcpyDeviceToHost));
+			HIPCHK(hipMemcpy(worked.data(), ctx->d_cmargin + (size_t)ctx->cm_cap * NCELLS, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+			// frames whose colour chunks were all in the mask: the retry returned at once and computed no margin
+			for (size_t k = 0; k < n; ++k) if (!worked[k]) std::memset((uint32_t*)out + k * NCELLS, 0xFF, (size_t)NCELLS * sizeof(uint32_t));
 			return (int64_t)bytes;
 		}
 		case CIMBAR_HIP_TAP_GROUP_CELLS:

@@ -247,7 +247,12 @@ __device__ __forceinline__ uint32_t fix_single_color(float c, float adjust_up, f
 	if (c < 0) c = 0;
 	return (uint32_t)c & 0xFFu;
 }
-__device__ __forceinline__ uint32_t best_color(float r, float g, float b, const float* m, bool active)
+// The class and, with MARGIN, the classifier's confidence in it: margin = (second-smallest) - (smallest) squared distance, 0 for a tie that
+// the first-minimum rule decides. One body for both so that class and margin cannot drift apart; best_color below is the class-only instance
+// (k_colors), the colour erasure retry (erasure.hip.inc) takes the margin as well.
+struct ColorFit { uint32_t best, margin; };
+template <bool MARGIN>
+__device__ __forceinline__ ColorFit color_fit(float r, float g, float b, const float* m, bool active)
 {
 	if (active) {
 		float s0 = 0, s1 = 0, s2 = 0;
@@ -275,14 +280,15 @@ __device__ __forceinline__ uint32_t best_color(float r, float g, float b, const 
 	if constexpr (NCOLORS != 4) {
 		// eight colours (getColor8_old): the |q_i| differ, so the distances themselves; the float compare of CimbDecoder.cpp:192-197 is exact
 		// for values this small
-		uint32_t best = 0, best_d = 0xFFFFFFFFu;
+		uint32_t best = 0, best_d = 0xFFFFFFFFu, second_d = 0xFFFFFFFFu;
 #pragma unroll
 		for (int i = 0; i < NCOLORS; ++i) {
 			const int q0 = c_palette[i][0] - c_palette[i][1], q1 = c_palette[i][1] - c_palette[i][2], q2 = c_palette[i][2] - c_palette[i][0];
 			const uint32_t d = (uint32_t)((rel0 - q0) * (rel0 - q0) + (rel1 - q1) * (rel1 - q1) + (rel2 - q2) * (rel2 - q2));
+			if constexpr (MARGIN) second_d = d < best_d ? best_d : (d < second_d ? d : second_d);
 			if (d < best_d) { best = (uint32_t)i; best_d = d; }
 		}
-		return best;
+		return ColorFit{best, MARGIN ? second_d - best_d : 0u};
 	}
 	const int g_ = rel1 - rel0, c_ = rel2 - rel0, y_ = rel1 - rel2, m_ = rel0 - rel1;   // green, cyan, yellow, magenta
 	const int t0 = LEGACY ? c_ : g_, t1 = LEGACY ? y_ : c_, t2 = LEGACY ? m_ : y_, t3 = LEGACY ? g_ : m_;
@@ -291,8 +297,16 @@ __device__ __forceinline__ uint32_t best_color(float r, float g, float b, const 
 	if (t1 > bt) { best_fit = 1; bt = t1; }
 	if (t2 > bt) { best_fit = 2; bt = t2; }
 	if (t3 > bt) { best_fit = 3; bt = t3; }
-	return best_fit;
+	uint32_t margin = 0;
+	if constexpr (MARGIN) {
+		// distance_i = |rel|^2 + |q|^2 - 2 * 255 * t_i, so second-smallest - smallest distance = 510 * (largest - second-largest term)
+		const int lo01 = t0 < t1 ? t0 : t1, hi01 = t0 < t1 ? t1 : t0, lo23 = t2 < t3 ? t2 : t3, hi23 = t2 < t3 ? t3 : t2;
+		const int second = hi01 > hi23 ? (lo01 > hi23 ? lo01 : hi23) : (lo23 > hi01 ? lo23 : hi01);
+		margin = 510u * (uint32_t)(bt - second);
+	}
+	return ColorFit{best_fit, margin};
 }
+__device__ __forceinline__ uint32_t best_color(float r, float g, float b, const float* m, bool active) { return color_fit<false>(r, g, b, m, active).best; }
 #pragma clang fp contract(fast)
 
 // K4: one wavefront per frame, after the symbol RS pass. Runs the chunk bookkeeping for blocks 0..39, then

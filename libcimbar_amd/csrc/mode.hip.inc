@@ -103,8 +103,8 @@ struct Tables {
 #include "k2b_flood.hip.inc"
 #include "k2c_floodwave.hip.inc"
 #include "k3_rs.hip.inc"
-#include "erasure.hip.inc"
 #include "k4_frame.hip.inc"
+#include "erasure.hip.inc"
 #include "combine.hip.inc"
 #include "k1_padded.hip.inc"
 #include "encode.hip.inc"

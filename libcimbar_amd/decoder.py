@@ -19,6 +19,9 @@ LIB_PATH = os.path.join(_HERE, "libcimbar_hip.so")
 MEM_HOST, MEM_DEVICE = 0, 1
 TAP_BITPLANE, TAP_SYMBOLS, TAP_COLORS, TAP_DRIFT, TAP_RS_OK, TAP_FLOOD, TAP_CCM, TAP_FLOOD_PATH, TAP_FLOOD_INFO, TAP_FLOOD_VERIFY = range(10)
 TAP_GROUP_CELLS, TAP_GROUP_MARGIN, TAP_GROUPS = 10, 11, 12
+TAP_COLOUR_MARGIN = 13
+# CIMBAR_HIP_COLOUR_MARGIN_SUGGESTED (include/cimbar_hip.h): the colour erasure threshold chosen on rendered frames (DESIGN_WIDENING.md)
+COLOUR_MARGIN_SUGGESTED = 32512
 
 # every symbol include/cimbar_hip.h declares (tests/test_capi_symbols.py checks the header against this list and the .so)
 EXPORTS = (
@@ -36,6 +39,7 @@ EXPORTS = (
     "cimbar_hip_scan_extract_decode_batch_fmt",
     "cimbar_hip_undistort_calibrate_fmt", "cimbar_hip_undistort_batch_fmt", "cimbar_hip_scan_undistort_extract_decode_batch_fmt",
     "cimbar_hip_rs_decode_erasures", "cimbar_hip_set_erasure_decode", "cimbar_hip_get_erasure_decode",
+    "cimbar_hip_set_colour_erasure_decode", "cimbar_hip_get_colour_erasure_decode",
     "cimbar_hip_decode_batch_combined", "cimbar_hip_scan_extract_decode_batch_combined_fmt",
     "cimbar_hip_auto_create", "cimbar_hip_auto_destroy", "cimbar_hip_auto_bufsize", "cimbar_hip_auto_last_error", "cimbar_hip_auto_reset_ccm",
     "cimbar_hip_auto_get_ccm", "cimbar_hip_auto_set_ccm", "cimbar_hip_auto_scan_extract_decode_batch_fmt",
@@ -168,6 +172,10 @@ def load_library(path=None):
     lib.cimbar_hip_set_erasure_decode.restype = i32
     lib.cimbar_hip_get_erasure_decode.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32)]
     lib.cimbar_hip_get_erasure_decode.restype = i32
+    lib.cimbar_hip_set_colour_erasure_decode.argtypes = [vp, i32, i32]
+    lib.cimbar_hip_set_colour_erasure_decode.restype = i32
+    lib.cimbar_hip_get_colour_erasure_decode.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    lib.cimbar_hip_get_colour_erasure_decode.restype = i32
     lib.cimbar_hip_mode_bufsize.argtypes = [i32]
     lib.cimbar_hip_mode_bufsize.restype = i32
     lib.cimbar_hip_ctx_bufsize.argtypes = [vp]
@@ -693,6 +701,18 @@ class HipDecoder:
                          "cimbar_hip_get_erasure_decode")
         return bool(rc), a.value, b.value, c.value
 
+    def set_colour_erasure_decode(self, colour_margin, max_erasures=-1):
+        """cimbar_hip_set_colour_erasure_decode: colour_margin <= 0 turns the colour retry off; max_erasures < 0 = parity - 8"""
+        self._check(self._lib.cimbar_hip_set_colour_erasure_decode(self._ctx, int(colour_margin), int(max_erasures)),
+                    "cimbar_hip_set_colour_erasure_decode")
+
+    def get_colour_erasure_decode(self):
+        """(on, colour_margin, max_erasures)"""
+        a, b = ctypes.c_int(), ctypes.c_int()
+        rc = self._check(self._lib.cimbar_hip_get_colour_erasure_decode(self._ctx, ctypes.byref(a), ctypes.byref(b)),
+                         "cimbar_hip_get_colour_erasure_decode")
+        return bool(rc), a.value, b.value
+
     def rs_decode_erasures(self, blocks, erasures):
         """Errors-and-erasures Reed-Solomon decode of caller-given blocks of this mode's code (cimbar_hip_rs_decode_erasures).
         blocks: (n, RS_BLOCK) uint8; erasures: a list of n sequences of byte positions (at most RS_BLOCK each, any count: more than
@@ -733,6 +753,7 @@ class HipDecoder:
             TAP_COLORS: ((n, self.geo.NCELLS), np.uint8), TAP_DRIFT: ((n, self.geo.NCELLS, 2), np.int8),
             TAP_RS_OK: ((n, self.geo.BLOCKS), np.uint8), TAP_FLOOD: ((n,), np.uint8), TAP_CCM: ((n, 10), np.float32), TAP_FLOOD_PATH: ((n,), np.uint8), TAP_FLOOD_INFO: ((n,), np.uint32), TAP_FLOOD_VERIFY: ((n,), np.uint32),
             TAP_GROUP_CELLS: ((n, self.geo.NCELLS), np.uint8), TAP_GROUP_MARGIN: ((n, self.geo.NCELLS), np.uint16), TAP_GROUPS: ((n,), np.int32),
+            TAP_COLOUR_MARGIN: ((n, self.geo.NCELLS), np.uint32),
         }
         shape, dt = shapes[what]
         out = np.zeros(shape, dtype=dt)
