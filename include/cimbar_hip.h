@@ -260,6 +260,52 @@ int64_t cimbar_hip_scan_extract_decode_batch_combined_fmt(cimbar_hip_ctx* ctx, c
                                                           int* groups_out, uint8_t* gchunks, uint32_t* gmasks, int* n_groups, int out_mem,
                                                           void* hip_stream);
 
+/* ---- chunk delivery: a batch's slots and masks -> what a fountain sink eats --------------------------------------------------------------
+ * The batch entry points above report a frame's chunks in fixed slots plus one mask word. The reference's receive interface has another shape:
+ * cimbard_scan_extract_decode returns the delivered chunks packed front to back (escrow_buffer_writer), and cimbard_fountain_decode(buf, size)
+ * walks such a buffer and hands fountain_decoder_sink::decode_frame one chunk at a time. cimbar_hip_deliver_chunks is that step for a whole batch,
+ * on the device, and can leave out what the sink would refuse anyway.
+ *   chunks / masks : n frames as any batch entry point writes them -- n * cimbar_hip_ctx_bufsize(ctx) bytes and n words (the gchunks / gmasks of
+ *                    a combined call have the same layout); in_mem says where they lie
+ *   candidates     : the (frame, slot) pairs whose mask bit is set, in ascending frame * chunks_per_frame + slot
+ *   flags          : 0 keeps every candidate (escrow_buffer_writer per frame, concatenated over the batch), else an OR of
+ *     CIMBAR_HIP_DELIVER_DROP_EMPTY  drop candidates whose header says file size 0 -- (b0 & 0x80) == 0 and b1 == b2 == b3 == 0,
+ *                                    FountainMetadata::file_size -- which fountain_decoder_sink::decode_frame refuses (-11): the all-zero chunks
+ *                                    of a too-small frame. Applied first: a dropped chunk takes no part in what follows
+ *     CIMBAR_HIP_DELIVER_DEDUP       of the candidates whose six header bytes (FountainMetadata::md_size) are equal, keep the first. All 48 bits
+ *                                    are compared, never a hash of them; payload bytes play no part (the sink keeps the first one too)
+ *     CIMBAR_HIP_DELIVER_REMEMBER    implies DEDUP; also drop candidates whose header an earlier REMEMBER call on this context delivered, and
+ *                                    remember the headers this call delivers
+ *   packed : the kept chunks back to back, n * cimbar_hip_ctx_bufsize(ctx) bytes of room; src (may be NULL): n * chunks_per_frame words of room,
+ *            src[k] = frame * chunks_per_frame + slot of packed chunk k; count: one word. Only packed[0 .. count * chunk_size) and
+ *            src[0 .. count) are written. out_mem says where the three lie.
+ * Device outputs: the call only enqueues on hip_stream and returns 0. Host outputs: it synchronises and returns count. in_mem and out_mem are
+ * independent; NULL hip_stream as for cimbar_hip_decode_batch. n <= 0, a null chunks / masks / packed / count, unknown flag bits, an unknown memory
+ * kind or more than 2^24 slots: CIMBAR_HIP_EINVAL, checked before anything is enqueued. cimbard_fountain_decode(packed, count * chunk_size) takes
+ * the result in one piece.
+ * The call reads no decode state and is ordered against nothing but hip_stream and the context's previous delivery call (they share scratch): after
+ * cimbar_hip_decode_batch_pipelined it goes on the caller's stream behind a cimbar_hip_pipeline_wait that covers the batch.
+ *
+ * REMEMBER keeps the delivered headers in a device-resident open-addressing table of full 48-bit keys that the context owns (allocated by the
+ * first REMEMBER call or by cimbar_hip_delivery_reset). Two rules hold:
+ *   1. a chunk that is not a duplicate is never dropped. The table is kept at most half full; a call whose new headers would pass that records
+ *      NONE of them, still drops what is already remembered, still dedups within itself, and sets the sticky `overflowed` flag: an overflow
+ *      lets duplicates through in later calls and loses nothing;
+ *   2. packed, src and count are a function of the inputs and the remembered set alone -- the same calls in the same order give the same bytes.
+ * cimbar_hip_delivery_reset forgets every header and clears the flag; capacity_log2 0 = the default (20: 2^20 entries, 8 MiB), else 4 .. 24
+ * (anything else: CIMBAR_HIP_EINVAL). cimbar_hip_delivery_stats waits for the delivery calls issued so far and reports the headers remembered,
+ * the table's entries (0 while there is no table) and the flag; each pointer may be NULL.
+ * The auto-detection objects are not covered (their chunk size differs from capture to capture). */
+enum {
+	CIMBAR_HIP_DELIVER_DEDUP = 1,
+	CIMBAR_HIP_DELIVER_REMEMBER = 2,
+	CIMBAR_HIP_DELIVER_DROP_EMPTY = 4
+};
+int64_t cimbar_hip_deliver_chunks(cimbar_hip_ctx* ctx, const uint8_t* chunks, const uint32_t* masks, int n, int in_mem, unsigned flags,
+                                  uint8_t* packed, int32_t* src, int32_t* count, int out_mem, void* hip_stream);
+int cimbar_hip_delivery_reset(cimbar_hip_ctx* ctx, int capacity_log2);
+int cimbar_hip_delivery_stats(cimbar_hip_ctx* ctx, int64_t* remembered, int64_t* capacity, int* overflowed);
+
 /* ---- the encode half ("next" row of the scope table: on-device frame synthesiser) --------------------------------------------
  * Encoder::encode_next (src/lib/encoder/Encoder.h:69-129) for n frames at once: each frame takes 7500 payload bytes (the 60
  * reads of 125 bytes a fountain_encoder_stream / ifstream would have served), RS(155,125)-encodes them (libcorrect encode.c:3-34),

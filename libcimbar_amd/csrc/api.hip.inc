@@ -30,6 +30,17 @@ inline bool ctx_pipe_view(cimbar_hip_ctx* ctx, hipStream_t* stream, hipEvent_t* 
 	return m68::ctx_pipe_view((m68::cimbar_hip_ctx*)ctx, stream, done);
 }
 
+inline deliver::View delivery_view(cimbar_hip_ctx* ctx)
+{
+	deliver::View v;
+	if (ctx_mode(ctx) == 67) m67::delivery_view((m67::cimbar_hip_ctx*)ctx, &v);
+	else if (ctx_mode(ctx) == 66) m66::delivery_view((m66::cimbar_hip_ctx*)ctx, &v);
+	else if (ctx_mode(ctx) == 4) m4::delivery_view((m4::cimbar_hip_ctx*)ctx, &v);
+	else if (ctx_mode(ctx) == 8) m8::delivery_view((m8::cimbar_hip_ctx*)ctx, &v);
+	else m68::delivery_view((m68::cimbar_hip_ctx*)ctx, &v);
+	return v;
+}
+
 }  // namespace
 
 extern "C" {
@@ -306,6 +317,24 @@ int cimbar_hip_stage_times(cimbar_hip_ctx* ctx, const char** names, float* ms, i
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;
 	return CIMBAR_FWD(cimbar_hip_stage_times, names, ms, max);
+}
+
+int64_t cimbar_hip_deliver_chunks(cimbar_hip_ctx* ctx, const uint8_t* chunks, const uint32_t* masks, int n, int in_mem, unsigned flags, uint8_t* packed, int32_t* src, int32_t* count, int out_mem, void* hip_stream)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return deliver::deliver_chunks(delivery_view(ctx), chunks, masks, n, in_mem, flags, packed, src, count, out_mem, hip_stream);
+}
+
+int cimbar_hip_delivery_reset(cimbar_hip_ctx* ctx, int capacity_log2)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return deliver::delivery_reset(delivery_view(ctx), capacity_log2);
+}
+
+int cimbar_hip_delivery_stats(cimbar_hip_ctx* ctx, int64_t* remembered, int64_t* capacity, int* overflowed)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return deliver::delivery_stats(delivery_view(ctx), remembered, capacity, overflowed);
 }
 
 int cimbar_hip_geometry(const cimbar_hip_ctx* ctx, int32_t out[CIMBAR_HIP_GEOMETRY_WORDS])

@@ -18,6 +18,7 @@
 //   K5 k_colors         6x6 cell mean -> CCM -> palette classifier
 //   K3 k_rs             (colours: 20 blocks)
 //   K7 k_frame_end      aligned_stream bookkeeping for the colour chunks, chunk mask, zero dropped slots, CCM carry-out
+//   D1-D4 k_deliver_*   chunk delivery: slots + masks -> the delivered chunks packed front to back, duplicates and empty chunks left out (deliver.hip.inc)
 //   E1 k_rs_encode / E2 k_render   the encode half (Encoder::encode_next): RS encode + tile render
 //   X1-X4 k_scan_* / k_warp        the stage in front (Scanner's image preparation, Deskewer's perspective warp)
 #include <hip/hip_runtime.h>
@@ -35,6 +36,9 @@
 #include <vector>
 
 #include "../../include/cimbar_hip.h"
+
+// chunk delivery: three integers of geometry, so one copy serves every mode (the contexts below own its state)
+#include "deliver.hip.inc"
 
 // One copy of the geometry-dependent code per supported mode (Config.h:19-44), then the mode-independent C ABI on top.
 #define CIMBAR_MODE 68

@@ -15,6 +15,7 @@ struct cimbar_hip_ctx {
 	bool cm_valid = false;                      // the last batch ran the colour retry (CIMBAR_HIP_TAP_COLOUR_MARGIN describes it)
 	uint8_t* d_er_buf = nullptr;                // cimbar_hip_rs_decode_erasures' staging for host-memory calls (grown on demand)
 	size_t d_er_cap = 0;
+	deliver::State* delivery = nullptr;         // cimbar_hip_deliver_chunks' scratch and remembered headers (deliver.hip.inc): nothing of it exists until the first call
 	// the group decode (cimbar_hip_decode_batch_combined / _scan_extract_decode_batch_combined_fmt, combine.hip.inc): per capture slot, grown on demand
 	int grp_cap = 0;
 	bool grp_valid = false;                     // the last batch was a combined one (the group taps describe it)
@@ -426,6 +427,7 @@ void destroy_ctx(cimbar_hip_ctx* ctx)
 	fr(ctx->d_masks); fr(ctx->flood.heap); fr(ctx->flood.prio); fr(ctx->flood.next); fr(ctx->d_fw_queue); fr(ctx->d_vsym); fr(ctx->d_vdrift); fr(ctx->d_vflag); fr(ctx->d_vtotals);
 	fr(ctx->d_ex_rgb); fr(ctx->d_ex_box); fr(ctx->d_ex_in); fr(ctx->d_ex_out); fr(ctx->d_ex_hist); fr(ctx->d_ex_thr); fr(ctx->d_ex_minv);
 	fr(ctx->d_ex_gray); fr(ctx->d_ex_frames); fr(ctx->d_scan_hits); fr(ctx->d_scan_nhits); fr(ctx->d_scan_res); fr(ctx->d_scan_offs); fr(ctx->d_scan_ovf); fr(ctx->d_scan_serial); fr(ctx->d_scan_conf); fr(ctx->d_scan_stage);
+	deliver::destroy(ctx->delivery);
 	fr(ctx->d_ud_img); fr(ctx->d_ud_ok); fr(ctx->d_ud_k1); fr(ctx->d_ud_status); fr(ctx->d_ud_xt);
 	if (ctx->h_ud_xt) (void)hipHostFree(ctx->h_ud_xt);
 	if (ctx->ev_ud_xt) (void)hipEventDestroy(ctx->ev_ud_xt);
@@ -731,6 +733,11 @@ int cimbar_hip_geometry(const cimbar_hip_ctx* ctx, int32_t out[CIMBAR_HIP_GEOMET
 
 // what comm.hip.inc needs of a context
 void ctx_view(cimbar_hip_ctx* ctx, int* device, std::string** err, int* frame_bytes) { *device = ctx->device; *err = &ctx->err; *frame_bytes = FRAME_BYTES; }
+// what deliver.hip.inc needs of one
+void delivery_view(cimbar_hip_ctx* ctx, deliver::View* v)
+{
+	v->device = ctx->device; v->err = &ctx->err; v->stream = ctx->stream; v->chunk = CHUNK; v->per = CHUNKS; v->state = &ctx->delivery;
+}
 // ... and of its pipeline: the stream the batch issued last through cimbar_hip_decode_batch_pipelined runs on, and the event that says "that batch is done"
 // (false: no pipelined batch has been issued yet)
 bool ctx_pipe_view(cimbar_hip_ctx* ctx, hipStream_t* stream, hipEvent_t* gathered)

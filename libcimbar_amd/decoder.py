@@ -43,7 +43,10 @@ EXPORTS = (
     "cimbar_hip_decode_batch_combined", "cimbar_hip_scan_extract_decode_batch_combined_fmt",
     "cimbar_hip_auto_create", "cimbar_hip_auto_destroy", "cimbar_hip_auto_bufsize", "cimbar_hip_auto_last_error", "cimbar_hip_auto_reset_ccm",
     "cimbar_hip_auto_get_ccm", "cimbar_hip_auto_set_ccm", "cimbar_hip_auto_scan_extract_decode_batch_fmt",
+    "cimbar_hip_deliver_chunks", "cimbar_hip_delivery_reset", "cimbar_hip_delivery_stats",
 )
+# cimbar_hip_deliver_chunks' flags
+DELIVER_DEDUP, DELIVER_REMEMBER, DELIVER_DROP_EMPTY = 1, 2, 4
 PNG_EHEADER, PNG_ESTREAM, PNG_ECODES, PNG_ESIZE, PNG_ECHECK = -30, -31, -32, -33, -34
 
 
@@ -168,6 +171,12 @@ def load_library(path=None):
     lib.cimbar_hip_auto_set_ccm.restype = i32
     lib.cimbar_hip_auto_scan_extract_decode_batch_fmt.argtypes = [vp, vp, i32, vp, u32, u32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp]
     lib.cimbar_hip_auto_scan_extract_decode_batch_fmt.restype = i64
+    lib.cimbar_hip_deliver_chunks.argtypes = [vp, vp, vp, i32, i32, u32, vp, vp, vp, i32, vp]
+    lib.cimbar_hip_deliver_chunks.restype = i64
+    lib.cimbar_hip_delivery_reset.argtypes = [vp, i32]
+    lib.cimbar_hip_delivery_reset.restype = i32
+    lib.cimbar_hip_delivery_stats.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i32)]
+    lib.cimbar_hip_delivery_stats.restype = i32
     lib.cimbar_hip_set_erasure_decode.argtypes = [vp, i32, i32, i32]
     lib.cimbar_hip_set_erasure_decode.restype = i32
     lib.cimbar_hip_get_erasure_decode.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32)]
@@ -742,6 +751,52 @@ class HipDecoder:
                                                             ctypes.c_void_p(counts_ptr), MEM_DEVICE, ctypes.c_void_p(msgs_ptr),
                                                             ctypes.c_void_p(status_ptr), ctypes.c_void_p(stream) if stream else None),
                     "cimbar_hip_rs_decode_erasures(device)")
+
+    # ------------------------------------------------------------------ chunk delivery (cimbar_hip_deliver_chunks)
+    @staticmethod
+    def delivery_flags(dedup=True, remember=False, drop_empty=True):
+        return (DELIVER_DEDUP if dedup else 0) | (DELIVER_REMEMBER if remember else 0) | (DELIVER_DROP_EMPTY if drop_empty else 0)
+
+    def deliver_chunks(self, chunks, masks, dedup=True, remember=False, drop_empty=True):
+        """chunks (n, chunks per frame, chunk size) uint8 and masks (n,) uint32 as a batch call returns them (or the gchunks / gmasks of a
+        combined one). Returns (packed (count, chunk size) uint8, src (count,) int32): the delivered chunks front to back in frame and slot
+        order -- packed.tobytes() is what cimbard_fountain_decode walks -- and the linear slot index frame * chunks per frame + slot of each.
+        drop_empty leaves out chunks whose header says file size 0, dedup every chunk whose six header bytes an earlier kept chunk of the call
+        has, remember (implies dedup) also those an earlier remember call on this decoder delivered."""
+        g = self.geo
+        masks = np.ascontiguousarray(masks, dtype=np.uint32).reshape(-1)
+        n = masks.shape[0]
+        chunks = np.ascontiguousarray(chunks, dtype=np.uint8)
+        if chunks.size != n * g.CHUNKS_PER_FRAME * g.CHUNK:
+            raise CimbarHipError(f"deliver_chunks: chunks must hold {n} x {g.CHUNKS_PER_FRAME} x {g.CHUNK} bytes")
+        packed = np.zeros((n * g.CHUNKS_PER_FRAME, g.CHUNK), np.uint8)
+        src = np.zeros(n * g.CHUNKS_PER_FRAME, np.int32)
+        count = ctypes.c_int32(0)
+        rc = self._lib.cimbar_hip_deliver_chunks(self._ctx, chunks.ctypes.data, masks.ctypes.data, n, MEM_HOST,
+                                                 self.delivery_flags(dedup, remember, drop_empty), packed.ctypes.data, src.ctypes.data,
+                                                 ctypes.addressof(count), MEM_HOST, None)
+        self._check(rc, "cimbar_hip_deliver_chunks")
+        return packed[:int(rc)], src[:int(rc)]
+
+    def deliver_chunks_device(self, chunks_ptr, masks_ptr, n, packed_ptr, src_ptr, count_ptr, dedup=True, remember=False, drop_empty=True,
+                              stream=None, flags=None):
+        """Device pointers in and out (src_ptr may be None / 0); asynchronous on `stream` (None / 0 = the null stream). `flags`, when given,
+        is passed as it is instead of the three switches."""
+        fl = self.delivery_flags(dedup, remember, drop_empty) if flags is None else int(flags)
+        rc = self._lib.cimbar_hip_deliver_chunks(self._ctx, ctypes.c_void_p(chunks_ptr), ctypes.c_void_p(masks_ptr), int(n), MEM_DEVICE, fl,
+                                                 ctypes.c_void_p(packed_ptr), ctypes.c_void_p(src_ptr) if src_ptr else None,
+                                                 ctypes.c_void_p(count_ptr), MEM_DEVICE, ctypes.c_void_p(stream) if stream else None)
+        self._check(rc, "cimbar_hip_deliver_chunks(device)")
+
+    def delivery_reset(self, capacity_log2=0):
+        """forget every remembered header; capacity_log2 0 = the default table (2^20 entries), else 4 .. 24"""
+        self._check(self._lib.cimbar_hip_delivery_reset(self._ctx, int(capacity_log2)), "cimbar_hip_delivery_reset")
+
+    def delivery_stats(self):
+        """(remembered headers, table entries, overflowed)"""
+        a, b, c = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int()
+        self._check(self._lib.cimbar_hip_delivery_stats(self._ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "cimbar_hip_delivery_stats")
+        return a.value, b.value, bool(c.value)
 
     def bufsize(self):
         """cimbard_get_bufsize() of this context's configuration"""
