@@ -553,8 +553,13 @@ enum {
 	CIMBAR_HIP_TAP_GROUP_MARGIN = 11, /* n_groups * cells u16  : the symbol's margin, 0xFFFF where the members' symbols agree */
 	CIMBAR_HIP_TAP_GROUPS = 12,       /* n int32               : the group of every capture, -1 for none */
 	/* the colour retry of the last batch (cimbar_hip_set_colour_erasure_decode; CIMBAR_HIP_EINVAL when that batch ran with the setting off) */
-	CIMBAR_HIP_TAP_COLOUR_MARGIN = 13 /* n * cells u32         : the classifier's margin of every cell, by linear cell index, of the frames the retry
+	CIMBAR_HIP_TAP_COLOUR_MARGIN = 13,/* n * cells u32         : the classifier's margin of every cell, by linear cell index, of the frames the retry
 	                                     worked on; 0xFFFFFFFF for all cells of a frame it skipped (all colour chunks in the mask) */
+	/* the anchor search of the last extract / scan_extract_decode call (n = that call's captures; valid without any decoded batch; an entry point that
+	 * searches its captures in several pieces describes the last piece) */
+	CIMBAR_HIP_TAP_SCAN_PATH = 14     /* n int32               : 0 = the fast search kernels answered, 1 = one of their fixed lists overflowed and the
+	                                     serial search answered, 2 = gave up (more than 16 overflowing captures in the batch, or the serial search's
+	                                     own lists overflowed): the capture is reported as a failure */
 };
 int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_bytes);
 

@@ -35,6 +35,7 @@ struct cimbar_hip_ctx {
 	// batch scratch (grown on demand)
 	int cap = 0;
 	int last_n = 0;
+	int scan_n = 0;                             // captures of the last anchor search (CIMBAR_HIP_TAP_SCAN_PATH describes it)
 	uint8_t* d_rgb = nullptr;         // staging for host-resident input
 	size_t d_rgb_cap = 0;
 	uint32_t* d_plane = nullptr;
@@ -1505,10 +1506,11 @@ int enqueue_scan(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_in, unsig
 	                   SCAN_ROW_PTS, false, ctx->d_scan_conf, ctx->d_scan_ovf);
 	hipLaunchKernelGGL(k_scan_final, dim3(n), dim3(64), 0, st, ctx->d_scan_hits, ctx->d_scan_offs, ctx->d_scan_conf, stage2, W, ctx->d_scan_ovf, ctx->d_scan_res);
 	// captures whose search overflowed one of the fixed-size lists above (status -1): Scanner::scan again, serially, lists in global memory
-	hipLaunchKernelGGL(k_scan_serial, dim3(n), dim3(64), 0, st, gimg, W, H, ctx->d_ex_thr, ctx->d_scan_serial, ctx->d_scan_ovf + n, ctx->d_scan_res);
+	hipLaunchKernelGGL(k_scan_serial, dim3(n), dim3(64), 0, st, gimg, W, H, ctx->d_ex_thr, ctx->d_scan_serial, ctx->d_scan_ovf + n, ctx->d_scan_ovf, ctx->d_scan_res);
 	hipLaunchKernelGGL(k_warp_matrices, dim3((n + 63) / 64), dim3(64), 0, st, ctx->d_scan_res[0].corners, sizeof(ScanResult) / sizeof(float),
 	                   &ctx->d_scan_res[0].status, sizeof(ScanResult) / sizeof(int), n, ctx->d_ex_minv);
 	HIPCHK(hipGetLastError());
+	ctx->scan_n = n;
 	return 0;
 }
 
@@ -1780,6 +1782,19 @@ int cimbar_hip_rs_decode_erasures(cimbar_hip_ctx* ctx, const uint8_t* blocks, in
 int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_bytes)
 {
 	if (!ctx || !out) return CIMBAR_HIP_EINVAL;
+	if (what == CIMBAR_HIP_TAP_SCAN_PATH) {
+		// which kernels answered the last anchor search, per capture: the fast kernels' overflow flag and the status the slow path left
+		if (ctx->scan_n <= 0) { ctx->err = "tap: no capture has been searched for anchors on this context yet"; return CIMBAR_HIP_EINVAL; }
+		const size_t m = (size_t)ctx->scan_n;
+		if (out_bytes < m * sizeof(int32_t)) { ctx->err = "tap: buffer too small"; return CIMBAR_HIP_EINVAL; }
+		HIPCHK(hipSetDevice(ctx->device));
+		HIPCHK(hipDeviceSynchronize());
+		std::vector<int> ovf(m), status(m);
+		HIPCHK(hipMemcpy(ovf.data(), ctx->d_scan_ovf, sizeof(int) * m, hipMemcpyDeviceToHost));
+		HIPCHK(hipMemcpy2D(status.data(), sizeof(int), &ctx->d_scan_res[0].status, sizeof(ScanResult), sizeof(int), m, hipMemcpyDeviceToHost));
+		for (size_t k = 0; k < m; ++k) ((int32_t*)out)[k] = status[k] < 0 ? 2 : (ovf[k] ? 1 : 0);
+		return (int64_t)(m * sizeof(int32_t));
+	}
 	if (ctx->last_n <= 0) { ctx->err = "tap: no batch has been decoded on this context yet"; return CIMBAR_HIP_EINVAL; }
 	HIPCHK(hipSetDevice(ctx->device));
 	HIPCHK(hipDeviceSynchronize());

@@ -715,10 +715,11 @@ __device__ void sr_rows(const SerialScanner& sc, SerialList& cand, bool merge_co
 // SCAN_SERIAL_CAP anchors, handed out through *slot_counter (zeroed by k_scan_stage1); grid = captures, a workgroup whose capture did not
 // overflow returns at once.
 __global__ __launch_bounds__(64) void k_scan_serial(const uint8_t* __restrict__ gray, int w, int h, const int* __restrict__ thr, ScanAnchor* __restrict__ scratch,
-                                                    int* __restrict__ slot_counter, ScanResult* __restrict__ results)
+                                                    int* __restrict__ slot_counter, int* __restrict__ overflow, ScanResult* __restrict__ results)
 {
 	const int f = blockIdx.x;
 	if (threadIdx.x != 0 || results[f].status != -1) return;
+	overflow[f] = 1;                                                    // (k_scan_final's own lists overflow without a flag: CIMBAR_HIP_TAP_SCAN_PATH reads this one)
 	const int slot = atomicAdd(slot_counter, 1);
 	if (slot >= SCAN_SERIAL_SLOTS) return;                              // more overflowed captures in one batch than there is scratch for: they keep status -1
 	ScanAnchor* base = scratch + (size_t)slot * 6 * SCAN_SERIAL_CAP;

@@ -20,6 +20,7 @@ MEM_HOST, MEM_DEVICE = 0, 1
 TAP_BITPLANE, TAP_SYMBOLS, TAP_COLORS, TAP_DRIFT, TAP_RS_OK, TAP_FLOOD, TAP_CCM, TAP_FLOOD_PATH, TAP_FLOOD_INFO, TAP_FLOOD_VERIFY = range(10)
 TAP_GROUP_CELLS, TAP_GROUP_MARGIN, TAP_GROUPS = 10, 11, 12
 TAP_COLOUR_MARGIN = 13
+TAP_SCAN_PATH = 14
 # CIMBAR_HIP_COLOUR_MARGIN_SUGGESTED (include/cimbar_hip.h): the colour erasure threshold chosen on rendered frames (DESIGN_WIDENING.md)
 COLOUR_MARGIN_SUGGESTED = 32512
 
@@ -808,7 +809,7 @@ class HipDecoder:
             TAP_COLORS: ((n, self.geo.NCELLS), np.uint8), TAP_DRIFT: ((n, self.geo.NCELLS, 2), np.int8),
             TAP_RS_OK: ((n, self.geo.BLOCKS), np.uint8), TAP_FLOOD: ((n,), np.uint8), TAP_CCM: ((n, 10), np.float32), TAP_FLOOD_PATH: ((n,), np.uint8), TAP_FLOOD_INFO: ((n,), np.uint32), TAP_FLOOD_VERIFY: ((n,), np.uint32),
             TAP_GROUP_CELLS: ((n, self.geo.NCELLS), np.uint8), TAP_GROUP_MARGIN: ((n, self.geo.NCELLS), np.uint16), TAP_GROUPS: ((n,), np.int32),
-            TAP_COLOUR_MARGIN: ((n, self.geo.NCELLS), np.uint32),
+            TAP_COLOUR_MARGIN: ((n, self.geo.NCELLS), np.uint32), TAP_SCAN_PATH: ((n,), np.int32),
         }
         shape, dt = shapes[what]
         out = np.zeros(shape, dtype=dt)

@@ -153,6 +153,13 @@ int co_deskew(const uint8_t* rgb, int sw, int sh, const float* corners8, uint8_t
 
 /* Scanner::scan (Scanner.cpp:183-202) on the 0/255 image: up to 4 anchors {x, xmax, y, ymax} (top-left, top-right, bottom-left, bottom-right); returns the count */
 int co_scan_anchors(const uint8_t* binary, int w, int h, int32_t* anchors16);
+/* counters of the last co_scan_anchors on this thread (test infrastructure: they say how close a capture comes to the device kernels' fixed lists) */
+int co_scan_debug_max_list(void);
+int co_scan_debug_row_hits(void);       /* the most hits in one primary row */
+int co_scan_debug_primary_hits(void);   /* hits of all primary rows */
+int co_scan_debug_candidates(void);     /* candidates before filter_candidates */
+int co_scan_debug_equal_sizes(void);    /* 1 = two of them have equal size */
+int co_scan_debug_counter(int which);   /* 0..3 the four above, 4.. see cimbar_oracle_extract.c */
 /* Extractor::extract (Extractor.h:29-45): 0 failure / 1 success / 2 needs sharpen; corners8 = Corners::all(); out = deskewed 1024x1024 RGB8 */
 int co_extract(const uint8_t* rgb, int w, int h, uint8_t* out1024, float* corners8);
 

@@ -311,6 +311,24 @@ typedef struct { const uint8_t* img; int w, h, skip, cutoff; } scanner_t;
 typedef struct { anchor_t* v; int n, cap; } alist;
 static __thread int g_dbg_max_list = 0;   /* longest list any scan built during the last co_scan_anchors (sizes the device kernel's fixed lists) */
 int co_scan_debug_max_list(void) { return g_dbg_max_list; }
+/* more about the last co_scan_anchors, for tests that aim captures at the device kernels' fixed capacities (tests/scan_hostile_cases.py) */
+enum { DBG_ROW_HITS, DBG_PRIMARY_HITS, DBG_CANDIDATES, DBG_EQUAL_SIZES, DBG_ROW_CHANGES, DBG_CONFIRM_CHANGES, DBG_CONFIRM_LIST, DBG_HIT_CONFIRMED,
+       DBG_ROWS, DBG_OUTSIDE, DBG_BR_ROWS, DBG_BR_ROW_HITS, DBG_BR_HITS, DBG_BR_CANDIDATES, DBG_COUNT };
+static __thread int g_dbg[DBG_COUNT];
+static __thread int g_dbg_stage = 0;    /* 0 = outside a row scan, 1 = in the rows of scan_primary, 2 = in those of add_bottom_right_corner */
+static void dbg_max(int which, int v) { if (v > g_dbg[which]) g_dbg[which] = v; }
+int co_scan_debug_row_hits(void) { return g_dbg[DBG_ROW_HITS]; }             /* the most hits in one primary row */
+int co_scan_debug_primary_hits(void) { return g_dbg[DBG_PRIMARY_HITS]; }     /* all primary rows together */
+int co_scan_debug_candidates(void) { return g_dbg[DBG_CANDIDATES]; }         /* candidates before filter_candidates */
+int co_scan_debug_equal_sizes(void) { return g_dbg[DBG_EQUAL_SIZES]; }       /* 1 = two of those candidates have the same Anchor::size */
+/* which: 4 most run boundaries on one row-scan line (either stage), 5 on one column / diagonal / confirm line, 6 longest list of one hit's column,
+ * diagonal or confirm scans, 7 most candidates one hit confirmed, 8 primary rows, 9 pixel tests outside the image (confirm scans at the border),
+ * 10..13 the bottom-right stage's rows, most hits in a row, hits, candidates; 0..3 the four getters above */
+int co_scan_debug_counter(int which) { return which >= 0 && which < DBG_COUNT ? g_dbg[which] : -1; }
+/* run boundaries of a scan line as the device's scan_line counts them: activity changes starting inactive, plus the flush of a run still active at the end */
+typedef struct { int prev, n; } dbg_line;
+static void dbg_line_px(dbg_line* l, int active) { if (active != l->prev) { l->n++; l->prev = active; } }
+static void dbg_line_end(dbg_line* l) { dbg_max(g_dbg_stage ? DBG_ROW_CHANGES : DBG_CONFIRM_CHANGES, l->n + (l->prev ? 1 : 0)); }
 static void al_push(alist* l, anchor_t a)
 {
 	if (l->n + 1 > g_dbg_max_list) g_dbg_max_list = l->n + 1;
@@ -319,7 +337,7 @@ static void al_push(alist* l, anchor_t a)
 }
 static int test_pixel(const scanner_t* sc, int x, int y)
 {
-	if (x < 0 || y < 0 || x >= sc->w || y >= sc->h) return 0;   /* the reference reads out of bounds here (confirm scans next to the image border) */
+	if (x < 0 || y < 0 || x >= sc->w || y >= sc->h) { g_dbg[DBG_OUTSIDE]++; return 0; }   /* the reference reads out of bounds here (confirm scans next to the image border) */
 	return sc->img[(size_t)y * sc->w + x] > 127;
 }
 
@@ -331,10 +349,14 @@ static int scan_horizontal(const scanner_t* sc, int kind, alist* pts, int y, int
 	const int init = pts->n;
 	scan_state st;
 	ss_init(&st, kind);
+	dbg_line dl = {0, 0};
 	for (int x = xstart; x < xend; ++x) {
-		const int res = ss_process(&st, test_pixel(sc, x, y));
+		const int px = test_pixel(sc, x, y);
+		dbg_line_px(&dl, px);
+		const int res = ss_process(&st, px);
 		if (res > 0) { anchor_t a = {x - res, x - 1, y, y}; al_push(pts, a); }
 	}
+	dbg_line_end(&dl);
 	const int res = ss_process(&st, 0);
 	if (res > 0) { anchor_t a = {xend - res, xend - 1, y, y}; al_push(pts, a); }
 	return init != pts->n;
@@ -349,10 +371,14 @@ static int scan_vertical(const scanner_t* sc, int kind, alist* pts, int x, int x
 	const int init = pts->n;
 	scan_state st;
 	ss_init(&st, kind);
+	dbg_line dl = {0, 0};
 	for (int y = ystart; y < yend; ++y) {
-		const int res = ss_process(&st, test_pixel(sc, xavg, y));
+		const int px = test_pixel(sc, xavg, y);
+		dbg_line_px(&dl, px);
+		const int res = ss_process(&st, px);
 		if (res > 0) { anchor_t a = {xavg, xavg, y - res, y - 1}; al_push(pts, a); }
 	}
+	dbg_line_end(&dl);
 	const int res = ss_process(&st, 0);
 	if (res > 0) { anchor_t a = {xavg, xavg, yend - res, yend - 1}; al_push(pts, a); }
 	return init != pts->n;
@@ -368,10 +394,14 @@ static int scan_diagonal(const scanner_t* sc, int kind, alist* pts, int xstart, 
 	scan_state st;
 	ss_init(&st, kind);
 	int x = xstart, y = ystart;
+	dbg_line dl = {0, 0};
 	for (; x < xend && y < yend; ++x, ++y) {
-		const int res = ss_process(&st, test_pixel(sc, x, y));
+		const int px = test_pixel(sc, x, y);
+		dbg_line_px(&dl, px);
+		const int res = ss_process(&st, px);
 		if (res > 0) { anchor_t a = {x - res, x - 1, y - res, y - 1}; al_push(pts, a); }
 	}
+	dbg_line_end(&dl);
 	const int res = ss_process(&st, 0);
 	if (res > 0) { anchor_t a = {x - res, x - 1, y - res, y - 1}; al_push(pts, a); }
 	return init != pts->n;
@@ -385,6 +415,7 @@ static int t4_confirm(const scanner_t* sc, int kind, anchor_t* hint, int merge_c
 		const int xstart = hint->x - a_xrange(hint), xend = hint->xmax + a_xrange(hint), yavg = a_yavg(hint);
 		for (int dy = -1; dy <= 1; ++dy)
 			if (!scan_horizontal(sc, kind, &cf, yavg + dy, xstart, xend)) { free(cf.v); return 0; }
+		dbg_max(DBG_CONFIRM_LIST, cf.n);
 		int confirm = 0;
 		for (int k = 0; k < cf.n; ++k)
 			if (a_mergeable(&cf.v[k], hint, sc->cutoff)) {
@@ -400,6 +431,7 @@ static int t4_confirm(const scanner_t* sc, int kind, anchor_t* hint, int merge_c
 		const int ystart = hint->y - a_yrange(hint), yend = hint->ymax + a_yrange(hint), xavg = a_xavg(hint);
 		for (int dx = -1; dx <= 1; ++dx)
 			if (!scan_vertical(sc, kind, &cf, xavg + dx, xavg + dx, ystart, yend)) { free(cf.v); return 0; }
+		dbg_max(DBG_CONFIRM_LIST, cf.n);
 		int confirm = 0;
 		for (int k = 0; k < cf.n; ++k)
 			if (a_mergeable(&cf.v[k], hint, sc->cutoff)) {
@@ -420,11 +452,14 @@ static void on_t1_scan(const scanner_t* sc, int kind, const anchor_t* found, ali
 		if (a_mergeable(&candidates->v[k], found, sc->cutoff)) return;
 	alist col = {0, 0, 0};
 	scan_vertical(sc, kind, &col, found->x, found->xmax, found->y - 3 * a_xrange(found), found->ymax + 3 * a_xrange(found));
+	dbg_max(DBG_CONFIRM_LIST, col.n);
+	const int before = candidates->n;
 	for (int k = 0; k < col.n; ++k) {
 		const anchor_t* p = &col.v[k];
 		alist dg = {0, 0, 0};
 		const int yr = a_yrange(p);
 		if (scan_diagonal(sc, kind, &dg, a_xavg(p) - 2 * yr, a_xavg(p) + 2 * yr, p->y - yr, p->ymax + yr)) {
+			dbg_max(DBG_CONFIRM_LIST, dg.n);
 			int confirm = 0;
 			anchor_t merged = *p;
 			for (int q = 0; q < dg.n; ++q)
@@ -433,6 +468,7 @@ static void on_t1_scan(const scanner_t* sc, int kind, const anchor_t* found, ali
 		}
 		free(dg.v);
 	}
+	dbg_max(DBG_HIT_CONFIRMED, candidates->n - before);
 	free(col.v);
 }
 
@@ -443,8 +479,18 @@ static void t1_scan_rows(const scanner_t* sc, int kind, alist* candidates, int m
 	if (y < 0) y = skip;
 	if (yend < 0 || yend > sc->h) yend = sc->h;
 	alist pts = {0, 0, 0};
-	for (; y < yend; y += skip) scan_horizontal(sc, kind, &pts, y, xstart, xend);
+	const int second = kind != 114;
+	g_dbg_stage = second ? 2 : 1;
+	for (; y < yend; y += skip) {
+		const int before = pts.n;
+		scan_horizontal(sc, kind, &pts, y, xstart, xend);
+		g_dbg[second ? DBG_BR_ROWS : DBG_ROWS]++;
+		dbg_max(second ? DBG_BR_ROW_HITS : DBG_ROW_HITS, pts.n - before);
+	}
+	g_dbg_stage = 0;
+	g_dbg[second ? DBG_BR_HITS : DBG_PRIMARY_HITS] = pts.n;
 	for (int k = 0; k < pts.n; ++k) on_t1_scan(sc, kind, &pts.v[k], candidates, merge_confirms);
+	g_dbg[second ? DBG_BR_CANDIDATES : DBG_CANDIDATES] = candidates->n;
 	free(pts.v);
 }
 
@@ -454,8 +500,11 @@ int co_scan_anchors(const uint8_t* binary, int w, int h, int32_t* anchors16)
 {
 	scanner_t sc = {binary, w, h, (h < w ? h : w) / 60, w / 30};   /* Scanner.h:168-174: _skip, _mergeCutoff */
 	g_dbg_max_list = 0;
+	memset(g_dbg, 0, sizeof g_dbg);
 	alist cand = {0, 0, 0};
 	t1_scan_rows(&sc, 114, &cand, 1, -1, -1, -1, -1, -1);            /* scan_primary, Scanner.cpp:171-181 */
+	for (int i = 0; i < cand.n; ++i)
+		for (int j = i + 1; j < cand.n; ++j) if (a_size(&cand.v[i]) == a_size(&cand.v[j])) g_dbg[DBG_EQUAL_SIZES] = 1;
 	/* filter_candidates, Scanner.cpp:79-103 (std::sort on <= 16 elements is an insertion sort: stable) */
 	unsigned cutoff = 0;
 	if (cand.n >= 3) {
