@@ -1,5 +1,5 @@
 // api.hip.inc -- part of cimbar_hip.hip: the extern "C" entry points of include/cimbar_hip.h. The geometry-dependent implementation exists once
-// per mode (mode.hip.inc -> namespaces m68, m67); a context remembers its mode in its first word and every call is forwarded to that copy.
+// per mode (mode.hip.inc -> namespaces m68, m67, m66, m4, m8); a context remembers its mode in its first word and every call is forwarded to that copy.
 namespace {
 
 inline int ctx_mode(const cimbar_hip_ctx* ctx) { return *reinterpret_cast<const int*>(ctx); }

@@ -177,25 +177,31 @@ struct cimbar_hip_auto {
 	cimbar_hip_ctx* ctx[AUTO_MAX] = {};   // one context per candidate, in creation order
 	int slot = 0;                         // cimbar_hip_auto_bufsize
 	std::string err;
-	hipStream_t stream = nullptr;
-	float* d_carry = nullptr;             // [10] the one carried matrix + [10] its value at the start of the call
+	Stream stream;
+	DevBuf<float> d_carry;                // [10] the one carried matrix + [10] its value at the start of the call
 	// per call, grown on demand
-	int cap = 0;
-	int* d_pos = nullptr;                 // [K + 1][n]: slot of capture f in phase k's batch, -1 = did not reach it
-	int* d_list = nullptr;                // [K + 1][n]: the captures of phase k's batch (row 0 unused: the first phase is every capture in order)
-	uint8_t* d_dense = nullptr;           // a later phase's captures, gathered
-	size_t d_dense_cap = 0;
-	int* d_acc = nullptr;                 // [n] accepted candidate (K = none)
-	int* d_small = nullptr;               // [AUTO_MAX] phase counts, [1] changed
-	int* h_small = nullptr;               // pinned: the same
-	unsigned long long* d_total = nullptr;
-	unsigned long long* h_total = nullptr;
-	uint8_t* d_chunks[AUTO_MAX] = {};     // per candidate: [n][its frame bytes]
-	uint32_t* d_masks[AUTO_MAX] = {};
-	float* d_carry_in[AUTO_MAX] = {};     // per candidate: [n][10]
-	uint8_t* d_out = nullptr;             // host-memory outputs: [n][slot] chunks, then masks, modes, status
-	uint8_t* d_in = nullptr;              // host-memory captures
-	size_t d_in_cap = 0;
+	int cap = 0;                          // captures the per-capture buffers below hold
+	DevBuf<int> d_pos;                    // [K + 1][n]: slot of capture f in phase k's batch, -1 = did not reach it
+	DevBuf<int> d_list;                   // [K + 1][n]: the captures of phase k's batch (row 0 unused: the first phase is every capture in order)
+	DevBuf<uint8_t> d_dense;              // a later phase's captures, gathered
+	DevBuf<int> d_acc;                    // [n] accepted candidate (K = none)
+	DevBuf<int> d_small;                  // [AUTO_MAX] phase counts, [1] changed
+	PinnedBuf<int> h_small;               // the same
+	DevBuf<unsigned long long> d_total;
+	PinnedBuf<unsigned long long> h_total;
+	DevBuf<uint8_t> d_chunks[AUTO_MAX];   // per candidate: [n][its frame bytes]
+	DevBuf<uint32_t> d_masks[AUTO_MAX];
+	DevBuf<float> d_carry_in[AUTO_MAX];   // per candidate: [n][10]
+	DevBuf<uint8_t> d_out;                // host-memory outputs: [n][slot] chunks, then masks, modes, status
+	DevBuf<uint8_t> d_in;                 // host-memory captures
+
+	// everything in flight is waited for, then the contexts go; the members free what is left
+	~cimbar_hip_auto()
+	{
+		(void)hipSetDevice(device);
+		(void)hipDeviceSynchronize();
+		for (int k = 0; k < nmodes; ++k) if (ctx[k]) cimbar_hip_destroy(ctx[k]);
+	}
 };
 
 namespace {
@@ -209,46 +215,23 @@ namespace {
 		}                                                                                                 \
 	} while (0)
 
-template <typename T>
-hipError_t auto_regrow(T*& p, size_t count)
-{
-	if (p) { hipError_t e = hipFree(p); p = nullptr; if (e != hipSuccess) return e; }
-	return hipMalloc((void**)&p, sizeof(T) * (count ? count : 1));
-}
-
 int auto_capacity(cimbar_hip_auto* a, int n)
 {
 	if (n <= a->cap) return 0;
 	AUTOCHK(hipDeviceSynchronize());
 	a->cap = 0;
 	const size_t N = (size_t)n;
-	AUTOCHK(auto_regrow(a->d_pos, (AUTO_MAX + 1) * N));
-	AUTOCHK(auto_regrow(a->d_list, (AUTO_MAX + 1) * N));
-	AUTOCHK(auto_regrow(a->d_acc, N));
+	AUTOCHK(a->d_pos.reserve((AUTO_MAX + 1) * N));
+	AUTOCHK(a->d_list.reserve((AUTO_MAX + 1) * N));
+	AUTOCHK(a->d_acc.reserve(N));
 	for (int k = 0; k < a->nmodes; ++k) {
-		AUTOCHK(auto_regrow(a->d_chunks[k], N * cimbar_hip_mode_bufsize(a->modes[k])));
-		AUTOCHK(auto_regrow(a->d_masks[k], N));
-		AUTOCHK(auto_regrow(a->d_carry_in[k], N * 10));
+		AUTOCHK(a->d_chunks[k].reserve(N * cimbar_hip_mode_bufsize(a->modes[k])));
+		AUTOCHK(a->d_masks[k].reserve(N));
+		AUTOCHK(a->d_carry_in[k].reserve(N * 10));
 	}
-	AUTOCHK(auto_regrow(a->d_out, (N * a->slot + 15) / 16 * 16 + N * 12));
+	AUTOCHK(a->d_out.reserve((N * a->slot + 15) / 16 * 16 + N * 12));
 	a->cap = n;
 	return 0;
-}
-
-void auto_free(cimbar_hip_auto* a)
-{
-	(void)hipSetDevice(a->device);
-	(void)hipDeviceSynchronize();
-	for (int k = 0; k < a->nmodes; ++k) {
-		if (a->ctx[k]) cimbar_hip_destroy(a->ctx[k]);
-		(void)hipFree(a->d_chunks[k]); (void)hipFree(a->d_masks[k]); (void)hipFree(a->d_carry_in[k]);
-	}
-	(void)hipFree(a->d_carry); (void)hipFree(a->d_pos); (void)hipFree(a->d_list); (void)hipFree(a->d_dense); (void)hipFree(a->d_acc); (void)hipFree(a->d_small); (void)hipFree(a->d_total);
-	(void)hipFree(a->d_out); (void)hipFree(a->d_in);
-	if (a->h_small) (void)hipHostFree(a->h_small);
-	if (a->h_total) (void)hipHostFree(a->h_total);
-	if (a->stream) (void)hipStreamDestroy(a->stream);
-	delete a;
 }
 
 bool auto_mode_ok(int m) { return m == 68 || m == 67 || m == 66 || m == 4 || m == 8; }
@@ -273,23 +256,21 @@ int cimbar_hip_auto_create(int device, const int* modes, int n_modes, cimbar_hip
 		a->modes[i] = modes[i];
 		const int b = cimbar_hip_mode_bufsize(modes[i]);
 		if (b > a->slot) a->slot = b;
-		if (int r = cimbar_hip_create(device, modes[i], &a->ctx[i])) { a->ctx[i] = nullptr; auto_free(a); return r; }
+		if (int r = cimbar_hip_create(device, modes[i], &a->ctx[i])) { a->ctx[i] = nullptr; delete a; return r; }
 	}
-	auto fail = [&]() { auto_free(a); return CIMBAR_HIP_EHIP; };
+	auto fail = [&]() { delete a; return CIMBAR_HIP_EHIP; };
 	if (hipSetDevice(device) != hipSuccess) return fail();
-	if (hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking) != hipSuccess) return fail();
-	if (hipMalloc((void**)&a->d_carry, sizeof(float) * 20) != hipSuccess || hipMemset(a->d_carry, 0, sizeof(float) * 20) != hipSuccess) return fail();
-	if (hipMalloc((void**)&a->d_small, sizeof(int) * (AUTO_MAX + 1)) != hipSuccess) return fail();
-	if (hipMalloc((void**)&a->d_total, sizeof(unsigned long long)) != hipSuccess) return fail();
-	if (hipHostMalloc((void**)&a->h_small, sizeof(int) * (AUTO_MAX + 1), hipHostMallocDefault) != hipSuccess) return fail();
-	if (hipHostMalloc((void**)&a->h_total, sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) return fail();
+	if (a->stream.create() != hipSuccess) return fail();
+	if (a->d_carry.reserve(20) != hipSuccess || hipMemset(a->d_carry, 0, sizeof(float) * 20) != hipSuccess) return fail();
+	if (a->d_small.reserve(AUTO_MAX + 1) != hipSuccess || a->d_total.reserve(1) != hipSuccess) return fail();
+	if (a->h_small.reserve(AUTO_MAX + 1) != hipSuccess || a->h_total.reserve(1) != hipSuccess) return fail();
 	*out = a;
 	return 0;
 }
 
 void cimbar_hip_auto_destroy(cimbar_hip_auto* a)
 {
-	if (a) auto_free(a);
+	delete a;
 }
 
 int cimbar_hip_auto_bufsize(const cimbar_hip_auto* a) { return a ? a->slot : CIMBAR_HIP_EINVAL; }
@@ -362,7 +343,8 @@ int64_t cimbar_hip_auto_scan_extract_decode_batch_fmt(cimbar_hip_auto* a, const 
 	if (int r = auto_capacity(a, n)) return r;
 	const uint8_t* d_in = img;
 	if (img_mem == CIMBAR_HIP_MEM_HOST) {
-		if (cbytes * n > a->d_in_cap) { AUTOCHK(hipStreamSynchronize(st)); a->d_in_cap = 0; AUTOCHK(auto_regrow(a->d_in, cbytes * n)); a->d_in_cap = cbytes * n; }
+		if (cbytes * n > a->d_in.capacity()) AUTOCHK(hipStreamSynchronize(st));   // (what an earlier call on this stream still reads is about to be replaced)
+		AUTOCHK(a->d_in.reserve(cbytes * n));
 		AUTOCHK(hipMemcpyAsync(a->d_in, img, cbytes * n, hipMemcpyHostToDevice, st));
 		d_in = a->d_in;
 	}
@@ -394,7 +376,7 @@ int64_t cimbar_hip_auto_scan_extract_decode_batch_fmt(cimbar_hip_auto* a, const 
 			AUTOCHK(hipStreamSynchronize(st));
 			m = a->h_small[0];
 			if (m == 0) break;
-			if (cbytes * m > a->d_dense_cap) { a->d_dense_cap = 0; AUTOCHK(auto_regrow(a->d_dense, cbytes * m)); a->d_dense_cap = cbytes * m; }
+			AUTOCHK(a->d_dense.reserve(cbytes * m));
 			hipLaunchKernelGGL(k_auto_gather, dim3(64, m), dim3(256), 0, st, d_in, cbytes, list, a->d_dense);
 			d_phase = a->d_dense;
 		}
@@ -463,7 +445,7 @@ int64_t cimbar_hip_auto_scan_extract_decode_batch_fmt(cimbar_hip_auto* a, const 
 		AUTOCHK(hipMemcpyAsync(status, o_status, sizeof(int) * N, hipMemcpyDeviceToHost, st));
 	}
 	AUTOCHK(hipStreamSynchronize(st));
-	return (int64_t)*a->h_total;
+	return (int64_t)a->h_total[0];
 }
 
 }  // extern "C"

@@ -58,8 +58,8 @@ const int* auto_status(cimbar_hip_ctx* ctx, int* stride)
 	return &ctx->d_scan_res[0].status;
 }
 // ... its scan results (what a later phase's k_auto_scan_gather reads), and the matrix each of its frames derived ({9 floats, valid}, k_frame_mid)
-const void* auto_scan_results(cimbar_hip_ctx* ctx) { return ctx->d_scan_res; }
-const float* auto_ccm_frames(cimbar_hip_ctx* ctx) { return ctx->d_ccm_frames; }
+const void* auto_scan_results(cimbar_hip_ctx* ctx) { return ctx->d_scan_res.get(); }
+const float* auto_ccm_frames(cimbar_hip_ctx* ctx) { return ctx->cur().d_ccm_frames; }
 
 // One phase's symbol half for m device-resident captures (dense: capture i of the phase at d_in + i * capture bytes). src_scan == nullptr: the
 // first phase, which scans them itself; else the first phase's scan results, src_scan[list[i]] for capture i. Symbol chunks into d_chunks.
@@ -70,7 +70,7 @@ int auto_symbols(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_in, unsig
 	if (int r = drain_pipeline_into(ctx, st)) return r;
 	if (int r = extract_state(ctx, m)) return r;
 	if (int r = ensure_capacity(ctx, m)) return r;
-	if ((size_t)m * FRAME_RGB > ctx->d_ex_frames_cap) { HIPCHK(regrow(ctx->d_ex_frames, (size_t)m * FRAME_RGB)); ctx->d_ex_frames_cap = (size_t)m * FRAME_RGB; }
+	HIPCHK(ctx->d_ex_frames.reserve((size_t)m * FRAME_RGB));
 	if (!src_scan) {
 		if (int r = enqueue_scan(ctx, st, d_in, width, height, fmt, m)) return r;
 	} else {
@@ -93,7 +93,7 @@ int auto_select(cimbar_hip_ctx* ctx, hipStream_t st, int m, const int* list, int
 {
 	int stride;
 	const int* status = auto_status(ctx, &stride);
-	hipLaunchKernelGGL(k_auto_select, dim3((m + 255) / 256), dim3(256), 0, st, ctx->d_states, status, stride, m, list, list_next, pos_next, count);
+	hipLaunchKernelGGL(k_auto_select, dim3((m + 255) / 256), dim3(256), 0, st, ctx->cur().d_states, status, stride, m, list, list_next, pos_next, count);
 	HIPCHK(hipGetLastError());
 	return 0;
 }
@@ -103,15 +103,16 @@ int auto_select(cimbar_hip_ctx* ctx, hipStream_t st, int m, const int* list, int
 // dropped chunk slots), so that the round gives what a first one with these matrices would have.
 int auto_colours(cimbar_hip_ctx* ctx, hipStream_t st, int m, int cc, const float* d_carry_in, uint8_t* d_chunks, uint32_t* d_masks, bool again)
 {
+	cimbar_hip_ctx::ScratchSet& cur = ctx->cur();
 	if (again) {
-		if (!LEGACY) hipLaunchKernelGGL((k_rs<4>), dim3((m * SYM_BLOCKS + 3) / 4), dim3(256), 0, st, ctx->d_symbols, ctx->tb, 0, m, 0, d_chunks, ctx->d_rs_ok, 0);
-		hipLaunchKernelGGL(k_frame_mid, dim3(m), dim3(64), 0, st, ctx->d_ex_frames, ctx->d_cellmean, ctx->tb, d_chunks, ctx->d_rs_ok, cc, ctx->d_states, ctx->d_ccm_frames, 0, 0);
+		if (!LEGACY) hipLaunchKernelGGL((k_rs<4>), dim3((m * SYM_BLOCKS + 3) / 4), dim3(256), 0, st, cur.d_symbols, ctx->tb, 0, m, 0, d_chunks, cur.d_rs_ok, 0);
+		hipLaunchKernelGGL(k_frame_mid, dim3(m), dim3(64), 0, st, ctx->d_ex_frames, cur.d_cellmean, ctx->tb, d_chunks, cur.d_rs_ok, cc, cur.d_states, cur.d_ccm_frames, 0, 0);
 	}
-	hipLaunchKernelGGL((k_colors<true>), dim3(K5_BLOCKS, m), dim3(256), 0, st, ctx->d_ex_frames, ctx->d_cellmean, ctx->tb, ctx->d_ccm_frames, d_carry_in,
-	                   ctx->d_flood, ctx->d_drift, ctx->d_colors, ctx->d_ccm_used, 0);
-	if (LEGACY) hipLaunchKernelGGL((k_rs<(LEGACY ? CELL_BITS : 6)>), dim3((m * ALL_BLOCKS + 3) / 4), dim3(256), 0, st, ctx->d_symbols, ctx->tb, 0, m, 0, d_chunks, ctx->d_rs_ok, 0, ctx->d_colors);
-	else hipLaunchKernelGGL((k_rs<2>), dim3((m * COL_BLOCKS + 3) / 4), dim3(256), 0, st, ctx->d_colors, ctx->tb, 0, m, SYM_CHUNKS, d_chunks, ctx->d_rs_ok, SYM_BLOCKS);
-	hipLaunchKernelGGL(k_frame_end, dim3(m), dim3(64), 0, st, ctx->d_rs_ok, ctx->d_states, d_chunks, d_masks, ctx->d_ccm_used, ctx->d_carry, 0, 0, 0);
+	hipLaunchKernelGGL((k_colors<true>), dim3(K5_BLOCKS, m), dim3(256), 0, st, ctx->d_ex_frames, cur.d_cellmean, ctx->tb, cur.d_ccm_frames, d_carry_in,
+	                   cur.d_flood, cur.d_drift, cur.d_colors, cur.d_ccm_used, 0);
+	if (LEGACY) hipLaunchKernelGGL((k_rs<(LEGACY ? CELL_BITS : 6)>), dim3((m * ALL_BLOCKS + 3) / 4), dim3(256), 0, st, cur.d_symbols, ctx->tb, 0, m, 0, d_chunks, cur.d_rs_ok, 0, cur.d_colors);
+	else hipLaunchKernelGGL((k_rs<2>), dim3((m * COL_BLOCKS + 3) / 4), dim3(256), 0, st, cur.d_colors, ctx->tb, 0, m, SYM_CHUNKS, d_chunks, cur.d_rs_ok, SYM_BLOCKS);
+	hipLaunchKernelGGL(k_frame_end, dim3(m), dim3(64), 0, st, cur.d_rs_ok, cur.d_states, d_chunks, d_masks, cur.d_ccm_used, ctx->d_carry, 0, 0, 0);
 	int stride;
 	const int* status = auto_status(ctx, &stride);
 	hipLaunchKernelGGL(k_mask_failed, dim3(m), dim3(256), 0, st, status, stride, m, d_masks, d_chunks);

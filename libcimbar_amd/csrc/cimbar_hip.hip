@@ -31,11 +31,16 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/cimbar_hip.h"
+
+// the owners of device buffers, page-locked buffers, events and streams: what every context below is made of
+#include "devbuf.hip.inc"
 
 // chunk delivery: three integers of geometry, so one copy serves every mode (the contexts below own its state)
 #include "deliver.hip.inc"

@@ -189,14 +189,14 @@ __global__ __launch_bounds__(256) void k_deliver_copy(const uint8_t* __restrict_
 
 // ------------------------------------------------------------------------------------------------ host side
 struct State {
-	hipEvent_t ev_last = nullptr;             // behind the last call's kernels: the next call, on whatever stream, starts after it (they share the scratch below)
+	Event ev_last;                            // behind the last call's kernels: the next call, on whatever stream, starts after it (they share the scratch below)
 	bool used = false;
-	Ctl* d_ctl = nullptr;
-	unsigned long long* d_table = nullptr;    // the remembered headers: open addressing, full 48-bit keys | KEY_TAG, never more than half full
+	DevBuf<Ctl> d_ctl;
+	DevBuf<unsigned long long> d_table;       // the remembered headers: open addressing, full 48-bit keys | KEY_TAG, never more than half full
 	int cap_log2 = 0;                         // 0: no table yet
-	uint8_t* d_scratch = nullptr; size_t scratch_cap = 0;   // the call's table, kept words, bases, count
-	uint8_t* d_in = nullptr; size_t in_cap = 0;             // staging for host-memory input
-	uint8_t* d_out = nullptr; size_t out_cap = 0;           // ... and output
+	DevBuf<uint8_t> d_scratch;                // the call's table, kept words, bases, count
+	DevBuf<uint8_t> d_in;                     // staging for host-memory input
+	DevBuf<uint8_t> d_out;                    // ... and output
 };
 
 // what the entry points need of a context (filled by the context's mode: host.hip.inc delivery_view)
@@ -205,16 +205,8 @@ struct View {
 	std::string* err = nullptr;
 	hipStream_t stream = nullptr;
 	int chunk = 0, per = 0;
-	State** state = nullptr;
+	std::unique_ptr<State>* state = nullptr;
 };
-
-void destroy(State* s)
-{
-	if (!s) return;
-	if (s->ev_last) (void)hipEventDestroy(s->ev_last);
-	for (void* p : {(void*)s->d_ctl, (void*)s->d_table, (void*)s->d_scratch, (void*)s->d_in, (void*)s->d_out}) if (p) (void)hipFree(p);
-	delete s;
-}
 
 #define DELIVER_CHK(call)                                                                                \
 	do {                                                                                                  \
@@ -228,12 +220,11 @@ void destroy(State* s)
 int ensure_state(const View& v)
 {
 	if (*v.state) return 0;
-	State* s = new State;
-	hipError_t e = hipEventCreateWithFlags(&s->ev_last, hipEventDisableTiming);
-	if (e == hipSuccess) e = hipMalloc(&s->d_ctl, sizeof(Ctl));
-	if (e == hipSuccess) e = hipMemset(s->d_ctl, 0, sizeof(Ctl));
-	if (e != hipSuccess) { destroy(s); DELIVER_CHK(e); }
-	*v.state = s;
+	std::unique_ptr<State> s(new State);
+	DELIVER_CHK(s->ev_last.create());
+	DELIVER_CHK(s->d_ctl.reserve(1));
+	DELIVER_CHK(hipMemset(s->d_ctl, 0, sizeof(Ctl)));
+	*v.state = std::move(s);
 	return 0;
 }
 
@@ -244,14 +235,12 @@ int quiesce(const View& v, State* s)
 	return 0;
 }
 
-int grow(const View& v, State* s, uint8_t*& p, size_t& cap, size_t need)
+// room for `need` bytes in one of the state's buffers, replaced only once nothing in flight uses it
+int reserve_idle(const View& v, State* s, DevBuf<uint8_t>& buf, size_t need)
 {
-	if (need <= cap) return 0;
+	if (need <= buf.capacity()) return 0;
 	if (int r = quiesce(v, s)) return r;
-	cap = 0;
-	if (p) { hipError_t e = hipFree(p); p = nullptr; DELIVER_CHK(e); }
-	DELIVER_CHK(hipMalloc(&p, need));
-	cap = need;
+	DELIVER_CHK(buf.reserve(need));
 	return 0;
 }
 
@@ -261,8 +250,8 @@ int reset_table(const View& v, State* s, int cap_log2)
 	if (int r = quiesce(v, s)) return r;
 	if (s->cap_log2 != cap_log2) {
 		s->cap_log2 = 0;
-		if (s->d_table) { hipError_t e = hipFree(s->d_table); s->d_table = nullptr; DELIVER_CHK(e); }
-		DELIVER_CHK(hipMalloc(&s->d_table, sizeof(unsigned long long) << cap_log2));
+		DELIVER_CHK(s->d_table.release());   // (a smaller table is a smaller allocation)
+		DELIVER_CHK(s->d_table.reserve((size_t)1 << cap_log2));
 		s->cap_log2 = cap_log2;
 	}
 	DELIVER_CHK(hipMemset(s->d_table, 0, sizeof(unsigned long long) << cap_log2));
@@ -289,7 +278,7 @@ int64_t deliver_chunks(const View& v, const uint8_t* chunks, const uint32_t* mas
 
 	DELIVER_CHK(hipSetDevice(v.device));
 	if (int r = ensure_state(v)) return r;
-	State* s = *v.state;
+	State* s = v.state->get();
 	// the stream rules of cimbar_hip_decode_batch: NULL is the null stream when a device buffer is involved, the context's own stream otherwise
 	const bool any_device = in_mem == CIMBAR_HIP_MEM_DEVICE || out_mem == CIMBAR_HIP_MEM_DEVICE;
 	hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (any_device ? (hipStream_t)nullptr : v.stream);
@@ -300,10 +289,10 @@ int64_t deliver_chunks(const View& v, const uint8_t* chunks, const uint32_t* mas
 	const size_t off_kept = up8(sizeof(unsigned long long) * tsize), off_first = up8(off_kept + sizeof(uint32_t) * (size_t)n),
 	             off_where = up8(off_first + sizeof(uint32_t) * tsize), off_base = up8(off_where + sizeof(int32_t) * (size_t)total),
 	             off_count = up8(off_base + sizeof(uint32_t) * (size_t)n), need = off_count + 8;
-	if (int r = grow(v, s, s->d_scratch, s->scratch_cap, need)) return r;
+	if (int r = reserve_idle(v, s, s->d_scratch, need)) return r;
 	const size_t in_bytes = up8((size_t)total * cs), out_bytes = up8((size_t)total * cs);
-	if (in_mem == CIMBAR_HIP_MEM_HOST) if (int r = grow(v, s, s->d_in, s->in_cap, in_bytes + sizeof(uint32_t) * (size_t)n)) return r;
-	if (out_mem == CIMBAR_HIP_MEM_HOST) if (int r = grow(v, s, s->d_out, s->out_cap, out_bytes + sizeof(int32_t) * (size_t)total)) return r;
+	if (in_mem == CIMBAR_HIP_MEM_HOST) if (int r = reserve_idle(v, s, s->d_in, in_bytes + sizeof(uint32_t) * (size_t)n)) return r;
+	if (out_mem == CIMBAR_HIP_MEM_HOST) if (int r = reserve_idle(v, s, s->d_out, out_bytes + sizeof(int32_t) * (size_t)total)) return r;
 	if (remember && !s->cap_log2) if (int r = reset_table(v, s, DEFAULT_CAP_LOG2)) return r;
 
 	if (s->used) DELIVER_CHK(hipStreamWaitEvent(st, s->ev_last, 0));
@@ -315,9 +304,9 @@ int64_t deliver_chunks(const View& v, const uint8_t* chunks, const uint32_t* mas
 		d_chunks = s->d_in;
 		d_masks = reinterpret_cast<const uint32_t*>(s->d_in + in_bytes);
 	}
-	uint8_t* d_packed = out_mem == CIMBAR_HIP_MEM_DEVICE ? packed : s->d_out;
+	uint8_t* d_packed = out_mem == CIMBAR_HIP_MEM_DEVICE ? packed : s->d_out.get();
 	int32_t* d_src = out_mem == CIMBAR_HIP_MEM_DEVICE ? src : (src ? reinterpret_cast<int32_t*>(s->d_out + out_bytes) : nullptr);
-	unsigned long long* d_keys = reinterpret_cast<unsigned long long*>(s->d_scratch);
+	unsigned long long* d_keys = reinterpret_cast<unsigned long long*>(s->d_scratch.get());
 	uint32_t* d_kept = reinterpret_cast<uint32_t*>(s->d_scratch + off_kept);
 	uint32_t* d_first = reinterpret_cast<uint32_t*>(s->d_scratch + off_first);
 	int32_t* d_where = reinterpret_cast<int32_t*>(s->d_scratch + off_where);
@@ -358,13 +347,13 @@ int delivery_reset(const View& v, int capacity_log2)
 	}
 	DELIVER_CHK(hipSetDevice(v.device));
 	if (int r = ensure_state(v)) return r;
-	return reset_table(v, *v.state, capacity_log2 ? capacity_log2 : DEFAULT_CAP_LOG2);
+	return reset_table(v, v.state->get(), capacity_log2 ? capacity_log2 : DEFAULT_CAP_LOG2);
 }
 
 int delivery_stats(const View& v, int64_t* remembered, int64_t* capacity, int* overflowed)
 {
 	Ctl c{};
-	State* s = *v.state;
+	State* s = v.state->get();
 	if (s) {
 		DELIVER_CHK(hipSetDevice(v.device));
 		if (int r = quiesce(v, s)) return r;

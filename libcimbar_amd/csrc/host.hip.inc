@@ -4,25 +4,24 @@
 struct cimbar_hip_ctx {
 	int mode_tag = MODE_VAL;                  // FIRST member: api.hip.inc reads it through the opaque pointer to pick the namespace
 	int device = 0;
-	hipStream_t stream = nullptr;
-	hipStream_t stream2 = nullptr;            // second half of a batch's tail kernels (see enqueue)
-	hipEvent_t ev_k1 = nullptr, ev_join = nullptr, ev_mid[8] = {};
+	// Everything below that owns something (devbuf.hip.inc) frees it in its destructor, after the body of ~cimbar_hip_ctx() at the end of this struct.
+	Stream stream;
+	Stream stream2;                           // second half of a batch's tail kernels (see enqueue)
+	Event ev_k1, ev_join, ev_mid[8];
 	int tail_split = 1, tail_parts = 2;
-	uint32_t* h_flagged = nullptr;    // pinned, written by k_count_flagged at the end of every ordinary batch: [0] frames that left the parallel path, [1] frames of that batch,
+	PinnedBuf<uint32_t> h_flagged;    // written by k_count_flagged at the end of every ordinary batch: [0] frames that left the parallel path, [1] frames of that batch,
 	                                  // [2] frames the exact replay had to take.
 	int er_sym = 0, er_col = -1, er_max = -1;   // cimbar_hip_set_erasure_decode: off while er_sym <= 0 (k_erasure_frame is then never launched)
 	int ec_margin = 0, ec_max = -1;             // cimbar_hip_set_colour_erasure_decode: off while ec_margin <= 0 (k_colour_erasure_frame is then never launched)
 	bool cm_valid = false;                      // the last batch ran the colour retry (CIMBAR_HIP_TAP_COLOUR_MARGIN describes it)
-	uint8_t* d_er_buf = nullptr;                // cimbar_hip_rs_decode_erasures' staging for host-memory calls (grown on demand)
-	size_t d_er_cap = 0;
-	deliver::State* delivery = nullptr;         // cimbar_hip_deliver_chunks' scratch and remembered headers (deliver.hip.inc): nothing of it exists until the first call
+	DevBuf<uint8_t> d_er_buf;                   // cimbar_hip_rs_decode_erasures' staging for host-memory calls (grown on demand)
+	std::unique_ptr<deliver::State> delivery;   // cimbar_hip_deliver_chunks' scratch and remembered headers (deliver.hip.inc): nothing of it exists until the first call
 	// the group decode (cimbar_hip_decode_batch_combined / _scan_extract_decode_batch_combined_fmt, combine.hip.inc): per capture slot, grown on demand
-	int grp_cap = 0;
 	bool grp_valid = false;                     // the last batch was a combined one (the group taps describe it)
-	uint8_t* d_gsym = nullptr; uint8_t* d_gcol = nullptr; uint16_t* d_gmargin = nullptr; uint8_t* d_grs_ok = nullptr;   // [n][NCELLS], [n][ALL_BLOCKS]
-	uint32_t* d_gagree = nullptr; uint32_t* d_gdisp = nullptr; int* d_groups = nullptr; int* d_gmem = nullptr; int* d_gcount = nullptr; int* d_groups_in = nullptr;
-	int* d_ngroups = nullptr;                   // 1 int
-	uint8_t* d_gchunks = nullptr; uint32_t* d_gmasks = nullptr;   // staging for host-memory group outputs
+	DevBuf<uint8_t> d_gsym, d_gcol; DevBuf<uint16_t> d_gmargin; DevBuf<uint8_t> d_grs_ok;   // [n][NCELLS], [n][ALL_BLOCKS]
+	DevBuf<uint32_t> d_gagree, d_gdisp; DevBuf<int> d_groups, d_gmem, d_gcount, d_groups_in;
+	DevBuf<int> d_ngroups;                      // 1 int
+	DevBuf<uint8_t> d_gchunks; DevBuf<uint32_t> d_gmasks;   // staging for host-memory group outputs
 	int wave_adapt = 1;               // CIMBAR_HIP_FLOOD_WAVE_ADAPT=0: run k_flood_wave in front of every exact replay, whatever it achieved before
 	bool wave_ran = false;            // k_flood_wave ran in the batch h_flagged describes
 	int wave_skip_left = 0;           // batches that still go straight to the exact replay (see enqueue)
@@ -30,56 +29,49 @@ struct cimbar_hip_ctx {
 	bool no_split_once = false;       // set by the capture path around its enqueue(): deskewed captures all take the exact flood, and two half-batch flood
 	                                  // launches on two queues run one after the other in effect (1024 captures: 62 ms split, 42 ms as one launch)
 	std::string err;
-	Tables tb{};
+	Tables tb{};                      // what the kernels take by value: filled by build_tables from the owners beside it
+	DevBuf<ushort2> tb_cell_xy; DevBuf<uint16_t> tb_stream_cell, tb_cell_grid, tb_ccm_grid; DevBuf<int16_t> tb_grid_cell, tb_cand;
 	uint64_t tile_hashes[16] = {};   // as computed at create (also in c_tile)
-	// batch scratch (grown on demand)
-	int cap = 0;
 	int last_n = 0;
 	int scan_n = 0;                             // captures of the last anchor search (CIMBAR_HIP_TAP_SCAN_PATH describes it)
-	uint8_t* d_rgb = nullptr;         // staging for host-resident input
-	size_t d_rgb_cap = 0;
-	uint32_t* d_plane = nullptr;
-	uint32_t* d_cellmean = nullptr;
-	uint8_t* d_symbols = nullptr;
-	uint8_t* d_colors = nullptr;
-	int8_t* d_drift = nullptr;
-	uint32_t* d_flood = nullptr;
-	uint8_t* d_rs_ok = nullptr;
-	FrameState* d_states = nullptr;
-	float* d_ccm_frames = nullptr;
-	float* d_ccm_used = nullptr;
-	uint32_t* d_cmargin = nullptr;    // the colour retry's margins [cm_cap][NCELLS], then its per-frame "worked on" words [cm_cap]; allocated once the setting is on
-	int cm_cap = 0;
-	// the pipelined entry point rotates through `pipe_depth` sets of the intermediates above (the members are always the set in
-	// use by the newest batch; the others are parked here) and as many streams, so that several batches are in flight at once
+	DevBuf<uint8_t> d_rgb;            // staging for host-resident input
+	// the intermediates of a batch (grown on demand). A context has `pipe_depth` sets of them and as many streams: the pipelined entry point steps to the
+	// next set with every batch, so that several batches are in flight at once; every other call uses the set the newest batch used (cur())
 	static constexpr int MAXP = 4;
 	struct ScratchSet {
-		int cap = 0;
-		uint32_t* d_plane = nullptr; uint32_t* d_cellmean = nullptr; uint8_t* d_symbols = nullptr; uint8_t* d_colors = nullptr;
-		int8_t* d_drift = nullptr; uint32_t* d_flood = nullptr; uint8_t* d_rs_ok = nullptr; FrameState* d_states = nullptr;
-		float* d_ccm_frames = nullptr; float* d_ccm_used = nullptr;
-		uint32_t* d_cmargin = nullptr; int cm_cap = 0;
-	} parked[MAXP];
+		int cap = 0;                      // frames the set holds
+		DevBuf<uint32_t> d_plane, d_cellmean;
+		DevBuf<uint8_t> d_symbols, d_colors;
+		DevBuf<int8_t> d_drift;
+		DevBuf<uint32_t> d_flood;         // [cap] frame flags, then [cap] what k_flood_wave made of the frame (CIMBAR_HIP_TAP_FLOOD_INFO); zeroed when it grows
+		DevBuf<uint8_t> d_rs_ok;
+		DevBuf<FrameState> d_states;
+		DevBuf<float> d_ccm_frames, d_ccm_used;
+		DevBuf<uint32_t> d_cmargin;       // the colour retry's margins [cm_cap][NCELLS], then its per-frame "worked on" words [cm_cap]; allocated once the setting is on
+		int cm_cap = 0;
+	} sets[MAXP];
 	int pipe_depth = 3;               // batches in flight (CIMBAR_HIP_PIPE_DEPTH): 3 measured best once every step reads HBM (4 distinct input batches): 0.81 vs 0.85 ms at 4
 #ifdef CIMBAR_PROBES
-	int dbg_skip = 0;                 // CIMBAR_HIP_DEBUG_SKIP (probe builds only, -DCIMBAR_PROBES: tools/build_probes.sh): bit mask of chain kernels NOT launched -- timing experiments, results are then wrong
+	int dbg_skip = 0;                 // CIMBAR_HIP_DEBUG_SKIP (probe builds only, -DCIMBAR_PROBES: python -m libcimbar_amd.build --probes): bit mask of chain kernels NOT launched -- timing experiments, results are then wrong
 #else
 	static constexpr int dbg_skip = 0; // the product library cannot drop a kernel: the switch and the k_rs<.., NOSYND> instances only exist in a -DCIMBAR_PROBES build
 #endif
-	int pipe_set = 0;                 // which set the member pointers above currently are
+	int pipe_set = 0;                 // the set in use
+	ScratchSet& cur() { return sets[pipe_set]; }
 	bool pipe_used[MAXP] = {};
-	hipStream_t pstream[MAXP] = {};
-	hipEvent_t ev_pk1[MAXP] = {}, ev_pdone[MAXP] = {};
-	hipEvent_t ev_pgather[MAXP] = {};  // cimbar_hip_pipeline_gather: "the exchange behind this set's batch is over" (an event of its own: the NEXT batch's colour pass waits for
+	Stream pstream_own[MAXP];         // the streams the pipeline needs beyond stream / stream2 ([0], [1] stay empty)
+	hipStream_t pstream[MAXP] = {};   // set k's stream: stream, stream2, then pstream_own[k]
+	Event ev_pk1[MAXP], ev_pdone[MAXP];
+	Event ev_pgather[MAXP];            // cimbar_hip_pipeline_gather: "the exchange behind this set's batch is over" (an event of its own: the NEXT batch's colour pass waits for
 	bool pipe_gathered[MAXP] = {};     // ev_pdone only -- the carry-over must not wait for other ranks). pipeline_wait waits for both where a gather was issued
 	// one frame per call, up to pipe_depth of them in flight (cimbar_hip_decode_frame_async / _wait): slot s rides on scratch set s and stream s of the
 	// pipeline above -- frame k+1's host-to-device copy runs on another queue than frame k's kernels, which is the whole point
 	struct FrameSlot {
-		uint8_t* d_rgb = nullptr;        // the frame on the device
-		uint8_t* d_out = nullptr;        // its chunks [FRAME_OUT_STRIDE] + mask [4]
-		uint8_t* h_out = nullptr;        // page-locked: where the one device-to-host copy lands
-		uint8_t* h_in = nullptr;         // page-locked staging for frames that arrive in pageable memory (allocated when one does)
-		hipEvent_t done = nullptr;
+		DevBuf<uint8_t> d_rgb;           // the frame on the device
+		DevBuf<uint8_t> d_out;           // its chunks [FRAME_OUT_STRIDE] + mask [4]
+		PinnedBuf<uint8_t> h_out;        // where the one device-to-host copy lands
+		PinnedBuf<uint8_t> h_in;         // staging for frames that arrive in pageable memory (allocated when one does)
+		Event done;
 		uint8_t* user_chunks = nullptr; uint32_t* user_mask = nullptr;
 		long long ticket = -1;           // >= 0: in flight
 	} fslot[MAXP];
@@ -88,47 +80,46 @@ struct cimbar_hip_ctx {
 	int k1_lds_pad = 0;               // CIMBAR_HIP_K1_LDS_PAD: dynamic LDS bytes reserved per K1 workgroup (an occupancy cap for experiments: 30000 -> two workgroups per CU)
 	size_t warp_scratch = (size_t)4 << 30;   // CIMBAR_HIP_WARP_SCRATCH_MB: what the two-pass warp may hold of converted captures at a time (it goes through a batch in passes of that many captures, at most WARP_CHUNK)
 	int warp_twopass = 1;             // CIMBAR_HIP_WARP_TWOPASS=0: NV12 / 4:2:0 captures are converted inside the warp kernel, tap by tap, instead of once per source pixel ahead of it
-	int4* d_ex_box = nullptr; int d_ex_box_cap = 0;          // ... and the box of every capture (k_roi_boxes)
-	uint8_t* d_ex_rgb = nullptr; size_t d_ex_rgb_cap = 0;   // ... the capture-shaped RGB8 scratch of that conversion, WARP_CHUNK captures at a time
+	DevBuf<int4> d_ex_box;            // ... and the box of every capture (k_roi_boxes)
+	DevBuf<uint8_t> d_ex_rgb;         // ... the capture-shaped RGB8 scratch of that conversion, WARP_CHUNK captures at a time
 	int frame_stage = 0;              // CIMBAR_HIP_FRAME_STAGE=1: pageable frames go through the context's own page-locked staging instead of the runtime's
 	int frame_zerocopy = 1;           // CIMBAR_HIP_FRAME_ZEROCOPY=0: chunks + mask go to device memory and come back with a copy, instead of being written to page-locked host memory by the kernels
 	int frame_copystream = 0;         // CIMBAR_HIP_FRAME_COPYSTREAM=1: every frame's host-to-device copy on one stream of its own (never queued behind another frame's copy back)
-	hipStream_t fcopy = nullptr;
-	hipEvent_t ev_fcopy[MAXP] = {};
+	Stream fcopy;
+	Event ev_fcopy[MAXP];
 	struct FrameResult { long long ticket = -1; int rc = 0; } fresult[16];   // return values of frames that are complete but not yet asked for
-	float* d_carry = nullptr;         // 10 floats
-	uint8_t* d_template = nullptr;    // encode half: empty frame (background, anchors, guides)
-	uint8_t* d_gen_log = nullptr;     // encode half: logs of the 30 low generator coefficients
-	uint8_t* d_payload = nullptr;     // encode half: staging for host-resident payload
-	size_t d_payload_cap = 0;
-	uint8_t* d_chunks = nullptr;      // staging for host-resident output: shared by every scratch set, so it has a capacity of its own
-	uint32_t* d_masks = nullptr;
-	int out_cap = 0;
+	DevBuf<float> d_carry;            // 10 floats
+	DevBuf<uint8_t> d_template;       // encode half: empty frame (background, anchors, guides)
+	DevBuf<uint8_t> d_gen_log;        // encode half: logs of the 30 low generator coefficients
+	DevBuf<uint8_t> d_payload;        // encode half: staging for host-resident payload
+	DevBuf<uint8_t> d_chunks;         // staging for host-resident output: shared by every scratch set, so it grows on its own
+	DevBuf<uint32_t> d_masks;
 	// extractor stage (scan_preprocess / deskew_batch): staging + small per-frame state
-	uint8_t* d_ex_in = nullptr; size_t d_ex_in_cap = 0;
+	DevBuf<uint8_t> d_ex_in;
 	// set by decode_frame around ONE decode of an image larger than the frame (CimbReader's _gridPadding case): enqueue() then runs K1p on it
 	const uint8_t* pad_src = nullptr; int pad_w = 0, pad_h = 0, pad_off = 0;
-	uint8_t* d_ex_out = nullptr; size_t d_ex_out_cap = 0;
-	uint32_t* d_ex_hist = nullptr; int* d_ex_thr = nullptr; double* d_ex_minv = nullptr; int d_ex_n = 0;
-	uint8_t* d_ex_gray = nullptr; size_t d_ex_gray_cap = 0;   // blurred gray captures (what the anchor search reads)
-	uint8_t* d_ex_frames = nullptr; size_t d_ex_frames_cap = 0;   // deskewed frames of scan_extract_decode
-	uint32_t* d_scan_hits = nullptr; int* d_scan_nhits = nullptr; ScanResult* d_scan_res = nullptr;
-	ScanAnchor* d_scan_serial = nullptr;   // scratch lists of k_scan_serial (captures whose anchor search overflowed the fast kernels' lists)
-	int* d_scan_offs = nullptr; int* d_scan_ovf = nullptr; ScanConf* d_scan_conf = nullptr; ScanStage* d_scan_stage = nullptr;   // stage[0..n) primary, [n..2n) bottom-right
-	double* h_ex_minv = nullptr;      // pinned staging for the warp matrices (an async copy must not read a pageable temporary)
-	hipEvent_t ev_ex_minv = nullptr;  // the last copy out of h_ex_minv
+	DevBuf<uint8_t> d_ex_out;
+	DevBuf<uint32_t> d_ex_hist; DevBuf<int> d_ex_thr; DevBuf<double> d_ex_minv;
+	DevBuf<uint8_t> d_ex_gray;        // blurred gray captures (what the anchor search reads)
+	DevBuf<uint8_t> d_ex_frames;      // deskewed frames of scan_extract_decode
+	DevBuf<uint32_t> d_scan_hits; DevBuf<int> d_scan_nhits; DevBuf<ScanResult> d_scan_res;
+	DevBuf<ScanAnchor> d_scan_serial;   // scratch lists of k_scan_serial (captures whose anchor search overflowed the fast kernels' lists)
+	DevBuf<int> d_scan_offs, d_scan_ovf; DevBuf<ScanConf> d_scan_conf; DevBuf<ScanStage> d_scan_stage;   // stage[0..n) primary, [n..2n) bottom-right
+	PinnedBuf<double> h_ex_minv;      // staging for the warp matrices (an async copy must not read a pageable temporary)
+	Event ev_ex_minv;                 // the last copy out of h_ex_minv
 	// lens undistortion (cimbar_hip_undistort_* / cimbar_hip_scan_undistort_extract_decode_batch_fmt): nothing of it exists until one of those is called
-	uint8_t* d_ud_img = nullptr; size_t d_ud_img_cap = 0;    // the undistorted RGB8 captures of one group (at most ud_scratch bytes, see undistort_group)
-	int* d_ud_ok = nullptr; double* d_ud_k1 = nullptr; int* d_ud_status = nullptr; int d_ud_n = 0;   // per capture of a call
-	double* d_ud_xt = nullptr; double* h_ud_xt = nullptr; int ud_xt_cap = 0;   // the column table of U2 (device + pinned staging)
-	hipEvent_t ev_ud_xt = nullptr;    // the last copy out of h_ud_xt
+	DevBuf<uint8_t> d_ud_img;         // the undistorted RGB8 captures of one group (at most ud_scratch bytes, see undistort_group)
+	DevBuf<int> d_ud_ok; DevBuf<double> d_ud_k1; DevBuf<int> d_ud_status;   // per capture of a call
+	DevBuf<double> d_ud_xt; PinnedBuf<double> h_ud_xt;   // the column table of U2 (device + page-locked staging)
+	Event ev_ud_xt;                   // the last copy out of h_ud_xt
 	size_t ud_scratch = (size_t)256 << 20;   // CIMBAR_HIP_UNDISTORT_SCRATCH_MB
-	FloodScratch flood{};
+	FloodScratch flood{};             // by value into the flood kernels: filled by ensure_flood_areas from the owners beside it
+	DevBuf<uint32_t> flood_heap, flood_next; DevBuf<uint8_t> flood_prio;
 	int flood_cap = 0;                // spill areas allocated in flood.heap (grown to what the launches use: one frame -> 0.6 MB, a full batch -> 610 MB)
-	uint32_t* d_fw_queue = nullptr;   // k_flood_wave: one work queue of NCELLS entries per resident workgroup
+	DevBuf<uint32_t> d_fw_queue;      // k_flood_wave: one work queue of NCELLS entries per resident workgroup
 	int flood_verify = 0;             // CIMBAR_HIP_FLOOD_VERIFY=1: every frame k_flood_wave certified is replayed exactly as well and compared (see enqueue)
-	uint8_t* d_vsym = nullptr; int8_t* d_vdrift = nullptr; uint32_t* d_vflag = nullptr; int vcap = 0;   // its buffers: saved batch results, [n] flags + [n] differing cells
-	unsigned long long* d_vtotals = nullptr;                                                           // [2] certified frames replayed / frames that differed, since create
+	DevBuf<uint8_t> d_vsym; DevBuf<int8_t> d_vdrift; DevBuf<uint32_t> d_vflag; int vcap = 0;   // its buffers: saved batch results, [n] flags + [n] differing cells
+	DevBuf<unsigned long long> d_vtotals;                                                    // [2] certified frames replayed / frames that differed, since create
 	int flood_dense_grid = 2048;      // workgroups of a full-size dense launch (CIMBAR_HIP_FLOOD_DENSE_GRID, <= 2048)
 	int flood_dense = -1;             // exact replay at eight frames per CU (k_flood3<HEAP_LDS8, true>): -1 = where a launch has more frames than four per CU hold,
 	                                  // 0 = never, 1 = always (CIMBAR_HIP_FLOOD_DENSE)
@@ -136,8 +127,21 @@ struct cimbar_hip_ctx {
 	// timing
 	bool timing = false;
 	static constexpr int NSTAGE = 8;
-	hipEvent_t ev[NSTAGE + 1] = {};
+	Event ev[NSTAGE + 1];
 	float stage_ms[NSTAGE] = {};
+
+	// (also what the early returns of cimbar_hip_create run: whatever exists by then is freed by the members, after this body)
+	~cimbar_hip_ctx()
+	{
+		(void)hipSetDevice(device);
+		// frames started with cimbar_hip_decode_frame_async and never waited for still have kernels writing into the context's page-locked buffers
+		(void)hipDeviceSynchronize();
+		if (flood_verify && d_vtotals) {
+			unsigned long long t[2] = {0, 0};
+			if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(t, d_vtotals, sizeof t, hipMemcpyDeviceToHost) == hipSuccess)
+				std::fprintf(stderr, "cimbar_hip: CIMBAR_HIP_FLOOD_VERIFY (mode %d): %llu certified frames replayed exactly, %llu differed\n", MODE_VAL, t[0], t[1]);
+		}
+	}
 };
 
 namespace {
@@ -311,28 +315,29 @@ int build_tables(cimbar_hip_ctx* ctx)
 		gexp[i] = (uint8_t)element;
 		if (i < 256) glog[element] = (uint8_t)i;
 	}
-	HIPCHK(hipMalloc(&ctx->tb.cell_xy, sizeof(ushort2) * NCELLS));
-	HIPCHK(hipMalloc(&ctx->tb.stream_cell, sizeof(uint16_t) * NCELLS));
+	HIPCHK(ctx->tb_cell_xy.reserve(NCELLS));
+	HIPCHK(ctx->tb_stream_cell.reserve(NCELLS));
 	std::vector<uint16_t> cell_grid(NCELLS);
 	for (int i = 0; i < NCELLS; ++i) cell_grid[i] = (uint16_t)((((int)xy[i].y - OFFSET) / PITCH) * DIM_X + ((int)xy[i].x - OFFSET) / PITCH);
-	HIPCHK(hipMalloc(&ctx->tb.cell_grid, sizeof(uint16_t) * NCELLS));
-	HIPCHK(hipMemcpy(ctx->tb.cell_grid, cell_grid.data(), sizeof(uint16_t) * NCELLS, hipMemcpyHostToDevice));
+	HIPCHK(ctx->tb_cell_grid.reserve(NCELLS));
+	HIPCHK(hipMemcpy(ctx->tb_cell_grid, cell_grid.data(), sizeof(uint16_t) * NCELLS, hipMemcpyHostToDevice));
 	std::vector<int16_t> grid_cell((size_t)DIM_X * DIM_Y, (int16_t)-1);
 	for (int i = 0; i < NCELLS; ++i) grid_cell[cell_grid[i]] = (int16_t)i;
-	HIPCHK(hipMalloc(&ctx->tb.grid_cell, sizeof(int16_t) * grid_cell.size()));
-	HIPCHK(hipMemcpy(ctx->tb.grid_cell, grid_cell.data(), sizeof(int16_t) * grid_cell.size(), hipMemcpyHostToDevice));
+	HIPCHK(ctx->tb_grid_cell.reserve(grid_cell.size()));
+	HIPCHK(hipMemcpy(ctx->tb_grid_cell, grid_cell.data(), sizeof(int16_t) * grid_cell.size(), hipMemcpyHostToDevice));
 	std::vector<uint16_t> ccm_grid(NHDR_CELLS);
 	for (int q = 0; q < NHDR_CELLS; ++q) {
 		// CimbReader.cpp:188-196: header c starts at stream cell c * capacity(6 bits) * 8 / CHUNKS / 2 bits = c * NCELLS * 3 / CHUNKS
 		const int cell = sc[(NCELLS / NHDR) * (q / 24) + q % 24];
 		ccm_grid[q] = (uint16_t)((((int)xy[cell].y - OFFSET) / PITCH) * DIM_X + ((int)xy[cell].x - OFFSET) / PITCH);
 	}
-	HIPCHK(hipMalloc(&ctx->tb.ccm_grid, sizeof(uint16_t) * NHDR_CELLS));
-	HIPCHK(hipMemcpy(ctx->tb.ccm_grid, ccm_grid.data(), sizeof(uint16_t) * NHDR_CELLS, hipMemcpyHostToDevice));
-	HIPCHK(hipMalloc(&ctx->tb.cand, sizeof(int16_t) * NCELLS * 12));
-	HIPCHK(hipMemcpy(ctx->tb.cell_xy, xy.data(), sizeof(ushort2) * NCELLS, hipMemcpyHostToDevice));
-	HIPCHK(hipMemcpy(ctx->tb.stream_cell, sc.data(), sizeof(uint16_t) * NCELLS, hipMemcpyHostToDevice));
-	HIPCHK(hipMemcpy(ctx->tb.cand, cand.data(), sizeof(int16_t) * NCELLS * 12, hipMemcpyHostToDevice));
+	HIPCHK(ctx->tb_ccm_grid.reserve(NHDR_CELLS));
+	HIPCHK(hipMemcpy(ctx->tb_ccm_grid, ccm_grid.data(), sizeof(uint16_t) * NHDR_CELLS, hipMemcpyHostToDevice));
+	HIPCHK(ctx->tb_cand.reserve((size_t)NCELLS * 12));
+	HIPCHK(hipMemcpy(ctx->tb_cell_xy, xy.data(), sizeof(ushort2) * NCELLS, hipMemcpyHostToDevice));
+	HIPCHK(hipMemcpy(ctx->tb_stream_cell, sc.data(), sizeof(uint16_t) * NCELLS, hipMemcpyHostToDevice));
+	HIPCHK(hipMemcpy(ctx->tb_cand, cand.data(), sizeof(int16_t) * NCELLS * 12, hipMemcpyHostToDevice));
+	ctx->tb = Tables{ctx->tb_cell_xy, ctx->tb_stream_cell, ctx->tb_cell_grid, ctx->tb_grid_cell, ctx->tb_ccm_grid, ctx->tb_cand};
 	HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(c_gf_exp), gexp, 512));
 	HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(c_gf_log), glog, 256));
 	// generator polynomial prod_{i=1..ecc_bytes} (x + alpha^i), low -> high (libcorrect reed-solomon.c:5-12, polynomial.c:205-240)
@@ -345,118 +350,81 @@ int build_tables(cimbar_hip_ctx* ctx)
 	}
 	uint8_t gen_log[RS_PARITY];
 	for (int j = 0; j < RS_PARITY; ++j) gen_log[j] = glog[gen[j]];
-	HIPCHK(hipMalloc(&ctx->d_gen_log, RS_PARITY));
+	HIPCHK(ctx->d_gen_log.reserve(RS_PARITY));
 	HIPCHK(hipMemcpy(ctx->d_gen_log, gen_log, RS_PARITY, hipMemcpyHostToDevice));
 	return 0;
 }
 
-template <typename T>
-hipError_t regrow(T*& p, size_t count)
+// the colour retry's margin buffer follows its scratch set: as many frames as the set holds, grown where the setting is on
+int ensure_margin_capacity(cimbar_hip_ctx* ctx, cimbar_hip_ctx::ScratchSet& cur)
 {
-	if (p) { hipError_t e = hipFree(p); p = nullptr; if (e != hipSuccess) return e; }
-	return hipMalloc(&p, sizeof(T) * count);
-}
-
-// the colour retry's margin buffer follows the scratch set in use: as many frames as the set holds, grown where the setting is on
-int ensure_margin_capacity(cimbar_hip_ctx* ctx)
-{
-	if (ctx->ec_margin <= 0 || ctx->cm_cap >= ctx->cap) return 0;
-	ctx->cm_cap = 0;
-	HIPCHK(regrow(ctx->d_cmargin, (size_t)ctx->cap * (NCELLS + 1)));
-	ctx->cm_cap = ctx->cap;
+	if (ctx->ec_margin <= 0 || cur.cm_cap >= cur.cap) return 0;
+	cur.cm_cap = 0;
+	HIPCHK(cur.d_cmargin.reserve((size_t)cur.cap * (NCELLS + 1)));
+	cur.cm_cap = cur.cap;
 	return 0;
 }
 
+// room for a batch of n frames in the scratch set in use and in what every set shares
 int ensure_capacity(cimbar_hip_ctx* ctx, int n)
 {
+	cimbar_hip_ctx::ScratchSet& cur = ctx->cur();
 	size_t N = (size_t)n;
-	if (n > ctx->out_cap) {
-		// not part of the rotating scratch sets: every set's batches stage their host-bound results here
-		ctx->out_cap = 0;
-		HIPCHK(regrow(ctx->d_chunks, N * FRAME_BYTES));
-		HIPCHK(regrow(ctx->d_masks, N));
-		ctx->out_cap = n;
-	}
-	if (n <= ctx->cap) return ensure_margin_capacity(ctx);
-	ctx->cap = 0;   // a failed regrow below must not leave a stale capacity behind
-	HIPCHK(regrow(ctx->d_plane, N * PLANE_WORDS));
-	HIPCHK(regrow(ctx->d_cellmean, N * GRID_CELLS));
-	HIPCHK(regrow(ctx->d_symbols, N * NCELLS));
-	HIPCHK(regrow(ctx->d_colors, N * NCELLS));
-	HIPCHK(regrow(ctx->d_drift, N * NCELLS * 2));
-	HIPCHK(regrow(ctx->d_flood, 2 * N));   // [N] frame flags, then [N] what k_flood_wave made of the frame (CIMBAR_HIP_TAP_FLOOD_INFO)
-	HIPCHK(hipMemset(ctx->d_flood, 0, sizeof(uint32_t) * 2 * N));
-	HIPCHK(regrow(ctx->d_rs_ok, N * ALL_BLOCKS));
-	HIPCHK(regrow(ctx->d_states, N));
-	HIPCHK(regrow(ctx->d_ccm_frames, N * 10));
-	HIPCHK(regrow(ctx->d_ccm_used, N * 10));
-	if (!ctx->d_fw_queue) HIPCHK(regrow(ctx->d_fw_queue, (size_t)FW_GRID * NCELLS));
-	ctx->cap = n;
-	return ensure_margin_capacity(ctx);
+	// not part of the scratch sets: every set's batches stage their host-bound results here
+	HIPCHK(ctx->d_chunks.reserve(N * FRAME_BYTES));
+	HIPCHK(ctx->d_masks.reserve(N));
+	HIPCHK(ctx->d_fw_queue.ensure((size_t)FW_GRID * NCELLS));
+	if (n <= cur.cap) return ensure_margin_capacity(ctx, cur);
+	cur.cap = 0;   // (what `d_flood + cap` and the taps read: never more than every buffer below holds)
+	HIPCHK(cur.d_plane.reserve(N * PLANE_WORDS));
+	HIPCHK(cur.d_cellmean.reserve(N * GRID_CELLS));
+	HIPCHK(cur.d_symbols.reserve(N * NCELLS));
+	HIPCHK(cur.d_colors.reserve(N * NCELLS));
+	HIPCHK(cur.d_drift.reserve(N * NCELLS * 2));
+	HIPCHK(cur.d_flood.reserve(2 * N));
+	HIPCHK(hipMemset(cur.d_flood, 0, sizeof(uint32_t) * 2 * N));
+	HIPCHK(cur.d_rs_ok.reserve(N * ALL_BLOCKS));
+	HIPCHK(cur.d_states.reserve(N));
+	HIPCHK(cur.d_ccm_frames.reserve(N * 10));
+	HIPCHK(cur.d_ccm_used.reserve(N * 10));
+	cur.cap = n;
+	return ensure_margin_capacity(ctx, cur);
 }
 
 int ensure_verify_capacity(cimbar_hip_ctx* ctx, int n)
 {
 	if (n <= ctx->vcap) return 0;
 	ctx->vcap = 0;
-	HIPCHK(regrow(ctx->d_vsym, (size_t)n * NCELLS));
-	HIPCHK(regrow(ctx->d_vdrift, (size_t)n * NCELLS * 2));
-	HIPCHK(regrow(ctx->d_vflag, (size_t)n * 2));
+	HIPCHK(ctx->d_vsym.reserve((size_t)n * NCELLS));
+	HIPCHK(ctx->d_vdrift.reserve((size_t)n * NCELLS * 2));
+	HIPCHK(ctx->d_vflag.reserve((size_t)n * 2));
 	HIPCHK(hipMemset(ctx->d_vflag, 0xFF, sizeof(uint32_t) * (size_t)n * 2));
-	if (!ctx->d_vtotals) { HIPCHK(regrow(ctx->d_vtotals, (size_t)2)); HIPCHK(hipMemset(ctx->d_vtotals, 0, 2 * sizeof(unsigned long long))); }
+	if (!ctx->d_vtotals) { HIPCHK(ctx->d_vtotals.reserve(2)); HIPCHK(hipMemset(ctx->d_vtotals, 0, 2 * sizeof(unsigned long long))); }
 	ctx->vcap = n;
 	return 0;
 }
 
-void destroy_ctx(cimbar_hip_ctx* ctx)
+// host-resident input of a call goes through a device buffer of the context (grown on demand): *d = where the kernels read it
+int stage_input(cimbar_hip_ctx* ctx, hipStream_t st, DevBuf<uint8_t>& buf, const uint8_t* src, size_t bytes, int mem, const uint8_t** d)
 {
-	if (!ctx) return;
-	(void)hipSetDevice(ctx->device);
-	// frames started with cimbar_hip_decode_frame_async and never waited for still have kernels writing into the context's page-locked buffers
-	(void)hipDeviceSynchronize();
-	if (ctx->flood_verify && ctx->d_vtotals) {
-		unsigned long long t[2] = {0, 0};
-		if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(t, ctx->d_vtotals, sizeof t, hipMemcpyDeviceToHost) == hipSuccess)
-			std::fprintf(stderr, "cimbar_hip: CIMBAR_HIP_FLOOD_VERIFY (mode %d): %llu certified frames replayed exactly, %llu differed\n", MODE_VAL, t[0], t[1]);
+	*d = src;
+	if (mem == CIMBAR_HIP_MEM_HOST) {
+		HIPCHK(buf.reserve(bytes));
+		HIPCHK(hipMemcpyAsync(buf, src, bytes, hipMemcpyHostToDevice, st));
+		*d = buf;
 	}
-	auto fr = [](void* p) { if (p) (void)hipFree(p); };
-	fr(ctx->tb.cell_xy); fr(ctx->tb.stream_cell); fr(ctx->tb.cand); fr(ctx->tb.ccm_grid); fr(ctx->tb.cell_grid); fr(ctx->tb.grid_cell);
-	fr(ctx->d_gsym); fr(ctx->d_gcol); fr(ctx->d_gmargin); fr(ctx->d_grs_ok); fr(ctx->d_gagree); fr(ctx->d_gdisp); fr(ctx->d_groups); fr(ctx->d_gmem); fr(ctx->d_gcount);
-	fr(ctx->d_groups_in); fr(ctx->d_ngroups); fr(ctx->d_gchunks); fr(ctx->d_gmasks);
-	fr(ctx->d_template); fr(ctx->d_gen_log); fr(ctx->d_er_buf); fr(ctx->d_payload); fr(ctx->d_rgb); fr(ctx->d_plane); fr(ctx->d_cellmean); fr(ctx->d_symbols); fr(ctx->d_colors); fr(ctx->d_drift); fr(ctx->d_flood);
-	fr(ctx->d_rs_ok); fr(ctx->d_states); fr(ctx->d_ccm_frames); fr(ctx->d_ccm_used); fr(ctx->d_cmargin); fr(ctx->d_carry); fr(ctx->d_chunks);
-	fr(ctx->d_masks); fr(ctx->flood.heap); fr(ctx->flood.prio); fr(ctx->flood.next); fr(ctx->d_fw_queue); fr(ctx->d_vsym); fr(ctx->d_vdrift); fr(ctx->d_vflag); fr(ctx->d_vtotals);
-	fr(ctx->d_ex_rgb); fr(ctx->d_ex_box); fr(ctx->d_ex_in); fr(ctx->d_ex_out); fr(ctx->d_ex_hist); fr(ctx->d_ex_thr); fr(ctx->d_ex_minv);
-	fr(ctx->d_ex_gray); fr(ctx->d_ex_frames); fr(ctx->d_scan_hits); fr(ctx->d_scan_nhits); fr(ctx->d_scan_res); fr(ctx->d_scan_offs); fr(ctx->d_scan_ovf); fr(ctx->d_scan_serial); fr(ctx->d_scan_conf); fr(ctx->d_scan_stage);
-	deliver::destroy(ctx->delivery);
-	fr(ctx->d_ud_img); fr(ctx->d_ud_ok); fr(ctx->d_ud_k1); fr(ctx->d_ud_status); fr(ctx->d_ud_xt);
-	if (ctx->h_ud_xt) (void)hipHostFree(ctx->h_ud_xt);
-	if (ctx->ev_ud_xt) (void)hipEventDestroy(ctx->ev_ud_xt);
-	if (ctx->h_ex_minv) (void)hipHostFree(ctx->h_ex_minv);
-	if (ctx->h_flagged) (void)hipHostFree(ctx->h_flagged);
-	if (ctx->ev_ex_minv) (void)hipEventDestroy(ctx->ev_ex_minv);
-	for (auto& e : ctx->ev) if (e) (void)hipEventDestroy(e);
-	if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-	if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
-	for (int k = 2; k < cimbar_hip_ctx::MAXP; ++k) if (ctx->pstream[k]) (void)hipStreamDestroy(ctx->pstream[k]);
-	for (hipEvent_t e : {ctx->ev_k1, ctx->ev_join}) if (e) (void)hipEventDestroy(e);
-	for (hipEvent_t e : ctx->ev_mid) if (e) (void)hipEventDestroy(e);
-	for (hipEvent_t e : ctx->ev_pk1) if (e) (void)hipEventDestroy(e);
-	for (hipEvent_t e : ctx->ev_pdone) if (e) (void)hipEventDestroy(e);
-	for (hipEvent_t e : ctx->ev_pgather) if (e) (void)hipEventDestroy(e);
-	if (ctx->fcopy) (void)hipStreamDestroy(ctx->fcopy);
-	for (hipEvent_t e : ctx->ev_fcopy) if (e) (void)hipEventDestroy(e);
-	for (auto& fs : ctx->fslot) {
-		fr(fs.d_rgb); fr(fs.d_out);
-		if (fs.h_out) (void)hipHostFree(fs.h_out);
-		if (fs.h_in) (void)hipHostFree(fs.h_in);
-		if (fs.done) (void)hipEventDestroy(fs.done);
+	return 0;
+}
+
+// ... and host-bound output: *d = where the kernels write it (the caller copies it back)
+int stage_output(cimbar_hip_ctx* ctx, DevBuf<uint8_t>& buf, uint8_t* dst, size_t bytes, int mem, uint8_t** d)
+{
+	*d = dst;
+	if (mem == CIMBAR_HIP_MEM_HOST) {
+		HIPCHK(buf.reserve(bytes));
+		*d = buf;
 	}
-	for (auto& a : ctx->parked) {
-		fr(a.d_plane); fr(a.d_cellmean); fr(a.d_symbols); fr(a.d_colors); fr(a.d_drift); fr(a.d_flood);
-		fr(a.d_rs_ok); fr(a.d_states); fr(a.d_ccm_frames); fr(a.d_ccm_used); fr(a.d_cmargin);
-	}
-	delete ctx;
+	return 0;
 }
 
 // pipelined batches in flight use the scratch sets and the tail stream: anything else that touches them on `st` waits first
@@ -467,21 +435,8 @@ int drain_pipeline_into(cimbar_hip_ctx* ctx, hipStream_t st)
 	return 0;
 }
 
-// park the set in use, take the next one (each set is owned by exactly one of: the members, one parked[] slot)
-void rotate_scratch_sets(cimbar_hip_ctx* ctx)
-{
-	auto exchange = [&](cimbar_hip_ctx::ScratchSet& a) {
-		std::swap(ctx->cap, a.cap);
-		std::swap(ctx->d_plane, a.d_plane); std::swap(ctx->d_cellmean, a.d_cellmean); std::swap(ctx->d_symbols, a.d_symbols);
-		std::swap(ctx->d_colors, a.d_colors); std::swap(ctx->d_drift, a.d_drift); std::swap(ctx->d_flood, a.d_flood);
-		std::swap(ctx->d_rs_ok, a.d_rs_ok); std::swap(ctx->d_states, a.d_states); std::swap(ctx->d_ccm_frames, a.d_ccm_frames);
-		std::swap(ctx->d_ccm_used, a.d_ccm_used);
-		std::swap(ctx->d_cmargin, a.d_cmargin); std::swap(ctx->cm_cap, a.cm_cap);
-	};
-	exchange(ctx->parked[ctx->pipe_set]);                       // members (set pipe_set) -> its slot; members now empty
-	ctx->pipe_set = (ctx->pipe_set + 1) % ctx->pipe_depth;
-	exchange(ctx->parked[ctx->pipe_set]);                       // slot of the next set -> members; that slot now empty
-}
+// the next batch (or frame) takes the next set
+void rotate_scratch_sets(cimbar_hip_ctx* ctx) { ctx->pipe_set = (ctx->pipe_set + 1) % ctx->pipe_depth; }
 
 // enqueue the whole pipeline for n device-resident frames on stream `st`
 // one spill area (HEAP_CAP words) per flood workgroup a launch may start, [0, count): grown on demand -- a context that only ever decodes single
@@ -491,9 +446,10 @@ int ensure_flood_areas(cimbar_hip_ctx* ctx, int count)
 	if (count <= ctx->flood_cap) return 0;
 	HIPCHK(hipDeviceSynchronize());
 	ctx->flood_cap = 0;
-	HIPCHK(regrow(ctx->flood.heap, (size_t)count * HEAP_CAP));
-	HIPCHK(regrow(ctx->flood.prio, (size_t)count * PRIO_STRIDE));
-	if (!ctx->flood.next) { HIPCHK(regrow(ctx->flood.next, (size_t)2 * FLOOD_COUNTERS)); HIPCHK(hipMemset(ctx->flood.next, 0, sizeof(uint32_t) * 2 * FLOOD_COUNTERS)); }
+	HIPCHK(ctx->flood_heap.reserve((size_t)count * HEAP_CAP));
+	HIPCHK(ctx->flood_prio.reserve((size_t)count * PRIO_STRIDE));
+	if (!ctx->flood_next) { HIPCHK(ctx->flood_next.reserve((size_t)2 * FLOOD_COUNTERS)); HIPCHK(hipMemset(ctx->flood_next, 0, sizeof(uint32_t) * 2 * FLOOD_COUNTERS)); }
+	ctx->flood = FloodScratch{ctx->flood_heap, ctx->flood_next, ctx->flood_prio};
 	ctx->flood_cap = count;
 	return 0;
 }
@@ -508,10 +464,11 @@ inline int colour_erasure_max(const cimbar_hip_ctx* ctx) { return ctx->ec_max < 
 int enqueue(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_rgb, int n, int pre, int cc, uint8_t* d_chunks, uint32_t* d_masks, int plain = 0,
             bool pipe = false, const int* d_sel = nullptr, int sel_stride = 0, bool symbols_only = false)
 {
+	cimbar_hip_ctx::ScratchSet& cur = ctx->cur();
 	ctx->grp_valid = false;   // (the group taps describe a combined batch only until the next batch of any kind)
 	// the colour retry (erasure.hip.inc) runs behind every chain that reports chunks; the set in use holds its margins
 	const bool colour_retry = !LEGACY && !plain && !symbols_only && ctx->ec_margin > 0;
-	if (colour_retry) { if (int r = ensure_margin_capacity(ctx)) return r; }
+	if (colour_retry) { if (int r = ensure_margin_capacity(ctx, cur)) return r; }
 	ctx->cm_valid = colour_retry;
 	const bool tm = ctx->timing && !pipe;
 	int evi = 0;
@@ -546,21 +503,21 @@ int enqueue(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_rgb, int n, in
 			// the frame buffer d_rgb is OUTPUT here: K1p cuts the grid's window out of the larger image while it thresholds it
 			uint8_t* frame = const_cast<uint8_t*>(d_rgb);
 			const dim3 gp((IMG_W + 63) / 64, (IMG_H + 3) / 4);
-			if (pre) hipLaunchKernelGGL((k_threshold_padded<3, true>), gp, dim3(256), 0, st, ctx->pad_src, ctx->pad_w, ctx->pad_h, ctx->pad_off, ctx->d_plane, frame, ctx->d_flood);
-			else hipLaunchKernelGGL((k_threshold_padded<2, false>), gp, dim3(256), 0, st, ctx->pad_src, ctx->pad_w, ctx->pad_h, ctx->pad_off, ctx->d_plane, frame, ctx->d_flood);
-			hipLaunchKernelGGL(k_cellmean_padded, dim3((GRID_CELLS + 255) / 256), dim3(256), 0, st, frame, ctx->d_cellmean);
+			if (pre) hipLaunchKernelGGL((k_threshold_padded<3, true>), gp, dim3(256), 0, st, ctx->pad_src, ctx->pad_w, ctx->pad_h, ctx->pad_off, cur.d_plane, frame, cur.d_flood);
+			else hipLaunchKernelGGL((k_threshold_padded<2, false>), gp, dim3(256), 0, st, ctx->pad_src, ctx->pad_w, ctx->pad_h, ctx->pad_off, cur.d_plane, frame, cur.d_flood);
+			hipLaunchKernelGGL(k_cellmean_padded, dim3((GRID_CELLS + 255) / 256), dim3(256), 0, st, frame, cur.d_cellmean);
 		} else if (d_sel) {
 			// pre == -1 ("guess", cimbar.cpp:190): the extractor's verdict decides per frame; each variant returns at once for the other's frames
-			if (pre_tall) hipLaunchKernelGGL((k_threshold<3, true, K1_TALLROWS>), gt, dim3(256), 0, st, d_rgb, ctx->d_plane, ctx->d_cellmean, ctx->d_flood, f0, d_sel, sel_stride);
-			else hipLaunchKernelGGL((k_threshold<3, true>), g, dim3(256), 0, st, d_rgb, ctx->d_plane, ctx->d_cellmean, ctx->d_flood, f0, d_sel, sel_stride);
-			hipLaunchKernelGGL((k_threshold<2, false>), g, dim3(256), 0, st, d_rgb, ctx->d_plane, ctx->d_cellmean, ctx->d_flood, f0, d_sel, sel_stride);
+			if (pre_tall) hipLaunchKernelGGL((k_threshold<3, true, K1_TALLROWS>), gt, dim3(256), 0, st, d_rgb, cur.d_plane, cur.d_cellmean, cur.d_flood, f0, d_sel, sel_stride);
+			else hipLaunchKernelGGL((k_threshold<3, true>), g, dim3(256), 0, st, d_rgb, cur.d_plane, cur.d_cellmean, cur.d_flood, f0, d_sel, sel_stride);
+			hipLaunchKernelGGL((k_threshold<2, false>), g, dim3(256), 0, st, d_rgb, cur.d_plane, cur.d_cellmean, cur.d_flood, f0, d_sel, sel_stride);
 		} else if (pre) {
-			if (pre_tall) hipLaunchKernelGGL((k_threshold<3, true, K1_TALLROWS>), gt, dim3(256), 0, st, d_rgb, ctx->d_plane, ctx->d_cellmean, ctx->d_flood, f0, (const int*)nullptr, 0);
-			else hipLaunchKernelGGL((k_threshold<3, true>), g, dim3(256), 0, st, d_rgb, ctx->d_plane, ctx->d_cellmean, ctx->d_flood, f0, (const int*)nullptr, 0);
+			if (pre_tall) hipLaunchKernelGGL((k_threshold<3, true, K1_TALLROWS>), gt, dim3(256), 0, st, d_rgb, cur.d_plane, cur.d_cellmean, cur.d_flood, f0, (const int*)nullptr, 0);
+			else hipLaunchKernelGGL((k_threshold<3, true>), g, dim3(256), 0, st, d_rgb, cur.d_plane, cur.d_cellmean, cur.d_flood, f0, (const int*)nullptr, 0);
 		} else if (ctx->k1_tall > 0 || (ctx->k1_tall < 0 && pipe && n >= K1_TALL_MIN))
 			// inside the pipelined loop: tall strips (fewer row steps and halo rows per frame; the uneven drain is covered by the other batches in flight)
-			hipLaunchKernelGGL((k_threshold<2, false, K1_TALLROWS>), dim3(K1_TALL_BLOCKS, n), dim3(256), (size_t)ctx->k1_lds_pad, st, d_rgb, ctx->d_plane, ctx->d_cellmean, ctx->d_flood, f0, (const int*)nullptr, 0);
-		else hipLaunchKernelGGL((k_threshold<2, false>), g, dim3(256), (size_t)ctx->k1_lds_pad, st, d_rgb, ctx->d_plane, ctx->d_cellmean, ctx->d_flood, f0, (const int*)nullptr, 0);
+			hipLaunchKernelGGL((k_threshold<2, false, K1_TALLROWS>), dim3(K1_TALL_BLOCKS, n), dim3(256), (size_t)ctx->k1_lds_pad, st, d_rgb, cur.d_plane, cur.d_cellmean, cur.d_flood, f0, (const int*)nullptr, 0);
+		else hipLaunchKernelGGL((k_threshold<2, false>), g, dim3(256), (size_t)ctx->k1_lds_pad, st, d_rgb, cur.d_plane, cur.d_cellmean, cur.d_flood, f0, (const int*)nullptr, 0);
 	}
 	HIPCHK(mark());
 	// Everything after K1 is a chain of small kernels per frame (symbols -> flood -> RS -> header/CCM -> colours -> RS -> masks), some of
@@ -585,7 +542,7 @@ int enqueue(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_rgb, int n, in
 	auto tail = [&](hipStream_t s, int fa, int m, int part) -> hipError_t {
 		// part 0: up to k_frame_mid, part 1: the rest
 		if (part == 0) {
-			if (!(ctx->dbg_skip & 1)) hipLaunchKernelGGL(k_symbols, dim3(K2_BLOCKS, m), dim3(256), 0, s, ctx->d_plane, ctx->tb, ctx->d_symbols, ctx->d_flood, fa);
+			if (!(ctx->dbg_skip & 1)) hipLaunchKernelGGL(k_symbols, dim3(K2_BLOCKS, m), dim3(256), 0, s, cur.d_plane, ctx->tb, cur.d_symbols, cur.d_flood, fa);
 			if (hipError_t e = (s == st ? mark() : hipSuccess)) return e;
 			{
 				// the two halves of a split batch may run their flood kernels at the same time: each gets its own half of the spill areas
@@ -595,11 +552,11 @@ int enqueue(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_rgb, int n, in
 					// first the batch-parallel pass for frames whose flood provably does not depend on the tie order (it clears their flag to 2)
 					const int wareas = pipe ? FW_GRID / ctx->pipe_depth : (split ? FW_GRID / 2 : FW_GRID);
 					const int warea0 = pipe ? ctx->pipe_set * wareas : ((split && s != st) ? FW_GRID / 2 : 0);
-					hipLaunchKernelGGL(k_flood_wave, dim3(m < wareas ? m : wareas), dim3(256), 0, s, ctx->d_plane, ctx->tb, ctx->d_fw_queue, ctx->d_flood,
-					                   ctx->d_symbols, ctx->d_drift, fa, m, warea0, ctx->d_flood + ctx->cap);
+					hipLaunchKernelGGL(k_flood_wave, dim3(m < wareas ? m : wareas), dim3(256), 0, s, cur.d_plane, ctx->tb, ctx->d_fw_queue, cur.d_flood,
+					                   cur.d_symbols, cur.d_drift, fa, m, warea0, cur.d_flood + cur.cap);
 				} else if (ctx->flood_wave && !(ctx->dbg_skip & 2)) {
 					// skipped by the scheduler: CIMBAR_HIP_TAP_FLOOD_INFO must not show what the pass said about some earlier batch
-					if (hipError_t e = hipMemsetAsync(ctx->d_flood + ctx->cap + fa, 0xFF, sizeof(uint32_t) * (size_t)m, s)) return e;
+					if (hipError_t e = hipMemsetAsync(cur.d_flood + cur.cap + fa, 0xFF, sizeof(uint32_t) * (size_t)m, s)) return e;
 				}
 				const int counter = pipe ? ctx->pipe_set : ((split && s != st) ? 1 : 0);          // (launches that may overlap use different frame counters)
 				auto exact_flood = [&](const uint32_t* flags) {
@@ -613,55 +570,55 @@ int enqueue(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_rgb, int n, in
 					// more frames than four per CU hold: eight per CU (per-cell state as bits in LDS + bytes in global memory, a 4 160-slot LDS heap)
 					// (CIMBAR_HIP_FLOOD_DENSE_GRID: fewer workgroups than that, e.g. 1 792 = seven per CU, leave LDS for another stream's kernels while they run)
 					const int areas8 = FLOOD_DENSE_PER * areas * ctx->flood_dense_grid / (FLOOD_DENSE_PER * FLOOD_GRID);
-					hipLaunchKernelGGL((k_flood3<HEAP_LDS8, true>), hand_out(m < areas8 ? m : areas8), dim3(128), 0, s, ctx->d_plane, ctx->tb, ctx->flood, flags, ctx->d_symbols, ctx->d_drift, fa, m,
+					hipLaunchKernelGGL((k_flood3<HEAP_LDS8, true>), hand_out(m < areas8 ? m : areas8), dim3(128), 0, s, cur.d_plane, ctx->tb, ctx->flood, flags, cur.d_symbols, cur.d_drift, fa, m,
 					                   FLOOD_DENSE_PER * area0, counter);
 				} else if (m <= areas3)
-					hipLaunchKernelGGL((k_flood3<HEAP_LDS, false>), dim3(m), dim3(128), 0, s, ctx->d_plane, ctx->tb, ctx->flood, flags, ctx->d_symbols, ctx->d_drift, fa, m, area0, counter);
+					hipLaunchKernelGGL((k_flood3<HEAP_LDS, false>), dim3(m), dim3(128), 0, s, cur.d_plane, ctx->tb, ctx->flood, flags, cur.d_symbols, cur.d_drift, fa, m, area0, counter);
 				else
-					hipLaunchKernelGGL((k_flood3<HEAP_LDS4, false>), hand_out(m < areas ? m : areas), dim3(128), 0, s, ctx->d_plane, ctx->tb, ctx->flood, flags, ctx->d_symbols, ctx->d_drift, fa, m, area0, counter);
+					hipLaunchKernelGGL((k_flood3<HEAP_LDS4, false>), hand_out(m < areas ? m : areas), dim3(128), 0, s, cur.d_plane, ctx->tb, ctx->flood, flags, cur.d_symbols, cur.d_drift, fa, m, area0, counter);
 				};
-				exact_flood(ctx->d_flood);
+				exact_flood(cur.d_flood);
 				if (ctx->flood_verify && ctx->flood_wave && !(ctx->dbg_skip & 2)) {
 					// CIMBAR_HIP_FLOOD_VERIFY: what k_flood_wave certified (flag 2) is set aside, the same frames are replayed exactly, and the two
 					// results are compared cell by cell (symbol and drifted position). The exact result is what stays -- a wrong certificate would be
 					// counted (cimbar_hip_flood_verify_totals, CIMBAR_HIP_TAP_FLOOD_VERIFY) AND repaired.
-					hipLaunchKernelGGL(k_verify_begin, dim3(m), dim3(256), 0, s, ctx->d_flood, ctx->d_symbols, ctx->d_drift, ctx->d_vflag, ctx->d_vsym, ctx->d_vdrift, fa, ctx->vcap);
+					hipLaunchKernelGGL(k_verify_begin, dim3(m), dim3(256), 0, s, cur.d_flood, cur.d_symbols, cur.d_drift, ctx->d_vflag, ctx->d_vsym, ctx->d_vdrift, fa, ctx->vcap);
 					exact_flood(ctx->d_vflag);
-					hipLaunchKernelGGL(k_verify_end, dim3(m), dim3(256), 0, s, ctx->d_symbols, ctx->d_drift, ctx->d_vflag, ctx->d_vsym, ctx->d_vdrift, fa, ctx->vcap, ctx->d_vtotals);
+					hipLaunchKernelGGL(k_verify_end, dim3(m), dim3(256), 0, s, cur.d_symbols, cur.d_drift, ctx->d_vflag, ctx->d_vsym, ctx->d_vdrift, fa, ctx->vcap, ctx->d_vtotals);
 				}
 			}
 			if (hipError_t e = (s == st ? mark() : hipSuccess)) return e;
 			// (legacy modes have ONE stream, decoded after the colour pass; the stage-time slot stays so that the names keep their meaning)
 #ifdef CIMBAR_PROBES
-			if (!LEGACY && (ctx->dbg_skip & 128)) hipLaunchKernelGGL((k_rs<4, true>), dim3((m * SYM_BLOCKS + 3) / 4), dim3(256), 0, s, ctx->d_symbols, ctx->tb, fa, m, 0, d_chunks, ctx->d_rs_ok, 0, (const uint8_t*)nullptr);
+			if (!LEGACY && (ctx->dbg_skip & 128)) hipLaunchKernelGGL((k_rs<4, true>), dim3((m * SYM_BLOCKS + 3) / 4), dim3(256), 0, s, cur.d_symbols, ctx->tb, fa, m, 0, d_chunks, cur.d_rs_ok, 0, (const uint8_t*)nullptr);
 			else
 #endif
-			if (!LEGACY && !(ctx->dbg_skip & 4)) hipLaunchKernelGGL((k_rs<4>), dim3((m * SYM_BLOCKS + 3) / 4), dim3(256), 0, s, ctx->d_symbols, ctx->tb, fa, m, 0, d_chunks, ctx->d_rs_ok, 0);
+			if (!LEGACY && !(ctx->dbg_skip & 4)) hipLaunchKernelGGL((k_rs<4>), dim3((m * SYM_BLOCKS + 3) / 4), dim3(256), 0, s, cur.d_symbols, ctx->tb, fa, m, 0, d_chunks, cur.d_rs_ok, 0);
 			if (hipError_t e = (s == st ? mark() : hipSuccess)) return e;
-			if (!(ctx->dbg_skip & 8)) hipLaunchKernelGGL(k_frame_mid, dim3(m), dim3(64), 0, s, d_rgb, ctx->d_cellmean, ctx->tb, d_chunks, ctx->d_rs_ok, cc, ctx->d_states, ctx->d_ccm_frames, fa, plain);
+			if (!(ctx->dbg_skip & 8)) hipLaunchKernelGGL(k_frame_mid, dim3(m), dim3(64), 0, s, d_rgb, cur.d_cellmean, ctx->tb, d_chunks, cur.d_rs_ok, cc, cur.d_states, cur.d_ccm_frames, fa, plain);
 			return s == st ? mark() : hipSuccess;
 		}
-		if (!(ctx->dbg_skip & 16)) hipLaunchKernelGGL((k_colors<false>), dim3(K5_BLOCKS, m), dim3(256), 0, s, d_rgb, ctx->d_cellmean, ctx->tb, ctx->d_ccm_frames,
-		                   ctx->d_carry, ctx->d_flood, ctx->d_drift, ctx->d_colors, ctx->d_ccm_used, fa);
+		if (!(ctx->dbg_skip & 16)) hipLaunchKernelGGL((k_colors<false>), dim3(K5_BLOCKS, m), dim3(256), 0, s, d_rgb, cur.d_cellmean, ctx->tb, cur.d_ccm_frames,
+		                   ctx->d_carry, cur.d_flood, cur.d_drift, cur.d_colors, cur.d_ccm_used, fa);
 		if (hipError_t e = (s == st ? mark() : hipSuccess)) return e;
-		if (LEGACY) hipLaunchKernelGGL((k_rs<(LEGACY ? CELL_BITS : 6)>), dim3((m * ALL_BLOCKS + 3) / 4), dim3(256), 0, s, ctx->d_symbols, ctx->tb, fa, m, 0, d_chunks, ctx->d_rs_ok, 0, ctx->d_colors);
+		if (LEGACY) hipLaunchKernelGGL((k_rs<(LEGACY ? CELL_BITS : 6)>), dim3((m * ALL_BLOCKS + 3) / 4), dim3(256), 0, s, cur.d_symbols, ctx->tb, fa, m, 0, d_chunks, cur.d_rs_ok, 0, cur.d_colors);
 #ifdef CIMBAR_PROBES
-		else if (ctx->dbg_skip & 128) hipLaunchKernelGGL((k_rs<2, true>), dim3((m * COL_BLOCKS + 3) / 4), dim3(256), 0, s, ctx->d_colors, ctx->tb, fa, m, SYM_CHUNKS, d_chunks, ctx->d_rs_ok, SYM_BLOCKS, (const uint8_t*)nullptr);
+		else if (ctx->dbg_skip & 128) hipLaunchKernelGGL((k_rs<2, true>), dim3((m * COL_BLOCKS + 3) / 4), dim3(256), 0, s, cur.d_colors, ctx->tb, fa, m, SYM_CHUNKS, d_chunks, cur.d_rs_ok, SYM_BLOCKS, (const uint8_t*)nullptr);
 #endif
-		else if (!(ctx->dbg_skip & 32)) hipLaunchKernelGGL((k_rs<2>), dim3((m * COL_BLOCKS + 3) / 4), dim3(256), 0, s, ctx->d_colors, ctx->tb, fa, m, SYM_CHUNKS, d_chunks, ctx->d_rs_ok, SYM_BLOCKS);
+		else if (!(ctx->dbg_skip & 32)) hipLaunchKernelGGL((k_rs<2>), dim3((m * COL_BLOCKS + 3) / 4), dim3(256), 0, s, cur.d_colors, ctx->tb, fa, m, SYM_CHUNKS, d_chunks, cur.d_rs_ok, SYM_BLOCKS);
 		if (hipError_t e = (s == st ? mark() : hipSuccess)) return e;
 		// (split chain: the carry is written by k_carry_out after the join -- an earlier part's colour pass may still be reading the old one)
-		if (!(ctx->dbg_skip & 64)) hipLaunchKernelGGL(k_frame_end, dim3(m), dim3(64), 0, s, ctx->d_rs_ok, ctx->d_states, d_chunks, d_masks, ctx->d_ccm_used, ctx->d_carry, fa,
+		if (!(ctx->dbg_skip & 64)) hipLaunchKernelGGL(k_frame_end, dim3(m), dim3(64), 0, s, cur.d_rs_ok, cur.d_states, d_chunks, d_masks, cur.d_ccm_used, ctx->d_carry, fa,
 		                   (!split && fa + m == n) ? 1 : 0, plain);
 		// opt-in erasure retry of the symbol chunks the mask lacks (erasure.hip.inc); reads the frame's own intermediates only, writes its
 		// chunks and mask: the same stream, after k_frame_end, in every chain shape (split halves, pipelined sets)
 		if (!LEGACY && !plain && ctx->er_sym > 0)
-			hipLaunchKernelGGL(k_erasure_frame, dim3(m), dim3(256), 0, s, ctx->d_plane, ctx->tb, ctx->d_symbols, ctx->d_drift, ctx->d_flood, ctx->d_rs_ok,
+			hipLaunchKernelGGL(k_erasure_frame, dim3(m), dim3(256), 0, s, cur.d_plane, ctx->tb, cur.d_symbols, cur.d_drift, cur.d_flood, cur.d_rs_ok,
 			                   d_chunks, d_masks, fa, ctx->er_sym, erasure_max(ctx));
 		// ... and of the colour chunks it lacks (cimbar_hip_set_colour_erasure_decode), independent of the symbol retry and behind it
 		if (colour_retry)
-			hipLaunchKernelGGL(k_colour_erasure_frame, dim3(m), dim3(256), 0, s, d_rgb, ctx->d_cellmean, ctx->tb, ctx->d_colors, ctx->d_drift, ctx->d_flood,
-			                   ctx->d_ccm_used, ctx->d_rs_ok, d_chunks, d_masks, ctx->d_cmargin, ctx->d_cmargin + (size_t)ctx->cm_cap * NCELLS, fa,
+			hipLaunchKernelGGL(k_colour_erasure_frame, dim3(m), dim3(256), 0, s, d_rgb, cur.d_cellmean, ctx->tb, cur.d_colors, cur.d_drift, cur.d_flood,
+			                   cur.d_ccm_used, cur.d_rs_ok, d_chunks, d_masks, cur.d_cmargin, cur.d_cmargin + (size_t)cur.cm_cap * NCELLS, fa,
 			                   ctx->ec_margin, colour_erasure_max(ctx));
 		return s == st ? mark() : hipSuccess;
 	};
@@ -701,9 +658,9 @@ int enqueue(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_rgb, int n, in
 		}
 		HIPCHK(hipEventRecord(ctx->ev_join, sb));
 		HIPCHK(hipStreamWaitEvent(st, ctx->ev_join, 0));
-		hipLaunchKernelGGL(k_carry_out, dim3(1), dim3(64), 0, st, ctx->d_ccm_used, ctx->d_carry, f0 + n - 1);
+		hipLaunchKernelGGL(k_carry_out, dim3(1), dim3(64), 0, st, cur.d_ccm_used, ctx->d_carry, f0 + n - 1);
 	}
-	if (counted) hipLaunchKernelGGL(k_count_flagged, dim3(1), dim3(256), 0, st, ctx->d_flood, n, ctx->h_flagged);
+	if (counted) hipLaunchKernelGGL(k_count_flagged, dim3(1), dim3(256), 0, st, cur.d_flood, n, ctx->h_flagged);
 	HIPCHK(hipGetLastError());
 	ctx->last_n = n;
 	return 0;
@@ -765,9 +722,8 @@ int cimbar_hip_create(int device, int mode_val, cimbar_hip_ctx** out)
 
 	cimbar_hip_ctx* ctx = new cimbar_hip_ctx();
 	ctx->device = device;
-	auto fail = [&](int code) { destroy_ctx(ctx); return code; };
-	if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) return fail(CIMBAR_HIP_EHIP);
-	if (hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking) != hipSuccess) return fail(CIMBAR_HIP_EHIP);
+	auto fail = [&](int code) { delete ctx; return code; };
+	if (ctx->stream.create() != hipSuccess || ctx->stream2.create() != hipSuccess) return fail(CIMBAR_HIP_EHIP);
 	if (const char* v = std::getenv("CIMBAR_HIP_PIPE_DEPTH")) { int k = std::atoi(v); if (k >= 2 && k <= cimbar_hip_ctx::MAXP) ctx->pipe_depth = k; }
 	// As few streams as possible: the runtime multiplexes streams onto (by default) four hardware queues, and how the pipeline's
 	// streams fall onto them matters (measured, 1024-frame batches: depth 4 over six streams 0.81 ms per batch, slower than depth 2;
@@ -775,14 +731,16 @@ int cimbar_hip_create(int device, int mode_val, cimbar_hip_ctx** out)
 	// streams the context has anyway and adds only what the depth needs beyond them.
 	ctx->pstream[0] = ctx->stream;
 	ctx->pstream[1] = ctx->stream2;
-	for (int k = 2; k < ctx->pipe_depth; ++k)
-		if (hipStreamCreateWithFlags(&ctx->pstream[k], hipStreamNonBlocking) != hipSuccess) return fail(CIMBAR_HIP_EHIP);
-	for (hipEvent_t* e : {&ctx->ev_k1, &ctx->ev_join})
-		if (hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) return fail(CIMBAR_HIP_EHIP);
-	for (hipEvent_t& e : ctx->ev_mid) if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return fail(CIMBAR_HIP_EHIP);
-	for (hipEvent_t& e : ctx->ev_pk1) if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return fail(CIMBAR_HIP_EHIP);
-	for (hipEvent_t& e : ctx->ev_pdone) if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return fail(CIMBAR_HIP_EHIP);
-	for (hipEvent_t& e : ctx->ev_pgather) if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return fail(CIMBAR_HIP_EHIP);
+	for (int k = 2; k < ctx->pipe_depth; ++k) {
+		if (ctx->pstream_own[k].create() != hipSuccess) return fail(CIMBAR_HIP_EHIP);
+		ctx->pstream[k] = ctx->pstream_own[k];
+	}
+	for (Event* e : {&ctx->ev_k1, &ctx->ev_join})
+		if (e->create() != hipSuccess) return fail(CIMBAR_HIP_EHIP);
+	for (Event& e : ctx->ev_mid) if (e.create() != hipSuccess) return fail(CIMBAR_HIP_EHIP);
+	for (Event& e : ctx->ev_pk1) if (e.create() != hipSuccess) return fail(CIMBAR_HIP_EHIP);
+	for (Event& e : ctx->ev_pdone) if (e.create() != hipSuccess) return fail(CIMBAR_HIP_EHIP);
+	for (Event& e : ctx->ev_pgather) if (e.create() != hipSuccess) return fail(CIMBAR_HIP_EHIP);
 	if (const char* v = std::getenv("CIMBAR_HIP_TAIL_SPLIT")) ctx->tail_split = std::atoi(v);
 	if (const char* v = std::getenv("CIMBAR_HIP_FLOOD_WAVE")) ctx->flood_wave = std::atoi(v) != 0;
 	if (const char* v = std::getenv("CIMBAR_HIP_FLOOD_WAVE_ADAPT")) ctx->wave_adapt = std::atoi(v) != 0;
@@ -801,17 +759,17 @@ int cimbar_hip_create(int device, int mode_val, cimbar_hip_ctx** out)
 	if (const char* v = std::getenv("CIMBAR_HIP_FRAME_ZEROCOPY")) ctx->frame_zerocopy = std::atoi(v);
 	if (const char* v = std::getenv("CIMBAR_HIP_FRAME_COPYSTREAM")) ctx->frame_copystream = std::atoi(v);
 	if (const char* v = std::getenv("CIMBAR_HIP_TAIL_PARTS")) { int k = std::atoi(v); if (k >= 2 && k <= 8 && k % 2 == 0) ctx->tail_parts = k; }
-	for (auto& e : ctx->ev) if (hipEventCreate(&e) != hipSuccess) return fail(CIMBAR_HIP_EHIP);
-	if (hipMalloc(&ctx->d_carry, sizeof(float) * 10) != hipSuccess) return fail(CIMBAR_HIP_ENOMEM);
+	for (Event& e : ctx->ev) if (e.create(hipEventDefault) != hipSuccess) return fail(CIMBAR_HIP_EHIP);
+	if (ctx->d_carry.reserve(10) != hipSuccess) return fail(CIMBAR_HIP_ENOMEM);
 	if (hipMemset(ctx->d_carry, 0, sizeof(float) * 10) != hipSuccess) return fail(CIMBAR_HIP_EHIP);
 	if (build_tables(ctx) != 0) return fail(CIMBAR_HIP_EHIP);
-	if (hipHostMalloc((void**)&ctx->h_flagged, 4 * sizeof(uint32_t), hipHostMallocDefault) == hipSuccess) { ctx->h_flagged[0] = ctx->h_flagged[1] = ctx->h_flagged[2] = 0; }
-	else { ctx->h_flagged = nullptr; (void)hipGetLastError(); }        // (only a heuristic's input: do without)
+	if (ctx->h_flagged.reserve(4) == hipSuccess) { ctx->h_flagged[0] = ctx->h_flagged[1] = ctx->h_flagged[2] = 0; }
+	else (void)hipGetLastError();        // (only a heuristic's input: do without)
 	*out = ctx;
 	return CIMBAR_HIP_OK;
 }
 
-void cimbar_hip_destroy(cimbar_hip_ctx* ctx) { destroy_ctx(ctx); }
+void cimbar_hip_destroy(cimbar_hip_ctx* ctx) { delete ctx; }
 
 const char* cimbar_hip_last_error(const cimbar_hip_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 
@@ -883,23 +841,20 @@ int check_combine(cimbar_hip_ctx* ctx, const char* who, int n, CombineArgs& cb)
 
 int ensure_group_capacity(cimbar_hip_ctx* ctx, int n)
 {
-	if (n <= ctx->grp_cap) return 0;
 	const size_t N = (size_t)n;
-	ctx->grp_cap = 0;
-	HIPCHK(regrow(ctx->d_gsym, N * NCELLS));
-	HIPCHK(regrow(ctx->d_gcol, N * NCELLS));
-	HIPCHK(regrow(ctx->d_gmargin, N * NCELLS));
-	HIPCHK(regrow(ctx->d_grs_ok, N * ALL_BLOCKS));
-	HIPCHK(regrow(ctx->d_gagree, N));
-	HIPCHK(regrow(ctx->d_gdisp, N));
-	HIPCHK(regrow(ctx->d_groups, N));
-	HIPCHK(regrow(ctx->d_gmem, N * GMAX));
-	HIPCHK(regrow(ctx->d_gcount, N));
-	HIPCHK(regrow(ctx->d_groups_in, N));
-	if (!ctx->d_ngroups) HIPCHK(regrow(ctx->d_ngroups, (size_t)1));
-	HIPCHK(regrow(ctx->d_gchunks, N * FRAME_BYTES));
-	HIPCHK(regrow(ctx->d_gmasks, N));
-	ctx->grp_cap = n;
+	HIPCHK(ctx->d_gsym.reserve(N * NCELLS));
+	HIPCHK(ctx->d_gcol.reserve(N * NCELLS));
+	HIPCHK(ctx->d_gmargin.reserve(N * NCELLS));
+	HIPCHK(ctx->d_grs_ok.reserve(N * ALL_BLOCKS));
+	HIPCHK(ctx->d_gagree.reserve(N));
+	HIPCHK(ctx->d_gdisp.reserve(N));
+	HIPCHK(ctx->d_groups.reserve(N));
+	HIPCHK(ctx->d_gmem.reserve(N * GMAX));
+	HIPCHK(ctx->d_gcount.reserve(N));
+	HIPCHK(ctx->d_groups_in.reserve(N));
+	HIPCHK(ctx->d_ngroups.ensure(1));
+	HIPCHK(ctx->d_gchunks.reserve(N * FRAME_BYTES));
+	HIPCHK(ctx->d_gmasks.reserve(N));
 	return 0;
 }
 
@@ -910,6 +865,7 @@ int enqueue_combine(cimbar_hip_ctx* ctx, hipStream_t st, int n, const uint8_t* d
                     const CombineArgs& cb, int out_mem)
 {
 	if (int r = ensure_group_capacity(ctx, n)) return r;
+	cimbar_hip_ctx::ScratchSet& cur = ctx->cur();
 	// (device outputs: the caller's buffers; host outputs: the context's staging, which exists from here on)
 	uint8_t* d_gchunks = out_mem == CIMBAR_HIP_MEM_DEVICE ? cb.gchunks : ctx->d_gchunks;
 	uint32_t* d_gmasks = out_mem == CIMBAR_HIP_MEM_DEVICE ? cb.gmasks : ctx->d_gmasks;
@@ -917,10 +873,10 @@ int enqueue_combine(cimbar_hip_ctx* ctx, hipStream_t st, int n, const uint8_t* d
 	HIPCHK(hipMemsetAsync(ctx->d_gcount, 0, sizeof(int) * (size_t)n, st));
 	HIPCHK(hipMemsetAsync(ctx->d_gdisp, 0, sizeof(uint32_t) * (size_t)n, st));
 	if (!cb.groups_in && n > 1)
-		hipLaunchKernelGGL(k_group_agree, dim3(n - 1), dim3(256), 0, st, ctx->d_symbols, ctx->d_colors, n, ctx->d_gagree);
+		hipLaunchKernelGGL(k_group_agree, dim3(n - 1), dim3(256), 0, st, cur.d_symbols, cur.d_colors, n, ctx->d_gagree);
 	hipLaunchKernelGGL(k_group_walk, dim3(1), dim3(64), 0, st, ctx->d_gagree, n, d_status, stride, cb.groups_in ? ctx->d_groups_in : (const int*)nullptr,
 	                   cb.min_agree, cb.max_group, ctx->d_groups, ctx->d_gmem, ctx->d_gcount, ctx->d_ngroups);
-	hipLaunchKernelGGL(k_group_cells, dim3(GC_BLOCKS, n), dim3(256), 0, st, ctx->d_plane, ctx->tb, ctx->d_symbols, ctx->d_colors, ctx->d_drift, ctx->d_flood,
+	hipLaunchKernelGGL(k_group_cells, dim3(GC_BLOCKS, n), dim3(256), 0, st, cur.d_plane, ctx->tb, cur.d_symbols, cur.d_colors, cur.d_drift, cur.d_flood,
 	                   ctx->d_gmem, ctx->d_gcount, ctx->d_ngroups, ctx->d_gsym, ctx->d_gcol, ctx->d_gmargin, ctx->d_gdisp);
 	if constexpr (LEGACY) {
 		hipLaunchKernelGGL((k_rs<CELL_BITS, false, true>), dim3((n * ALL_BLOCKS + 3) / 4), dim3(256), 0, st, ctx->d_gsym, ctx->tb, 0, n, 0, d_gchunks, ctx->d_grs_ok, 0,
@@ -989,13 +945,8 @@ int64_t decode_batch_impl(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rg
 	if (int r = drain_pipeline_into(ctx, st)) return r;
 	if (int r = ensure_capacity(ctx, n)) return r;
 
-	const uint8_t* d_rgb = rgb;
-	if (rgb_mem == CIMBAR_HIP_MEM_HOST) {
-		size_t need = (size_t)n * FRAME_RGB;
-		if (need > ctx->d_rgb_cap) { HIPCHK(regrow(ctx->d_rgb, need)); ctx->d_rgb_cap = need; }
-		HIPCHK(hipMemcpyAsync(ctx->d_rgb, rgb, need, hipMemcpyHostToDevice, st));
-		d_rgb = ctx->d_rgb;
-	}
+	const uint8_t* d_rgb = nullptr;
+	if (int r = stage_input(ctx, st, ctx->d_rgb, rgb, (size_t)n * FRAME_RGB, rgb_mem, &d_rgb)) return r;
 	uint8_t* d_chunks = out_mem == CIMBAR_HIP_MEM_DEVICE ? chunks : ctx->d_chunks;
 	uint32_t* d_masks = out_mem == CIMBAR_HIP_MEM_DEVICE ? masks : ctx->d_masks;
 
@@ -1078,17 +1029,12 @@ int64_t cimbar_hip_decode_plain_batch(cimbar_hip_ctx* ctx, const uint8_t* rgb, i
 	hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (any_device ? (hipStream_t)nullptr : ctx->stream);
 	if (int r = drain_pipeline_into(ctx, st)) return r;
 	if (int r = ensure_capacity(ctx, n)) return r;
-	const uint8_t* d_rgb = rgb;
-	if (rgb_mem == CIMBAR_HIP_MEM_HOST) {
-		size_t need = (size_t)n * FRAME_RGB;
-		if (need > ctx->d_rgb_cap) { HIPCHK(regrow(ctx->d_rgb, need)); ctx->d_rgb_cap = need; }
-		HIPCHK(hipMemcpyAsync(ctx->d_rgb, rgb, need, hipMemcpyHostToDevice, st));
-		d_rgb = ctx->d_rgb;
-	}
+	const uint8_t* d_rgb = nullptr;
+	if (int r = stage_input(ctx, st, ctx->d_rgb, rgb, (size_t)n * FRAME_RGB, rgb_mem, &d_rgb)) return r;
 	uint8_t* d_bytes = out_mem == CIMBAR_HIP_MEM_DEVICE ? bytes : ctx->d_chunks;
 	if (int r = enqueue(ctx, st, d_rgb, n, should_preprocess, color_correction, d_bytes, ctx->d_masks, 1)) return r;
 	if (block_ok)
-		HIPCHK(hipMemcpyAsync(block_ok, ctx->d_rs_ok, (size_t)n * ALL_BLOCKS, out_mem == CIMBAR_HIP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+		HIPCHK(hipMemcpyAsync(block_ok, ctx->cur().d_rs_ok, (size_t)n * ALL_BLOCKS, out_mem == CIMBAR_HIP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
 	if (out_mem == CIMBAR_HIP_MEM_DEVICE) return 0;
 	HIPCHK(hipMemcpyAsync(bytes, d_bytes, (size_t)n * FRAME_BYTES, hipMemcpyDeviceToHost, st));
 	HIPCHK(hipStreamSynchronize(st));
@@ -1115,8 +1061,8 @@ int cimbar_hip_decode_frame_sync(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsign
 		if ((uint64_t)width * height * 3 >= (1ull << 31)) { ctx->err = "decode_frame: image of 2 GiB or more"; return CIMBAR_HIP_EDIM; }
 		HIPCHK(hipSetDevice(ctx->device));
 		const size_t row = (size_t)width * 3, bytes = row * height;
-		if (bytes > ctx->d_ex_in_cap) { HIPCHK(regrow(ctx->d_ex_in, bytes)); ctx->d_ex_in_cap = bytes; }
-		if ((size_t)FRAME_RGB > ctx->d_rgb_cap) { HIPCHK(regrow(ctx->d_rgb, (size_t)FRAME_RGB)); ctx->d_rgb_cap = FRAME_RGB; }
+		HIPCHK(ctx->d_ex_in.reserve(bytes));
+		HIPCHK(ctx->d_rgb.reserve((size_t)FRAME_RGB));
 		HIPCHK(hipDeviceSynchronize());   // (single-image edge path: nothing of an earlier call may still be reading the scratch)
 		HIPCHK(hipMemcpy2D(ctx->d_ex_in, row, rgb, stride ? stride : row, row, height, hipMemcpyHostToDevice));
 		const unsigned ex = width - (unsigned)IMG_W, ey = height - (unsigned)IMG_H;
@@ -1186,12 +1132,10 @@ long long cimbar_hip_decode_frame_async(cimbar_hip_ctx* ctx, const uint8_t* rgb,
 	cimbar_hip_ctx::FrameSlot& fs = ctx->fslot[set];
 	hipStream_t own = ctx->pstream[set];
 	(void)frame_slot_finish(ctx, fs);          // at most pipe_depth frames in flight: the one that used this slot is delivered now
-	if (!fs.d_rgb) {
-		HIPCHK(hipMalloc((void**)&fs.d_rgb, (size_t)FRAME_RGB));
-		HIPCHK(hipMalloc((void**)&fs.d_out, FRAME_OUT_STRIDE + 16));
-		HIPCHK(hipHostMalloc((void**)&fs.h_out, FRAME_OUT_STRIDE + 16, hipHostMallocDefault));
-		HIPCHK(hipEventCreateWithFlags(&fs.done, hipEventDisableTiming));
-	}
+	HIPCHK(fs.d_rgb.ensure((size_t)FRAME_RGB));
+	HIPCHK(fs.d_out.ensure(FRAME_OUT_STRIDE + 16));
+	HIPCHK(fs.h_out.ensure(FRAME_OUT_STRIDE + 16));
+	HIPCHK(fs.done.create());
 	if (int r = ensure_capacity(ctx, 1)) return r;
 	const size_t row = (size_t)IMG_W * 3;
 	const uint8_t* src = rgb;
@@ -1203,7 +1147,7 @@ long long cimbar_hip_decode_frame_async(cimbar_hip_ctx* ctx, const uint8_t* rgb,
 		// hipMemcpy2DAsync, which may pin the user's pages and return with the DMA still pending: such an image is always copied to the context's
 		// page-locked staging here (141 us per frame on one host thread), as every pageable image is with CIMBAR_HIP_FRAME_STAGE=1. Either way host
 		// work that overlaps the previous frames' kernels. (tests/test_gpu_frame_async.py scribbles over such a buffer right after the call.)
-		if (!fs.h_in) HIPCHK(hipHostMalloc((void**)&fs.h_in, (size_t)FRAME_RGB, hipHostMallocDefault));
+		HIPCHK(fs.h_in.ensure((size_t)FRAME_RGB));
 		if (src_stride == row) std::memcpy(fs.h_in, rgb, (size_t)FRAME_RGB);
 		else for (int y = 0; y < IMG_H; ++y) std::memcpy(fs.h_in + (size_t)y * row, rgb + (size_t)y * src_stride, row);
 		src = fs.h_in;
@@ -1211,10 +1155,8 @@ long long cimbar_hip_decode_frame_async(cimbar_hip_ctx* ctx, const uint8_t* rgb,
 	}
 	hipStream_t cs = own;
 	if (ctx->frame_copystream) {
-		if (!ctx->fcopy) {
-			HIPCHK(hipStreamCreateWithFlags(&ctx->fcopy, hipStreamNonBlocking));
-			for (hipEvent_t& e : ctx->ev_fcopy) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-		}
+		HIPCHK(ctx->fcopy.create());
+		for (Event& e : ctx->ev_fcopy) HIPCHK(e.create());
 		cs = ctx->fcopy;
 	}
 	if (src_stride == row) HIPCHK(hipMemcpyAsync(fs.d_rgb, src, (size_t)FRAME_RGB, hipMemcpyHostToDevice, cs));
@@ -1222,7 +1164,7 @@ long long cimbar_hip_decode_frame_async(cimbar_hip_ctx* ctx, const uint8_t* rgb,
 	if (cs != own) { HIPCHK(hipEventRecord(ctx->ev_fcopy[set], cs)); HIPCHK(hipStreamWaitEvent(own, ctx->ev_fcopy[set], 0)); }
 	// the chunks and the mask are written where the host reads them: page-locked host memory is device-visible, the Reed-Solomon kernels store 7.5 KB
 	// into it over the link and no copy back (one more DMA packet with its latency) is queued behind the frame
-	uint8_t* const out = ctx->frame_zerocopy ? fs.h_out : fs.d_out;
+	uint8_t* const out = ctx->frame_zerocopy ? fs.h_out.get() : fs.d_out.get();
 	if (int r = enqueue(ctx, own, fs.d_rgb, 1, should_preprocess, color_correction, out, reinterpret_cast<uint32_t*>(out + FRAME_OUT_STRIDE), 0, true)) return r;
 	if (!ctx->frame_zerocopy) HIPCHK(hipMemcpyAsync(fs.h_out, fs.d_out, FRAME_OUT_STRIDE + sizeof(uint32_t), hipMemcpyDeviceToHost, own));
 	HIPCHK(hipEventRecord(fs.done, own));
@@ -1311,18 +1253,9 @@ int launch_warp_ctx(cimbar_hip_ctx* ctx, hipStream_t st, int fmt, const uint8_t*
 	const size_t fit = ctx->warp_scratch / per;
 	const int chunk = (int)(fit < 1 ? 1 : (fit < (size_t)WARP_CHUNK ? fit : (size_t)WARP_CHUNK));
 	const size_t need = per * (size_t)(n < chunk ? n : chunk);
-	if (need > ctx->d_ex_rgb_cap) {
-		HIPCHK(hipStreamSynchronize(st));          // (the scratch a warp still in flight reads is about to be replaced)
-		ctx->d_ex_rgb_cap = 0;
-		HIPCHK(regrow(ctx->d_ex_rgb, need));
-		ctx->d_ex_rgb_cap = need;
-	}
-	if (n > ctx->d_ex_box_cap) {
-		HIPCHK(hipStreamSynchronize(st));
-		ctx->d_ex_box_cap = 0;
-		HIPCHK(regrow(ctx->d_ex_box, (size_t)n));
-		ctx->d_ex_box_cap = n;
-	}
+	if (need > ctx->d_ex_rgb.capacity() || (size_t)n > ctx->d_ex_box.capacity()) HIPCHK(hipStreamSynchronize(st));   // (the scratch a warp still in flight reads is about to be replaced)
+	HIPCHK(ctx->d_ex_rgb.reserve(need));
+	HIPCHK(ctx->d_ex_box.reserve((size_t)n));
 	hipLaunchKernelGGL(k_roi_boxes, dim3((n + 63) / 64), dim3(64), 0, st, d_minv, n, (int)width, (int)height, IMG_W, IMG_H, ctx->d_ex_box);
 	for (int lo = 0; lo < n; lo += chunk) {
 		const int m = n - lo < chunk ? n - lo : chunk;
@@ -1347,22 +1280,19 @@ int check_capture(cimbar_hip_ctx* ctx, const char* who, unsigned width, unsigned
 
 int extract_state(cimbar_hip_ctx* ctx, int n)
 {
-	if (n <= ctx->d_ex_n) return 0;
-	HIPCHK(regrow(ctx->d_ex_hist, (size_t)n * 256));
-	HIPCHK(regrow(ctx->d_ex_thr, (size_t)n));
-	HIPCHK(regrow(ctx->d_ex_minv, (size_t)n * 9));
-	HIPCHK(regrow(ctx->d_scan_hits, (size_t)n * SCAN_MAX_ROWS * SCAN_ROW_PTS));
-	HIPCHK(regrow(ctx->d_scan_nhits, (size_t)n * SCAN_MAX_ROWS));
-	HIPCHK(regrow(ctx->d_scan_res, (size_t)n));
-	HIPCHK(regrow(ctx->d_scan_offs, (size_t)n * (SCAN_MAX_ROWS + 1)));
-	HIPCHK(regrow(ctx->d_scan_ovf, (size_t)n + 1));           // + the slow path's slot counter
-	if (!ctx->d_scan_serial) HIPCHK(regrow(ctx->d_scan_serial, (size_t)SCAN_SERIAL_SLOTS * 6 * SCAN_SERIAL_CAP));
-	HIPCHK(regrow(ctx->d_scan_conf, (size_t)n * SCAN_HMAX));
-	HIPCHK(regrow(ctx->d_scan_stage, (size_t)n * 2));
-	if (ctx->h_ex_minv) { HIPCHK(hipHostFree(ctx->h_ex_minv)); ctx->h_ex_minv = nullptr; }
-	HIPCHK(hipHostMalloc(&ctx->h_ex_minv, sizeof(double) * 9 * (size_t)n, hipHostMallocDefault));
-	if (!ctx->ev_ex_minv) HIPCHK(hipEventCreateWithFlags(&ctx->ev_ex_minv, hipEventDisableTiming));
-	ctx->d_ex_n = n;
+	HIPCHK(ctx->d_ex_hist.reserve((size_t)n * 256));
+	HIPCHK(ctx->d_ex_thr.reserve((size_t)n));
+	HIPCHK(ctx->d_ex_minv.reserve((size_t)n * 9));
+	HIPCHK(ctx->d_scan_hits.reserve((size_t)n * SCAN_MAX_ROWS * SCAN_ROW_PTS));
+	HIPCHK(ctx->d_scan_nhits.reserve((size_t)n * SCAN_MAX_ROWS));
+	HIPCHK(ctx->d_scan_res.reserve((size_t)n));
+	HIPCHK(ctx->d_scan_offs.reserve((size_t)n * (SCAN_MAX_ROWS + 1)));
+	HIPCHK(ctx->d_scan_ovf.reserve((size_t)n + 1));           // + the slow path's slot counter
+	HIPCHK(ctx->d_scan_serial.ensure((size_t)SCAN_SERIAL_SLOTS * 6 * SCAN_SERIAL_CAP));
+	HIPCHK(ctx->d_scan_conf.reserve((size_t)n * SCAN_HMAX));
+	HIPCHK(ctx->d_scan_stage.reserve((size_t)n * 2));
+	HIPCHK(ctx->h_ex_minv.reserve((size_t)n * 9));
+	HIPCHK(ctx->ev_ex_minv.create());
 	return 0;
 }
 
@@ -1390,17 +1320,10 @@ int cimbar_hip_scan_preprocess_fmt(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsi
 	if (int r = drain_pipeline_into(ctx, st)) return r;
 	if (int r = extract_state(ctx, n)) return r;
 	const size_t px = (size_t)width * height;
-	const uint8_t* d_in = rgb;
-	if (rgb_mem == CIMBAR_HIP_MEM_HOST) {
-		if (cbytes * n > ctx->d_ex_in_cap) { HIPCHK(regrow(ctx->d_ex_in, cbytes * n)); ctx->d_ex_in_cap = cbytes * n; }
-		HIPCHK(hipMemcpyAsync(ctx->d_ex_in, rgb, cbytes * n, hipMemcpyHostToDevice, st));
-		d_in = ctx->d_ex_in;
-	}
-	uint8_t* d_out = binary;
-	if (out_mem == CIMBAR_HIP_MEM_HOST) {
-		if (px * n > ctx->d_ex_out_cap) { HIPCHK(regrow(ctx->d_ex_out, px * n)); ctx->d_ex_out_cap = px * n; }
-		d_out = ctx->d_ex_out;
-	}
+	const uint8_t* d_in = nullptr;
+	if (int r = stage_input(ctx, st, ctx->d_ex_in, rgb, cbytes * n, rgb_mem, &d_in)) return r;
+	uint8_t* d_out = nullptr;
+	if (int r = stage_output(ctx, ctx->d_ex_out, binary, px * n, out_mem, &d_out)) return r;
 	HIPCHK(hipMemsetAsync(ctx->d_ex_hist, 0, sizeof(uint32_t) * 256 * (size_t)n, st));
 	launch_gray_blur(st, unit, fmt, d_in, width, height, n, d_out, ctx->d_ex_hist);
 	hipLaunchKernelGGL(k_scan_otsu, dim3((n + 63) / 64), dim3(64), 0, st, ctx->d_ex_hist, (int)width, (int)height, n, ctx->d_ex_thr);
@@ -1440,17 +1363,10 @@ int cimbar_hip_deskew_batch_fmt(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsigne
 	for (int f = 0; f < n; ++f) deskew_inverse_matrix(corners + (size_t)f * 8, ctx->h_ex_minv + (size_t)f * 9);
 	HIPCHK(hipMemcpyAsync(ctx->d_ex_minv, ctx->h_ex_minv, sizeof(double) * 9 * (size_t)n, hipMemcpyHostToDevice, st));
 	HIPCHK(hipEventRecord(ctx->ev_ex_minv, st));
-	const uint8_t* d_in = rgb;
-	if (rgb_mem == CIMBAR_HIP_MEM_HOST) {
-		if (cbytes * n > ctx->d_ex_in_cap) { HIPCHK(regrow(ctx->d_ex_in, cbytes * n)); ctx->d_ex_in_cap = cbytes * n; }
-		HIPCHK(hipMemcpyAsync(ctx->d_ex_in, rgb, cbytes * n, hipMemcpyHostToDevice, st));
-		d_in = ctx->d_ex_in;
-	}
-	uint8_t* d_out = frames;
-	if (out_mem == CIMBAR_HIP_MEM_HOST) {
-		if ((size_t)n * FRAME_RGB > ctx->d_ex_out_cap) { HIPCHK(regrow(ctx->d_ex_out, (size_t)n * FRAME_RGB)); ctx->d_ex_out_cap = (size_t)n * FRAME_RGB; }
-		d_out = ctx->d_ex_out;
-	}
+	const uint8_t* d_in = nullptr;
+	if (int r = stage_input(ctx, st, ctx->d_ex_in, rgb, cbytes * n, rgb_mem, &d_in)) return r;
+	uint8_t* d_out = nullptr;
+	if (int r = stage_output(ctx, ctx->d_ex_out, frames, (size_t)n * FRAME_RGB, out_mem, &d_out)) return r;
 	if (int r = launch_warp_ctx(ctx, st, fmt, d_in, width, height, n, ctx->d_ex_minv, d_out)) return r;
 	HIPCHK(hipGetLastError());
 	if (out_mem == CIMBAR_HIP_MEM_DEVICE) return 0;
@@ -1483,7 +1399,7 @@ int enqueue_scan(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_in, unsig
 	if (unit != 3 && unit != 5 && unit != 9 && unit != 17) { ctx->err = "extract: captures of 8500 px or more on the short side need a 33x33 blur, not implemented"; return CIMBAR_HIP_EDIM; }
 	if (width > 65535u || height > 65535u) { ctx->err = "extract: capture larger than 65535 px on a side"; return CIMBAR_HIP_EDIM; }
 	const size_t px = (size_t)width * height;
-	if (px * n > ctx->d_ex_gray_cap) { HIPCHK(regrow(ctx->d_ex_gray, px * n)); ctx->d_ex_gray_cap = px * n; }
+	HIPCHK(ctx->d_ex_gray.reserve(px * n));
 	HIPCHK(hipMemsetAsync(ctx->d_ex_hist, 0, sizeof(uint32_t) * 256 * (size_t)n, st));
 	launch_gray_blur(st, unit, fmt, d_in, width, height, n, ctx->d_ex_gray, ctx->d_ex_hist);
 	hipLaunchKernelGGL(k_scan_otsu, dim3((n + 63) / 64), dim3(64), 0, st, ctx->d_ex_hist, (int)width, (int)height, n, ctx->d_ex_thr);
@@ -1514,17 +1430,6 @@ int enqueue_scan(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_in, unsig
 	return 0;
 }
 
-int stage_captures(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* rgb, size_t bytes, int rgb_mem, const uint8_t** d_in)
-{
-	*d_in = rgb;
-	if (rgb_mem == CIMBAR_HIP_MEM_HOST) {
-		if (bytes > ctx->d_ex_in_cap) { HIPCHK(regrow(ctx->d_ex_in, bytes)); ctx->d_ex_in_cap = bytes; }
-		HIPCHK(hipMemcpyAsync(ctx->d_ex_in, rgb, bytes, hipMemcpyHostToDevice, st));
-		*d_in = ctx->d_ex_in;
-	}
-	return 0;
-}
-
 }  // namespace
 
 int cimbar_hip_extract_batch_fmt(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsigned width, unsigned height, int format, int n, int rgb_mem, uint8_t* frames,
@@ -1544,12 +1449,9 @@ int cimbar_hip_extract_batch_fmt(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsign
 	if (int r = drain_pipeline_into(ctx, st)) return r;
 	if (int r = extract_state(ctx, n)) return r;
 	const uint8_t* d_in = nullptr;
-	if (int r = stage_captures(ctx, st, rgb, cbytes * n, rgb_mem, &d_in)) return r;
-	uint8_t* d_out = frames;
-	if (out_mem == CIMBAR_HIP_MEM_HOST) {
-		if ((size_t)n * FRAME_RGB > ctx->d_ex_out_cap) { HIPCHK(regrow(ctx->d_ex_out, (size_t)n * FRAME_RGB)); ctx->d_ex_out_cap = (size_t)n * FRAME_RGB; }
-		d_out = ctx->d_ex_out;
-	}
+	if (int r = stage_input(ctx, st, ctx->d_ex_in, rgb, cbytes * n, rgb_mem, &d_in)) return r;
+	uint8_t* d_out = nullptr;
+	if (int r = stage_output(ctx, ctx->d_ex_out, frames, (size_t)n * FRAME_RGB, out_mem, &d_out)) return r;
 	if (int r = enqueue_scan(ctx, st, d_in, width, height, fmt, n)) return r;
 	if (int r = launch_warp_ctx(ctx, st, fmt, d_in, width, height, n, ctx->d_ex_minv, d_out)) return r;
 	HIPCHK(hipGetLastError());
@@ -1590,8 +1492,8 @@ int64_t scan_extract_decode_impl(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsign
 	if (int r = extract_state(ctx, n)) return r;
 	if (int r = ensure_capacity(ctx, n)) return r;
 	const uint8_t* d_in = nullptr;
-	if (int r = stage_captures(ctx, st, rgb, cbytes * n, rgb_mem, &d_in)) return r;
-	if ((size_t)n * FRAME_RGB > ctx->d_ex_frames_cap) { HIPCHK(regrow(ctx->d_ex_frames, (size_t)n * FRAME_RGB)); ctx->d_ex_frames_cap = (size_t)n * FRAME_RGB; }
+	if (int r = stage_input(ctx, st, ctx->d_ex_in, rgb, cbytes * n, rgb_mem, &d_in)) return r;
+	HIPCHK(ctx->d_ex_frames.reserve((size_t)n * FRAME_RGB));
 	if (int r = enqueue_scan(ctx, st, d_in, width, height, fmt, n)) return r;
 	if (int r = launch_warp_ctx(ctx, st, fmt, d_in, width, height, n, ctx->d_ex_minv, ctx->d_ex_frames)) return r;
 	uint8_t* d_chunks = out_mem == CIMBAR_HIP_MEM_DEVICE ? chunks : ctx->d_chunks;
@@ -1646,7 +1548,7 @@ int cimbar_hip_set_template(cimbar_hip_ctx* ctx, const uint8_t* rgb_template, in
 {
 	if (!ctx || !rgb_template) return CIMBAR_HIP_EINVAL;
 	HIPCHK(hipSetDevice(ctx->device));
-	if (!ctx->d_template) HIPCHK(hipMalloc(&ctx->d_template, FRAME_RGB));
+	HIPCHK(ctx->d_template.ensure(FRAME_RGB));
 	HIPCHK(hipMemcpy(ctx->d_template, rgb_template, FRAME_RGB, mem == CIMBAR_HIP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
 	return 0;
 }
@@ -1666,27 +1568,19 @@ int cimbar_hip_encode_batch(cimbar_hip_ctx* ctx, const uint8_t* payload, int n, 
 	hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (any_device ? (hipStream_t)nullptr : ctx->stream);
 	if (int r = drain_pipeline_into(ctx, st)) return r;
 	if (int r = ensure_capacity(ctx, n)) return r;
-	const uint8_t* d_payload = payload;
-	if (payload_mem == CIMBAR_HIP_MEM_HOST) {
-		const size_t need = (size_t)n * FRAME_BYTES;
-		if (need > ctx->d_payload_cap) { HIPCHK(regrow(ctx->d_payload, need)); ctx->d_payload_cap = need; }
-		HIPCHK(hipMemcpyAsync(ctx->d_payload, payload, need, hipMemcpyHostToDevice, st));
-		d_payload = ctx->d_payload;
-	}
-	uint8_t* d_out = rgb_out;
-	if (rgb_mem == CIMBAR_HIP_MEM_HOST) {
-		const size_t need = (size_t)n * FRAME_RGB;
-		if (need > ctx->d_rgb_cap) { HIPCHK(regrow(ctx->d_rgb, need)); ctx->d_rgb_cap = need; }
-		d_out = ctx->d_rgb;
-	}
+	const uint8_t* d_payload = nullptr;
+	if (int r = stage_input(ctx, st, ctx->d_payload, payload, (size_t)n * FRAME_BYTES, payload_mem, &d_payload)) return r;
+	uint8_t* d_out = nullptr;
+	if (int r = stage_output(ctx, ctx->d_rgb, rgb_out, (size_t)n * FRAME_RGB, rgb_mem, &d_out)) return r;
+	cimbar_hip_ctx::ScratchSet& cur = ctx->cur();
 	uint8_t* d_stream = nullptr;
 	if (LEGACY) {   // the RS-encoded stream as bytes, cut into 6-bit cells by a second kernel (the plane scratch is free here and large enough)
 		static_assert((size_t)ALL_BLOCKS * RS_BLOCK <= (size_t)PLANE_WORDS * 4, "the encoded stream fits the bit-plane scratch");
-		d_stream = reinterpret_cast<uint8_t*>(ctx->d_plane);
+		d_stream = reinterpret_cast<uint8_t*>(cur.d_plane.get());
 	}
-	hipLaunchKernelGGL(k_rs_encode, dim3((n * ALL_BLOCKS + 3) / 4), dim3(256), 0, st, d_payload, ctx->tb, ctx->d_gen_log, n, ctx->d_symbols, ctx->d_colors, d_stream);
-	if (LEGACY) hipLaunchKernelGGL(k_fields_legacy, dim3((NCELLS + 255) / 256, n), dim3(256), 0, st, d_stream, ctx->tb, n, ctx->d_symbols, ctx->d_colors);
-	hipLaunchKernelGGL(k_render, dim3((IMG_H + 3) / 4, n), dim3(256), 0, st, ctx->d_symbols, ctx->d_colors, ctx->d_template, d_out);
+	hipLaunchKernelGGL(k_rs_encode, dim3((n * ALL_BLOCKS + 3) / 4), dim3(256), 0, st, d_payload, ctx->tb, ctx->d_gen_log, n, cur.d_symbols, cur.d_colors, d_stream);
+	if (LEGACY) hipLaunchKernelGGL(k_fields_legacy, dim3((NCELLS + 255) / 256, n), dim3(256), 0, st, d_stream, ctx->tb, n, cur.d_symbols, cur.d_colors);
+	hipLaunchKernelGGL(k_render, dim3((IMG_H + 3) / 4, n), dim3(256), 0, st, cur.d_symbols, cur.d_colors, ctx->d_template, d_out);
 	HIPCHK(hipGetLastError());
 	if (rgb_mem == CIMBAR_HIP_MEM_HOST) {
 		HIPCHK(hipMemcpyAsync(rgb_out, d_out, (size_t)n * FRAME_RGB, hipMemcpyDeviceToHost, st));
@@ -1724,10 +1618,10 @@ int cimbar_hip_set_colour_erasure_decode(cimbar_hip_ctx* ctx, int colour_margin,
 	// (read when a batch is enqueued: batches already issued keep the setting they were issued with)
 	ctx->ec_margin = colour_margin > 0 ? colour_margin : 0;
 	ctx->ec_max = max_erasures < 0 ? -1 : max_erasures;
-	if (ctx->ec_margin > 0 && ctx->cap > 0) {
+	if (ctx->ec_margin > 0 && ctx->cur().cap > 0) {
 		// the margin buffer (CIMBAR_HIP_TAP_COLOUR_MARGIN) exists from the first time the setting is on; a context that has not decoded yet gets it with its scratch
 		HIPCHK(hipSetDevice(ctx->device));
-		if (int r = ensure_margin_capacity(ctx)) return r;
+		if (int r = ensure_margin_capacity(ctx, ctx->cur())) return r;
 	}
 	return 0;
 }
@@ -1757,11 +1651,8 @@ int cimbar_hip_rs_decode_erasures(cimbar_hip_ctx* ctx, const uint8_t* blocks, in
 	// stream here, the null stream for device memory: the convention of cimbar_hip_encode_batch / cimbar_hip_decode_batch.
 	hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
 	const size_t nb = (size_t)n * RS_BLOCK, nm = (size_t)n * RS_DATA, need = 2 * nb + 2 * (size_t)n + nm;
-	if (need > ctx->d_er_cap) {
-		HIPCHK(hipStreamSynchronize(st));   // (a previous call's copies on another stream are complete: every host-memory call synchronises)
-		HIPCHK(regrow(ctx->d_er_buf, need));
-		ctx->d_er_cap = need;
-	}
+	if (need > ctx->d_er_buf.capacity()) HIPCHK(hipStreamSynchronize(st));   // (a previous call's copies on another stream are complete: every host-memory call synchronises)
+	HIPCHK(ctx->d_er_buf.reserve(need));
 	uint8_t* d = ctx->d_er_buf;
 	uint8_t *d_blocks = d, *d_er = d + nb, *d_counts = d + 2 * nb, *d_msgs = d_counts + n;
 	int8_t* d_status = reinterpret_cast<int8_t*>(d_msgs + nm);
@@ -1799,32 +1690,32 @@ int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_byte
 	HIPCHK(hipSetDevice(ctx->device));
 	HIPCHK(hipDeviceSynchronize());
 	const size_t n = (size_t)ctx->last_n;
+	cimbar_hip_ctx::ScratchSet& cur = ctx->cur();
 	const void* src = nullptr;
 	size_t bytes = 0;
 	switch (what) {
 		case CIMBAR_HIP_TAP_BITPLANE: {
 			bytes = n * (size_t)IMG_W * IMG_H / 8;                     // CimbReader::_grayscale's layout: the bits of a frame back to back
 			if (out_bytes < bytes) { ctx->err = "tap: buffer too small"; return CIMBAR_HIP_EINVAL; }
-			uint8_t* tmp = nullptr;
-			HIPCHK(hipMalloc(&tmp, bytes));
+			DevBuf<uint8_t> tmp;
+			HIPCHK(tmp.reserve(bytes));
 			size_t nw = bytes / 4;
-			hipLaunchKernelGGL(k_plane_bytes, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_plane, tmp, nw);
+			hipLaunchKernelGGL(k_plane_bytes, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, ctx->stream, cur.d_plane, tmp, nw);
 			hipError_t e = hipMemcpyAsync(out, tmp, bytes, hipMemcpyDeviceToHost, ctx->stream);
 			if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-			(void)hipFree(tmp);
 			HIPCHK(e);
 			return (int64_t)bytes;
 		}
-		case CIMBAR_HIP_TAP_SYMBOLS: src = ctx->d_symbols; bytes = n * NCELLS; break;
-		case CIMBAR_HIP_TAP_COLORS: src = ctx->d_colors; bytes = n * NCELLS; break;
-		case CIMBAR_HIP_TAP_DRIFT: src = ctx->d_drift; bytes = n * NCELLS * 2; break;
-		case CIMBAR_HIP_TAP_RS_OK: src = ctx->d_rs_ok; bytes = n * ALL_BLOCKS; break;
-		case CIMBAR_HIP_TAP_CCM: src = ctx->d_ccm_used; bytes = n * 10 * sizeof(float); break;
+		case CIMBAR_HIP_TAP_SYMBOLS: src = cur.d_symbols; bytes = n * NCELLS; break;
+		case CIMBAR_HIP_TAP_COLORS: src = cur.d_colors; bytes = n * NCELLS; break;
+		case CIMBAR_HIP_TAP_DRIFT: src = cur.d_drift; bytes = n * NCELLS * 2; break;
+		case CIMBAR_HIP_TAP_RS_OK: src = cur.d_rs_ok; bytes = n * ALL_BLOCKS; break;
+		case CIMBAR_HIP_TAP_CCM: src = cur.d_ccm_used; bytes = n * 10 * sizeof(float); break;
 		case CIMBAR_HIP_TAP_FLOOD: {
 			bytes = n;
 			if (out_bytes < bytes) { ctx->err = "tap: buffer too small"; return CIMBAR_HIP_EINVAL; }
 			std::vector<uint32_t> tmp(n);
-			HIPCHK(hipMemcpy(tmp.data(), ctx->d_flood, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+			HIPCHK(hipMemcpy(tmp.data(), cur.d_flood, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
 			for (size_t k = 0; k < n; ++k) ((uint8_t*)out)[k] = tmp[k] ? 1 : 0;
 			return (int64_t)bytes;
 		}
@@ -1832,8 +1723,8 @@ int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_byte
 			bytes = n * sizeof(uint32_t);
 			if (out_bytes < bytes) { ctx->err = "tap: buffer too small"; return CIMBAR_HIP_EINVAL; }
 			std::vector<uint32_t> fl(n);
-			HIPCHK(hipMemcpy(fl.data(), ctx->d_flood, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
-			HIPCHK(hipMemcpy(out, ctx->d_flood + ctx->cap, bytes, hipMemcpyDeviceToHost));
+			HIPCHK(hipMemcpy(fl.data(), cur.d_flood, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+			HIPCHK(hipMemcpy(out, cur.d_flood + cur.cap, bytes, hipMemcpyDeviceToHost));
 			for (size_t k = 0; k < n; ++k) if (!fl[k]) ((uint32_t*)out)[k] = 0xFFFFFFFFu;   // frame never flagged: the batch-parallel flood did not look at it
 			return (int64_t)bytes;
 		}
@@ -1841,7 +1732,7 @@ int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_byte
 			bytes = n;
 			if (out_bytes < bytes) { ctx->err = "tap: buffer too small"; return CIMBAR_HIP_EINVAL; }
 			std::vector<uint32_t> tmp(n);
-			HIPCHK(hipMemcpy(tmp.data(), ctx->d_flood, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+			HIPCHK(hipMemcpy(tmp.data(), cur.d_flood, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
 			for (size_t k = 0; k < n; ++k) ((uint8_t*)out)[k] = (uint8_t)tmp[k];
 			return (int64_t)bytes;
 		}
@@ -1854,12 +1745,12 @@ int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_byte
 			return (int64_t)bytes;
 		}
 		case CIMBAR_HIP_TAP_COLOUR_MARGIN: {
-			if (!ctx->cm_valid || !ctx->d_cmargin || (size_t)ctx->cm_cap < n) { ctx->err = "tap: the last batch ran without colour erasure decoding (cimbar_hip_set_colour_erasure_decode)"; return CIMBAR_HIP_EINVAL; }
+			if (!ctx->cm_valid || !cur.d_cmargin || (size_t)cur.cm_cap < n) { ctx->err = "tap: the last batch ran without colour erasure decoding (cimbar_hip_set_colour_erasure_decode)"; return CIMBAR_HIP_EINVAL; }
 			bytes = n * NCELLS * sizeof(uint32_t);
 			if (out_bytes < bytes) { ctx->err = "tap: buffer too small"; return CIMBAR_HIP_EINVAL; }
 			std::vector<uint32_t> worked(n);
-			HIPCHK(hipMemcpy(out, ctx->d_cmargin, bytes, hipMemcpyDeviceToHost));
-			HIPCHK(hipMemcpy(worked.data(), ctx->d_cmargin + (size_t)ctx->cm_cap * NCELLS, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+			HIPCHK(hipMemcpy(out, cur.d_cmargin, bytes, hipMemcpyDeviceToHost));
+			HIPCHK(hipMemcpy(worked.data(), cur.d_cmargin + (size_t)cur.cm_cap * NCELLS, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
 			// frames whose colour chunks were all in the mask: the retry returned at once and computed no margin
 			for (size_t k = 0; k < n; ++k) if (!worked[k]) std::memset((uint32_t*)out + k * NCELLS, 0xFF, (size_t)NCELLS * sizeof(uint32_t));
 			return (int64_t)bytes;
@@ -1901,7 +1792,7 @@ int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_byte
 	if (what == CIMBAR_HIP_TAP_DRIFT) {
 		// frames that took the parallel path never wrote their (all-zero) drift
 		std::vector<uint32_t> fl(n);
-		HIPCHK(hipMemcpy(fl.data(), ctx->d_flood, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+		HIPCHK(hipMemcpy(fl.data(), cur.d_flood, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
 		for (size_t k = 0; k < n; ++k) if (!fl[k]) std::memset((uint8_t*)out + k * NCELLS * 2, 0, (size_t)NCELLS * 2);
 	}
 	return (int64_t)bytes;
@@ -1998,34 +1889,20 @@ int undistort_group(const cimbar_hip_ctx* ctx, unsigned width, unsigned height, 
 // read a pageable temporary), and -- with `group` > 0 -- the image scratch of one group
 int undistort_state(cimbar_hip_ctx* ctx, hipStream_t st, int n, const double ir[9], unsigned width, unsigned height, int group)
 {
-	if (n > ctx->d_ud_n) {
-		HIPCHK(hipStreamSynchronize(st));
-		ctx->d_ud_n = 0;
-		HIPCHK(regrow(ctx->d_ud_ok, (size_t)n));
-		HIPCHK(regrow(ctx->d_ud_k1, (size_t)n));
-		HIPCHK(regrow(ctx->d_ud_status, (size_t)n));
-		ctx->d_ud_n = n;
-	}
-	if (!ctx->ev_ud_xt) HIPCHK(hipEventCreateWithFlags(&ctx->ev_ud_xt, hipEventDisableTiming));
+	// (each of these is replaced behind whatever `st` still has in flight that reads it)
+	const size_t need = (size_t)width * height * 3 * (size_t)group;
+	if ((size_t)n > ctx->d_ud_status.capacity() || width > ctx->d_ud_xt.capacity() || need > ctx->d_ud_img.capacity()) HIPCHK(hipStreamSynchronize(st));
+	HIPCHK(ctx->d_ud_ok.reserve((size_t)n));
+	HIPCHK(ctx->d_ud_k1.reserve((size_t)n));
+	HIPCHK(ctx->d_ud_status.reserve((size_t)n));
+	HIPCHK(ctx->ev_ud_xt.create());
 	HIPCHK(hipEventSynchronize(ctx->ev_ud_xt));
-	if ((int)width > ctx->ud_xt_cap) {
-		HIPCHK(hipStreamSynchronize(st));
-		ctx->ud_xt_cap = 0;
-		HIPCHK(regrow(ctx->d_ud_xt, (size_t)width));
-		if (ctx->h_ud_xt) { HIPCHK(hipHostFree(ctx->h_ud_xt)); ctx->h_ud_xt = nullptr; }
-		HIPCHK(hipHostMalloc(&ctx->h_ud_xt, sizeof(double) * width, hipHostMallocDefault));
-		ctx->ud_xt_cap = (int)width;
-	}
+	HIPCHK(ctx->d_ud_xt.reserve((size_t)width));
+	HIPCHK(ctx->h_ud_xt.reserve((size_t)width));
+	HIPCHK(ctx->d_ud_img.reserve(need));
 	undistort_column_table(ir, (int)width, ctx->h_ud_xt);
 	HIPCHK(hipMemcpyAsync(ctx->d_ud_xt, ctx->h_ud_xt, sizeof(double) * width, hipMemcpyHostToDevice, st));
 	HIPCHK(hipEventRecord(ctx->ev_ud_xt, st));
-	const size_t need = (size_t)width * height * 3 * (size_t)group;
-	if (need > ctx->d_ud_img_cap) {
-		HIPCHK(hipStreamSynchronize(st));
-		ctx->d_ud_img_cap = 0;
-		HIPCHK(regrow(ctx->d_ud_img, need));
-		ctx->d_ud_img_cap = need;
-	}
 	return 0;
 }
 
@@ -2084,7 +1961,7 @@ int cimbar_hip_undistort_calibrate_fmt(cimbar_hip_ctx* ctx, const uint8_t* img, 
 	const int group = undistort_group(ctx, width, height, n);
 	if (int r = undistort_state(ctx, st, n, ir, width, height, 0)) return r;
 	const uint8_t* d_in = nullptr;
-	if (int r = stage_captures(ctx, st, img, cbytes * n, img_mem, &d_in)) return r;
+	if (int r = stage_input(ctx, st, ctx->d_ex_in, img, cbytes * n, img_mem, &d_in)) return r;
 	for (int lo = 0; lo < n; lo += group) {
 		const int m = n - lo < group ? n - lo : group;
 		if (int r = enqueue_undistort_calibrate(ctx, st, d_in + (size_t)lo * cbytes, width, height, fmt, m, ctx->d_ud_ok + lo, ctx->d_ud_k1 + lo)) return r;
@@ -2107,7 +1984,7 @@ int cimbar_hip_undistort_batch_fmt(cimbar_hip_ctx* ctx, const uint8_t* img, unsi
 	const int group = undistort_group(ctx, width, height, n);
 	if (int r = undistort_state(ctx, st, n, ir, width, height, out_mem == CIMBAR_HIP_MEM_HOST ? group : 0)) return r;
 	const uint8_t* d_in = nullptr;
-	if (int r = stage_captures(ctx, st, img, cbytes * n, img_mem, &d_in)) return r;
+	if (int r = stage_input(ctx, st, ctx->d_ex_in, img, cbytes * n, img_mem, &d_in)) return r;
 	const size_t per = (size_t)width * height * 3;
 	if (params) hipLaunchKernelGGL(k_undistort_fill, dim3((n + 63) / 64), dim3(64), 0, st, n, P.k1, ctx->d_ud_ok, ctx->d_ud_k1);
 	for (int lo = 0; lo < n; lo += group) {
@@ -2143,8 +2020,8 @@ int64_t cimbar_hip_scan_undistort_extract_decode_batch_fmt(cimbar_hip_ctx* ctx, 
 	const int group = undistort_group(ctx, width, height, n);
 	if (int r = undistort_state(ctx, st, n, ir, width, height, group)) return r;
 	const uint8_t* d_in = nullptr;
-	if (int r = stage_captures(ctx, st, img, cbytes * n, img_mem, &d_in)) return r;
-	if ((size_t)n * FRAME_RGB > ctx->d_ex_frames_cap) { HIPCHK(regrow(ctx->d_ex_frames, (size_t)n * FRAME_RGB)); ctx->d_ex_frames_cap = (size_t)n * FRAME_RGB; }
+	if (int r = stage_input(ctx, st, ctx->d_ex_in, img, cbytes * n, img_mem, &d_in)) return r;
+	HIPCHK(ctx->d_ex_frames.reserve((size_t)n * FRAME_RGB));
 	// cimbar.cpp:135-146 per capture, a group at a time: calibrate on the raw capture, remap (a failed calibration leaves the image as it was), then
 	// Extractor::extract on the result; the deskewed frames of the whole batch then go through ONE decode, as in scan_extract_decode_batch
 	for (int lo = 0; lo < n; lo += group) {

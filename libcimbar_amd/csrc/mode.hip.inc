@@ -1,5 +1,5 @@
 // mode.hip.inc -- everything that depends on the frame geometry: constants, kernels, context and host logic. Included by cimbar_hip.hip once per
-// supported mode with CIMBAR_MODE / CIMBAR_NS set; each copy lives in its own namespace (m68, m67) and api.hip.inc dispatches the C ABI on the
+// supported mode with CIMBAR_MODE / CIMBAR_NS set; each copy lives in its own namespace (m68, m67, m66, m4, m8) and api.hip.inc dispatches the C ABI on the
 // context's mode.
 namespace CIMBAR_NS __attribute__((visibility("hidden"))) {
 
