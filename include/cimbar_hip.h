@@ -228,7 +228,8 @@ int cimbar_hip_rs_decode_erasures(cimbar_hip_ctx* ctx, const uint8_t* blocks, in
  *   grouping     groups_in == NULL: agree(k, k+1) = the cells whose symbol and colour are both equal in captures k and k+1. Walking left to
  *                right, capture k starts a new group when it is the first, when agree(k-1, k) * 1000 < min_agree_permille * cells, when the
  *                previous group already has max_group members, or when capture k-1 or k is unusable (capture path: its extraction failed).
- *                Unusable captures are in no group (-1); groups are numbered 0, 1, ... in capture order; groups never span two calls.
+ *                Unusable captures are in no group (-1); groups are numbered 0, 1, ... in capture order. These calls' groups do not span two calls;
+ *                the stream calls below carry the open group from call to call.
  *                groups_in != NULL (host memory, n ints): the caller's groups -- each -1 or an id, ids starting at 0 and rising by one, each
  *                id's captures contiguous and at most max_group; anything else is CIMBAR_HIP_EINVAL. On the capture path a capture whose
  *                extraction failed is left out of its group (and reported -1); a group left without members delivers nothing.
@@ -259,6 +260,41 @@ int64_t cimbar_hip_scan_extract_decode_batch_combined_fmt(cimbar_hip_ctx* ctx, c
                                                           int min_agree_permille, int max_group, uint8_t* chunks, uint32_t* masks, int* status,
                                                           int* groups_out, uint8_t* gchunks, uint32_t* gmasks, int* n_groups, int out_mem,
                                                           void* hip_stream);
+
+/* Multi-capture decoding across calls. A live receiver hands over one capture per call, or a few; these calls keep the group that is still
+ * open at the end of a call on the device (at most max_group - 1 members, copies the context owns, about 0.2 MB each) and go on with it in
+ * the next stream call. Take a sequence of stream calls on one context whose last call has flush != 0: the groups they report, in order, are
+ * the groups ONE cimbar_hip_decode_batch_combined (or _scan_extract_decode_batch_combined_fmt) call reports for the concatenation of their
+ * captures with groups_in == NULL and the same settings -- members, gchunks, gmask, erasure retry and all. Each group is reported by the call
+ * in which it closes. chunks / masks / status and the colour-correction carry are the plain call's for the same input.
+ *   a group closes  when a capture starts a new one (agree(k-1, k) * 1000 < min_agree_permille * cells), when it reaches max_group members (at
+ *                   once, in the call of that member), when an unusable capture follows it (capture path), or when flush != 0
+ *   groups_out      n ints (may be NULL), the call's own captures: the call-local id of the capture's group if it closes in this call (0, 1, ...
+ *                   in closing order = capture order), CIMBAR_HIP_GROUP_OPEN if it stays open, -1 if the capture is unusable
+ *   gchunks / gmasks / gsizes  n + 1 slots (capture 0 can close the carried group, every capture can close a group of its own, the flush closes
+ *                   the last); slots at or above the closed count are zero. gsizes[g] = the members of group g, those of earlier calls
+ *                   included (may be NULL)
+ *   n_groups        the groups closed by this call (may be NULL); host outputs: also the return value
+ *   n == 0          allowed with flush != 0 (closes and reports the open group; with nothing open: 0 groups; no image argument is read);
+ *                   without a flush CIMBAR_HIP_EINVAL
+ *   min_agree_permille / max_group  resolved as above and fixed by the first stream call after create or cimbar_hip_combine_stream_reset: a call that
+ *                   resolves to other values is CIMBAR_HIP_EINVAL, checked before anything is enqueued. should_preprocess, color_correction, n
+ *                   and the capture size may change from call to call. There is no groups_in.
+ * Device outputs: the call enqueues and returns 0; whether a group is open, its members and their slots are decided on the device, nothing
+ * is read back. Other calls on the context may run between two stream calls (cimbar_hip_decode_batch, the plain combined calls, delivery, the
+ * pipelined entry): the stream neither sees their captures nor is disturbed by them. Consecutive stream calls are ordered against each other,
+ * whatever their hip_stream. The group taps after a stream call describe the groups it closed.
+ * cimbar_hip_combine_stream_reset waits for the stream calls issued so far, drops the open group and forgets the fixed parameters. */
+enum { CIMBAR_HIP_GROUP_OPEN = -2 };
+int64_t cimbar_hip_decode_batch_combined_stream(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rgb_mem, int should_preprocess, int color_correction,
+                                                int min_agree_permille, int max_group, int flush, uint8_t* chunks, uint32_t* masks, int* groups_out,
+                                                uint8_t* gchunks, uint32_t* gmasks, int* gsizes, int* n_groups, int out_mem, void* hip_stream);
+int64_t cimbar_hip_scan_extract_decode_batch_combined_stream_fmt(cimbar_hip_ctx* ctx, const uint8_t* img, unsigned width, unsigned height, int format,
+                                                                 int n, int img_mem, int preprocess, int color_correction, int min_agree_permille,
+                                                                 int max_group, int flush, uint8_t* chunks, uint32_t* masks, int* status,
+                                                                 int* groups_out, uint8_t* gchunks, uint32_t* gmasks, int* gsizes, int* n_groups,
+                                                                 int out_mem, void* hip_stream);
+int cimbar_hip_combine_stream_reset(cimbar_hip_ctx* ctx);
 
 /* ---- chunk delivery: a batch's slots and masks -> what a fountain sink eats --------------------------------------------------------------
  * The batch entry points above report a frame's chunks in fixed slots plus one mask word. The reference's receive interface has another shape:

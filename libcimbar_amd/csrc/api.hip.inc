@@ -221,6 +221,32 @@ int64_t cimbar_hip_scan_extract_decode_batch_combined_fmt(cimbar_hip_ctx* ctx, c
 	                  min_agree_permille, max_group, chunks, masks, status, groups_out, gchunks, gmasks, n_groups, out_mem, hip_stream);
 }
 
+int64_t cimbar_hip_decode_batch_combined_stream(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rgb_mem, int should_preprocess, int color_correction,
+                                                int min_agree_permille, int max_group, int flush, uint8_t* chunks, uint32_t* masks, int* groups_out,
+                                                uint8_t* gchunks, uint32_t* gmasks, int* gsizes, int* n_groups, int out_mem, void* hip_stream)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return CIMBAR_FWD(cimbar_hip_decode_batch_combined_stream, rgb, n, rgb_mem, should_preprocess, color_correction, min_agree_permille, max_group, flush,
+	                  chunks, masks, groups_out, gchunks, gmasks, gsizes, n_groups, out_mem, hip_stream);
+}
+
+int64_t cimbar_hip_scan_extract_decode_batch_combined_stream_fmt(cimbar_hip_ctx* ctx, const uint8_t* img, unsigned width, unsigned height, int format,
+                                                                 int n, int img_mem, int preprocess, int color_correction, int min_agree_permille,
+                                                                 int max_group, int flush, uint8_t* chunks, uint32_t* masks, int* status,
+                                                                 int* groups_out, uint8_t* gchunks, uint32_t* gmasks, int* gsizes, int* n_groups,
+                                                                 int out_mem, void* hip_stream)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return CIMBAR_FWD(cimbar_hip_scan_extract_decode_batch_combined_stream_fmt, img, width, height, format, n, img_mem, preprocess, color_correction,
+	                  min_agree_permille, max_group, flush, chunks, masks, status, groups_out, gchunks, gmasks, gsizes, n_groups, out_mem, hip_stream);
+}
+
+int cimbar_hip_combine_stream_reset(cimbar_hip_ctx* ctx)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return CIMBAR_FWD(cimbar_hip_combine_stream_reset);
+}
+
 int cimbar_hip_encode_batch(cimbar_hip_ctx* ctx, const uint8_t* payload, int n, int payload_mem, uint8_t* rgb_out, int rgb_mem, void* hip_stream)
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;

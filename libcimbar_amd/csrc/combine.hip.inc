@@ -12,6 +12,9 @@
 //                      combined decode did not deliver, and (erasure decoding on) the erasure retry of the symbol chunks still missing
 // Every kernel after G2 is launched for n captures' worth of groups and returns at once at or above the device-side group count, so nothing
 // here waits for the host.
+// The plain combined calls' groups do not span calls; the stream calls' (..._combined_stream) do: the group still open at the end of a call is
+// kept in a carry store the context owns (at most GMAX - 1 members, copies) and the next stream call walks a virtual batch, the carried
+// members followed by its own captures. See "the stream calls" below.
 constexpr int GMAX = 8;                    // captures per group at most (the max_group argument is <= this)
 constexpr int GROUP_MAX_DEFAULT = 4, GROUP_AGREE_DEFAULT = 750;
 constexpr uint16_t MARGIN_NONE = 0xFFFFu;  // the symbol of the cell is not disputed
@@ -117,12 +120,47 @@ __global__ __launch_bounds__(64) void k_group_walk(const uint32_t* __restrict__ 
 // Phase 1 settles every cell whose symbols agree and whose colour vote has one winner (no hash needed); the rest are queued per wavefront
 // and phase 2 gives each of them a lane of its own: the cost grows with the disputed cells only.
 constexpr int GC_CELLS = 1024, GC_BLOCKS = (NCELLS + GC_CELLS - 1) / GC_CELLS;
-__global__ __launch_bounds__(256) void k_group_cells(const uint32_t* __restrict__ plane, Tables tb, const uint8_t* __restrict__ symbols,
-                                                     const uint8_t* __restrict__ colors, const int8_t* __restrict__ drift,
-                                                     const uint32_t* __restrict__ flood_flag, const int* __restrict__ gmem,
-                                                     const int* __restrict__ gcount, const int* __restrict__ ngroups, uint8_t* __restrict__ gsym,
-                                                     uint8_t* __restrict__ gcol, uint16_t* __restrict__ gmargin, uint32_t* __restrict__ gdisp)
+
+// The carry store of the stream calls, by value into their kernels: CARRY_SLOTS members' worth of what G1, G3 and G4 read of a member, and
+// the number of occupied slots (always slots 0 .. *count - 1, in capture order). A member id below CARRY_SLOTS names a slot, id - CARRY_SLOTS
+// a capture of the call's batch. An unusable capture is in no group, so a slot is a usable capture by construction and holds no status.
+constexpr int CARRY_SLOTS = GMAX - 1;
+constexpr size_t CS_CELLS = ((size_t)NCELLS + 15) / 16 * 16, CS_DRIFT = ((size_t)NCELLS * 2 + 15) / 16 * 16, CS_PLANE = ((size_t)PLANE_WORDS + 3) / 4 * 4,
+                 CS_CHUNKS = ((size_t)FRAME_BYTES + 15) / 16 * 16;   // slot strides (bytes, bytes, words, bytes): every slot starts on 16 bytes
+struct CarryStore {
+	uint8_t* symbols; uint8_t* colors; uint32_t* plane; int8_t* drift; uint32_t* flood; uint8_t* chunks; uint32_t* masks;
+	int* count;
+};
+
+// (CARRY = false is the plain calls' kernel as it always was: a member id is a batch index and `cs` is not read)
+template <bool CARRY>
+__device__ __forceinline__ void group_cells_body(const uint32_t* __restrict__ plane, const Tables& tb, const uint8_t* __restrict__ symbols,
+                                                 const uint8_t* __restrict__ colors, const int8_t* __restrict__ drift,
+                                                 const uint32_t* __restrict__ flood_flag, const int* __restrict__ gmem,
+                                                 const int* __restrict__ gcount, const int* __restrict__ ngroups, uint8_t* __restrict__ gsym,
+                                                 uint8_t* __restrict__ gcol, uint16_t* __restrict__ gmargin, uint32_t* __restrict__ gdisp,
+                                                 const CarryStore& cs)
 {
+	auto sym_of = [&](int f) -> const uint8_t* {
+		if constexpr (CARRY) return f < CARRY_SLOTS ? cs.symbols + (size_t)f * CS_CELLS : symbols + (size_t)(f - CARRY_SLOTS) * NCELLS;
+		else return symbols + (size_t)f * NCELLS;
+	};
+	auto col_of = [&](int f) -> const uint8_t* {
+		if constexpr (CARRY) return f < CARRY_SLOTS ? cs.colors + (size_t)f * CS_CELLS : colors + (size_t)(f - CARRY_SLOTS) * NCELLS;
+		else return colors + (size_t)f * NCELLS;
+	};
+	auto drift_of = [&](int f) -> const int8_t* {
+		if constexpr (CARRY) return f < CARRY_SLOTS ? cs.drift + (size_t)f * CS_DRIFT : drift + (size_t)(f - CARRY_SLOTS) * NCELLS * 2;
+		else return drift + (size_t)f * NCELLS * 2;
+	};
+	auto plane_of = [&](int f) -> const uint32_t* {
+		if constexpr (CARRY) return f < CARRY_SLOTS ? cs.plane + (size_t)f * CS_PLANE : plane + (size_t)(f - CARRY_SLOTS) * PLANE_WORDS;
+		else return plane + (size_t)f * PLANE_WORDS;
+	};
+	auto flood_of = [&](int f) -> uint32_t {
+		if constexpr (CARRY) return f < CARRY_SLOTS ? cs.flood[f] : flood_flag[f - CARRY_SLOTS];
+		else return flood_flag[f];
+	};
 	const int g = blockIdx.y;
 	if (g >= *ngroups) return;
 	__shared__ int s_mem[GMAX];
@@ -132,7 +170,7 @@ __global__ __launch_bounds__(256) void k_group_cells(const uint32_t* __restrict_
 	if (threadIdx.x < GMAX) {
 		const int f = (int)threadIdx.x < m ? gmem[(size_t)g * GMAX + threadIdx.x] : 0;
 		s_mem[threadIdx.x] = f;
-		s_flood[threadIdx.x] = (int)threadIdx.x < m ? flood_flag[f] : 0u;
+		s_flood[threadIdx.x] = (int)threadIdx.x < m ? flood_of(f) : 0u;
 	}
 	__syncthreads();
 	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -151,8 +189,8 @@ __global__ __launch_bounds__(256) void k_group_cells(const uint32_t* __restrict_
 			bool sym_eq = true;
 #pragma unroll
 			for (int c = 0; c < GMAX; ++c) {
-				sy[c] = c < m ? symbols[(size_t)s_mem[c] * NCELLS + i] & 15u : 0u;
-				co[c] = c < m ? colors[(size_t)s_mem[c] * NCELLS + i] : 0u;
+				sy[c] = c < m ? sym_of(s_mem[c])[i] & 15u : 0u;
+				co[c] = c < m ? col_of(s_mem[c])[i] : 0u;
 				sym_eq = sym_eq && (c >= m || sy[c] == sy[0]);
 			}
 			// plurality: the first member's colour among those with the most votes, and whether another colour has as many
@@ -200,12 +238,13 @@ __global__ __launch_bounds__(256) void k_group_cells(const uint32_t* __restrict_
 			sy[c] = co[c] = 0;
 			if (c < m) {
 				const int f = s_mem[c];
-				sy[c] = symbols[(size_t)f * NCELLS + i] & 15u;
-				co[c] = colors[(size_t)f * NCELLS + i];
+				sy[c] = sym_of(f)[i] & 15u;
+				co[c] = col_of(f)[i];
 				const bool flooded = s_flood[c] != 0;
-				const int dx = flooded ? drift[((size_t)f * NCELLS + i) * 2] : 0, dy = flooded ? drift[((size_t)f * NCELLS + i) * 2 + 1] : 0;
+				const int8_t* dr = drift_of(f);
+				const int dx = flooded ? dr[(size_t)i * 2] : 0, dy = flooded ? dr[(size_t)i * 2 + 1] : 0;
 				uint32_t rows[10];
-				window_rows(plane + (size_t)f * PLANE_WORDS, (int)xy.x + dx - 1, (int)xy.y + dy - 1, rows);
+				window_rows(plane_of(f), (int)xy.x + dx - 1, (int)xy.y + dy - 1, rows);
 				H[c] = window_hash(rows, 4);
 #pragma unroll
 				for (int t = 0; t < 16; ++t) score[t] += 2 * (int)__popcll(H[c] ^ c_tile[t]) - (sy[c] == (uint32_t)t ? 1 : 0);
@@ -252,6 +291,16 @@ __global__ __launch_bounds__(256) void k_group_cells(const uint32_t* __restrict_
 	}
 }
 
+
+__global__ __launch_bounds__(256) void k_group_cells(const uint32_t* __restrict__ plane, Tables tb, const uint8_t* __restrict__ symbols,
+                                                     const uint8_t* __restrict__ colors, const int8_t* __restrict__ drift,
+                                                     const uint32_t* __restrict__ flood_flag, const int* __restrict__ gmem,
+                                                     const int* __restrict__ gcount, const int* __restrict__ ngroups, uint8_t* __restrict__ gsym,
+                                                     uint8_t* __restrict__ gcol, uint16_t* __restrict__ gmargin, uint32_t* __restrict__ gdisp)
+{
+	group_cells_body<false>(plane, tb, symbols, colors, drift, flood_flag, gmem, gcount, ngroups, gsym, gcol, gmargin, gdisp, CarryStore{});
+}
+
 // G4: one workgroup per group slot (n of them). A slot at or above the group count, or a group left without members, gets zero chunks and
 // mask 0. Otherwise:
 //   cmask  the aligned_stream bookkeeping over the combined decode's block flags, the symbol blocks then the colour blocks with one state
@@ -262,15 +311,18 @@ __global__ __launch_bounds__(256) void k_group_cells(const uint32_t* __restrict_
 //          then stream position, at most e_max) -- and accepted as in k_erasure_frame (a codeword, nothing in the padding, and with erasures
 //          2 errors <= p - e - ERASURE_SLACK). A chunk whose blocks are all accepted joins the mask with its bytes.
 // gmask = cmask | the members' masks | the chunks the retry added; slots of chunks outside it are zero.
-__global__ __launch_bounds__(256) void k_group_end(const uint8_t* __restrict__ gsym, const uint16_t* __restrict__ gmargin, Tables tb,
-                                                   const int* __restrict__ gmem, const int* __restrict__ gcount, const int* __restrict__ ngroups,
-                                                   const uint8_t* __restrict__ grs_ok, const uint8_t* __restrict__ chunks,
-                                                   const uint32_t* __restrict__ masks, const uint32_t* __restrict__ gdisp, uint8_t* __restrict__ gchunks,
-                                                   uint32_t* __restrict__ gmasks, int e_on, int e_max)
+// (CARRY: a member id is a carry slot or CARRY_SLOTS + a batch index, as in G3, and the member count of every slot goes to gsizes)
+template <bool CARRY>
+__device__ __forceinline__ void group_end_body(const uint8_t* __restrict__ gsym, const uint16_t* __restrict__ gmargin, const Tables& tb,
+                                               const int* __restrict__ gmem, const int* __restrict__ gcount, const int* __restrict__ ngroups,
+                                               const uint8_t* __restrict__ grs_ok, const uint8_t* __restrict__ chunks,
+                                               const uint32_t* __restrict__ masks, const uint32_t* __restrict__ gdisp, uint8_t* __restrict__ gchunks,
+                                               uint32_t* __restrict__ gmasks, int e_on, int e_max, const CarryStore& cs, int* __restrict__ gsizes)
 {
 	const int g = blockIdx.x;
 	uint8_t* gc = gchunks + (size_t)g * FRAME_BYTES;
 	const int m = g < *ngroups ? gcount[g] : 0;
+	if constexpr (CARRY) { if (threadIdx.x == 0) gsizes[g] = m; }
 	if (m == 0) {
 		for (int k = threadIdx.x; k < FRAME_BYTES; k += 256) gc[k] = 0;
 		if (threadIdx.x == 0) gmasks[g] = 0;
@@ -284,7 +336,8 @@ __global__ __launch_bounds__(256) void k_group_end(const uint8_t* __restrict__ g
 	if (threadIdx.x < GMAX) {
 		const int f = (int)threadIdx.x < m ? gmem[(size_t)g * GMAX + threadIdx.x] : 0;
 		s_mem[threadIdx.x] = f;
-		s_mmask[threadIdx.x] = (int)threadIdx.x < m ? masks[f] : 0u;
+		if constexpr (CARRY) s_mmask[threadIdx.x] = (int)threadIdx.x < m ? (f < CARRY_SLOTS ? cs.masks[f] : masks[f - CARRY_SLOTS]) : 0u;
+		else s_mmask[threadIdx.x] = (int)threadIdx.x < m ? masks[f] : 0u;
 	}
 	// a group whose members agree on every cell has each member's cells, so its combined decode is each member's errors-only decode (a
 	// subset of the member's mask, the same bytes) and the retry finds no disputed cell: the members' chunks are the whole answer, and the
@@ -384,11 +437,207 @@ __global__ __launch_bounds__(256) void k_group_end(const uint8_t* __restrict__ g
 		if (mmask & bit) {
 			int c = 0;
 			while (!(s_mmask[c] & bit)) ++c;
-			const uint8_t* src = chunks + (size_t)s_mem[c] * FRAME_BYTES + (size_t)j * CHUNK;
+			const uint8_t* src;
+			if constexpr (CARRY) src = (s_mem[c] < CARRY_SLOTS ? cs.chunks + (size_t)s_mem[c] * CS_CHUNKS : chunks + (size_t)(s_mem[c] - CARRY_SLOTS) * FRAME_BYTES) + (size_t)j * CHUNK;
+			else src = chunks + (size_t)s_mem[c] * FRAME_BYTES + (size_t)j * CHUNK;
 			for (int k = threadIdx.x; k < CHUNK; k += 256) dst[k] = src[k];
 		} else if (!(emask & bit)) {
 			for (int k = threadIdx.x; k < CHUNK; k += 256) dst[k] = 0;
 		}
 	}
 	if (threadIdx.x == 0) gmasks[g] = (cmask | mmask | emask) & FULL;
+}
+
+__global__ __launch_bounds__(256) void k_group_end(const uint8_t* __restrict__ gsym, const uint16_t* __restrict__ gmargin, Tables tb,
+                                                   const int* __restrict__ gmem, const int* __restrict__ gcount, const int* __restrict__ ngroups,
+                                                   const uint8_t* __restrict__ grs_ok, const uint8_t* __restrict__ chunks,
+                                                   const uint32_t* __restrict__ masks, const uint32_t* __restrict__ gdisp, uint8_t* __restrict__ gchunks,
+                                                   uint32_t* __restrict__ gmasks, int e_on, int e_max)
+{
+	group_end_body<false>(gsym, gmargin, tb, gmem, gcount, ngroups, grs_ok, chunks, masks, gdisp, gchunks, gmasks, e_on, e_max, CarryStore{}, nullptr);
+}
+
+// ------------------------------------------------------------------------------------------------ the stream calls
+// cimbar_hip_decode_batch_combined_stream / _scan_extract_decode_batch_combined_stream_fmt: the same decode over a VIRTUAL batch, the c = *cs.count
+// carried members (one group by construction, c < max_group) followed by the call's n captures. Virtual capture j < c is carry slot j, virtual
+// capture j >= c is capture k = j - c of the call. Only groups that CLOSE in the call get ids, are decoded (G3, k_rs LIVE, G4 run over
+// n + 1 group slots) and reported; the group still open at the end is copied into the carry store by k_group_carry. c, the open group and
+// its members never leave the device.
+
+// G1s: one workgroup per capture k < n: agree[k] = agree(predecessor, k), the predecessor being capture k - 1 or, for k = 0, the last
+// carried member (nothing carried: agree[0] is not written and not read)
+__global__ __launch_bounds__(256) void k_group_agree_stream(const uint8_t* __restrict__ symbols, const uint8_t* __restrict__ colors, int n, CarryStore cs,
+                                                            uint32_t* __restrict__ agree)
+{
+	const int k = blockIdx.x;
+	if (k >= n) return;
+	const int c = *cs.count;
+	if (k == 0 && c == 0) return;
+	const uint32_t* s1 = reinterpret_cast<const uint32_t*>(symbols + (size_t)k * NCELLS);
+	const uint32_t* c1 = reinterpret_cast<const uint32_t*>(colors + (size_t)k * NCELLS);
+	const uint32_t* s0 = k > 0 ? s1 - NCELLS / 4 : reinterpret_cast<const uint32_t*>(cs.symbols + (size_t)(c - 1) * CS_CELLS);
+	const uint32_t* c0 = k > 0 ? c1 - NCELLS / 4 : reinterpret_cast<const uint32_t*>(cs.colors + (size_t)(c - 1) * CS_CELLS);
+	constexpr int W = NCELLS / 4;
+	constexpr uint32_t CM = 0x01010101u * (uint32_t)(NCOLORS - 1);
+	uint32_t cnt = 0;
+	for (int w = threadIdx.x; w < W; w += 256) {
+		const uint32_t x = ((s0[w] ^ s1[w]) & 0x0F0F0F0Fu) | ((c0[w] ^ c1[w]) & CM);
+		cnt += ((x & 0xFFu) == 0u) + ((x & 0xFF00u) == 0u) + ((x & 0xFF0000u) == 0u) + ((x >> 24) == 0u);
+	}
+	for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o);
+	__shared__ uint32_t s_part[4];
+	if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = cnt;
+	__syncthreads();
+	if (threadIdx.x == 0) agree[k] = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+}
+
+// G2s: k_group_walk's walk (groups_in == nullptr) over the virtual batch, 64 virtual captures per step. Virtual capture j starts a group when it is
+// usable and j == 0, or j - 1 is unusable, or j >= max(c, 1) and agree[j - c] * 1000 < min_agree * NCELLS, or the group before already has max_group
+// members -- so the carried members open group 0 and count toward its cap. The LAST group stays open when there is no flush, its last member
+// is the last virtual capture (which is then usable) and it has fewer than max_group members; every other group closes.
+//   groups[k]   the id of capture k's group or -1 (the open group's members get its id here; k_group_carry turns them into GROUP_OPEN)
+//   gmem/gcount as in k_group_walk, a member being its carry slot (j < c) or CARRY_SLOTS + k; n + 1 group slots, gcount zeroed by the host
+//   *ngroups    the groups that close in this call (the open one has the id *ngroups); *open_size = the open group's members or 0
+// What a step hands to the next is either a ballot's popcount or a __shfl of lane 63, read back through readfirstlane so that it stays in
+// scalar registers whatever the compiler can prove.
+__global__ __launch_bounds__(64) void k_group_walk_stream(const uint32_t* __restrict__ agree, int n, const int* __restrict__ status, int stride,
+                                                          int min_agree, int max_group, int flush, CarryStore cs, int* __restrict__ groups,
+                                                          int* __restrict__ gmem, int* __restrict__ gcount, int* __restrict__ ngroups,
+                                                          int* __restrict__ open_size)
+{
+	const int lane = threadIdx.x;
+	const unsigned long long below = (1ull << lane) - 1ull, upto = below | (1ull << lane);
+	const int c = __builtin_amdgcn_readfirstlane(*cs.count);
+	const int N = c + n;
+	int run_carry = 0, starts_carry = 0, mem_carry = 0, base_carry = 0, prev_id = -1, top = -1;
+	bool prev_u = false, last_u = false;
+	auto fetch = [&](int j, uint32_t& a, int& st) {
+		const int k = j - c;
+		a = (j > 0 && k >= 0 && j < N) ? agree[k] : 0xFFFFFFFFu;      // (inside the carried group: agreement is implied)
+		st = (status && k >= 0 && j < N) ? status[(size_t)k * stride] : 1;
+	};
+	uint32_t a_cur; int st_cur;
+	fetch(lane, a_cur, st_cur);
+	for (int j0 = 0; j0 < N; j0 += 64) {
+		const int j = j0 + lane;
+		uint32_t a_nxt; int st_nxt;
+		fetch(j + 64, a_nxt, st_nxt);
+		const bool in = j < N;
+		const bool u = in && st_cur > 0;
+		const unsigned long long ub = __ballot(u);
+		if (N - 1 - j0 < 64) last_u = ((ub >> (N - 1 - j0)) & 1ull) != 0;
+		const bool u_prev = lane == 0 ? prev_u : ((ub >> (lane - 1)) & 1ull) != 0;
+		const bool brk = in && (j == 0 || !u_prev || (j >= c && (unsigned long long)a_cur * 1000ull < (unsigned long long)min_agree * NCELLS));
+		const unsigned long long bb = __ballot(brk) & upto;
+		const int run = bb ? j0 + 63 - __clzll(bb) : run_carry;          // the latest break at or before j
+		const bool start = u && (j - run) % max_group == 0;
+		const unsigned long long sb = __ballot(start);
+		const int id = u ? starts_carry + (int)__popcll(sb & upto) - 1 : -1;
+		run_carry = __builtin_amdgcn_readfirstlane(__shfl(run, 63));
+		starts_carry += (int)__popcll(sb);
+		const int id_prev_lane = __shfl(id, lane > 0 ? lane - 1 : 0);
+		const int id_prev = lane == 0 ? prev_id : id_prev_lane;
+		const bool head = id >= 0 && (j == 0 || id_prev != id);
+		const bool member = id >= 0;
+		const unsigned long long mb = __ballot(member), hb = __ballot(head) & upto;
+		const int before = mem_carry + (int)__popcll(mb & below);           // members of the virtual batch in front of j
+		const int hl = hb ? 63 - __clzll(hb) : lane;
+		const int at_head = __shfl(before, hl);
+		const int base = hb ? at_head : base_carry;                          // members in front of j's group
+		if (in && j >= c) groups[j - c] = id;
+		if (member) {
+			gmem[(size_t)id * GMAX + (before - base)] = j < c ? j : CARRY_SLOTS + (j - c);
+			atomicAdd(&gcount[id], 1);
+		}
+		top = id > top ? id : top;
+		prev_id = __builtin_amdgcn_readfirstlane(__shfl(id, 63));
+		prev_u = __builtin_amdgcn_readfirstlane(__shfl((int)u, 63)) != 0;
+		mem_carry += (int)__popcll(mb);
+		base_carry = __builtin_amdgcn_readfirstlane(__shfl(base, 63));
+		a_cur = a_nxt; st_cur = st_nxt;
+	}
+	for (int o = 32; o >= 1; o >>= 1) { const int t = __shfl_xor(top, o); top = t > top ? t : top; }
+	// lanes past the last virtual capture are in no group and head none, so lane 63's base is the last group's: its size is what follows it
+	const int last_size = top >= 0 ? mem_carry - base_carry : 0;
+	const bool open = !flush && top >= 0 && last_u && last_size < max_group;
+	if (lane == 0) {
+		*ngroups = open ? top : top + 1;
+		*open_size = open ? last_size : 0;
+	}
+}
+
+__global__ __launch_bounds__(256) void k_group_cells_stream(const uint32_t* __restrict__ plane, Tables tb, const uint8_t* __restrict__ symbols,
+                                                            const uint8_t* __restrict__ colors, const int8_t* __restrict__ drift,
+                                                            const uint32_t* __restrict__ flood_flag, const int* __restrict__ gmem,
+                                                            const int* __restrict__ gcount, const int* __restrict__ ngroups, uint8_t* __restrict__ gsym,
+                                                            uint8_t* __restrict__ gcol, uint16_t* __restrict__ gmargin, uint32_t* __restrict__ gdisp,
+                                                            CarryStore cs)
+{
+	group_cells_body<true>(plane, tb, symbols, colors, drift, flood_flag, gmem, gcount, ngroups, gsym, gcol, gmargin, gdisp, cs);
+}
+
+__global__ __launch_bounds__(256) void k_group_end_stream(const uint8_t* __restrict__ gsym, const uint16_t* __restrict__ gmargin, Tables tb,
+                                                          const int* __restrict__ gmem, const int* __restrict__ gcount, const int* __restrict__ ngroups,
+                                                          const uint8_t* __restrict__ grs_ok, const uint8_t* __restrict__ chunks,
+                                                          const uint32_t* __restrict__ masks, const uint32_t* __restrict__ gdisp,
+                                                          uint8_t* __restrict__ gchunks, uint32_t* __restrict__ gmasks, int e_on, int e_max, CarryStore cs,
+                                                          int* __restrict__ gsizes)
+{
+	group_end_body<true>(gsym, gmargin, tb, gmem, gcount, ngroups, grs_ok, chunks, masks, gdisp, gchunks, gmasks, e_on, e_max, cs, gsizes);
+}
+
+// bytes from src to dst by the whole workgroup: 16 bytes per lane where both ends and the length allow it, else dwords, else bytes
+__device__ __forceinline__ void carry_copy(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, size_t bytes)
+{
+	const uintptr_t a = (uintptr_t)dst | (uintptr_t)src | (uintptr_t)bytes;
+	if ((a & 15u) == 0) {
+		const uint4* s = reinterpret_cast<const uint4*>(src);
+		uint4* d = reinterpret_cast<uint4*>(dst);
+		for (size_t k = threadIdx.x; k < bytes / 16; k += 256) d[k] = s[k];
+	} else if ((a & 3u) == 0) {
+		const uint32_t* s = reinterpret_cast<const uint32_t*>(src);
+		uint32_t* d = reinterpret_cast<uint32_t*>(dst);
+		for (size_t k = threadIdx.x; k < bytes / 4; k += 256) d[k] = s[k];
+	} else {
+		for (size_t k = threadIdx.x; k < bytes; k += 256) dst[k] = src[k];
+	}
+}
+
+// G5 k_group_carry, behind G4: the open group (*open_size members, gmem row *ngroups) becomes the carry store, member r in slot r; no open
+// group: the store is empty. One workgroup per (slice, slot): CARRY_PARTS slices of each of the five arrays.
+// A member that is itself carried needs no move and no staging copy: the carried members are the first virtual captures and open group 0,
+// so in an open group that holds them member r IS slot r for every r < c, and only members from the call's batch (slots >= c, which no
+// source occupies) are written. Slots at or above the new count keep stale bytes nothing reads.
+// Workgroup (0, 0) also writes GROUP_OPEN over the open members' entries of groups[] and, last, the new count (every reader of the count
+// is a later launch on the stream calls' order).
+constexpr int CARRY_PARTS = 4, CARRY_ARRAYS = 5, GROUP_OPEN_ID = -2;
+__global__ __launch_bounds__(256) void k_group_carry(const uint32_t* __restrict__ plane, const uint8_t* __restrict__ symbols,
+                                                     const uint8_t* __restrict__ colors, const int8_t* __restrict__ drift,
+                                                     const uint32_t* __restrict__ flood_flag, const uint8_t* __restrict__ chunks,
+                                                     const uint32_t* __restrict__ masks, const int* __restrict__ gmem, const int* __restrict__ ngroups,
+                                                     const int* __restrict__ open_size, int* __restrict__ groups, CarryStore cs)
+{
+	const int r = blockIdx.y, arr = blockIdx.x / CARRY_PARTS, part = blockIdx.x % CARRY_PARTS;
+	const int m = *open_size;
+	const int* mem = gmem + (size_t)*ngroups * GMAX;
+	if (blockIdx.x == 0 && r == 0) {
+		if ((int)threadIdx.x < m) { const int f = mem[threadIdx.x]; if (f >= CARRY_SLOTS) groups[f - CARRY_SLOTS] = GROUP_OPEN_ID; }
+		if (threadIdx.x == 0) *cs.count = m;     // (read by this launch's other workgroups through open_size, never through the count)
+	}
+	if (r >= m) return;
+	const int f = mem[r];
+	if (f < CARRY_SLOTS) return;                 // already slot r
+	const size_t k = (size_t)(f - CARRY_SLOTS);
+	const uint8_t* src; uint8_t* dst; size_t bytes;
+	switch (arr) {
+		case 0: src = symbols + k * NCELLS; dst = cs.symbols + (size_t)r * CS_CELLS; bytes = NCELLS; break;
+		case 1: src = colors + k * NCELLS; dst = cs.colors + (size_t)r * CS_CELLS; bytes = NCELLS; break;
+		case 2: src = reinterpret_cast<const uint8_t*>(drift + k * NCELLS * 2); dst = reinterpret_cast<uint8_t*>(cs.drift + (size_t)r * CS_DRIFT); bytes = (size_t)NCELLS * 2; break;
+		case 3: src = reinterpret_cast<const uint8_t*>(plane + k * PLANE_WORDS); dst = reinterpret_cast<uint8_t*>(cs.plane + (size_t)r * CS_PLANE); bytes = (size_t)PLANE_WORDS * 4; break;
+		default: src = chunks + k * FRAME_BYTES; dst = cs.chunks + (size_t)r * CS_CHUNKS; bytes = FRAME_BYTES; break;
+	}
+	// this workgroup's slice: whole 16-byte units, the last slice takes the rest
+	const size_t per = (bytes / CARRY_PARTS) & ~(size_t)15, lo = per * part, hi = part == CARRY_PARTS - 1 ? bytes : lo + per;
+	carry_copy(dst + lo, src + lo, hi - lo);
+	if (arr == 0 && part == 0 && threadIdx.x == 0) { cs.flood[r] = flood_flag[k]; cs.masks[r] = masks[k]; }
 }

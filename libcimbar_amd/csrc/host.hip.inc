@@ -1,6 +1,18 @@
 // host.hip.inc -- part of cimbar_hip.hip (one translation unit; included at file scope after the kernels).
 // host side: context, tables, launch structure, C ABI
 // ================================================================================================ host side / C ABI
+// what the stream calls of the group decode keep between calls (combine.hip.inc, "the stream calls"): the carry store, its device-side
+// counters and the event that orders one stream call behind the one before. Nothing of it exists until the first stream call.
+struct CombineStream {
+	DevBuf<uint8_t> symbols, colors, chunks; DevBuf<uint32_t> plane, flood, masks; DevBuf<int8_t> drift;
+	DevBuf<int> words;                        // [0] occupied slots, [1] members of the open group of the call in flight (k_group_walk_stream -> k_group_carry)
+	DevBuf<int> gsizes;                       // staging for host-memory gsizes, n + 1 ints, grown on demand
+	Event ev_last;                            // behind the last stream call's work: the next one, on whatever stream, starts after it
+	bool used = false;
+	int min_agree = 0, max_group = 0;         // fixed by the first stream call after create / reset (0: not yet)
+	CarryStore store() const { return CarryStore{symbols, colors, plane, drift, flood, chunks, masks, words}; }
+};
+
 struct cimbar_hip_ctx {
 	int mode_tag = MODE_VAL;                  // FIRST member: api.hip.inc reads it through the opaque pointer to pick the namespace
 	int device = 0;
@@ -22,6 +34,7 @@ struct cimbar_hip_ctx {
 	DevBuf<uint32_t> d_gagree, d_gdisp; DevBuf<int> d_groups, d_gmem, d_gcount, d_groups_in;
 	DevBuf<int> d_ngroups;                      // 1 int
 	DevBuf<uint8_t> d_gchunks; DevBuf<uint32_t> d_gmasks;   // staging for host-memory group outputs
+	std::unique_ptr<CombineStream> cstream;     // cimbar_hip_decode_batch_combined_stream / _scan_extract_decode_batch_combined_stream_fmt
 	int wave_adapt = 1;               // CIMBAR_HIP_FLOOD_WAVE_ADAPT=0: run k_flood_wave in front of every exact replay, whatever it achieved before
 	bool wave_ran = false;            // k_flood_wave ran in the batch h_flagged describes
 	int wave_skip_left = 0;           // batches that still go straight to the exact replay (see enqueue)
@@ -816,6 +829,8 @@ struct CombineArgs {
 	const int* groups_in;     // host memory, n ints, or nullptr: the device groups the captures
 	int min_agree, max_group; // resolved (750 / 4 for <= 0)
 	int* groups_out; uint8_t* gchunks; uint32_t* gmasks; int* n_groups;
+	// the stream calls: groups may span calls (n + 1 group slots, gsizes may be nullptr); groups_in is nullptr
+	bool stream = false; int flush = 0; int* gsizes = nullptr;
 };
 
 // the argument checks of the combined entry points, before anything is enqueued
@@ -825,6 +840,17 @@ int check_combine(cimbar_hip_ctx* ctx, const char* who, int n, CombineArgs& cb)
 	if (cb.max_group > GMAX) { ctx->err = std::string(who) + ": max_group above 8"; return CIMBAR_HIP_EINVAL; }
 	if (cb.max_group <= 0) cb.max_group = GROUP_MAX_DEFAULT;
 	if (cb.min_agree <= 0) cb.min_agree = GROUP_AGREE_DEFAULT;
+	if (cb.stream) {
+		if (n == 0 && !cb.flush) { ctx->err = std::string(who) + ": n == 0 without a flush"; return CIMBAR_HIP_EINVAL; }
+		if (!ctx->cstream) ctx->cstream.reset(new (std::nothrow) CombineStream);
+		if (!ctx->cstream) { ctx->err = std::string(who) + ": out of memory"; return CIMBAR_HIP_EINVAL; }
+		CombineStream& s = *ctx->cstream;
+		if (s.max_group != 0 && (s.max_group != cb.max_group || s.min_agree != cb.min_agree)) {
+			ctx->err = std::string(who) + ": min_agree_permille / max_group differ from the stream's (cimbar_hip_combine_stream_reset starts another)";
+			return CIMBAR_HIP_EINVAL;
+		}
+		s.max_group = cb.max_group; s.min_agree = cb.min_agree;
+	}
 	if (cb.groups_in) {
 		// -1 or an id; ids start at 0 and rise by one; each id's captures contiguous and at most max_group
 		int next = 0, cur = -1, cnt = 0;
@@ -893,6 +919,93 @@ int enqueue_combine(cimbar_hip_ctx* ctx, hipStream_t st, int n, const uint8_t* d
 	return 0;
 }
 
+// the stream calls' buffers: the carry store (fixed size, allocated by the first stream call) and the n + 1 group slots
+int ensure_stream_capacity(cimbar_hip_ctx* ctx, int n)
+{
+	if (int r = ensure_group_capacity(ctx, n + 1)) return r;
+	CombineStream& s = *ctx->cstream;
+	HIPCHK(s.ev_last.create());
+	HIPCHK(s.symbols.ensure(CARRY_SLOTS * CS_CELLS));
+	HIPCHK(s.colors.ensure(CARRY_SLOTS * CS_CELLS));
+	HIPCHK(s.drift.ensure(CARRY_SLOTS * CS_DRIFT));
+	HIPCHK(s.plane.ensure(CARRY_SLOTS * CS_PLANE));
+	HIPCHK(s.chunks.ensure(CARRY_SLOTS * CS_CHUNKS));
+	HIPCHK(s.flood.ensure(CARRY_SLOTS));
+	HIPCHK(s.masks.ensure(CARRY_SLOTS));
+	if (!s.words) { HIPCHK(s.words.ensure(2)); HIPCHK(hipMemset(s.words, 0, sizeof(int) * 2)); }
+	HIPCHK(s.gsizes.reserve((size_t)n + 1));
+	return 0;
+}
+
+// The stream calls' G1-G5 behind a batch's per-capture decode (none for n == 0), on the same stream and behind the stream call before: the
+// virtual batch is the carry store's members followed by the n captures. Group outputs have n + 1 slots.
+int enqueue_combine_stream(cimbar_hip_ctx* ctx, hipStream_t st, int n, const uint8_t* d_chunks, const uint32_t* d_masks, const int* d_status, int stride,
+                           const CombineArgs& cb, int out_mem)
+{
+	if (int r = ensure_stream_capacity(ctx, n)) return r;
+	CombineStream& s = *ctx->cstream;
+	cimbar_hip_ctx::ScratchSet& cur = ctx->cur();
+	const CarryStore cs = s.store();
+	const int slots = n + 1;
+	uint8_t* d_gchunks = out_mem == CIMBAR_HIP_MEM_DEVICE ? cb.gchunks : ctx->d_gchunks;
+	uint32_t* d_gmasks = out_mem == CIMBAR_HIP_MEM_DEVICE ? cb.gmasks : ctx->d_gmasks;
+	int* d_gsizes = (out_mem == CIMBAR_HIP_MEM_DEVICE && cb.gsizes) ? cb.gsizes : s.gsizes;
+	if (s.used) HIPCHK(hipStreamWaitEvent(st, s.ev_last, 0));
+	s.used = true;
+	HIPCHK(hipMemsetAsync(ctx->d_gcount, 0, sizeof(int) * (size_t)slots, st));
+	HIPCHK(hipMemsetAsync(ctx->d_gdisp, 0, sizeof(uint32_t) * (size_t)slots, st));
+	if (n > 0)
+		hipLaunchKernelGGL(k_group_agree_stream, dim3(n), dim3(256), 0, st, cur.d_symbols, cur.d_colors, n, cs, ctx->d_gagree);
+	hipLaunchKernelGGL(k_group_walk_stream, dim3(1), dim3(64), 0, st, ctx->d_gagree, n, d_status, stride, cb.min_agree, cb.max_group, cb.flush ? 1 : 0, cs,
+	                   ctx->d_groups, ctx->d_gmem, ctx->d_gcount, ctx->d_ngroups, s.words + 1);
+	hipLaunchKernelGGL(k_group_cells_stream, dim3(GC_BLOCKS, slots), dim3(256), 0, st, cur.d_plane, ctx->tb, cur.d_symbols, cur.d_colors, cur.d_drift,
+	                   cur.d_flood, ctx->d_gmem, ctx->d_gcount, ctx->d_ngroups, ctx->d_gsym, ctx->d_gcol, ctx->d_gmargin, ctx->d_gdisp, cs);
+	if constexpr (LEGACY) {
+		hipLaunchKernelGGL((k_rs<CELL_BITS, false, true>), dim3((slots * ALL_BLOCKS + 3) / 4), dim3(256), 0, st, ctx->d_gsym, ctx->tb, 0, slots, 0, d_gchunks,
+		                   ctx->d_grs_ok, 0, (const uint8_t*)ctx->d_gcol, (const int*)ctx->d_ngroups, (const uint32_t*)ctx->d_gdisp);
+	} else {
+		hipLaunchKernelGGL((k_rs<4, false, true>), dim3((slots * SYM_BLOCKS + 3) / 4), dim3(256), 0, st, ctx->d_gsym, ctx->tb, 0, slots, 0, d_gchunks,
+		                   ctx->d_grs_ok, 0, (const uint8_t*)nullptr, (const int*)ctx->d_ngroups, (const uint32_t*)ctx->d_gdisp);
+		hipLaunchKernelGGL((k_rs<2, false, true>), dim3((slots * COL_BLOCKS + 3) / 4), dim3(256), 0, st, ctx->d_gcol, ctx->tb, 0, slots, SYM_CHUNKS, d_gchunks,
+		                   ctx->d_grs_ok, SYM_BLOCKS, (const uint8_t*)nullptr, (const int*)ctx->d_ngroups, (const uint32_t*)ctx->d_gdisp);
+	}
+	hipLaunchKernelGGL(k_group_end_stream, dim3(slots), dim3(256), 0, st, ctx->d_gsym, ctx->d_gmargin, ctx->tb, ctx->d_gmem, ctx->d_gcount, ctx->d_ngroups,
+	                   ctx->d_grs_ok, d_chunks, d_masks, ctx->d_gdisp, d_gchunks, d_gmasks, (!LEGACY && ctx->er_sym > 0) ? 1 : 0, erasure_max(ctx), cs, d_gsizes);
+	hipLaunchKernelGGL(k_group_carry, dim3(CARRY_ARRAYS * CARRY_PARTS, CARRY_SLOTS), dim3(256), 0, st, cur.d_plane, cur.d_symbols, cur.d_colors, cur.d_drift,
+	                   cur.d_flood, d_chunks, d_masks, ctx->d_gmem, ctx->d_ngroups, s.words + 1, ctx->d_groups, cs);
+	HIPCHK(hipGetLastError());
+	return 0;
+}
+
+// the end of a stream call: finish_batch with n + 1 group slots and gsizes, and the event the next stream call waits for
+int64_t finish_stream(cimbar_hip_ctx* ctx, hipStream_t st, int n, uint8_t* chunks, uint32_t* masks, const uint8_t* d_chunks, const uint32_t* d_masks,
+                      int out_mem, const CombineArgs& cb)
+{
+	CombineStream& s = *ctx->cstream;
+	const hipMemcpyKind kind = out_mem == CIMBAR_HIP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+	const size_t slots = (size_t)n + 1;
+	int ng = 0;
+	if (cb.groups_out && n > 0) HIPCHK(hipMemcpyAsync(cb.groups_out, ctx->d_groups, sizeof(int) * (size_t)n, kind, st));
+	if (out_mem == CIMBAR_HIP_MEM_DEVICE) {
+		if (cb.n_groups) HIPCHK(hipMemcpyAsync(cb.n_groups, ctx->d_ngroups, sizeof(int), kind, st));
+	} else {
+		if (n > 0) {
+			HIPCHK(hipMemcpyAsync(chunks, d_chunks, (size_t)n * FRAME_BYTES, hipMemcpyDeviceToHost, st));
+			HIPCHK(hipMemcpyAsync(masks, d_masks, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
+		}
+		HIPCHK(hipMemcpyAsync(cb.gchunks, ctx->d_gchunks, slots * FRAME_BYTES, hipMemcpyDeviceToHost, st));
+		HIPCHK(hipMemcpyAsync(cb.gmasks, ctx->d_gmasks, sizeof(uint32_t) * slots, hipMemcpyDeviceToHost, st));
+		if (cb.gsizes) HIPCHK(hipMemcpyAsync(cb.gsizes, s.gsizes, sizeof(int) * slots, hipMemcpyDeviceToHost, st));
+		HIPCHK(hipMemcpyAsync(&ng, ctx->d_ngroups, sizeof(int), hipMemcpyDeviceToHost, st));
+	}
+	HIPCHK(hipEventRecord(s.ev_last, st));
+	ctx->grp_valid = true;
+	if (out_mem == CIMBAR_HIP_MEM_DEVICE) return 0;
+	HIPCHK(hipStreamSynchronize(st));
+	if (cb.n_groups) *cb.n_groups = ng;
+	return ng;
+}
+
 // the end of a batch call: device outputs are enqueued (group ids and count included) and 0 returned; host outputs are copied back, then
 // the call synchronises and returns the good bytes over the batch, or with `cb` the group count
 int64_t finish_batch(cimbar_hip_ctx* ctx, hipStream_t st, int n, uint8_t* chunks, uint32_t* masks, const uint8_t* d_chunks, const uint32_t* d_masks,
@@ -930,8 +1043,10 @@ int64_t finish_batch(cimbar_hip_ctx* ctx, hipStream_t st, int n, uint8_t* chunks
 int64_t decode_batch_impl(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rgb_mem, int should_preprocess, int color_correction, uint8_t* chunks,
                           uint32_t* masks, int out_mem, void* hip_stream, CombineArgs* cb)
 {
-	const char* who = cb ? "decode_batch_combined" : "decode_batch";
-	if (!rgb || !chunks || !masks || n <= 0) { ctx->err = std::string(who) + ": null buffer or n <= 0"; return CIMBAR_HIP_EINVAL; }
+	const bool strm = cb && cb->stream;
+	const char* who = strm ? "decode_batch_combined_stream" : cb ? "decode_batch_combined" : "decode_batch";
+	// (a stream call may bring no capture at all: n == 0 with a flush closes the open group)
+	if (strm ? (n < 0 || (n > 0 && (!rgb || !chunks || !masks))) : (!rgb || !chunks || !masks || n <= 0)) { ctx->err = std::string(who) + ": null buffer or n <= 0"; return CIMBAR_HIP_EINVAL; }
 	if ((rgb_mem != CIMBAR_HIP_MEM_HOST && rgb_mem != CIMBAR_HIP_MEM_DEVICE) || (out_mem != CIMBAR_HIP_MEM_HOST && out_mem != CIMBAR_HIP_MEM_DEVICE)) {
 		ctx->err = std::string(who) + ": rgb_mem / out_mem must be CIMBAR_HIP_MEM_HOST or CIMBAR_HIP_MEM_DEVICE";
 		return CIMBAR_HIP_EINVAL;
@@ -943,6 +1058,10 @@ int64_t decode_batch_impl(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rg
 	const bool any_device = rgb_mem == CIMBAR_HIP_MEM_DEVICE || out_mem == CIMBAR_HIP_MEM_DEVICE;
 	hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (any_device ? (hipStream_t)nullptr : ctx->stream);
 	if (int r = drain_pipeline_into(ctx, st)) return r;
+	if (strm && n == 0) {
+		if (int r = enqueue_combine_stream(ctx, st, 0, nullptr, nullptr, nullptr, 0, *cb, out_mem)) return r;
+		return finish_stream(ctx, st, 0, chunks, masks, nullptr, nullptr, out_mem, *cb);
+	}
 	if (int r = ensure_capacity(ctx, n)) return r;
 
 	const uint8_t* d_rgb = nullptr;
@@ -951,6 +1070,10 @@ int64_t decode_batch_impl(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rg
 	uint32_t* d_masks = out_mem == CIMBAR_HIP_MEM_DEVICE ? masks : ctx->d_masks;
 
 	if (int r = enqueue(ctx, st, d_rgb, n, should_preprocess, color_correction, d_chunks, d_masks)) return r;
+	if (strm) {
+		if (int r = enqueue_combine_stream(ctx, st, n, d_chunks, d_masks, nullptr, 0, *cb, out_mem)) return r;
+		return finish_stream(ctx, st, n, chunks, masks, d_chunks, d_masks, out_mem, *cb);
+	}
 	if (cb)
 		if (int r = enqueue_combine(ctx, st, n, d_chunks, d_masks, nullptr, 0, *cb, out_mem)) return r;
 	return finish_batch(ctx, st, n, chunks, masks, d_chunks, d_masks, out_mem, cb);
@@ -972,6 +1095,28 @@ int64_t cimbar_hip_decode_batch_combined(cimbar_hip_ctx* ctx, const uint8_t* rgb
 	if (!ctx) return CIMBAR_HIP_EINVAL;
 	CombineArgs cb{groups_in, min_agree_permille, max_group, groups_out, gchunks, gmasks, n_groups};
 	return decode_batch_impl(ctx, rgb, n, rgb_mem, should_preprocess, color_correction, chunks, masks, out_mem, hip_stream, &cb);
+}
+
+int64_t cimbar_hip_decode_batch_combined_stream(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rgb_mem, int should_preprocess, int color_correction,
+                                                int min_agree_permille, int max_group, int flush, uint8_t* chunks, uint32_t* masks, int* groups_out,
+                                                uint8_t* gchunks, uint32_t* gmasks, int* gsizes, int* n_groups, int out_mem, void* hip_stream)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	CombineArgs cb{nullptr, min_agree_permille, max_group, groups_out, gchunks, gmasks, n_groups, true, flush, gsizes};
+	return decode_batch_impl(ctx, rgb, n, rgb_mem, should_preprocess, color_correction, chunks, masks, out_mem, hip_stream, &cb);
+}
+
+// drop the open group and the fixed parameters: the next stream call starts a stream of its own
+int cimbar_hip_combine_stream_reset(cimbar_hip_ctx* ctx)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	if (!ctx->cstream) return 0;
+	CombineStream& s = *ctx->cstream;
+	HIPCHK(hipSetDevice(ctx->device));
+	if (s.used) HIPCHK(hipEventSynchronize(s.ev_last));
+	if (s.words) HIPCHK(hipMemset(s.words, 0, sizeof(int) * 2));
+	s.min_agree = s.max_group = 0;
+	return 0;
 }
 
 int cimbar_hip_decode_batch_pipelined(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int should_preprocess, int color_correction,
@@ -1476,7 +1621,17 @@ int64_t scan_extract_decode_impl(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsign
                                  int preprocess, int color_correction, uint8_t* chunks, uint32_t* masks, int* status, int out_mem,
                                  void* hip_stream, CombineArgs* cb)
 {
-	const char* who = cb ? "scan_extract_decode_batch_combined" : "scan_extract_decode_batch";
+	const bool strm = cb && cb->stream;
+	const char* who = strm ? "scan_extract_decode_batch_combined_stream" : cb ? "scan_extract_decode_batch_combined" : "scan_extract_decode_batch";
+	if (strm && n == 0) {   // (no capture: a flush closes the open group; no image argument is read)
+		if (out_mem != CIMBAR_HIP_MEM_HOST && out_mem != CIMBAR_HIP_MEM_DEVICE) { ctx->err = std::string(who) + ": out_mem must be CIMBAR_HIP_MEM_HOST or CIMBAR_HIP_MEM_DEVICE"; return CIMBAR_HIP_EINVAL; }
+		if (int r = check_combine(ctx, who, n, *cb)) return r;
+		HIPCHK(hipSetDevice(ctx->device));
+		hipStream_t st0 = hip_stream ? (hipStream_t)hip_stream : (out_mem == CIMBAR_HIP_MEM_DEVICE ? (hipStream_t)nullptr : ctx->stream);
+		if (int r = drain_pipeline_into(ctx, st0)) return r;
+		if (int r = enqueue_combine_stream(ctx, st0, 0, nullptr, nullptr, nullptr, 0, *cb, out_mem)) return r;
+		return finish_stream(ctx, st0, 0, chunks, masks, nullptr, nullptr, out_mem, *cb);
+	}
 	if (!rgb || !chunks || !masks || n <= 0 || width < 8 || height < 8) { ctx->err = std::string(who) + ": null buffer, n <= 0 or a capture smaller than 8x8"; return CIMBAR_HIP_EINVAL; }
 	if ((rgb_mem != CIMBAR_HIP_MEM_HOST && rgb_mem != CIMBAR_HIP_MEM_DEVICE) || (out_mem != CIMBAR_HIP_MEM_HOST && out_mem != CIMBAR_HIP_MEM_DEVICE)) {
 		ctx->err = std::string(who) + ": rgb_mem / out_mem must be CIMBAR_HIP_MEM_HOST or CIMBAR_HIP_MEM_DEVICE";
@@ -1510,10 +1665,12 @@ int64_t scan_extract_decode_impl(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsign
 	hipLaunchKernelGGL(k_mask_failed, dim3(n), dim3(256), 0, st, &ctx->d_scan_res[0].status, stride, n, d_masks, d_chunks);
 	HIPCHK(hipGetLastError());
 	// ... nor any group (it is in none)
-	if (cb)
+	if (strm) { if (int r = enqueue_combine_stream(ctx, st, n, d_chunks, d_masks, &ctx->d_scan_res[0].status, stride, *cb, out_mem)) return r; }
+	else if (cb)
 		if (int r = enqueue_combine(ctx, st, n, d_chunks, d_masks, &ctx->d_scan_res[0].status, stride, *cb, out_mem)) return r;
 	const hipMemcpyKind kind = out_mem == CIMBAR_HIP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
 	if (status) HIPCHK(hipMemcpy2DAsync(status, sizeof(int), &ctx->d_scan_res[0].status, sizeof(ScanResult), sizeof(int), (size_t)n, kind, st));
+	if (strm) return finish_stream(ctx, st, n, chunks, masks, d_chunks, d_masks, out_mem, *cb);
 	return finish_batch(ctx, st, n, chunks, masks, d_chunks, d_masks, out_mem, cb);
 }
 
@@ -1534,6 +1691,17 @@ int64_t cimbar_hip_scan_extract_decode_batch_combined_fmt(cimbar_hip_ctx* ctx, c
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;
 	CombineArgs cb{groups_in, min_agree_permille, max_group, groups_out, gchunks, gmasks, n_groups};
+	return scan_extract_decode_impl(ctx, rgb, width, height, format, n, rgb_mem, preprocess, color_correction, chunks, masks, status, out_mem, hip_stream, &cb);
+}
+
+int64_t cimbar_hip_scan_extract_decode_batch_combined_stream_fmt(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsigned width, unsigned height, int format,
+                                                                 int n, int rgb_mem, int preprocess, int color_correction, int min_agree_permille,
+                                                                 int max_group, int flush, uint8_t* chunks, uint32_t* masks, int* status,
+                                                                 int* groups_out, uint8_t* gchunks, uint32_t* gmasks, int* gsizes, int* n_groups,
+                                                                 int out_mem, void* hip_stream)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	CombineArgs cb{nullptr, min_agree_permille, max_group, groups_out, gchunks, gmasks, n_groups, true, flush, gsizes};
 	return scan_extract_decode_impl(ctx, rgb, width, height, format, n, rgb_mem, preprocess, color_correction, chunks, masks, status, out_mem, hip_stream, &cb);
 }
 

@@ -19,6 +19,7 @@ LIB_PATH = os.path.join(_HERE, "libcimbar_hip.so")
 MEM_HOST, MEM_DEVICE = 0, 1
 TAP_BITPLANE, TAP_SYMBOLS, TAP_COLORS, TAP_DRIFT, TAP_RS_OK, TAP_FLOOD, TAP_CCM, TAP_FLOOD_PATH, TAP_FLOOD_INFO, TAP_FLOOD_VERIFY = range(10)
 TAP_GROUP_CELLS, TAP_GROUP_MARGIN, TAP_GROUPS = 10, 11, 12
+GROUP_OPEN = -2   # CIMBAR_HIP_GROUP_OPEN: the capture's group is still open at the end of a stream call
 TAP_COLOUR_MARGIN = 13
 TAP_SCAN_PATH = 14
 # CIMBAR_HIP_COLOUR_MARGIN_SUGGESTED (include/cimbar_hip.h): the colour erasure threshold chosen on rendered frames (DESIGN_WIDENING.md)
@@ -42,6 +43,7 @@ EXPORTS = (
     "cimbar_hip_rs_decode_erasures", "cimbar_hip_set_erasure_decode", "cimbar_hip_get_erasure_decode",
     "cimbar_hip_set_colour_erasure_decode", "cimbar_hip_get_colour_erasure_decode",
     "cimbar_hip_decode_batch_combined", "cimbar_hip_scan_extract_decode_batch_combined_fmt",
+    "cimbar_hip_decode_batch_combined_stream", "cimbar_hip_scan_extract_decode_batch_combined_stream_fmt", "cimbar_hip_combine_stream_reset",
     "cimbar_hip_auto_create", "cimbar_hip_auto_destroy", "cimbar_hip_auto_bufsize", "cimbar_hip_auto_last_error", "cimbar_hip_auto_reset_ccm",
     "cimbar_hip_auto_get_ccm", "cimbar_hip_auto_set_ccm", "cimbar_hip_auto_scan_extract_decode_batch_fmt",
     "cimbar_hip_deliver_chunks", "cimbar_hip_delivery_reset", "cimbar_hip_delivery_stats",
@@ -156,6 +158,13 @@ def load_library(path=None):
     lib.cimbar_hip_scan_extract_decode_batch_combined_fmt.argtypes = [vp, vp, u32, u32, i32, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp,
                                                                       vp, i32, vp]
     lib.cimbar_hip_scan_extract_decode_batch_combined_fmt.restype = i64
+    lib.cimbar_hip_decode_batch_combined_stream.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp]
+    lib.cimbar_hip_decode_batch_combined_stream.restype = i64
+    lib.cimbar_hip_scan_extract_decode_batch_combined_stream_fmt.argtypes = [vp, vp, u32, u32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp,
+                                                                             vp, vp, vp, i32, vp]
+    lib.cimbar_hip_scan_extract_decode_batch_combined_stream_fmt.restype = i64
+    lib.cimbar_hip_combine_stream_reset.argtypes = [vp]
+    lib.cimbar_hip_combine_stream_reset.restype = i32
     lib.cimbar_hip_auto_create.argtypes = [i32, vp, i32, ctypes.POINTER(vp)]
     lib.cimbar_hip_auto_create.restype = i32
     lib.cimbar_hip_auto_destroy.argtypes = [vp]
@@ -482,6 +491,65 @@ class HipDecoder:
             int(max_group), chunks.ctypes.data, masks.ctypes.data, status.ctypes.data, gout.ctypes.data, gchunks.ctypes.data, gmasks.ctypes.data,
             ctypes.byref(ng), MEM_HOST, None), "cimbar_hip_scan_extract_decode_batch_combined_fmt")
         return int(rc), chunks, masks, status, gout, gchunks, gmasks
+
+    def _stream_outputs(self, n):
+        geo = self.geo
+        return (np.zeros((n, geo.CHUNKS_PER_FRAME, geo.CHUNK), dtype=np.uint8), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.int32),
+                np.zeros((n + 1, geo.CHUNKS_PER_FRAME, geo.CHUNK), dtype=np.uint8), np.zeros(n + 1, dtype=np.uint32), np.zeros(n + 1, dtype=np.int32))
+
+    def decode_batch_combined_stream(self, frames, flush=False, min_agree_permille=0, max_group=0, should_preprocess=False, color_correction=2):
+        """Multi-capture decoding across calls (cimbar_hip_decode_batch_combined_stream): the group still open at the end of a call is carried
+        into the next stream call; flush closes it. frames as for decode_batch, or None / empty with flush. Returns (n_closed, chunks,
+        masks, groups, gchunks, gmasks, gsizes): groups has the call-local id of a capture's group if it closed in this call, GROUP_OPEN if
+        it stays open; the group outputs have n + 1 slots (zero from n_closed on)."""
+        if frames is None:
+            frames = np.zeros((0,) + tuple(self.geo.FRAME_SHAPE), dtype=np.uint8)
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        n = frames.shape[0]
+        if frames.shape[1:] != self.geo.FRAME_SHAPE:
+            raise CimbarHipError(f"decode_batch_combined_stream: frames must be (n,{self.geo.IMG_H},{self.geo.IMG_W},3) uint8")
+        chunks, masks, gout, gchunks, gmasks, gsizes = self._stream_outputs(n)
+        ng = ctypes.c_int(0)
+        rc = self._check(self._lib.cimbar_hip_decode_batch_combined_stream(
+            self._ctx, frames.ctypes.data if n else None, n, MEM_HOST, int(bool(should_preprocess)), int(color_correction), int(min_agree_permille),
+            int(max_group), int(bool(flush)), chunks.ctypes.data if n else None, masks.ctypes.data if n else None, gout.ctypes.data if n else None,
+            gchunks.ctypes.data, gmasks.ctypes.data, gsizes.ctypes.data, ctypes.byref(ng), MEM_HOST, None), "cimbar_hip_decode_batch_combined_stream")
+        assert rc == ng.value
+        return int(rc), chunks, masks, gout, gchunks, gmasks, gsizes
+
+    def decode_batch_combined_stream_device(self, frames_ptr, n, chunks_ptr, masks_ptr, groups_out_ptr, gchunks_ptr, gmasks_ptr, gsizes_ptr, n_groups_ptr,
+                                            flush=False, min_agree_permille=0, max_group=0, should_preprocess=False, color_correction=2, stream=None):
+        """Device pointers in and out (gchunks / gmasks / gsizes: n + 1 slots; groups_out_ptr / gsizes_ptr / n_groups_ptr may be 0); enqueues on
+        `stream` (None / 0 = the null stream) and returns at once -- nothing about the open group is read back."""
+        vp = ctypes.c_void_p
+        self._check(self._lib.cimbar_hip_decode_batch_combined_stream(
+            self._ctx, vp(frames_ptr or None), int(n), MEM_DEVICE, int(bool(should_preprocess)), int(color_correction), int(min_agree_permille),
+            int(max_group), int(bool(flush)), vp(chunks_ptr or None), vp(masks_ptr or None), vp(groups_out_ptr or None), vp(gchunks_ptr), vp(gmasks_ptr),
+            vp(gsizes_ptr or None), vp(n_groups_ptr or None), MEM_DEVICE, vp(stream) if stream else None), "cimbar_hip_decode_batch_combined_stream(device)")
+
+    def scan_extract_decode_batch_combined_stream(self, captures, flush=False, min_agree_permille=0, max_group=0, preprocess=-1, color_correction=2,
+                                                  size=None, fmt=3):
+        """The capture path across calls (cimbar_hip_scan_extract_decode_batch_combined_stream_fmt); captures = None with flush closes the open
+        group. Returns (n_closed, chunks, masks, status, groups, gchunks, gmasks, gsizes); an unusable capture is in no group and closes
+        the group in front of it."""
+        if captures is None:
+            n, w, h, ptr = 0, 0, 0, None
+        else:
+            captures, n, w, h, fmt = self._captures(captures, size, fmt)
+            ptr = captures.ctypes.data
+        chunks, masks, gout, gchunks, gmasks, gsizes = self._stream_outputs(n)
+        status = np.zeros(n, dtype=np.int32)
+        ng = ctypes.c_int(0)
+        rc = self._check(self._lib.cimbar_hip_scan_extract_decode_batch_combined_stream_fmt(
+            self._ctx, ptr, w, h, int(fmt), n, MEM_HOST, int(preprocess), int(color_correction), int(min_agree_permille), int(max_group),
+            int(bool(flush)), chunks.ctypes.data if n else None, masks.ctypes.data if n else None, status.ctypes.data if n else None,
+            gout.ctypes.data if n else None, gchunks.ctypes.data, gmasks.ctypes.data, gsizes.ctypes.data, ctypes.byref(ng), MEM_HOST, None),
+            "cimbar_hip_scan_extract_decode_batch_combined_stream_fmt")
+        return int(rc), chunks, masks, status, gout, gchunks, gmasks, gsizes
+
+    def combine_stream_reset(self):
+        """drop the open group and the stream's fixed min_agree_permille / max_group"""
+        self._check(self._lib.cimbar_hip_combine_stream_reset(self._ctx), "cimbar_hip_combine_stream_reset")
 
     def decode_plain_batch(self, frames, should_preprocess=False, color_correction=2):
         """Decoder::decode (the --no-fountain path) for frames (n,1024,1024,3) uint8 numpy. Returns (bytes_written,
