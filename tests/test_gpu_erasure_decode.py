@@ -9,6 +9,7 @@ device encoder renders from known payloads.
   the mask; prints how often a chunk was added.
 - Pipelined: the glare frames through decode_batch_pipelined / pipeline_wait give what decode_batch gives.
 - Settings: get reflects set; modes 4 / 8 refuse it; decode_plain_batch refuses to run while it is on.
+Which chunks the retry must deliver is pinned in tests/test_gpu_symbol_erasure_model.py (the model: tests/symbol_erasure_model.py).
 """
 import numpy as np
 import pytest
