@@ -261,6 +261,28 @@ int64_t cimbar_hip_scan_extract_decode_batch_combined_fmt(cimbar_hip_ctx* ctx, c
                                                           int* groups_out, uint8_t* gchunks, uint32_t* gmasks, int* n_groups, int out_mem,
                                                           void* hip_stream);
 
+/* Colour vote in the group decode (off after cimbar_hip_create). The group decode above settles a disputed colour by counting heads, and in a
+ * group of two every colour disagreement is a tie. With the vote on, cimbar_hip_decode_batch_combined and
+ * cimbar_hip_scan_extract_decode_batch_combined_fmt weigh each member's colour by the classifier's confidence in it instead. For one cell whose
+ * members' colours differ (a "colour dispute"):
+ *   marg_c   = member c's classifier margin, exactly what CIMBAR_HIP_TAP_COLOUR_MARGIN defines (the mean and the matrix its colour pass
+ *              classified the cell from); w_c = marg_c + 1, so that a zero-margin member still decides between colours nobody else voted for
+ *   score(k) = the sum of w_c over the members whose colour is k; the group colour is the k with the largest score, ties to the lowest k
+ *   gm       = the largest score minus the second-largest (a colour nobody voted for scores 0): the group colour margin
+ * A cell whose members agree on the colour is settled as before and has no margin. The group's symbols, the symbol margin, the per-capture
+ * outputs and the colour-correction state do not depend on the setting; only the colour of colour-disputed cells can change, and with it the
+ * group's colour chunks.
+ * Group colour retry: with cimbar_hip_set_colour_erasure_decode(colour_margin, max_erasures) on as well, the colour chunks gmask still lacks
+ * after the group fill are retried on the voted cells: a colour-stream byte's score is max over its four cells of colour_margin - gm (a cell
+ * without a colour dispute contributes nothing), flagged when > 0, the max_erasures highest scores become erasures (ties to the lower byte),
+ * and retry, acceptance and the mask update are the per-capture colour retry's. Chunks already in gmask are never rewritten. There is no
+ * second threshold; with the vote on and the colour erasure setting off only the vote changes.
+ * Modes 4 and 8 refuse on != 0 (EINVAL): the coupled stream has no colour chunks of its own. Not covered: the stream calls below
+ * (..._combined_stream) behave with the setting on exactly as with it off -- the carried members hold no means and no matrices to recompute
+ * margins from. Takes effect for combined batches issued after the call. get: writes 1 or 0 to *on and returns 0. */
+int cimbar_hip_set_group_colour_vote(cimbar_hip_ctx* ctx, int on);
+int cimbar_hip_get_group_colour_vote(cimbar_hip_ctx* ctx, int* on);
+
 /* Multi-capture decoding across calls. A live receiver hands over one capture per call, or a few; these calls keep the group that is still
  * open at the end of a call on the device (at most max_group - 1 members, copies the context owns, about 0.2 MB each) and go on with it in
  * the next stream call. Take a sequence of stream calls on one context whose last call has flush != 0: the groups they report, in order, are
@@ -593,9 +615,14 @@ enum {
 	                                     worked on; 0xFFFFFFFF for all cells of a frame it skipped (all colour chunks in the mask) */
 	/* the anchor search of the last extract / scan_extract_decode call (n = that call's captures; valid without any decoded batch; an entry point that
 	 * searches its captures in several pieces describes the last piece) */
-	CIMBAR_HIP_TAP_SCAN_PATH = 14     /* n int32               : 0 = the fast search kernels answered, 1 = one of their fixed lists overflowed and the
+	CIMBAR_HIP_TAP_SCAN_PATH = 14,    /* n int32               : 0 = the fast search kernels answered, 1 = one of their fixed lists overflowed and the
 	                                     serial search answered, 2 = gave up (more than 16 overflowing captures in the batch, or the serial search's
 	                                     own lists overflowed): the capture is reported as a failure */
+	/* the colour vote of the last plain combined batch (cimbar_hip_set_group_colour_vote; CIMBAR_HIP_EINVAL when that batch ran with the setting
+	 * off, was a stream call, or was no combined batch) */
+	CIMBAR_HIP_TAP_GROUP_COLOUR_MARGIN = 15, /* n_groups * cells u32: the group colour margin gm, 0xFFFFFFFF where the members' colours all agree */
+	CIMBAR_HIP_TAP_GROUP_COLOUR_WEIGHTS = 16 /* n * cells u32       : the weight each capture contributed to its group's vote; 0 for cells without a
+	                                            colour dispute and for captures in no group */
 };
 int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_bytes);
 

@@ -6,6 +6,8 @@
 //   G2 k_group_walk    one wavefront walks the captures left to right and numbers the runs ("groups"), or takes the caller's numbering; it
 //                      writes every group's members (capture indices, ascending, at most GMAX) and the group count to device memory
 //   G3 k_group_cells   per group and cell: the combined symbol, colour and margin (the rule below); unanimous cells cost one compare
+//   G3c k_group_colour (opt-in, cimbar_hip_set_group_colour_vote) the colour of colour-disputed cells by the members' classifier margins, and
+//                      behind G4 k_group_colour_retry, the erasure retry of the colour chunks still missing -- see "colour vote" below
 //   K3 k_rs            the same Reed-Solomon kernels as a capture's decode, over the groups' cells (LIVE: workgroups past the count return,
 //                      and so does every wavefront of a group whose members agree on every cell -- see k_group_end)
 //   G4 k_group_end     the aligned_stream bookkeeping of k_frame_mid + k_frame_end over the group's blocks, the members' chunks for what the
@@ -455,6 +457,206 @@ __global__ __launch_bounds__(256) void k_group_end(const uint8_t* __restrict__ g
                                                    uint32_t* __restrict__ gmasks, int e_on, int e_max)
 {
 	group_end_body<false>(gsym, gmargin, tb, gmem, gcount, ngroups, grs_ok, chunks, masks, gdisp, gchunks, gmasks, e_on, e_max, CarryStore{}, nullptr);
+}
+
+// ------------------------------------------------------------------------------------------------ colour vote and group colour retry
+// Opt-in (cimbar_hip_set_group_colour_vote, modes 68 / 67 / 66, the plain combined calls only). With the setting off neither kernel is launched.
+// G3c k_group_colour, behind G3 and in front of the groups' Reed-Solomon pass: one workgroup per group slot; a slot at or above the group count
+// and a group G3 did not flag (gdisp: no cell differs) return at once. For a cell whose members' colours differ (a "colour dispute"):
+//   w_c      = margin_c + 1, margin_c = color_fit<true> of member c from exactly what k_colors classified the cell from -- the K1 cell mean, or
+//              mean6x6 at the drifted position where the member took the flood pass -- under the member's matrix in force (ccm_used, active flag
+//              included): what CIMBAR_HIP_TAP_COLOUR_MARGIN defines. The + 1 lets a zero-margin member still decide between colours nobody
+//              else voted for.
+//   score(k) = sum of w_c over the members with col_c == k (u32: at most 8 * 390 151)
+//   colour   = argmax score, ties to the lowest colour index; gm = the best score minus the second-best (a colour nobody voted for scores 0)
+// gcol gets the colour, gcm the margin gm, gcw[member capture] the weight. A cell without a colour dispute keeps G3's colour, gcm = GCM_NONE
+// and weight 0. The symbol side (gsym, gmargin) is not touched. Nothing is written for an unflagged group: the taps fill those in.
+// Phase 1 compares the members' colour bytes four cells per dword, settles the agreeing cells (16-byte stores where all four agree) and queues
+// the disputed ones per wavefront; phase 2 gives each queued cell a lane. The scores live in NCOLORS registers; the member loop is not unrolled.
+constexpr uint32_t GCM_NONE = 0xFFFFFFFFu;
+constexpr int GV_WORDS = NCELLS / 4, GV_ROUNDS = (GV_WORDS + 255) / 256, GV_QCAP = GV_ROUNDS * 64 * 4;   // a wavefront's share of the cells at most
+static_assert(NCELLS <= 65536, "a queued cell index fits 16 bits");
+
+__global__ __launch_bounds__(256) void k_group_colour(const uint8_t* __restrict__ rgb, const uint32_t* __restrict__ cellmean, Tables tb,
+                                                      const uint8_t* __restrict__ colors, const int8_t* __restrict__ drift,
+                                                      const uint32_t* __restrict__ flood_flag, const float* __restrict__ ccm_used,
+                                                      const int* __restrict__ gmem, const int* __restrict__ gcount, const int* __restrict__ ngroups,
+                                                      const uint32_t* __restrict__ gdisp, uint8_t* __restrict__ gcol, uint32_t* __restrict__ gcm,
+                                                      uint32_t* __restrict__ gcw)
+{
+	if constexpr (LEGACY) return;                          // (one coupled stream: the host never launches it there)
+	const int g = blockIdx.x;
+	if (g >= *ngroups || gdisp[g] == 0) return;            // (uniform over the workgroup)
+	const int m = gcount[g] < GMAX ? gcount[g] : GMAX;
+	__shared__ int s_mem[GMAX];
+	__shared__ uint32_t s_flood[GMAX];
+	__shared__ float s_ccm[GMAX][10];
+	__shared__ uint16_t s_q[4][GV_QCAP];
+	if (threadIdx.x < GMAX) {
+		const int f = (int)threadIdx.x < m ? gmem[(size_t)g * GMAX + threadIdx.x] : 0;
+		s_mem[threadIdx.x] = f;
+		s_flood[threadIdx.x] = (int)threadIdx.x < m ? flood_flag[f] : 0u;
+	}
+	if (threadIdx.x < GMAX * 10) {
+		const int c = threadIdx.x / 10, k = threadIdx.x % 10;
+		s_ccm[c][k] = c < m ? ccm_used[(size_t)gmem[(size_t)g * GMAX + c] * 10 + k] : 0.0f;
+	}
+	__syncthreads();
+	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+	uint8_t* oc = gcol + (size_t)g * NCELLS;
+	uint32_t* om = gcm + (size_t)g * NCELLS;
+	constexpr uint32_t CM = 0x01010101u * (uint32_t)(NCOLORS - 1);
+	// phase 1
+	int qn = 0;
+	for (int r = 0; r < GV_ROUNDS; ++r) {
+		const int w = r * 256 + (int)threadIdx.x;
+		uint32_t x = 0;
+		if (w < GV_WORDS) {
+			const uint32_t c0 = reinterpret_cast<const uint32_t*>(colors + (size_t)s_mem[0] * NCELLS)[w];
+			for (int c = 1; c < m; ++c) x |= (reinterpret_cast<const uint32_t*>(colors + (size_t)s_mem[c] * NCELLS)[w] ^ c0) & CM;
+			if (x == 0) {
+				reinterpret_cast<uint4*>(om)[w] = make_uint4(GCM_NONE, GCM_NONE, GCM_NONE, GCM_NONE);
+				for (int c = 0; c < m; ++c) reinterpret_cast<uint4*>(gcw + (size_t)s_mem[c] * NCELLS)[w] = make_uint4(0u, 0u, 0u, 0u);
+			} else {
+#pragma unroll
+				for (int b = 0; b < 4; ++b)
+					if (((x >> (8 * b)) & 0xFFu) == 0) {
+						om[4 * w + b] = GCM_NONE;
+						for (int c = 0; c < m; ++c) gcw[(size_t)s_mem[c] * NCELLS + 4 * w + b] = 0u;
+					}
+			}
+		}
+#pragma unroll
+		for (int b = 0; b < 4; ++b) {
+			const bool need = ((x >> (8 * b)) & 0xFFu) != 0;
+			const unsigned long long qb = __ballot(need);
+			if (need) s_q[wv][qn + (int)__popcll(qb & ((1ull << lane) - 1ull))] = (uint16_t)(4 * w + b);
+			qn += (int)__popcll(qb);
+		}
+	}
+	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+	__builtin_amdgcn_wave_barrier();
+	// phase 2: one colour-disputed cell per lane
+	for (int q = lane; q < qn; q += 64) {
+		const int i = s_q[wv][q];
+		const ushort2 xy = tb.cell_xy[i];
+		const uint32_t slot = tb.cell_grid[i];
+		uint32_t score[NCOLORS];
+#pragma unroll
+		for (int k = 0; k < NCOLORS; ++k) score[k] = 0;
+		for (int c = 0; c < m; ++c) {
+			const int f = s_mem[c];
+			uint32_t col[3];
+			if (s_flood[c] != 0) {
+				const int x = (int)xy.x + drift[((size_t)f * NCELLS + i) * 2], y = (int)xy.y + drift[((size_t)f * NCELLS + i) * 2 + 1];
+				mean6x6(rgb + (size_t)f * FRAME_RGB, x + 1, y + 1, col);
+			} else {
+				const uint32_t mv = cellmean[(size_t)f * GRID_CELLS + slot];
+				col[0] = mv & 0xFFu; col[1] = (mv >> 8) & 0xFFu; col[2] = (mv >> 16) & 0xFFu;
+			}
+			const uint32_t wgt = color_fit<true>((float)col[0], (float)col[1], (float)col[2], s_ccm[c], s_ccm[c][9] != 0.0f).margin + 1u;
+			const uint32_t mine = colors[(size_t)f * NCELLS + i] & (uint32_t)(NCOLORS - 1);
+#pragma unroll
+			for (int k = 0; k < NCOLORS; ++k) score[k] += mine == (uint32_t)k ? wgt : 0u;
+			gcw[(size_t)f * NCELLS + i] = wgt;
+		}
+		uint32_t best = score[0], second = 0, win = 0;
+#pragma unroll
+		for (int k = 1; k < NCOLORS; ++k) {
+			if (score[k] > best) { second = best; best = score[k]; win = (uint32_t)k; }
+			else if (score[k] > second) second = score[k];
+		}
+		oc[i] = (uint8_t)win;
+		om[i] = best - second;
+	}
+}
+
+// G4c k_group_colour_retry, behind G4 (armed by the vote together with cimbar_hip_set_colour_erasure_decode): k_colour_erasure_frame's retry over
+// the group's cells, a kernel of its own so that the frame retry's code stays what it was. One workgroup per group slot; a slot at or above
+// the count, a group without members, an unflagged group (nothing disputed: nothing to flag, and its Reed-Solomon pass was skipped) and a
+// group whose colour chunks are all in gmask return at once. Otherwise, for the colour chunks gmask lacks after G4's fill:
+//  * a colour-stream byte's score is max over its four cells of c_margin - gm; a cell without a colour dispute contributes nothing; flagged
+//    when > 0; the e_max highest scores become erasures, ties to the lower byte (er_select)
+//  * retry, acceptance (status 1 and, with erasures, 2 errors <= p - e - ERASURE_SLACK) and the mask update as in k_colour_erasure_frame, block
+//    for block; chunks already in gmask are never rewritten, the slots of colour chunks still missing are zeroed again
+__global__ __launch_bounds__(256) void k_group_colour_retry(const uint8_t* __restrict__ gcol, const uint32_t* __restrict__ gcm, Tables tb,
+                                                            const int* __restrict__ gcount, const int* __restrict__ ngroups,
+                                                            const uint32_t* __restrict__ gdisp, const uint8_t* __restrict__ grs_ok,
+                                                            uint8_t* __restrict__ gchunks, uint32_t* __restrict__ gmasks, int c_margin, int e_max)
+{
+	if constexpr (LEGACY) return;
+	constexpr uint32_t COL_MASK = ((1u << COL_CHUNKS) - 1u) << SYM_CHUNKS;
+	constexpr int NB = COL_BLOCKS > 0 ? COL_BLOCKS : 1;
+	const int g = blockIdx.x;
+	if (g >= *ngroups || gcount[g] == 0 || gdisp[g] == 0) return;   // (uniform over the workgroup)
+	const uint32_t mask = gmasks[g];
+	if ((mask & COL_MASK) == COL_MASK) return;
+	__shared__ RsEraShared s;
+	__shared__ int32_t s_score[4][192];
+	__shared__ uint8_t s_pos[4][64];
+	__shared__ int8_t s_st[NB];
+	er_tables(s);
+	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+	const uint8_t* cf = gcol + (size_t)g * NCELLS;
+	const uint32_t* mg = gcm + (size_t)g * NCELLS;
+	uint8_t* fc = gchunks + (size_t)g * FRAME_BYTES;
+	for (int b = SYM_BLOCKS + wv; b < ALL_BLOCKS; b += 4) {
+		const int j = b / BLOCKS_PER_CHUNK, cb = b - SYM_BLOCKS;
+		if (mask & (1u << j)) { if (lane == 0) s_st[cb] = 2; continue; }
+		const bool ok = grs_ok[(size_t)g * ALL_BLOCKS + b] != 0;
+		uint8_t* enc = s.enc[wv];
+		int32_t* score = s_score[wv];
+		for (int k = lane; k < RS_BLOCK; k += 64) {
+			const int sidx = (RS_BLOCK * cb + k) * 4;
+			int best = INT_MIN;
+			uint32_t v = 0;
+#pragma unroll
+			for (int q = 0; q < 4; ++q) {
+				const int cell = tb.stream_cell[sidx + q];
+				v = (v << 2) | (cf[cell] & 3u);
+				if (!ok) {
+					const uint32_t gm = mg[cell];
+					const int sc = gm == GCM_NONE ? INT_MIN : c_margin - (int)gm;
+					best = sc > best ? sc : best;
+				}
+			}
+			enc[k] = (uint8_t)v;
+			score[k] = best;
+		}
+		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+		__builtin_amdgcn_wave_barrier();
+		int e = 0;
+		if (!ok) {
+			e = er_select(score, lane, e_max, s_pos[wv]);
+			if (e == 0) { if (lane == 0) s_st[cb] = -2; continue; }   // nothing to erase: errors-only already failed it
+		}
+		int nerr = 0;
+		int st = er_decode(s, wv, lane, e, s_pos[wv], &nerr);
+		if (st == 1 && e > 0 && 2 * nerr > RS_PARITY - e - ERASURE_SLACK) st = 0;   // (the slack rule of k_erasure_frame)
+		if (st == 1) {
+			uint8_t* dst = fc + (size_t)j * CHUNK + (size_t)(b % BLOCKS_PER_CHUNK) * RS_DATA;
+			for (int k = lane; k < RS_DATA; k += 64) dst[k] = enc[k];
+		}
+		if (lane == 0) s_st[cb] = (int8_t)st;
+	}
+	__syncthreads();
+	__shared__ uint32_t s_new;
+	if (threadIdx.x == 0) {
+		uint32_t nm = mask;
+		for (int j = SYM_CHUNKS; j < CHUNKS; ++j) {
+			if (mask & (1u << j)) continue;
+			bool all = true;
+			for (int q = 0; q < BLOCKS_PER_CHUNK; ++q) all = all && s_st[j * BLOCKS_PER_CHUNK + q - SYM_BLOCKS] == 1;
+			if (all) nm |= 1u << j;
+		}
+		s_new = nm;
+		gmasks[g] = nm;
+	}
+	__syncthreads();
+	const uint32_t nm = s_new;
+	for (int j = SYM_CHUNKS; j < CHUNKS; ++j)
+		if (!(nm & (1u << j)))
+			for (int k = threadIdx.x; k < CHUNK; k += 256) fc[(size_t)j * CHUNK + k] = 0;
 }
 
 // ------------------------------------------------------------------------------------------------ the stream calls

@@ -34,6 +34,9 @@ struct cimbar_hip_ctx {
 	DevBuf<uint32_t> d_gagree, d_gdisp; DevBuf<int> d_groups, d_gmem, d_gcount, d_groups_in;
 	DevBuf<int> d_ngroups;                      // 1 int
 	DevBuf<uint8_t> d_gchunks; DevBuf<uint32_t> d_gmasks;   // staging for host-memory group outputs
+	int gcv_on = 0;                             // cimbar_hip_set_group_colour_vote: off unless set (k_group_colour / k_group_colour_retry are then never launched)
+	bool gcv_valid = false;                     // the last batch was a plain combined one with the vote on (CIMBAR_HIP_TAP_GROUP_COLOUR_* describe it)
+	DevBuf<uint32_t> d_gcm, d_gcw;              // the vote's margins [groups][NCELLS] and member weights [captures][NCELLS]; allocated by the first combined call with the setting on
 	std::unique_ptr<CombineStream> cstream;     // cimbar_hip_decode_batch_combined_stream / _scan_extract_decode_batch_combined_stream_fmt
 	int wave_adapt = 1;               // CIMBAR_HIP_FLOOD_WAVE_ADAPT=0: run k_flood_wave in front of every exact replay, whatever it achieved before
 	bool wave_ran = false;            // k_flood_wave ran in the batch h_flagged describes
@@ -479,6 +482,7 @@ int enqueue(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_rgb, int n, in
 {
 	cimbar_hip_ctx::ScratchSet& cur = ctx->cur();
 	ctx->grp_valid = false;   // (the group taps describe a combined batch only until the next batch of any kind)
+	ctx->gcv_valid = false;
 	// the colour retry (erasure.hip.inc) runs behind every chain that reports chunks; the set in use holds its margins
 	const bool colour_retry = !LEGACY && !plain && !symbols_only && ctx->ec_margin > 0;
 	if (colour_retry) { if (int r = ensure_margin_capacity(ctx, cur)) return r; }
@@ -886,12 +890,18 @@ int ensure_group_capacity(cimbar_hip_ctx* ctx, int n)
 
 // G1-G4 behind a batch's per-capture decode, on the same stream; reads that decode's intermediates and outputs (d_chunks / d_masks), writes
 // the group outputs (d_gchunks / d_gmasks, n slots) and the context's group scratch. d_status: the capture path's extraction status (stride
-// ints apart), nullptr: every capture usable.
-int enqueue_combine(cimbar_hip_ctx* ctx, hipStream_t st, int n, const uint8_t* d_chunks, const uint32_t* d_masks, const int* d_status, int stride,
-                    const CombineArgs& cb, int out_mem)
+// ints apart), nullptr: every capture usable. d_rgb: the frames that decode read (the colour vote takes a flooded member's means from them).
+int enqueue_combine(cimbar_hip_ctx* ctx, hipStream_t st, int n, const uint8_t* d_rgb, const uint8_t* d_chunks, const uint32_t* d_masks, const int* d_status,
+                    int stride, const CombineArgs& cb, int out_mem)
 {
 	if (int r = ensure_group_capacity(ctx, n)) return r;
 	cimbar_hip_ctx::ScratchSet& cur = ctx->cur();
+	// the colour vote (cimbar_hip_set_group_colour_vote) and, with the colour erasure setting on as well, the group colour retry
+	const bool vote = !LEGACY && ctx->gcv_on != 0;
+	if (vote) {
+		HIPCHK(ctx->d_gcm.reserve((size_t)n * NCELLS));
+		HIPCHK(ctx->d_gcw.reserve((size_t)n * NCELLS));
+	}
 	// (device outputs: the caller's buffers; host outputs: the context's staging, which exists from here on)
 	uint8_t* d_gchunks = out_mem == CIMBAR_HIP_MEM_DEVICE ? cb.gchunks : ctx->d_gchunks;
 	uint32_t* d_gmasks = out_mem == CIMBAR_HIP_MEM_DEVICE ? cb.gmasks : ctx->d_gmasks;
@@ -904,6 +914,9 @@ int enqueue_combine(cimbar_hip_ctx* ctx, hipStream_t st, int n, const uint8_t* d
 	                   cb.min_agree, cb.max_group, ctx->d_groups, ctx->d_gmem, ctx->d_gcount, ctx->d_ngroups);
 	hipLaunchKernelGGL(k_group_cells, dim3(GC_BLOCKS, n), dim3(256), 0, st, cur.d_plane, ctx->tb, cur.d_symbols, cur.d_colors, cur.d_drift, cur.d_flood,
 	                   ctx->d_gmem, ctx->d_gcount, ctx->d_ngroups, ctx->d_gsym, ctx->d_gcol, ctx->d_gmargin, ctx->d_gdisp);
+	if (vote)
+		hipLaunchKernelGGL(k_group_colour, dim3(n), dim3(256), 0, st, d_rgb, cur.d_cellmean, ctx->tb, cur.d_colors, cur.d_drift, cur.d_flood, cur.d_ccm_used,
+		                   ctx->d_gmem, ctx->d_gcount, ctx->d_ngroups, ctx->d_gdisp, ctx->d_gcol, ctx->d_gcm, ctx->d_gcw);
 	if constexpr (LEGACY) {
 		hipLaunchKernelGGL((k_rs<CELL_BITS, false, true>), dim3((n * ALL_BLOCKS + 3) / 4), dim3(256), 0, st, ctx->d_gsym, ctx->tb, 0, n, 0, d_gchunks, ctx->d_grs_ok, 0,
 		                   (const uint8_t*)ctx->d_gcol, (const int*)ctx->d_ngroups, (const uint32_t*)ctx->d_gdisp);
@@ -915,7 +928,11 @@ int enqueue_combine(cimbar_hip_ctx* ctx, hipStream_t st, int n, const uint8_t* d
 	}
 	hipLaunchKernelGGL(k_group_end, dim3(n), dim3(256), 0, st, ctx->d_gsym, ctx->d_gmargin, ctx->tb, ctx->d_gmem, ctx->d_gcount, ctx->d_ngroups, ctx->d_grs_ok,
 	                   d_chunks, d_masks, ctx->d_gdisp, d_gchunks, d_gmasks, (!LEGACY && ctx->er_sym > 0) ? 1 : 0, erasure_max(ctx));
+	if (vote && ctx->ec_margin > 0)
+		hipLaunchKernelGGL(k_group_colour_retry, dim3(n), dim3(256), 0, st, ctx->d_gcol, ctx->d_gcm, ctx->tb, ctx->d_gcount, ctx->d_ngroups, ctx->d_gdisp,
+		                   ctx->d_grs_ok, d_gchunks, d_gmasks, ctx->ec_margin, colour_erasure_max(ctx));
 	HIPCHK(hipGetLastError());
+	ctx->gcv_valid = vote;
 	return 0;
 }
 
@@ -944,6 +961,7 @@ int enqueue_combine_stream(cimbar_hip_ctx* ctx, hipStream_t st, int n, const uin
 {
 	if (int r = ensure_stream_capacity(ctx, n)) return r;
 	CombineStream& s = *ctx->cstream;
+	ctx->gcv_valid = false;   // (the stream calls run without the colour vote, whatever the setting)
 	cimbar_hip_ctx::ScratchSet& cur = ctx->cur();
 	const CarryStore cs = s.store();
 	const int slots = n + 1;
@@ -1075,7 +1093,7 @@ int64_t decode_batch_impl(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rg
 		return finish_stream(ctx, st, n, chunks, masks, d_chunks, d_masks, out_mem, *cb);
 	}
 	if (cb)
-		if (int r = enqueue_combine(ctx, st, n, d_chunks, d_masks, nullptr, 0, *cb, out_mem)) return r;
+		if (int r = enqueue_combine(ctx, st, n, d_rgb, d_chunks, d_masks, nullptr, 0, *cb, out_mem)) return r;
 	return finish_batch(ctx, st, n, chunks, masks, d_chunks, d_masks, out_mem, cb);
 }
 
@@ -1667,7 +1685,7 @@ int64_t scan_extract_decode_impl(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsign
 	// ... nor any group (it is in none)
 	if (strm) { if (int r = enqueue_combine_stream(ctx, st, n, d_chunks, d_masks, &ctx->d_scan_res[0].status, stride, *cb, out_mem)) return r; }
 	else if (cb)
-		if (int r = enqueue_combine(ctx, st, n, d_chunks, d_masks, &ctx->d_scan_res[0].status, stride, *cb, out_mem)) return r;
+		if (int r = enqueue_combine(ctx, st, n, ctx->d_ex_frames, d_chunks, d_masks, &ctx->d_scan_res[0].status, stride, *cb, out_mem)) return r;
 	const hipMemcpyKind kind = out_mem == CIMBAR_HIP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
 	if (status) HIPCHK(hipMemcpy2DAsync(status, sizeof(int), &ctx->d_scan_res[0].status, sizeof(ScanResult), sizeof(int), (size_t)n, kind, st));
 	if (strm) return finish_stream(ctx, st, n, chunks, masks, d_chunks, d_masks, out_mem, *cb);
@@ -1800,6 +1818,22 @@ int cimbar_hip_get_colour_erasure_decode(cimbar_hip_ctx* ctx, int* colour_margin
 	if (colour_margin) *colour_margin = ctx->ec_margin;
 	if (max_erasures) *max_erasures = colour_erasure_max(ctx);
 	return ctx->ec_margin > 0 ? 1 : 0;
+}
+
+int cimbar_hip_set_group_colour_vote(cimbar_hip_ctx* ctx, int on)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	if (LEGACY && on) { ctx->err = "set_group_colour_vote: modes 4 and 8 carry one coupled stream; the colour vote covers the colour chunks of modes 68 / 67 / 66"; return CIMBAR_HIP_EINVAL; }
+	// (read when a combined batch is enqueued: batches already issued keep the setting they were issued with)
+	ctx->gcv_on = on ? 1 : 0;
+	return 0;
+}
+
+int cimbar_hip_get_group_colour_vote(cimbar_hip_ctx* ctx, int* on)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	if (on) *on = ctx->gcv_on;
+	return 0;
 }
 
 int cimbar_hip_rs_decode_erasures(cimbar_hip_ctx* ctx, const uint8_t* blocks, int n, const uint8_t* erasures, const uint8_t* counts, int mem,
@@ -1939,6 +1973,27 @@ int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_byte
 				HIPCHK(hipMemcpy(out, ctx->d_gsym, bytes, hipMemcpyDeviceToHost));
 				HIPCHK(hipMemcpy(col.data(), ctx->d_gcol, bytes, hipMemcpyDeviceToHost));
 				for (size_t k = 0; k < bytes; ++k) ((uint8_t*)out)[k] = (uint8_t)((col[k] << 4) | (((uint8_t*)out)[k] & 15u));
+			}
+			return (int64_t)bytes;
+		}
+		case CIMBAR_HIP_TAP_GROUP_COLOUR_MARGIN:
+		case CIMBAR_HIP_TAP_GROUP_COLOUR_WEIGHTS: {
+			if (!ctx->grp_valid || !ctx->gcv_valid || !ctx->d_gcm || !ctx->d_gcw) { ctx->err = "tap: the last batch was not a combined one with the colour vote on (cimbar_hip_set_group_colour_vote)"; return CIMBAR_HIP_EINVAL; }
+			int ng = 0;
+			HIPCHK(hipMemcpy(&ng, ctx->d_ngroups, sizeof(int), hipMemcpyDeviceToHost));
+			const size_t G = (size_t)ng, rows = what == CIMBAR_HIP_TAP_GROUP_COLOUR_MARGIN ? G : n;
+			bytes = rows * NCELLS * sizeof(uint32_t);
+			if (out_bytes < bytes) { ctx->err = "tap: buffer too small"; return CIMBAR_HIP_EINVAL; }
+			std::vector<uint32_t> disp(G);
+			std::vector<int> grp(n);
+			if (G) HIPCHK(hipMemcpy(disp.data(), ctx->d_gdisp, sizeof(uint32_t) * G, hipMemcpyDeviceToHost));
+			HIPCHK(hipMemcpy(grp.data(), ctx->d_groups, sizeof(int) * n, hipMemcpyDeviceToHost));
+			if (bytes) HIPCHK(hipMemcpy(out, what == CIMBAR_HIP_TAP_GROUP_COLOUR_MARGIN ? ctx->d_gcm.get() : ctx->d_gcw.get(), bytes, hipMemcpyDeviceToHost));
+			// a group whose members agree on every cell was skipped by the vote: no margin; its members, and captures in no group, gave no weight
+			if (what == CIMBAR_HIP_TAP_GROUP_COLOUR_MARGIN) {
+				for (size_t g = 0; g < G; ++g) if (!disp[g]) std::memset((uint32_t*)out + g * NCELLS, 0xFF, (size_t)NCELLS * sizeof(uint32_t));
+			} else {
+				for (size_t k = 0; k < n; ++k) if (grp[k] < 0 || (size_t)grp[k] >= G || !disp[grp[k]]) std::memset((uint32_t*)out + k * NCELLS, 0, (size_t)NCELLS * sizeof(uint32_t));
 			}
 			return (int64_t)bytes;
 		}
