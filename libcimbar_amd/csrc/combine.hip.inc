@@ -22,6 +22,24 @@ constexpr int GROUP_MAX_DEFAULT = 4, GROUP_AGREE_DEFAULT = 750;
 constexpr uint16_t MARGIN_NONE = 0xFFFFu;  // the symbol of the cell is not disputed
 static_assert(NCELLS % 4 == 0, "a frame's cells are whole dwords");
 
+// the agreeing cells of two captures (symbols s0 / s1, colours c0 / c1, NCELLS bytes each), counted by the whole workgroup
+__device__ __forceinline__ uint32_t agreeing_cells(const uint32_t* __restrict__ s0, const uint32_t* __restrict__ c0, const uint32_t* __restrict__ s1,
+                                                   const uint32_t* __restrict__ c1)
+{
+	constexpr int W = NCELLS / 4;
+	constexpr uint32_t CM = 0x01010101u * (uint32_t)(NCOLORS - 1);
+	uint32_t cnt = 0;
+	for (int w = threadIdx.x; w < W; w += 256) {
+		const uint32_t x = ((s0[w] ^ s1[w]) & 0x0F0F0F0Fu) | ((c0[w] ^ c1[w]) & CM);
+		cnt += ((x & 0xFFu) == 0u) + ((x & 0xFF00u) == 0u) + ((x & 0xFF0000u) == 0u) + ((x >> 24) == 0u);
+	}
+	for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o);
+	__shared__ uint32_t s_part[4];
+	if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = cnt;
+	__syncthreads();
+	return s_part[0] + s_part[1] + s_part[2] + s_part[3];
+}
+
 // G1: one workgroup per pair (k, k+1), k < n - 1
 __global__ __launch_bounds__(256) void k_group_agree(const uint8_t* __restrict__ symbols, const uint8_t* __restrict__ colors, int n,
                                                      uint32_t* __restrict__ agree)
@@ -30,18 +48,8 @@ __global__ __launch_bounds__(256) void k_group_agree(const uint8_t* __restrict__
 	if (k + 1 >= n) return;
 	const uint32_t* s0 = reinterpret_cast<const uint32_t*>(symbols + (size_t)k * NCELLS);
 	const uint32_t* c0 = reinterpret_cast<const uint32_t*>(colors + (size_t)k * NCELLS);
-	constexpr int W = NCELLS / 4;
-	constexpr uint32_t CM = 0x01010101u * (uint32_t)(NCOLORS - 1);
-	uint32_t cnt = 0;
-	for (int w = threadIdx.x; w < W; w += 256) {
-		const uint32_t x = ((s0[w] ^ s0[W + w]) & 0x0F0F0F0Fu) | ((c0[w] ^ c0[W + w]) & CM);
-		cnt += ((x & 0xFFu) == 0u) + ((x & 0xFF00u) == 0u) + ((x & 0xFF0000u) == 0u) + ((x >> 24) == 0u);
-	}
-	for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o);
-	__shared__ uint32_t s_part[4];
-	if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = cnt;
-	__syncthreads();
-	if (threadIdx.x == 0) agree[k] = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+	const uint32_t a = agreeing_cells(s0, c0, s0 + NCELLS / 4, c0 + NCELLS / 4);
+	if (threadIdx.x == 0) agree[k] = a;
 }
 
 // G2: one wavefront, 64 captures per step, everything carried in registers from step to step.
@@ -308,10 +316,9 @@ __global__ __launch_bounds__(256) void k_group_cells(const uint32_t* __restrict_
 //   cmask  the aligned_stream bookkeeping over the combined decode's block flags, the symbol blocks then the colour blocks with one state
 //          (what k_frame_mid and k_frame_end do for one frame; legacy modes: the one coupled stream)
 //   chunk j of the group = the combined decode's chunk j where cmask has it, else member chunk j of the lowest-index member that delivered it
-//   e_on   (erasure decoding, modes 68 / 67 / 66): every block of a symbol chunk still missing is decoded again -- a block errors-only decoding
-//          accepted with no erasures, a failed block with the stream bytes of the symbol-disputed cells as erasures (smallest margin first,
-//          then stream position, at most e_max) -- and accepted as in k_erasure_frame (a codeword, nothing in the padding, and with erasures
-//          2 errors <= p - e - ERASURE_SLACK). A chunk whose blocks are all accepted joins the mask with its bytes.
+//   e_on   (erasure decoding, modes 68 / 67 / 66): every block of a symbol chunk still missing is decoded again (er_retry_blocks) -- a block
+//          errors-only decoding accepted with no erasures, a failed block with the stream bytes of the symbol-disputed cells as erasures
+//          (smallest margin first, then stream position, at most e_max). A chunk whose blocks are all accepted joins the mask with its bytes.
 // gmask = cmask | the members' masks | the chunks the retry added; slots of chunks outside it are zero.
 // (CARRY: a member id is a carry slot or CARRY_SLOTS + a batch index, as in G3, and the member count of every slot goes to gsizes)
 template <bool CARRY>
@@ -333,7 +340,7 @@ __device__ __forceinline__ void group_end_body(const uint8_t* __restrict__ gsym,
 	constexpr uint32_t FULL = (1u << CHUNKS) - 1u, SYM_MASK = LEGACY ? 0u : (1u << SYM_CHUNKS) - 1u;
 	__shared__ int s_mem[GMAX];
 	__shared__ uint32_t s_mmask[GMAX];
-	__shared__ uint32_t s_cmask, s_emask;
+	__shared__ uint32_t s_cmask;
 	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 	if (threadIdx.x < GMAX) {
 		const int f = (int)threadIdx.x < m ? gmem[(size_t)g * GMAX + threadIdx.x] : 0;
@@ -345,7 +352,7 @@ __device__ __forceinline__ void group_end_body(const uint8_t* __restrict__ gsym,
 	// subset of the member's mask, the same bytes) and the retry finds no disputed cell: the members' chunks are the whole answer, and the
 	// Reed-Solomon pass skipped it (k_rs LIVE)
 	const bool disp = gdisp[g] != 0;
-	if (threadIdx.x == 0) { s_cmask = 0; s_emask = 0; }
+	if (threadIdx.x == 0) s_cmask = 0;
 	if (wv == 0 && disp) {
 		const uint8_t* ok = grs_ok + (size_t)g * ALL_BLOCKS;
 		static_assert(ALL_BLOCKS <= 128, "block flags fit two ballots");
@@ -363,75 +370,22 @@ __device__ __forceinline__ void group_end_body(const uint8_t* __restrict__ gsym,
 	const uint32_t cmask = s_cmask;
 	uint32_t mmask = 0;
 	for (int c = 0; c < m; ++c) mmask |= s_mmask[c];
+	uint32_t emask = 0;
 	if constexpr (!LEGACY) {
 		const uint32_t missing = SYM_MASK & ~(cmask | mmask);
 		if (e_on && disp && missing) {
-			__shared__ RsEraShared s;
-			__shared__ uint16_t s_key[4][192];
-			__shared__ uint8_t s_pos[4][64];
-			__shared__ int8_t s_st[SYM_BLOCKS];
-			er_tables(s);
 			const uint8_t* sym = gsym + (size_t)g * NCELLS;
 			const uint16_t* mg = gmargin + (size_t)g * NCELLS;
-			for (int b = wv; b < SYM_BLOCKS; b += 4) {
-				const int j = b / BLOCKS_PER_CHUNK;
-				if (!(missing & (1u << j))) continue;
-				const bool ok = grs_ok[(size_t)g * ALL_BLOCKS + b] != 0;
-				uint8_t* enc = s.enc[wv];
-				uint16_t* key = s_key[wv];
-				for (int k = lane; k < RS_BLOCK; k += 64) {
-					const int sidx = (RS_BLOCK * b + k) * 2;
-					const int c0 = tb.stream_cell[sidx], c1 = tb.stream_cell[sidx + 1];
-					enc[k] = (uint8_t)(((sym[c0] & 15u) << 4) | (sym[c1] & 15u));
-					const uint16_t m0 = mg[c0], m1 = mg[c1];
-					key[k] = m0 < m1 ? m0 : m1;
-				}
-				__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-				__builtin_amdgcn_wave_barrier();
-				int e = 0;
-				if (!ok) {
-					// rank of each flagged byte (a disputed cell) among the flagged ones: smaller margin first, then lower position
-					int mine = 0;
-					for (int k = lane; k < RS_BLOCK; k += 64) {
-						const int kk = key[k];
-						if (kk == MARGIN_NONE) continue;
-						int rank = 0;
-						for (int q = 0; q < RS_BLOCK; ++q) {
-							const int kq = key[q];
-							rank += (kq < kk || (kq == kk && q < k)) ? 1 : 0;
-						}
-						if (rank < e_max) { s_pos[wv][rank] = (uint8_t)k; ++mine; }
-					}
-					for (int o = 32; o >= 1; o >>= 1) mine += __shfl_xor(mine, o);
-					e = mine;
-					__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-					__builtin_amdgcn_wave_barrier();
-					if (e == 0) { if (lane == 0) s_st[b] = -2; continue; }
-				}
-				int nerr = 0;
-				int st = er_decode(s, wv, lane, e, s_pos[wv], &nerr);
-				if (st == 1 && e > 0 && 2 * nerr > RS_PARITY - e - ERASURE_SLACK) st = 0;
-				if (st == 1) {
-					uint8_t* dst = gc + (size_t)j * CHUNK + (size_t)(b % BLOCKS_PER_CHUNK) * RS_DATA;
-					for (int k = lane; k < RS_DATA; k += 64) dst[k] = enc[k];
-				}
-				if (lane == 0) s_st[b] = (int8_t)st;
-			}
-			__syncthreads();
-			if (threadIdx.x == 0) {
-				uint32_t em = 0;
-				for (int j = 0; j < SYM_CHUNKS; ++j) {
-					if (!(missing & (1u << j))) continue;
-					bool all = true;
-					for (int q = 0; q < BLOCKS_PER_CHUNK; ++q) all = all && s_st[j * BLOCKS_PER_CHUNK + q] == 1;
-					if (all) em |= 1u << j;
-				}
-				s_emask = em;
-			}
-			__syncthreads();
+			emask = er_retry_blocks<uint16_t, 0, SYM_BLOCKS>(missing, grs_ok + (size_t)g * ALL_BLOCKS, e_max, gc, [&](int b, int k, bool) {
+				const int sidx = (RS_BLOCK * b + k) * 2;
+				const int c0 = tb.stream_cell[sidx], c1 = tb.stream_cell[sidx + 1];
+				const uint32_t m0 = mg[c0], m1 = mg[c1];
+				// smallest margin first is highest score first with score = 0xFFFF - margin, ties to the lower byte either way, and an
+				// undisputed byte (both MARGIN_NONE = 0xFFFF) scores 0: not flagged. The score still fits the 16 bits of the margin.
+				return ErByte{((sym[c0] & 15u) << 4) | (sym[c1] & 15u), (int)(0xFFFFu - (m0 < m1 ? m0 : m1))};
+			});
 		}
 	}
-	const uint32_t emask = s_emask;
 	for (int j = 0; j < CHUNKS; ++j) {
 		const uint32_t bit = 1u << j;
 		if (cmask & bit) continue;
@@ -576,9 +530,9 @@ __global__ __launch_bounds__(256) void k_group_colour(const uint8_t* __restrict_
 // the count, a group without members, an unflagged group (nothing disputed: nothing to flag, and its Reed-Solomon pass was skipped) and a
 // group whose colour chunks are all in gmask return at once. Otherwise, for the colour chunks gmask lacks after G4's fill:
 //  * a colour-stream byte's score is max over its four cells of c_margin - gm; a cell without a colour dispute contributes nothing; flagged
-//    when > 0; the e_max highest scores become erasures, ties to the lower byte (er_select)
-//  * retry, acceptance (status 1 and, with erasures, 2 errors <= p - e - ERASURE_SLACK) and the mask update as in k_colour_erasure_frame, block
-//    for block; chunks already in gmask are never rewritten, the slots of colour chunks still missing are zeroed again
+//    when > 0
+//  * retry, acceptance and the mask update are er_retry_blocks and er_commit over the colour blocks; chunks already in gmask are never
+//    rewritten, the slots of colour chunks still missing are zeroed again
 __global__ __launch_bounds__(256) void k_group_colour_retry(const uint8_t* __restrict__ gcol, const uint32_t* __restrict__ gcm, Tables tb,
                                                             const int* __restrict__ gcount, const int* __restrict__ ngroups,
                                                             const uint32_t* __restrict__ gdisp, const uint8_t* __restrict__ grs_ok,
@@ -586,77 +540,30 @@ __global__ __launch_bounds__(256) void k_group_colour_retry(const uint8_t* __res
 {
 	if constexpr (LEGACY) return;
 	constexpr uint32_t COL_MASK = ((1u << COL_CHUNKS) - 1u) << SYM_CHUNKS;
-	constexpr int NB = COL_BLOCKS > 0 ? COL_BLOCKS : 1;
 	const int g = blockIdx.x;
 	if (g >= *ngroups || gcount[g] == 0 || gdisp[g] == 0) return;   // (uniform over the workgroup)
 	const uint32_t mask = gmasks[g];
 	if ((mask & COL_MASK) == COL_MASK) return;
-	__shared__ RsEraShared s;
-	__shared__ int32_t s_score[4][192];
-	__shared__ uint8_t s_pos[4][64];
-	__shared__ int8_t s_st[NB];
-	er_tables(s);
-	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 	const uint8_t* cf = gcol + (size_t)g * NCELLS;
 	const uint32_t* mg = gcm + (size_t)g * NCELLS;
 	uint8_t* fc = gchunks + (size_t)g * FRAME_BYTES;
-	for (int b = SYM_BLOCKS + wv; b < ALL_BLOCKS; b += 4) {
-		const int j = b / BLOCKS_PER_CHUNK, cb = b - SYM_BLOCKS;
-		if (mask & (1u << j)) { if (lane == 0) s_st[cb] = 2; continue; }
-		const bool ok = grs_ok[(size_t)g * ALL_BLOCKS + b] != 0;
-		uint8_t* enc = s.enc[wv];
-		int32_t* score = s_score[wv];
-		for (int k = lane; k < RS_BLOCK; k += 64) {
-			const int sidx = (RS_BLOCK * cb + k) * 4;
-			int best = INT_MIN;
-			uint32_t v = 0;
+	const uint32_t done = er_retry_blocks<int32_t, SYM_BLOCKS, COL_BLOCKS>(COL_MASK & ~mask, grs_ok + (size_t)g * ALL_BLOCKS, e_max, fc, [&](int b, int k, bool ok) {
+		const int sidx = (RS_BLOCK * (b - SYM_BLOCKS) + k) * 4;
+		int best = INT_MIN;
+		uint32_t v = 0;
 #pragma unroll
-			for (int q = 0; q < 4; ++q) {
-				const int cell = tb.stream_cell[sidx + q];
-				v = (v << 2) | (cf[cell] & 3u);
-				if (!ok) {
-					const uint32_t gm = mg[cell];
-					const int sc = gm == GCM_NONE ? INT_MIN : c_margin - (int)gm;
-					best = sc > best ? sc : best;
-				}
+		for (int q = 0; q < 4; ++q) {
+			const int cell = tb.stream_cell[sidx + q];
+			v = (v << 2) | (cf[cell] & 3u);
+			if (!ok) {
+				const uint32_t gm = mg[cell];
+				const int sc = gm == GCM_NONE ? INT_MIN : c_margin - (int)gm;
+				best = sc > best ? sc : best;
 			}
-			enc[k] = (uint8_t)v;
-			score[k] = best;
 		}
-		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-		__builtin_amdgcn_wave_barrier();
-		int e = 0;
-		if (!ok) {
-			e = er_select(score, lane, e_max, s_pos[wv]);
-			if (e == 0) { if (lane == 0) s_st[cb] = -2; continue; }   // nothing to erase: errors-only already failed it
-		}
-		int nerr = 0;
-		int st = er_decode(s, wv, lane, e, s_pos[wv], &nerr);
-		if (st == 1 && e > 0 && 2 * nerr > RS_PARITY - e - ERASURE_SLACK) st = 0;   // (the slack rule of k_erasure_frame)
-		if (st == 1) {
-			uint8_t* dst = fc + (size_t)j * CHUNK + (size_t)(b % BLOCKS_PER_CHUNK) * RS_DATA;
-			for (int k = lane; k < RS_DATA; k += 64) dst[k] = enc[k];
-		}
-		if (lane == 0) s_st[cb] = (int8_t)st;
-	}
-	__syncthreads();
-	__shared__ uint32_t s_new;
-	if (threadIdx.x == 0) {
-		uint32_t nm = mask;
-		for (int j = SYM_CHUNKS; j < CHUNKS; ++j) {
-			if (mask & (1u << j)) continue;
-			bool all = true;
-			for (int q = 0; q < BLOCKS_PER_CHUNK; ++q) all = all && s_st[j * BLOCKS_PER_CHUNK + q - SYM_BLOCKS] == 1;
-			if (all) nm |= 1u << j;
-		}
-		s_new = nm;
-		gmasks[g] = nm;
-	}
-	__syncthreads();
-	const uint32_t nm = s_new;
-	for (int j = SYM_CHUNKS; j < CHUNKS; ++j)
-		if (!(nm & (1u << j)))
-			for (int k = threadIdx.x; k < CHUNK; k += 256) fc[(size_t)j * CHUNK + k] = 0;
+		return ErByte{v, best};
+	});
+	er_commit(mask | done, gmasks + g, fc, SYM_CHUNKS, CHUNKS);
 }
 
 // ------------------------------------------------------------------------------------------------ the stream calls
@@ -679,18 +586,8 @@ __global__ __launch_bounds__(256) void k_group_agree_stream(const uint8_t* __res
 	const uint32_t* c1 = reinterpret_cast<const uint32_t*>(colors + (size_t)k * NCELLS);
 	const uint32_t* s0 = k > 0 ? s1 - NCELLS / 4 : reinterpret_cast<const uint32_t*>(cs.symbols + (size_t)(c - 1) * CS_CELLS);
 	const uint32_t* c0 = k > 0 ? c1 - NCELLS / 4 : reinterpret_cast<const uint32_t*>(cs.colors + (size_t)(c - 1) * CS_CELLS);
-	constexpr int W = NCELLS / 4;
-	constexpr uint32_t CM = 0x01010101u * (uint32_t)(NCOLORS - 1);
-	uint32_t cnt = 0;
-	for (int w = threadIdx.x; w < W; w += 256) {
-		const uint32_t x = ((s0[w] ^ s1[w]) & 0x0F0F0F0Fu) | ((c0[w] ^ c1[w]) & CM);
-		cnt += ((x & 0xFFu) == 0u) + ((x & 0xFF00u) == 0u) + ((x & 0xFF0000u) == 0u) + ((x >> 24) == 0u);
-	}
-	for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o);
-	__shared__ uint32_t s_part[4];
-	if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = cnt;
-	__syncthreads();
-	if (threadIdx.x == 0) agree[k] = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+	const uint32_t a = agreeing_cells(s0, c0, s1, c1);
+	if (threadIdx.x == 0) agree[k] = a;
 }
 
 // G2s: k_group_walk's walk (groups_in == nullptr) over the virtual batch, 64 virtual captures per step. Virtual capture j starts a group when it is

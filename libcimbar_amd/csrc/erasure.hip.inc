@@ -253,9 +253,9 @@ __global__ __launch_bounds__(256) void k_rs_erasures(const uint8_t* __restrict__
 	if (lane == 0) status[b] = (int8_t)st;
 }
 
-// ------------------------------------------------------------------------------------------------ erasure retry of a decoded frame
+// ------------------------------------------------------------------------------------------------ the erasure retry
 constexpr int ERASURE_SLACK = 6;
-// the selection both retries share: the rank of each flagged byte (score > 0) among the flagged ones, higher score first, then lower position;
+// the selection every retry shares: the rank of each flagged byte (score > 0) among the flagged ones, higher score first, then lower position;
 // the e_max best become erasures, pos[rank] = byte position. One wavefront per block; returns the erasure count (wave-uniform), pos visible
 // to the wave.
 template <class T>
@@ -277,6 +277,87 @@ __device__ __forceinline__ int er_select(const T* score, int lane, int e_max, ui
 	__builtin_amdgcn_wave_barrier();
 	return mine;
 }
+
+// The retry itself, for one frame or group and a workgroup of four wavefronts (all 256 threads call it): the wavefronts take the blocks
+// [B_FIRST, B_FIRST + NB) -- whole chunks -- of the chunks in `todo`, a block each at a time. gather(b, k, ok) gives stream byte k of block b
+// and, for a block errors-only decoding failed (!ok = rs_ok[b] == 0; the score of a decoded block is not read), its score: flagged when > 0.
+// It is all that differs between the callers. T is the type of a score row in LDS.
+//  * a failed block is decoded again with the e_max best-scored flagged bytes as erasures (er_select); none flagged: not retried, status -2
+//    (it would be errors-only again)
+//  * a block errors-only decoding accepted is decoded again with none: libcorrect's errors-only result (its chunk's slot has been zeroed)
+//  * status: er_decode's -1 / 0 / 1, and 1 only within the slack rule below; an accepted block's RS_DATA bytes go to its place in its chunk's
+//    slot under `fc`
+// Returns, uniform over the workgroup, the chunks of `todo` whose blocks were all accepted. The status of a block outside `todo` is neither
+// written nor read; nothing but the accepted blocks' bytes is written to global memory.
+// The LDS is the routine's own and it returns without a barrier behind its last read: call it at most once per kernel, or barrier between calls.
+struct ErByte { uint32_t byte; int score; };
+template <class T, int B_FIRST, int NB, class Gather>
+__device__ __forceinline__ uint32_t er_retry_blocks(uint32_t todo, const uint8_t* __restrict__ rs_ok, int e_max, uint8_t* __restrict__ fc, Gather gather)
+{
+	static_assert(B_FIRST % BLOCKS_PER_CHUNK == 0 && NB % BLOCKS_PER_CHUNK == 0, "whole chunks");
+	__shared__ RsEraShared s;
+	__shared__ T s_score[4][192];
+	__shared__ uint8_t s_pos[4][64];
+	__shared__ int8_t s_st[NB > 0 ? NB : 1];
+	__shared__ uint32_t s_done;
+	er_tables(s);
+	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+	for (int b = B_FIRST + wv; b < B_FIRST + NB; b += 4) {
+		const int j = b / BLOCKS_PER_CHUNK;
+		if (!(todo & (1u << j))) continue;
+		const bool ok = rs_ok[b] != 0;
+		uint8_t* enc = s.enc[wv];
+		T* score = s_score[wv];
+		for (int k = lane; k < RS_BLOCK; k += 64) {
+			const ErByte g = gather(b, k, ok);
+			enc[k] = (uint8_t)g.byte;
+			score[k] = (T)g.score;
+		}
+		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+		__builtin_amdgcn_wave_barrier();
+		int e = 0;
+		if (!ok) {
+			e = er_select(score, lane, e_max, s_pos[wv]);
+			if (e == 0) { if (lane == 0) s_st[b - B_FIRST] = -2; continue; }   // nothing to erase: errors-only already failed it
+		}
+		int nerr = 0;
+		int st = er_decode(s, wv, lane, e, s_pos[wv], &nerr);
+		// a retried block must also leave ERASURE_SLACK syndromes unused: a damaged block lies within s errors of SOME codeword on its n - e
+		// unerased bytes with probability ~ C(n - e, s) 255^s / 256^(p - e), which the codeword check cannot see (1 in 200 blocks at
+		// p - e = 8, s = 4); with 2 s <= p - e - 6 it is below 1e-14
+		if (st == 1 && e > 0 && 2 * nerr > RS_PARITY - e - ERASURE_SLACK) st = 0;
+		if (st == 1) {
+			uint8_t* dst = fc + (size_t)j * CHUNK + (size_t)(b % BLOCKS_PER_CHUNK) * RS_DATA;
+			for (int k = lane; k < RS_DATA; k += 64) dst[k] = enc[k];
+		}
+		if (lane == 0) s_st[b - B_FIRST] = (int8_t)st;
+	}
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		uint32_t done = 0;
+		for (int j = B_FIRST / BLOCKS_PER_CHUNK; j < (B_FIRST + NB) / BLOCKS_PER_CHUNK; ++j) {
+			if (!(todo & (1u << j))) continue;
+			bool all = true;
+			for (int q = 0; q < BLOCKS_PER_CHUNK; ++q) all = all && s_st[j * BLOCKS_PER_CHUNK + q - B_FIRST] == 1;
+			if (all) done |= 1u << j;
+		}
+		s_done = done;
+	}
+	__syncthreads();
+	return s_done;
+}
+
+// what the frame retries and the group colour retry do with the result: the mask `m` (the old one and the chunks the retry added) is written,
+// and the slots of the chunks [j0, j1) it still lacks are zeroed again
+__device__ __forceinline__ void er_commit(uint32_t m, uint32_t* __restrict__ mask_out, uint8_t* __restrict__ fc, int j0, int j1)
+{
+	if (threadIdx.x == 0) *mask_out = m;
+	for (int j = j0; j < j1; ++j)
+		if (!(m & (1u << j)))
+			for (int k = threadIdx.x; k < CHUNK; k += 256) fc[(size_t)j * CHUNK + k] = 0;
+}
+
+// ------------------------------------------------------------------------------------------------ symbol erasure retry of a decoded frame
 // Opt-in (cimbar_hip_set_erasure_decode), launched after k_frame_end on the same stream, one workgroup per frame, modes 68 / 67 / 66.
 // A frame whose symbol chunks are all in the mask returns at once (a clean batch costs one launch). Otherwise the four waves walk the symbol
 // blocks of the chunks the mask lacks:
@@ -289,8 +370,8 @@ __device__ __forceinline__ int er_select(const T* score, int lane, int e_max, ui
 //  * a block errors-only decoding failed is retried with those erasures (none flagged: not retried -- it would be errors-only again); a
 //    block it decoded is decoded again with none (libcorrect's errors-only result, because k_frame_end has zeroed the slots of the chunks the
 //    mask lacks). Then a chunk whose blocks are now all accepted (status 1) gets its bytes and its mask bit; the slots of chunks still
-//    missing are zeroed again. Chunks already in the mask, the colour chunks, rs_ok, the frame state and the colour-correction carry are
-//    not touched. (The colour chunks have a retry of their own: k_colour_erasure_frame below.)
+//    missing are zeroed again (er_retry_blocks, er_commit). Chunks already in the mask, the colour chunks, rs_ok, the frame state and the
+//    colour-correction carry are not touched. (The colour chunks have a retry of their own: k_colour_erasure_frame below.)
 __global__ __launch_bounds__(256) void k_erasure_frame(const uint32_t* __restrict__ plane, Tables tb, const uint8_t* __restrict__ symbols,
                                                        const int8_t* __restrict__ drift, const uint32_t* __restrict__ flood_flag,
                                                        const uint8_t* __restrict__ rs_ok, uint8_t* __restrict__ chunks, uint32_t* __restrict__ masks,
@@ -301,80 +382,31 @@ __global__ __launch_bounds__(256) void k_erasure_frame(const uint32_t* __restric
 	const int f = f0 + blockIdx.x;
 	const uint32_t mask = masks[f];
 	if ((mask & SYM_MASK) == SYM_MASK) return;             // (uniform over the workgroup)
-	__shared__ RsEraShared s;
-	__shared__ int16_t s_score[4][192];
-	__shared__ uint8_t s_pos[4][64];
-	__shared__ int8_t s_st[SYM_BLOCKS];
-	er_tables(s);
-	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 	const uint8_t* sym = symbols + (size_t)f * NCELLS;
 	const uint32_t* pl = plane + (size_t)f * PLANE_WORDS;
 	const bool flooded = flood_flag[f] != 0;
 	uint8_t* fc = chunks + (size_t)f * FRAME_BYTES;
-	for (int b = wv; b < SYM_BLOCKS; b += 4) {
-		const int j = b / BLOCKS_PER_CHUNK;
-		if (mask & (1u << j)) { if (lane == 0) s_st[b] = 2; continue; }
-		const bool ok = rs_ok[(size_t)f * ALL_BLOCKS + b] != 0;
-		uint8_t* enc = s.enc[wv];
-		int16_t* score = s_score[wv];
-		for (int k = lane; k < RS_BLOCK; k += 64) {
-			const int sidx = (RS_BLOCK * b + k) * 2;
-			int best = -32768;
-			uint32_t v = 0;
+	const uint32_t done = er_retry_blocks<int16_t, 0, SYM_BLOCKS>(SYM_MASK & ~mask, rs_ok + (size_t)f * ALL_BLOCKS, e_max, fc, [&](int b, int k, bool ok) {
+		const int sidx = (RS_BLOCK * b + k) * 2;
+		int best = -32768;
+		uint32_t v = 0;
 #pragma unroll
-			for (int q = 0; q < 2; ++q) {
-				const int cell = tb.stream_cell[sidx + q];
-				const uint32_t sy = sym[cell] & 15u;
-				v = (v << 4) | sy;
-				if (!ok) {
-					const ushort2 xy = tb.cell_xy[cell];
-					const int dx = flooded ? drift[((size_t)f * NCELLS + cell) * 2] : 0, dy = flooded ? drift[((size_t)f * NCELLS + cell) * 2 + 1] : 0;
-					uint32_t rows[10];
-					window_rows(pl, (int)xy.x + dx - 1, (int)xy.y + dy - 1, rows);
-					const int d = (int)__popcll(window_hash(rows, 4) ^ c_tile[sy]);
-					best = d - t_sym + 1 > best ? d - t_sym + 1 : best;
-				}
+		for (int q = 0; q < 2; ++q) {
+			const int cell = tb.stream_cell[sidx + q];
+			const uint32_t sy = sym[cell] & 15u;
+			v = (v << 4) | sy;
+			if (!ok) {
+				const ushort2 xy = tb.cell_xy[cell];
+				const int dx = flooded ? drift[((size_t)f * NCELLS + cell) * 2] : 0, dy = flooded ? drift[((size_t)f * NCELLS + cell) * 2 + 1] : 0;
+				uint32_t rows[10];
+				window_rows(pl, (int)xy.x + dx - 1, (int)xy.y + dy - 1, rows);
+				const int d = (int)__popcll(window_hash(rows, 4) ^ c_tile[sy]);
+				best = d - t_sym + 1 > best ? d - t_sym + 1 : best;
 			}
-			enc[k] = (uint8_t)v;
-			score[k] = (int16_t)best;
 		}
-		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-		__builtin_amdgcn_wave_barrier();
-		int e = 0;
-		if (!ok) {
-			e = er_select(score, lane, e_max, s_pos[wv]);
-			if (e == 0) { if (lane == 0) s_st[b] = -2; continue; }   // nothing to erase: errors-only already failed it
-		}
-		int nerr = 0;
-		int st = er_decode(s, wv, lane, e, s_pos[wv], &nerr);
-		// a retried block must also leave ERASURE_SLACK syndromes unused: a damaged block lies within s errors of SOME codeword on its n - e
-		// unerased bytes with probability ~ C(n - e, s) 255^s / 256^(p - e), which the codeword check cannot see (1 in 200 blocks at
-		// p - e = 8, s = 4); with 2 s <= p - e - 6 it is below 1e-14
-		if (st == 1 && e > 0 && 2 * nerr > RS_PARITY - e - ERASURE_SLACK) st = 0;
-		if (st == 1) {
-			uint8_t* dst = fc + (size_t)j * CHUNK + (size_t)(b % BLOCKS_PER_CHUNK) * RS_DATA;
-			for (int k = lane; k < RS_DATA; k += 64) dst[k] = enc[k];
-		}
-		if (lane == 0) s_st[b] = (int8_t)st;
-	}
-	__syncthreads();
-	__shared__ uint32_t s_new;
-	if (threadIdx.x == 0) {
-		uint32_t m = mask;
-		for (int j = 0; j < SYM_CHUNKS; ++j) {
-			if (mask & (1u << j)) continue;
-			bool all = true;
-			for (int q = 0; q < BLOCKS_PER_CHUNK; ++q) all = all && s_st[j * BLOCKS_PER_CHUNK + q] == 1;
-			if (all) m |= 1u << j;
-		}
-		s_new = m;
-		masks[f] = m;
-	}
-	__syncthreads();
-	const uint32_t m = s_new;
-	for (int j = 0; j < SYM_CHUNKS; ++j)
-		if (!(m & (1u << j)))
-			for (int k = threadIdx.x; k < CHUNK; k += 256) fc[(size_t)j * CHUNK + k] = 0;
+		return ErByte{v, best};
+	});
+	er_commit(mask | done, masks + f, fc, 0, SYM_CHUNKS);
 }
 
 // ------------------------------------------------------------------------------------------------ colour erasure retry of a decoded frame
@@ -386,12 +418,10 @@ __global__ __launch_bounds__(256) void k_erasure_frame(const uint32_t* __restric
 //    did, and the matrix in force (ccm_used[f], active flag included). The workgroup computes it for every cell of the frame once, into
 //    margins[f] (the tap).
 //  * selection: a colour-stream byte comes from four cells (2 bits each); its score is max over them of c_margin - margin(c), flagged when the
-//    score is > 0. The e_max highest scores are kept, ties to the lower byte position (er_select, as k_erasure_frame).
-//  * retry and acceptance as in k_erasure_frame, block for block: a block errors-only decoding failed is decoded again with those erasures (none
-//    flagged: not retried), a block it decoded is decoded again with none; accepted = status 1 and, with erasures, 2 errors <= p - e -
-//    ERASURE_SLACK. A colour chunk whose blocks are all accepted gets its bytes and its mask bit; the slots of colour chunks still missing
-//    are zeroed again. Chunks already in the mask, the symbol chunks, rs_ok, the frame state, the colours and the colour-correction carry are
-//    not touched.
+//    score is > 0. The e_max highest scores are kept, ties to the lower byte position.
+//  * retry, acceptance and the mask update are er_retry_blocks and er_commit over the colour blocks: a colour chunk whose blocks are all
+//    accepted gets its bytes and its mask bit; the slots of colour chunks still missing are zeroed again. Chunks already in the mask, the
+//    symbol chunks, rs_ok, the frame state, the colours and the colour-correction carry are not touched.
 __global__ __launch_bounds__(256) void k_colour_erasure_frame(const uint8_t* __restrict__ rgb, const uint32_t* __restrict__ cellmean, Tables tb,
                                                               const uint8_t* __restrict__ colors, const int8_t* __restrict__ drift,
                                                               const uint32_t* __restrict__ flood_flag, const float* __restrict__ ccm_used,
@@ -400,22 +430,15 @@ __global__ __launch_bounds__(256) void k_colour_erasure_frame(const uint8_t* __r
 {
 	if constexpr (LEGACY) return;                          // (one coupled stream: no colour-only blocks; the host never launches it there)
 	constexpr uint32_t COL_MASK = ((1u << COL_CHUNKS) - 1u) << SYM_CHUNKS;
-	constexpr int NB = COL_BLOCKS > 0 ? COL_BLOCKS : 1;
 	const int f = f0 + blockIdx.x;
 	const uint32_t mask = masks[f];
 	if ((mask & COL_MASK) == COL_MASK) {                   // (uniform over the workgroup)
 		if (threadIdx.x == 0) worked[f] = 0;
 		return;
 	}
-	__shared__ RsEraShared s;
-	__shared__ int32_t s_score[4][192];
-	__shared__ uint8_t s_pos[4][64];
-	__shared__ int8_t s_st[NB];
 	__shared__ float s_m[10];
-	er_tables(s);
 	if (threadIdx.x < 10) s_m[threadIdx.x] = ccm_used[(size_t)f * 10 + threadIdx.x];
 	__syncthreads();
-	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 	const bool flooded = flood_flag[f] != 0;
 	const bool active = s_m[9] != 0.0f;
 	uint32_t* mg = margins + (size_t)f * NCELLS;
@@ -435,60 +458,20 @@ __global__ __launch_bounds__(256) void k_colour_erasure_frame(const uint8_t* __r
 	__syncthreads();                                       // (the margins are read back below by other lanes of this workgroup)
 	const uint8_t* cf = colors + (size_t)f * NCELLS;
 	uint8_t* fc = chunks + (size_t)f * FRAME_BYTES;
-	for (int b = SYM_BLOCKS + wv; b < ALL_BLOCKS; b += 4) {
-		const int j = b / BLOCKS_PER_CHUNK, cb = b - SYM_BLOCKS;
-		if (mask & (1u << j)) { if (lane == 0) s_st[cb] = 2; continue; }
-		const bool ok = rs_ok[(size_t)f * ALL_BLOCKS + b] != 0;
-		uint8_t* enc = s.enc[wv];
-		int32_t* score = s_score[wv];
-		for (int k = lane; k < RS_BLOCK; k += 64) {
-			const int sidx = (RS_BLOCK * cb + k) * 4;
-			int best = INT_MIN;
-			uint32_t v = 0;
+	const uint32_t done = er_retry_blocks<int32_t, SYM_BLOCKS, COL_BLOCKS>(COL_MASK & ~mask, rs_ok + (size_t)f * ALL_BLOCKS, e_max, fc, [&](int b, int k, bool ok) {
+		const int sidx = (RS_BLOCK * (b - SYM_BLOCKS) + k) * 4;
+		int best = INT_MIN;
+		uint32_t v = 0;
 #pragma unroll
-			for (int q = 0; q < 4; ++q) {
-				const int cell = tb.stream_cell[sidx + q];
-				v = (v << 2) | (cf[cell] & 3u);
-				if (!ok) {
-					const int sc = c_margin - (int)mg[cell];
-					best = sc > best ? sc : best;
-				}
+		for (int q = 0; q < 4; ++q) {
+			const int cell = tb.stream_cell[sidx + q];
+			v = (v << 2) | (cf[cell] & 3u);
+			if (!ok) {
+				const int sc = c_margin - (int)mg[cell];
+				best = sc > best ? sc : best;
 			}
-			enc[k] = (uint8_t)v;
-			score[k] = best;
 		}
-		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-		__builtin_amdgcn_wave_barrier();
-		int e = 0;
-		if (!ok) {
-			e = er_select(score, lane, e_max, s_pos[wv]);
-			if (e == 0) { if (lane == 0) s_st[cb] = -2; continue; }   // nothing to erase: errors-only already failed it
-		}
-		int nerr = 0;
-		int st = er_decode(s, wv, lane, e, s_pos[wv], &nerr);
-		if (st == 1 && e > 0 && 2 * nerr > RS_PARITY - e - ERASURE_SLACK) st = 0;   // (the slack rule of k_erasure_frame)
-		if (st == 1) {
-			uint8_t* dst = fc + (size_t)j * CHUNK + (size_t)(b % BLOCKS_PER_CHUNK) * RS_DATA;
-			for (int k = lane; k < RS_DATA; k += 64) dst[k] = enc[k];
-		}
-		if (lane == 0) s_st[cb] = (int8_t)st;
-	}
-	__syncthreads();
-	__shared__ uint32_t s_new;
-	if (threadIdx.x == 0) {
-		uint32_t m = mask;
-		for (int j = SYM_CHUNKS; j < CHUNKS; ++j) {
-			if (mask & (1u << j)) continue;
-			bool all = true;
-			for (int q = 0; q < BLOCKS_PER_CHUNK; ++q) all = all && s_st[j * BLOCKS_PER_CHUNK + q - SYM_BLOCKS] == 1;
-			if (all) m |= 1u << j;
-		}
-		s_new = m;
-		masks[f] = m;
-	}
-	__syncthreads();
-	const uint32_t m = s_new;
-	for (int j = SYM_CHUNKS; j < CHUNKS; ++j)
-		if (!(m & (1u << j)))
-			for (int k = threadIdx.x; k < CHUNK; k += 256) fc[(size_t)j * CHUNK + k] = 0;
+		return ErByte{v, best};
+	});
+	er_commit(mask | done, masks + f, fc, SYM_CHUNKS, CHUNKS);
 }

@@ -888,6 +888,31 @@ int ensure_group_capacity(cimbar_hip_ctx* ctx, int n)
 	return 0;
 }
 
+// where a combined call's group chunks and masks go on the device: the caller's buffers (device outputs), or the context's staging (host
+// outputs; it exists once ensure_group_capacity has run)
+struct GroupOut { uint8_t* chunks; uint32_t* masks; };
+GroupOut group_out(cimbar_hip_ctx* ctx, const CombineArgs& cb, int out_mem)
+{
+	if (out_mem == CIMBAR_HIP_MEM_DEVICE) return {cb.gchunks, cb.gmasks};
+	return {ctx->d_gchunks, ctx->d_gmasks};
+}
+
+// the groups' Reed-Solomon pass over `slots` group slots (k_rs LIVE: see combine.hip.inc), from the combined cells into d_gchunks / d_grs_ok
+void launch_group_rs(cimbar_hip_ctx* ctx, hipStream_t st, int slots, uint8_t* d_gchunks)
+{
+	const int* ng = ctx->d_ngroups;
+	const uint32_t* disp = ctx->d_gdisp;
+	if constexpr (LEGACY) {
+		hipLaunchKernelGGL((k_rs<CELL_BITS, false, true>), dim3((slots * ALL_BLOCKS + 3) / 4), dim3(256), 0, st, ctx->d_gsym, ctx->tb, 0, slots, 0, d_gchunks,
+		                   ctx->d_grs_ok, 0, (const uint8_t*)ctx->d_gcol, ng, disp);
+	} else {
+		hipLaunchKernelGGL((k_rs<4, false, true>), dim3((slots * SYM_BLOCKS + 3) / 4), dim3(256), 0, st, ctx->d_gsym, ctx->tb, 0, slots, 0, d_gchunks,
+		                   ctx->d_grs_ok, 0, (const uint8_t*)nullptr, ng, disp);
+		hipLaunchKernelGGL((k_rs<2, false, true>), dim3((slots * COL_BLOCKS + 3) / 4), dim3(256), 0, st, ctx->d_gcol, ctx->tb, 0, slots, SYM_CHUNKS, d_gchunks,
+		                   ctx->d_grs_ok, SYM_BLOCKS, (const uint8_t*)nullptr, ng, disp);
+	}
+}
+
 // G1-G4 behind a batch's per-capture decode, on the same stream; reads that decode's intermediates and outputs (d_chunks / d_masks), writes
 // the group outputs (d_gchunks / d_gmasks, n slots) and the context's group scratch. d_status: the capture path's extraction status (stride
 // ints apart), nullptr: every capture usable. d_rgb: the frames that decode read (the colour vote takes a flooded member's means from them).
@@ -902,9 +927,7 @@ int enqueue_combine(cimbar_hip_ctx* ctx, hipStream_t st, int n, const uint8_t* d
 		HIPCHK(ctx->d_gcm.reserve((size_t)n * NCELLS));
 		HIPCHK(ctx->d_gcw.reserve((size_t)n * NCELLS));
 	}
-	// (device outputs: the caller's buffers; host outputs: the context's staging, which exists from here on)
-	uint8_t* d_gchunks = out_mem == CIMBAR_HIP_MEM_DEVICE ? cb.gchunks : ctx->d_gchunks;
-	uint32_t* d_gmasks = out_mem == CIMBAR_HIP_MEM_DEVICE ? cb.gmasks : ctx->d_gmasks;
+	const GroupOut out = group_out(ctx, cb, out_mem);
 	if (cb.groups_in) HIPCHK(hipMemcpyAsync(ctx->d_groups_in, cb.groups_in, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, st));
 	HIPCHK(hipMemsetAsync(ctx->d_gcount, 0, sizeof(int) * (size_t)n, st));
 	HIPCHK(hipMemsetAsync(ctx->d_gdisp, 0, sizeof(uint32_t) * (size_t)n, st));
@@ -917,20 +940,12 @@ int enqueue_combine(cimbar_hip_ctx* ctx, hipStream_t st, int n, const uint8_t* d
 	if (vote)
 		hipLaunchKernelGGL(k_group_colour, dim3(n), dim3(256), 0, st, d_rgb, cur.d_cellmean, ctx->tb, cur.d_colors, cur.d_drift, cur.d_flood, cur.d_ccm_used,
 		                   ctx->d_gmem, ctx->d_gcount, ctx->d_ngroups, ctx->d_gdisp, ctx->d_gcol, ctx->d_gcm, ctx->d_gcw);
-	if constexpr (LEGACY) {
-		hipLaunchKernelGGL((k_rs<CELL_BITS, false, true>), dim3((n * ALL_BLOCKS + 3) / 4), dim3(256), 0, st, ctx->d_gsym, ctx->tb, 0, n, 0, d_gchunks, ctx->d_grs_ok, 0,
-		                   (const uint8_t*)ctx->d_gcol, (const int*)ctx->d_ngroups, (const uint32_t*)ctx->d_gdisp);
-	} else {
-		hipLaunchKernelGGL((k_rs<4, false, true>), dim3((n * SYM_BLOCKS + 3) / 4), dim3(256), 0, st, ctx->d_gsym, ctx->tb, 0, n, 0, d_gchunks, ctx->d_grs_ok, 0,
-		                   (const uint8_t*)nullptr, (const int*)ctx->d_ngroups, (const uint32_t*)ctx->d_gdisp);
-		hipLaunchKernelGGL((k_rs<2, false, true>), dim3((n * COL_BLOCKS + 3) / 4), dim3(256), 0, st, ctx->d_gcol, ctx->tb, 0, n, SYM_CHUNKS, d_gchunks, ctx->d_grs_ok,
-		                   SYM_BLOCKS, (const uint8_t*)nullptr, (const int*)ctx->d_ngroups, (const uint32_t*)ctx->d_gdisp);
-	}
+	launch_group_rs(ctx, st, n, out.chunks);
 	hipLaunchKernelGGL(k_group_end, dim3(n), dim3(256), 0, st, ctx->d_gsym, ctx->d_gmargin, ctx->tb, ctx->d_gmem, ctx->d_gcount, ctx->d_ngroups, ctx->d_grs_ok,
-	                   d_chunks, d_masks, ctx->d_gdisp, d_gchunks, d_gmasks, (!LEGACY && ctx->er_sym > 0) ? 1 : 0, erasure_max(ctx));
+	                   d_chunks, d_masks, ctx->d_gdisp, out.chunks, out.masks, (!LEGACY && ctx->er_sym > 0) ? 1 : 0, erasure_max(ctx));
 	if (vote && ctx->ec_margin > 0)
 		hipLaunchKernelGGL(k_group_colour_retry, dim3(n), dim3(256), 0, st, ctx->d_gcol, ctx->d_gcm, ctx->tb, ctx->d_gcount, ctx->d_ngroups, ctx->d_gdisp,
-		                   ctx->d_grs_ok, d_gchunks, d_gmasks, ctx->ec_margin, colour_erasure_max(ctx));
+		                   ctx->d_grs_ok, out.chunks, out.masks, ctx->ec_margin, colour_erasure_max(ctx));
 	HIPCHK(hipGetLastError());
 	ctx->gcv_valid = vote;
 	return 0;
@@ -965,8 +980,7 @@ int enqueue_combine_stream(cimbar_hip_ctx* ctx, hipStream_t st, int n, const uin
 	cimbar_hip_ctx::ScratchSet& cur = ctx->cur();
 	const CarryStore cs = s.store();
 	const int slots = n + 1;
-	uint8_t* d_gchunks = out_mem == CIMBAR_HIP_MEM_DEVICE ? cb.gchunks : ctx->d_gchunks;
-	uint32_t* d_gmasks = out_mem == CIMBAR_HIP_MEM_DEVICE ? cb.gmasks : ctx->d_gmasks;
+	const GroupOut out = group_out(ctx, cb, out_mem);
 	int* d_gsizes = (out_mem == CIMBAR_HIP_MEM_DEVICE && cb.gsizes) ? cb.gsizes : s.gsizes;
 	if (s.used) HIPCHK(hipStreamWaitEvent(st, s.ev_last, 0));
 	s.used = true;
@@ -978,17 +992,9 @@ int enqueue_combine_stream(cimbar_hip_ctx* ctx, hipStream_t st, int n, const uin
 	                   ctx->d_groups, ctx->d_gmem, ctx->d_gcount, ctx->d_ngroups, s.words + 1);
 	hipLaunchKernelGGL(k_group_cells_stream, dim3(GC_BLOCKS, slots), dim3(256), 0, st, cur.d_plane, ctx->tb, cur.d_symbols, cur.d_colors, cur.d_drift,
 	                   cur.d_flood, ctx->d_gmem, ctx->d_gcount, ctx->d_ngroups, ctx->d_gsym, ctx->d_gcol, ctx->d_gmargin, ctx->d_gdisp, cs);
-	if constexpr (LEGACY) {
-		hipLaunchKernelGGL((k_rs<CELL_BITS, false, true>), dim3((slots * ALL_BLOCKS + 3) / 4), dim3(256), 0, st, ctx->d_gsym, ctx->tb, 0, slots, 0, d_gchunks,
-		                   ctx->d_grs_ok, 0, (const uint8_t*)ctx->d_gcol, (const int*)ctx->d_ngroups, (const uint32_t*)ctx->d_gdisp);
-	} else {
-		hipLaunchKernelGGL((k_rs<4, false, true>), dim3((slots * SYM_BLOCKS + 3) / 4), dim3(256), 0, st, ctx->d_gsym, ctx->tb, 0, slots, 0, d_gchunks,
-		                   ctx->d_grs_ok, 0, (const uint8_t*)nullptr, (const int*)ctx->d_ngroups, (const uint32_t*)ctx->d_gdisp);
-		hipLaunchKernelGGL((k_rs<2, false, true>), dim3((slots * COL_BLOCKS + 3) / 4), dim3(256), 0, st, ctx->d_gcol, ctx->tb, 0, slots, SYM_CHUNKS, d_gchunks,
-		                   ctx->d_grs_ok, SYM_BLOCKS, (const uint8_t*)nullptr, (const int*)ctx->d_ngroups, (const uint32_t*)ctx->d_gdisp);
-	}
+	launch_group_rs(ctx, st, slots, out.chunks);
 	hipLaunchKernelGGL(k_group_end_stream, dim3(slots), dim3(256), 0, st, ctx->d_gsym, ctx->d_gmargin, ctx->tb, ctx->d_gmem, ctx->d_gcount, ctx->d_ngroups,
-	                   ctx->d_grs_ok, d_chunks, d_masks, ctx->d_gdisp, d_gchunks, d_gmasks, (!LEGACY && ctx->er_sym > 0) ? 1 : 0, erasure_max(ctx), cs, d_gsizes);
+	                   ctx->d_grs_ok, d_chunks, d_masks, ctx->d_gdisp, out.chunks, out.masks, (!LEGACY && ctx->er_sym > 0) ? 1 : 0, erasure_max(ctx), cs, d_gsizes);
 	hipLaunchKernelGGL(k_group_carry, dim3(CARRY_ARRAYS * CARRY_PARTS, CARRY_SLOTS), dim3(256), 0, st, cur.d_plane, cur.d_symbols, cur.d_colors, cur.d_drift,
 	                   cur.d_flood, d_chunks, d_masks, ctx->d_gmem, ctx->d_ngroups, s.words + 1, ctx->d_groups, cs);
 	HIPCHK(hipGetLastError());
