@@ -277,9 +277,9 @@ int64_t cimbar_hip_scan_extract_decode_batch_combined_fmt(cimbar_hip_ctx* ctx, c
  * without a colour dispute contributes nothing), flagged when > 0, the max_erasures highest scores become erasures (ties to the lower byte),
  * and retry, acceptance and the mask update are the per-capture colour retry's. Chunks already in gmask are never rewritten. There is no
  * second threshold; with the vote on and the colour erasure setting off only the vote changes.
- * Modes 4 and 8 refuse on != 0 (EINVAL): the coupled stream has no colour chunks of its own. Not covered: the stream calls below
- * (..._combined_stream) behave with the setting on exactly as with it off -- the carried members hold no means and no matrices to recompute
- * margins from. Takes effect for combined batches issued after the call. get: writes 1 or 0 to *on and returns 0. */
+ * Modes 4 and 8 refuse on != 0 (EINVAL): the coupled stream has no colour chunks of its own. This setting governs the plain combined calls
+ * only: the stream calls below (..._combined_stream) behave with it on exactly as with it off, and have a setting of their own
+ * (cimbar_hip_set_stream_colour_vote). Takes effect for combined batches issued after the call. get: writes 1 or 0 to *on and returns 0. */
 int cimbar_hip_set_group_colour_vote(cimbar_hip_ctx* ctx, int on);
 int cimbar_hip_get_group_colour_vote(cimbar_hip_ctx* ctx, int* on);
 
@@ -317,6 +317,19 @@ int64_t cimbar_hip_scan_extract_decode_batch_combined_stream_fmt(cimbar_hip_ctx*
                                                                  int* groups_out, uint8_t* gchunks, uint32_t* gmasks, int* gsizes, int* n_groups,
                                                                  int out_mem, void* hip_stream);
 int cimbar_hip_combine_stream_reset(cimbar_hip_ctx* ctx);
+
+/* Colour vote in the stream calls (off after cimbar_hip_create; governs the stream calls only, as cimbar_hip_set_group_colour_vote governs the
+ * plain combined calls only). With it on, a sequence of stream calls whose last call has flush != 0 reports the group outputs -- gchunks,
+ * gmasks, gsizes, the colour of the combined cells and the group colour margin -- that ONE cimbar_hip_decode_batch_combined call with
+ * cimbar_hip_set_group_colour_vote(ctx, 1) reports for the concatenation of the captures, byte for byte, each group in the call in which it
+ * closes; with cimbar_hip_set_colour_erasure_decode on in both, the group colour retry included. A member's weight w_c = marg_c + 1 depends on
+ * the member alone, so the carry holds, per member, the weight of every cell (cells u32, about 50 KB in mode 68; allocated by the first stream
+ * call with the setting on) -- no means, matrices or frames.
+ * A stream samples the setting in its first call after create or cimbar_hip_combine_stream_reset and holds it, like min_agree_permille and
+ * max_group: a stream call that finds it changed is CIMBAR_HIP_EINVAL, checked before anything is enqueued, and leaves the open group as it
+ * was. Modes 4 and 8 refuse on != 0 (EINVAL). get: writes 1 or 0 to *on and returns 0. */
+int cimbar_hip_set_stream_colour_vote(cimbar_hip_ctx* ctx, int on);
+int cimbar_hip_get_stream_colour_vote(cimbar_hip_ctx* ctx, int* on);
 
 /* ---- chunk delivery: a batch's slots and masks -> what a fountain sink eats --------------------------------------------------------------
  * The batch entry points above report a frame's chunks in fixed slots plus one mask word. The reference's receive interface has another shape:
@@ -618,11 +631,16 @@ enum {
 	CIMBAR_HIP_TAP_SCAN_PATH = 14,    /* n int32               : 0 = the fast search kernels answered, 1 = one of their fixed lists overflowed and the
 	                                     serial search answered, 2 = gave up (more than 16 overflowing captures in the batch, or the serial search's
 	                                     own lists overflowed): the capture is reported as a failure */
-	/* the colour vote of the last plain combined batch (cimbar_hip_set_group_colour_vote; CIMBAR_HIP_EINVAL when that batch ran with the setting
-	 * off, was a stream call, or was no combined batch) */
+	/* the colour vote of the last combined batch: a plain one with cimbar_hip_set_group_colour_vote on, or a stream call of a stream with
+	 * cimbar_hip_set_stream_colour_vote on (CIMBAR_HIP_EINVAL when that batch ran with its setting off or was no combined batch). After a stream
+	 * call n_groups counts the groups closed in it and n its own captures. */
 	CIMBAR_HIP_TAP_GROUP_COLOUR_MARGIN = 15, /* n_groups * cells u32: the group colour margin gm, 0xFFFFFFFF where the members' colours all agree */
-	CIMBAR_HIP_TAP_GROUP_COLOUR_WEIGHTS = 16 /* n * cells u32       : the weight each capture contributed to its group's vote; 0 for cells without a
-	                                            colour dispute and for captures in no group */
+	CIMBAR_HIP_TAP_GROUP_COLOUR_WEIGHTS = 16,/* n * cells u32       : the weight each capture contributed to its group's vote; 0 for cells without a
+	                                            colour dispute and for captures in no group (stream call: in no group that closed in the call) */
+	/* the carry store after the last batch, when that was a stream call of a stream with cimbar_hip_set_stream_colour_vote on (else
+	 * CIMBAR_HIP_EINVAL) */
+	CIMBAR_HIP_TAP_STREAM_CARRY_WEIGHTS = 17 /* rows * cells u32    : the carried weights of slots 0 .. rows - 1 (the open group's members in capture
+	                                            order), every cell filled; rows = out_bytes / (cells * 4), CIMBAR_HIP_EINVAL above the occupied slots */
 };
 int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_bytes);
 

@@ -206,6 +206,18 @@ int cimbar_hip_get_group_colour_vote(cimbar_hip_ctx* ctx, int* on)
 	return CIMBAR_FWD(cimbar_hip_get_group_colour_vote, on);
 }
 
+int cimbar_hip_set_stream_colour_vote(cimbar_hip_ctx* ctx, int on)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return CIMBAR_FWD(cimbar_hip_set_stream_colour_vote, on);
+}
+
+int cimbar_hip_get_stream_colour_vote(cimbar_hip_ctx* ctx, int* on)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return CIMBAR_FWD(cimbar_hip_get_stream_colour_vote, on);
+}
+
 int cimbar_hip_rs_decode_erasures(cimbar_hip_ctx* ctx, const uint8_t* blocks, int n, const uint8_t* erasures, const uint8_t* counts, int mem,
                                   uint8_t* msgs, int8_t* status, void* hip_stream)
 {

@@ -136,10 +136,12 @@ constexpr int GC_CELLS = 1024, GC_BLOCKS = (NCELLS + GC_CELLS - 1) / GC_CELLS;
 // a capture of the call's batch. An unusable capture is in no group, so a slot is a usable capture by construction and holds no status.
 constexpr int CARRY_SLOTS = GMAX - 1;
 constexpr size_t CS_CELLS = ((size_t)NCELLS + 15) / 16 * 16, CS_DRIFT = ((size_t)NCELLS * 2 + 15) / 16 * 16, CS_PLANE = ((size_t)PLANE_WORDS + 3) / 4 * 4,
-                 CS_CHUNKS = ((size_t)FRAME_BYTES + 15) / 16 * 16;   // slot strides (bytes, bytes, words, bytes): every slot starts on 16 bytes
+                 CS_CHUNKS = ((size_t)FRAME_BYTES + 15) / 16 * 16,   // slot strides (bytes, bytes, words, bytes): every slot starts on 16 bytes
+                 CS_WEIGHTS = ((size_t)NCELLS + 3) / 4 * 4;          // (words)
 struct CarryStore {
 	uint8_t* symbols; uint8_t* colors; uint32_t* plane; int8_t* drift; uint32_t* flood; uint8_t* chunks; uint32_t* masks;
 	int* count;
+	uint32_t* weights;   // the colour vote's weight of every cell of a member (cimbar_hip_set_stream_colour_vote); nullptr while the stream runs without it
 };
 
 // (CARRY = false is the plain calls' kernel as it always was: a member id is a batch index and `cs` is not read)
@@ -414,7 +416,8 @@ __global__ __launch_bounds__(256) void k_group_end(const uint8_t* __restrict__ g
 }
 
 // ------------------------------------------------------------------------------------------------ colour vote and group colour retry
-// Opt-in (cimbar_hip_set_group_colour_vote, modes 68 / 67 / 66, the plain combined calls only). With the setting off neither kernel is launched.
+// Opt-in (modes 68 / 67 / 66): cimbar_hip_set_group_colour_vote for the plain combined calls, cimbar_hip_set_stream_colour_vote for the stream calls
+// (k_group_colour_stream and k_group_carry_weights under "the stream calls"). With a call's setting off none of these kernels is launched.
 // G3c k_group_colour, behind G3 and in front of the groups' Reed-Solomon pass: one workgroup per group slot; a slot at or above the group count
 // and a group G3 did not flag (gdisp: no cell differs) return at once. For a cell whose members' colours differ (a "colour dispute"):
 //   w_c      = margin_c + 1, margin_c = color_fit<true> of member c from exactly what k_colors classified the cell from -- the K1 cell mean, or
@@ -431,14 +434,31 @@ constexpr uint32_t GCM_NONE = 0xFFFFFFFFu;
 constexpr int GV_WORDS = NCELLS / 4, GV_ROUNDS = (GV_WORDS + 255) / 256, GV_QCAP = GV_ROUNDS * 64 * 4;   // a wavefront's share of the cells at most
 static_assert(NCELLS <= 65536, "a queued cell index fits 16 bits");
 
-__global__ __launch_bounds__(256) void k_group_colour(const uint8_t* __restrict__ rgb, const uint32_t* __restrict__ cellmean, Tables tb,
-                                                      const uint8_t* __restrict__ colors, const int8_t* __restrict__ drift,
-                                                      const uint32_t* __restrict__ flood_flag, const float* __restrict__ ccm_used,
-                                                      const int* __restrict__ gmem, const int* __restrict__ gcount, const int* __restrict__ ngroups,
-                                                      const uint32_t* __restrict__ gdisp, uint8_t* __restrict__ gcol, uint32_t* __restrict__ gcm,
-                                                      uint32_t* __restrict__ gcw)
+// (CARRY = false is the plain calls' kernel as it always was. CARRY, the stream calls' k_group_colour_stream: a member id below CARRY_SLOTS names a
+// carry slot, as in G3 -- its colour byte comes from cs.colors and its weight from the row k_group_carry_weights wrote while the member's batch was
+// on the device, so neither a mean nor a matrix is read for it, and it has no gcw row: gcw has one row per capture of the call)
+template <bool CARRY>
+__device__ __forceinline__ void group_colour_body(const uint8_t* __restrict__ rgb, const uint32_t* __restrict__ cellmean, const Tables& tb,
+                                                  const uint8_t* __restrict__ colors, const int8_t* __restrict__ drift,
+                                                  const uint32_t* __restrict__ flood_flag, const float* __restrict__ ccm_used,
+                                                  const int* __restrict__ gmem, const int* __restrict__ gcount, const int* __restrict__ ngroups,
+                                                  const uint32_t* __restrict__ gdisp, uint8_t* __restrict__ gcol, uint32_t* __restrict__ gcm,
+                                                  uint32_t* __restrict__ gcw, const CarryStore& cs)
 {
 	if constexpr (LEGACY) return;                          // (one coupled stream: the host never launches it there)
+	// a member id -> is it a carry slot, its index in the call's batch, its colour bytes
+	auto carried = [&](int f) -> bool {
+		if constexpr (CARRY) return f < CARRY_SLOTS;
+		else return false;
+	};
+	auto cap_of = [&](int f) -> int {
+		if constexpr (CARRY) return f - CARRY_SLOTS;
+		else return f;
+	};
+	auto col_of = [&](int f) -> const uint8_t* {
+		if constexpr (CARRY) return f < CARRY_SLOTS ? cs.colors + (size_t)f * CS_CELLS : colors + (size_t)(f - CARRY_SLOTS) * NCELLS;
+		else return colors + (size_t)f * NCELLS;
+	};
 	const int g = blockIdx.x;
 	if (g >= *ngroups || gdisp[g] == 0) return;            // (uniform over the workgroup)
 	const int m = gcount[g] < GMAX ? gcount[g] : GMAX;
@@ -449,11 +469,12 @@ __global__ __launch_bounds__(256) void k_group_colour(const uint8_t* __restrict_
 	if (threadIdx.x < GMAX) {
 		const int f = (int)threadIdx.x < m ? gmem[(size_t)g * GMAX + threadIdx.x] : 0;
 		s_mem[threadIdx.x] = f;
-		s_flood[threadIdx.x] = (int)threadIdx.x < m ? flood_flag[f] : 0u;
+		s_flood[threadIdx.x] = ((int)threadIdx.x < m && !carried(f)) ? flood_flag[cap_of(f)] : 0u;
 	}
 	if (threadIdx.x < GMAX * 10) {
 		const int c = threadIdx.x / 10, k = threadIdx.x % 10;
-		s_ccm[c][k] = c < m ? ccm_used[(size_t)gmem[(size_t)g * GMAX + c] * 10 + k] : 0.0f;
+		const int f = c < m ? gmem[(size_t)g * GMAX + c] : 0;
+		s_ccm[c][k] = (c < m && !carried(f)) ? ccm_used[(size_t)cap_of(f) * 10 + k] : 0.0f;
 	}
 	__syncthreads();
 	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -466,17 +487,19 @@ __global__ __launch_bounds__(256) void k_group_colour(const uint8_t* __restrict_
 		const int w = r * 256 + (int)threadIdx.x;
 		uint32_t x = 0;
 		if (w < GV_WORDS) {
-			const uint32_t c0 = reinterpret_cast<const uint32_t*>(colors + (size_t)s_mem[0] * NCELLS)[w];
-			for (int c = 1; c < m; ++c) x |= (reinterpret_cast<const uint32_t*>(colors + (size_t)s_mem[c] * NCELLS)[w] ^ c0) & CM;
+			const uint32_t c0 = reinterpret_cast<const uint32_t*>(col_of(s_mem[0]))[w];
+			for (int c = 1; c < m; ++c) x |= (reinterpret_cast<const uint32_t*>(col_of(s_mem[c]))[w] ^ c0) & CM;
 			if (x == 0) {
 				reinterpret_cast<uint4*>(om)[w] = make_uint4(GCM_NONE, GCM_NONE, GCM_NONE, GCM_NONE);
-				for (int c = 0; c < m; ++c) reinterpret_cast<uint4*>(gcw + (size_t)s_mem[c] * NCELLS)[w] = make_uint4(0u, 0u, 0u, 0u);
+				for (int c = 0; c < m; ++c)
+					if (!carried(s_mem[c])) reinterpret_cast<uint4*>(gcw + (size_t)cap_of(s_mem[c]) * NCELLS)[w] = make_uint4(0u, 0u, 0u, 0u);
 			} else {
 #pragma unroll
 				for (int b = 0; b < 4; ++b)
 					if (((x >> (8 * b)) & 0xFFu) == 0) {
 						om[4 * w + b] = GCM_NONE;
-						for (int c = 0; c < m; ++c) gcw[(size_t)s_mem[c] * NCELLS + 4 * w + b] = 0u;
+						for (int c = 0; c < m; ++c)
+							if (!carried(s_mem[c])) gcw[(size_t)cap_of(s_mem[c]) * NCELLS + 4 * w + b] = 0u;
 					}
 			}
 		}
@@ -499,7 +522,16 @@ __global__ __launch_bounds__(256) void k_group_colour(const uint8_t* __restrict_
 #pragma unroll
 		for (int k = 0; k < NCOLORS; ++k) score[k] = 0;
 		for (int c = 0; c < m; ++c) {
-			const int f = s_mem[c];
+			if constexpr (CARRY) {
+				if (carried(s_mem[c])) {               // its weight was taken when its batch was on the device; no gcw row
+					const uint32_t wgt = cs.weights[(size_t)s_mem[c] * CS_WEIGHTS + i];
+					const uint32_t mine = col_of(s_mem[c])[i] & (uint32_t)(NCOLORS - 1);
+#pragma unroll
+					for (int k = 0; k < NCOLORS; ++k) score[k] += mine == (uint32_t)k ? wgt : 0u;
+					continue;
+				}
+			}
+			const int f = cap_of(s_mem[c]);
 			uint32_t col[3];
 			if (s_flood[c] != 0) {
 				const int x = (int)xy.x + drift[((size_t)f * NCELLS + i) * 2], y = (int)xy.y + drift[((size_t)f * NCELLS + i) * 2 + 1];
@@ -523,6 +555,16 @@ __global__ __launch_bounds__(256) void k_group_colour(const uint8_t* __restrict_
 		oc[i] = (uint8_t)win;
 		om[i] = best - second;
 	}
+}
+
+__global__ __launch_bounds__(256) void k_group_colour(const uint8_t* __restrict__ rgb, const uint32_t* __restrict__ cellmean, Tables tb,
+                                                      const uint8_t* __restrict__ colors, const int8_t* __restrict__ drift,
+                                                      const uint32_t* __restrict__ flood_flag, const float* __restrict__ ccm_used,
+                                                      const int* __restrict__ gmem, const int* __restrict__ gcount, const int* __restrict__ ngroups,
+                                                      const uint32_t* __restrict__ gdisp, uint8_t* __restrict__ gcol, uint32_t* __restrict__ gcm,
+                                                      uint32_t* __restrict__ gcw)
+{
+	group_colour_body<false>(rgb, cellmean, tb, colors, drift, flood_flag, ccm_used, gmem, gcount, ngroups, gdisp, gcol, gcm, gcw, CarryStore{});
 }
 
 // G4c k_group_colour_retry, behind G4 (armed by the vote together with cimbar_hip_set_colour_erasure_decode): k_colour_erasure_frame's retry over
@@ -572,6 +614,8 @@ __global__ __launch_bounds__(256) void k_group_colour_retry(const uint8_t* __res
 // capture j >= c is capture k = j - c of the call. Only groups that CLOSE in the call get ids, are decoded (G3, k_rs LIVE, G4 run over
 // n + 1 group slots) and reported; the group still open at the end is copied into the carry store by k_group_carry. c, the open group and
 // its members never leave the device.
+// With cimbar_hip_set_stream_colour_vote on, the colour vote runs over the virtual batch as well (G3cs k_group_colour_stream, G4c as it is): the
+// carry store then holds the vote's weight of every cell of every carried member (G5w k_group_carry_weights) -- weights, not means or matrices.
 
 // G1s: one workgroup per capture k < n: agree[k] = agree(predecessor, k), the predecessor being capture k - 1 or, for k = 0, the last
 // carried member (nothing carried: agree[0] is not written and not read)
@@ -685,6 +729,19 @@ __global__ __launch_bounds__(256) void k_group_end_stream(const uint8_t* __restr
 	group_end_body<true>(gsym, gmargin, tb, gmem, gcount, ngroups, grs_ok, chunks, masks, gdisp, gchunks, gmasks, e_on, e_max, cs, gsizes);
 }
 
+// G3cs k_group_colour_stream (cimbar_hip_set_stream_colour_vote), behind G3s and in front of the groups' Reed-Solomon pass, n + 1 group slots: the
+// colour vote over the virtual batch. The weight of a carried member is read from its carried row; everything else is k_group_colour.
+__global__ __launch_bounds__(256) void k_group_colour_stream(const uint8_t* __restrict__ rgb, const uint32_t* __restrict__ cellmean, Tables tb,
+                                                             const uint8_t* __restrict__ colors, const int8_t* __restrict__ drift,
+                                                             const uint32_t* __restrict__ flood_flag, const float* __restrict__ ccm_used,
+                                                             const int* __restrict__ gmem, const int* __restrict__ gcount,
+                                                             const int* __restrict__ ngroups, const uint32_t* __restrict__ gdisp,
+                                                             uint8_t* __restrict__ gcol, uint32_t* __restrict__ gcm, uint32_t* __restrict__ gcw,
+                                                             CarryStore cs)
+{
+	group_colour_body<true>(rgb, cellmean, tb, colors, drift, flood_flag, ccm_used, gmem, gcount, ngroups, gdisp, gcol, gcm, gcw, cs);
+}
+
 // bytes from src to dst by the whole workgroup: 16 bytes per lane where both ends and the length allow it, else dwords, else bytes
 __device__ __forceinline__ void carry_copy(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, size_t bytes)
 {
@@ -739,4 +796,38 @@ __global__ __launch_bounds__(256) void k_group_carry(const uint32_t* __restrict_
 	const size_t per = (bytes / CARRY_PARTS) & ~(size_t)15, lo = per * part, hi = part == CARRY_PARTS - 1 ? bytes : lo + per;
 	carry_copy(dst + lo, src + lo, hi - lo);
 	if (arr == 0 && part == 0 && threadIdx.x == 0) { cs.flood[r] = flood_flag[k]; cs.masks[r] = masks[k]; }
+}
+
+// G5w k_group_carry_weights (cimbar_hip_set_stream_colour_vote), next to G5 and behind every reader of the carried weights: the colour vote's
+// weight of EVERY cell of the open group's members that come from the call's batch, w = color_fit<true>.margin + 1 from what k_colors classified
+// the cell from under the member's matrix in force -- k_group_colour's weight, which depends on the member alone, evaluated while the member's
+// means, frame and matrix are still on the device. One lane per cell, workgroup (cell block, slot r); r at or above the open group's size
+// returns at once, and so does a member that is itself carried: it is slot r and keeps its row (k_group_carry's rule).
+constexpr int CW_BLOCKS = (NCELLS + 255) / 256;
+__global__ __launch_bounds__(256) void k_group_carry_weights(const uint8_t* __restrict__ rgb, const uint32_t* __restrict__ cellmean, Tables tb,
+                                                             const int8_t* __restrict__ drift, const uint32_t* __restrict__ flood_flag,
+                                                             const float* __restrict__ ccm_used, const int* __restrict__ gmem,
+                                                             const int* __restrict__ ngroups, const int* __restrict__ open_size, CarryStore cs)
+{
+	if constexpr (LEGACY) return;                          // (the host never launches it there)
+	const int r = blockIdx.y;
+	if (r >= *open_size) return;                           // (uniform over the workgroup, as is the next)
+	const int f = gmem[(size_t)*ngroups * GMAX + r];
+	if (f < CARRY_SLOTS) return;                           // already slot r
+	const size_t k = (size_t)(f - CARRY_SLOTS);
+	__shared__ float s_m[10];
+	if (threadIdx.x < 10) s_m[threadIdx.x] = ccm_used[k * 10 + threadIdx.x];
+	__syncthreads();
+	const int i = blockIdx.x * 256 + (int)threadIdx.x;
+	if (i >= NCELLS) return;
+	uint32_t col[3];
+	if (flood_flag[k] != 0) {
+		const ushort2 xy = tb.cell_xy[i];
+		const int x = (int)xy.x + drift[(k * NCELLS + i) * 2], y = (int)xy.y + drift[(k * NCELLS + i) * 2 + 1];
+		mean6x6(rgb + k * FRAME_RGB, x + 1, y + 1, col);
+	} else {
+		const uint32_t mv = cellmean[k * GRID_CELLS + tb.cell_grid[i]];
+		col[0] = mv & 0xFFu; col[1] = (mv >> 8) & 0xFFu; col[2] = (mv >> 16) & 0xFFu;
+	}
+	cs.weights[(size_t)r * CS_WEIGHTS + i] = color_fit<true>((float)col[0], (float)col[1], (float)col[2], s_m, s_m[9] != 0.0f).margin + 1u;
 }

@@ -5,12 +5,14 @@
 // counters and the event that orders one stream call behind the one before. Nothing of it exists until the first stream call.
 struct CombineStream {
 	DevBuf<uint8_t> symbols, colors, chunks; DevBuf<uint32_t> plane, flood, masks; DevBuf<int8_t> drift;
+	DevBuf<uint32_t> weights;                 // [CARRY_SLOTS][CS_WEIGHTS] the colour vote's weights of the carried members; allocated by the first stream call with cimbar_hip_set_stream_colour_vote on
 	DevBuf<int> words;                        // [0] occupied slots, [1] members of the open group of the call in flight (k_group_walk_stream -> k_group_carry)
 	DevBuf<int> gsizes;                       // staging for host-memory gsizes, n + 1 ints, grown on demand
 	Event ev_last;                            // behind the last stream call's work: the next one, on whatever stream, starts after it
 	bool used = false;
 	int min_agree = 0, max_group = 0;         // fixed by the first stream call after create / reset (0: not yet)
-	CarryStore store() const { return CarryStore{symbols, colors, plane, drift, flood, chunks, masks, words}; }
+	int vote = 0;                             // ... and so is cimbar_hip_set_stream_colour_vote's value (read while max_group != 0)
+	CarryStore store() const { return CarryStore{symbols, colors, plane, drift, flood, chunks, masks, words, weights}; }
 };
 
 struct cimbar_hip_ctx {
@@ -35,8 +37,10 @@ struct cimbar_hip_ctx {
 	DevBuf<int> d_ngroups;                      // 1 int
 	DevBuf<uint8_t> d_gchunks; DevBuf<uint32_t> d_gmasks;   // staging for host-memory group outputs
 	int gcv_on = 0;                             // cimbar_hip_set_group_colour_vote: off unless set (k_group_colour / k_group_colour_retry are then never launched)
-	bool gcv_valid = false;                     // the last batch was a plain combined one with the vote on (CIMBAR_HIP_TAP_GROUP_COLOUR_* describe it)
-	DevBuf<uint32_t> d_gcm, d_gcw;              // the vote's margins [groups][NCELLS] and member weights [captures][NCELLS]; allocated by the first combined call with the setting on
+	int sgv_on = 0;                             // cimbar_hip_set_stream_colour_vote: the same for the stream calls (k_group_colour_stream / k_group_carry_weights / k_group_colour_retry)
+	bool gcv_valid = false;                     // the last batch was a combined one that ran the vote (CIMBAR_HIP_TAP_GROUP_COLOUR_* describe it)
+	int gcv_stream_n = -1;                      // ... >= 0: a stream call of that many captures (CIMBAR_HIP_TAP_STREAM_CARRY_WEIGHTS describes its carry store)
+	DevBuf<uint32_t> d_gcm, d_gcw;              // the vote's margins [groups][NCELLS] and member weights [captures][NCELLS]; allocated by the first combined call with its setting on
 	std::unique_ptr<CombineStream> cstream;     // cimbar_hip_decode_batch_combined_stream / _scan_extract_decode_batch_combined_stream_fmt
 	int wave_adapt = 1;               // CIMBAR_HIP_FLOOD_WAVE_ADAPT=0: run k_flood_wave in front of every exact replay, whatever it achieved before
 	bool wave_ran = false;            // k_flood_wave ran in the batch h_flagged describes
@@ -483,6 +487,7 @@ int enqueue(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_rgb, int n, in
 	cimbar_hip_ctx::ScratchSet& cur = ctx->cur();
 	ctx->grp_valid = false;   // (the group taps describe a combined batch only until the next batch of any kind)
 	ctx->gcv_valid = false;
+	ctx->gcv_stream_n = -1;
 	// the colour retry (erasure.hip.inc) runs behind every chain that reports chunks; the set in use holds its margins
 	const bool colour_retry = !LEGACY && !plain && !symbols_only && ctx->ec_margin > 0;
 	if (colour_retry) { if (int r = ensure_margin_capacity(ctx, cur)) return r; }
@@ -853,7 +858,13 @@ int check_combine(cimbar_hip_ctx* ctx, const char* who, int n, CombineArgs& cb)
 			ctx->err = std::string(who) + ": min_agree_permille / max_group differ from the stream's (cimbar_hip_combine_stream_reset starts another)";
 			return CIMBAR_HIP_EINVAL;
 		}
-		s.max_group = cb.max_group; s.min_agree = cb.min_agree;
+		// (so a group opened without carried weights never meets a vote, and the other way round)
+		const int vote = (!LEGACY && ctx->sgv_on != 0) ? 1 : 0;
+		if (s.max_group != 0 && s.vote != vote) {
+			ctx->err = std::string(who) + ": cimbar_hip_set_stream_colour_vote changed in mid-stream (cimbar_hip_combine_stream_reset starts another)";
+			return CIMBAR_HIP_EINVAL;
+		}
+		s.max_group = cb.max_group; s.min_agree = cb.min_agree; s.vote = vote;
 	}
 	if (cb.groups_in) {
 		// -1 or an id; ids start at 0 and rise by one; each id's captures contiguous and at most max_group
@@ -948,6 +959,7 @@ int enqueue_combine(cimbar_hip_ctx* ctx, hipStream_t st, int n, const uint8_t* d
 		                   ctx->d_grs_ok, out.chunks, out.masks, ctx->ec_margin, colour_erasure_max(ctx));
 	HIPCHK(hipGetLastError());
 	ctx->gcv_valid = vote;
+	ctx->gcv_stream_n = -1;
 	return 0;
 }
 
@@ -966,17 +978,27 @@ int ensure_stream_capacity(cimbar_hip_ctx* ctx, int n)
 	HIPCHK(s.masks.ensure(CARRY_SLOTS));
 	if (!s.words) { HIPCHK(s.words.ensure(2)); HIPCHK(hipMemset(s.words, 0, sizeof(int) * 2)); }
 	HIPCHK(s.gsizes.reserve((size_t)n + 1));
+	if (s.vote) {   // (a context that never turns the stream vote on pays nothing)
+		HIPCHK(s.weights.ensure(CARRY_SLOTS * CS_WEIGHTS));
+		HIPCHK(ctx->d_gcm.reserve(((size_t)n + 1) * NCELLS));
+		HIPCHK(ctx->d_gcw.reserve((size_t)(n > 0 ? n : 1) * NCELLS));
+	}
 	return 0;
 }
 
 // The stream calls' G1-G5 behind a batch's per-capture decode (none for n == 0), on the same stream and behind the stream call before: the
-// virtual batch is the carry store's members followed by the n captures. Group outputs have n + 1 slots.
-int enqueue_combine_stream(cimbar_hip_ctx* ctx, hipStream_t st, int n, const uint8_t* d_chunks, const uint32_t* d_masks, const int* d_status, int stride,
-                           const CombineArgs& cb, int out_mem)
+// virtual batch is the carry store's members followed by the n captures. Group outputs have n + 1 slots. d_rgb: the frames that decode read.
+// The colour vote here is the stream's own setting (cimbar_hip_set_stream_colour_vote, sampled by check_combine), never the plain calls'; with
+// it the vote runs over the virtual batch, with the colour erasure setting on as well the group colour retry, and the weights of the members
+// that stay open are carried. Every reader of the carried weights is launched in front of their writer; nothing waits for the host.
+int enqueue_combine_stream(cimbar_hip_ctx* ctx, hipStream_t st, int n, const uint8_t* d_rgb, const uint8_t* d_chunks, const uint32_t* d_masks,
+                           const int* d_status, int stride, const CombineArgs& cb, int out_mem)
 {
 	if (int r = ensure_stream_capacity(ctx, n)) return r;
 	CombineStream& s = *ctx->cstream;
-	ctx->gcv_valid = false;   // (the stream calls run without the colour vote, whatever the setting)
+	const bool vote = !LEGACY && s.vote != 0;
+	ctx->gcv_valid = vote;
+	ctx->gcv_stream_n = vote ? n : -1;
 	cimbar_hip_ctx::ScratchSet& cur = ctx->cur();
 	const CarryStore cs = s.store();
 	const int slots = n + 1;
@@ -992,11 +1014,20 @@ int enqueue_combine_stream(cimbar_hip_ctx* ctx, hipStream_t st, int n, const uin
 	                   ctx->d_groups, ctx->d_gmem, ctx->d_gcount, ctx->d_ngroups, s.words + 1);
 	hipLaunchKernelGGL(k_group_cells_stream, dim3(GC_BLOCKS, slots), dim3(256), 0, st, cur.d_plane, ctx->tb, cur.d_symbols, cur.d_colors, cur.d_drift,
 	                   cur.d_flood, ctx->d_gmem, ctx->d_gcount, ctx->d_ngroups, ctx->d_gsym, ctx->d_gcol, ctx->d_gmargin, ctx->d_gdisp, cs);
+	if (vote)
+		hipLaunchKernelGGL(k_group_colour_stream, dim3(slots), dim3(256), 0, st, d_rgb, cur.d_cellmean, ctx->tb, cur.d_colors, cur.d_drift, cur.d_flood,
+		                   cur.d_ccm_used, ctx->d_gmem, ctx->d_gcount, ctx->d_ngroups, ctx->d_gdisp, ctx->d_gcol, ctx->d_gcm, ctx->d_gcw, cs);
 	launch_group_rs(ctx, st, slots, out.chunks);
 	hipLaunchKernelGGL(k_group_end_stream, dim3(slots), dim3(256), 0, st, ctx->d_gsym, ctx->d_gmargin, ctx->tb, ctx->d_gmem, ctx->d_gcount, ctx->d_ngroups,
 	                   ctx->d_grs_ok, d_chunks, d_masks, ctx->d_gdisp, out.chunks, out.masks, (!LEGACY && ctx->er_sym > 0) ? 1 : 0, erasure_max(ctx), cs, d_gsizes);
+	if (vote && ctx->ec_margin > 0)
+		hipLaunchKernelGGL(k_group_colour_retry, dim3(slots), dim3(256), 0, st, ctx->d_gcol, ctx->d_gcm, ctx->tb, ctx->d_gcount, ctx->d_ngroups, ctx->d_gdisp,
+		                   ctx->d_grs_ok, out.chunks, out.masks, ctx->ec_margin, colour_erasure_max(ctx));
 	hipLaunchKernelGGL(k_group_carry, dim3(CARRY_ARRAYS * CARRY_PARTS, CARRY_SLOTS), dim3(256), 0, st, cur.d_plane, cur.d_symbols, cur.d_colors, cur.d_drift,
 	                   cur.d_flood, d_chunks, d_masks, ctx->d_gmem, ctx->d_ngroups, s.words + 1, ctx->d_groups, cs);
+	if (vote)
+		hipLaunchKernelGGL(k_group_carry_weights, dim3(CW_BLOCKS, CARRY_SLOTS), dim3(256), 0, st, d_rgb, cur.d_cellmean, ctx->tb, cur.d_drift, cur.d_flood,
+		                   cur.d_ccm_used, ctx->d_gmem, ctx->d_ngroups, s.words + 1, cs);
 	HIPCHK(hipGetLastError());
 	return 0;
 }
@@ -1083,7 +1114,7 @@ int64_t decode_batch_impl(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rg
 	hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (any_device ? (hipStream_t)nullptr : ctx->stream);
 	if (int r = drain_pipeline_into(ctx, st)) return r;
 	if (strm && n == 0) {
-		if (int r = enqueue_combine_stream(ctx, st, 0, nullptr, nullptr, nullptr, 0, *cb, out_mem)) return r;
+		if (int r = enqueue_combine_stream(ctx, st, 0, nullptr, nullptr, nullptr, nullptr, 0, *cb, out_mem)) return r;
 		return finish_stream(ctx, st, 0, chunks, masks, nullptr, nullptr, out_mem, *cb);
 	}
 	if (int r = ensure_capacity(ctx, n)) return r;
@@ -1095,7 +1126,7 @@ int64_t decode_batch_impl(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rg
 
 	if (int r = enqueue(ctx, st, d_rgb, n, should_preprocess, color_correction, d_chunks, d_masks)) return r;
 	if (strm) {
-		if (int r = enqueue_combine_stream(ctx, st, n, d_chunks, d_masks, nullptr, 0, *cb, out_mem)) return r;
+		if (int r = enqueue_combine_stream(ctx, st, n, d_rgb, d_chunks, d_masks, nullptr, 0, *cb, out_mem)) return r;
 		return finish_stream(ctx, st, n, chunks, masks, d_chunks, d_masks, out_mem, *cb);
 	}
 	if (cb)
@@ -1653,7 +1684,7 @@ int64_t scan_extract_decode_impl(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsign
 		HIPCHK(hipSetDevice(ctx->device));
 		hipStream_t st0 = hip_stream ? (hipStream_t)hip_stream : (out_mem == CIMBAR_HIP_MEM_DEVICE ? (hipStream_t)nullptr : ctx->stream);
 		if (int r = drain_pipeline_into(ctx, st0)) return r;
-		if (int r = enqueue_combine_stream(ctx, st0, 0, nullptr, nullptr, nullptr, 0, *cb, out_mem)) return r;
+		if (int r = enqueue_combine_stream(ctx, st0, 0, nullptr, nullptr, nullptr, nullptr, 0, *cb, out_mem)) return r;
 		return finish_stream(ctx, st0, 0, chunks, masks, nullptr, nullptr, out_mem, *cb);
 	}
 	if (!rgb || !chunks || !masks || n <= 0 || width < 8 || height < 8) { ctx->err = std::string(who) + ": null buffer, n <= 0 or a capture smaller than 8x8"; return CIMBAR_HIP_EINVAL; }
@@ -1689,7 +1720,7 @@ int64_t scan_extract_decode_impl(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsign
 	hipLaunchKernelGGL(k_mask_failed, dim3(n), dim3(256), 0, st, &ctx->d_scan_res[0].status, stride, n, d_masks, d_chunks);
 	HIPCHK(hipGetLastError());
 	// ... nor any group (it is in none)
-	if (strm) { if (int r = enqueue_combine_stream(ctx, st, n, d_chunks, d_masks, &ctx->d_scan_res[0].status, stride, *cb, out_mem)) return r; }
+	if (strm) { if (int r = enqueue_combine_stream(ctx, st, n, ctx->d_ex_frames, d_chunks, d_masks, &ctx->d_scan_res[0].status, stride, *cb, out_mem)) return r; }
 	else if (cb)
 		if (int r = enqueue_combine(ctx, st, n, ctx->d_ex_frames, d_chunks, d_masks, &ctx->d_scan_res[0].status, stride, *cb, out_mem)) return r;
 	const hipMemcpyKind kind = out_mem == CIMBAR_HIP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
@@ -1842,6 +1873,22 @@ int cimbar_hip_get_group_colour_vote(cimbar_hip_ctx* ctx, int* on)
 	return 0;
 }
 
+int cimbar_hip_set_stream_colour_vote(cimbar_hip_ctx* ctx, int on)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	if (LEGACY && on) { ctx->err = "set_stream_colour_vote: modes 4 and 8 carry one coupled stream; the colour vote covers the colour chunks of modes 68 / 67 / 66"; return CIMBAR_HIP_EINVAL; }
+	// (a stream samples it in its first call after create / reset and refuses a call that finds it changed: check_combine)
+	ctx->sgv_on = on ? 1 : 0;
+	return 0;
+}
+
+int cimbar_hip_get_stream_colour_vote(cimbar_hip_ctx* ctx, int* on)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	if (on) *on = ctx->sgv_on;
+	return 0;
+}
+
 int cimbar_hip_rs_decode_erasures(cimbar_hip_ctx* ctx, const uint8_t* blocks, int n, const uint8_t* erasures, const uint8_t* counts, int mem,
                                   uint8_t* msgs, int8_t* status, void* hip_stream)
 {
@@ -1984,16 +2031,18 @@ int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_byte
 		}
 		case CIMBAR_HIP_TAP_GROUP_COLOUR_MARGIN:
 		case CIMBAR_HIP_TAP_GROUP_COLOUR_WEIGHTS: {
-			if (!ctx->grp_valid || !ctx->gcv_valid || !ctx->d_gcm || !ctx->d_gcw) { ctx->err = "tap: the last batch was not a combined one with the colour vote on (cimbar_hip_set_group_colour_vote)"; return CIMBAR_HIP_EINVAL; }
+			if (!ctx->grp_valid || !ctx->gcv_valid || !ctx->d_gcm || !ctx->d_gcw) { ctx->err = "tap: the last batch was not a combined one with its colour vote on (cimbar_hip_set_group_colour_vote / cimbar_hip_set_stream_colour_vote)"; return CIMBAR_HIP_EINVAL; }
 			int ng = 0;
 			HIPCHK(hipMemcpy(&ng, ctx->d_ngroups, sizeof(int), hipMemcpyDeviceToHost));
+			// (a stream call: the groups that closed in it and its own captures -- a flush without captures has none)
+			const size_t n = ctx->gcv_stream_n >= 0 ? (size_t)ctx->gcv_stream_n : (size_t)ctx->last_n;
 			const size_t G = (size_t)ng, rows = what == CIMBAR_HIP_TAP_GROUP_COLOUR_MARGIN ? G : n;
 			bytes = rows * NCELLS * sizeof(uint32_t);
 			if (out_bytes < bytes) { ctx->err = "tap: buffer too small"; return CIMBAR_HIP_EINVAL; }
 			std::vector<uint32_t> disp(G);
 			std::vector<int> grp(n);
 			if (G) HIPCHK(hipMemcpy(disp.data(), ctx->d_gdisp, sizeof(uint32_t) * G, hipMemcpyDeviceToHost));
-			HIPCHK(hipMemcpy(grp.data(), ctx->d_groups, sizeof(int) * n, hipMemcpyDeviceToHost));
+			if (n) HIPCHK(hipMemcpy(grp.data(), ctx->d_groups, sizeof(int) * n, hipMemcpyDeviceToHost));
 			if (bytes) HIPCHK(hipMemcpy(out, what == CIMBAR_HIP_TAP_GROUP_COLOUR_MARGIN ? ctx->d_gcm.get() : ctx->d_gcw.get(), bytes, hipMemcpyDeviceToHost));
 			// a group whose members agree on every cell was skipped by the vote: no margin; its members, and captures in no group, gave no weight
 			if (what == CIMBAR_HIP_TAP_GROUP_COLOUR_MARGIN) {
@@ -2002,6 +2051,16 @@ int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_byte
 				for (size_t k = 0; k < n; ++k) if (grp[k] < 0 || (size_t)grp[k] >= G || !disp[grp[k]]) std::memset((uint32_t*)out + k * NCELLS, 0, (size_t)NCELLS * sizeof(uint32_t));
 			}
 			return (int64_t)bytes;
+		}
+		case CIMBAR_HIP_TAP_STREAM_CARRY_WEIGHTS: {
+			// the carried weight rows of slots 0 .. rows - 1, rows = what the buffer holds; every cell of an occupied slot is filled
+			if (!ctx->grp_valid || !ctx->gcv_valid || ctx->gcv_stream_n < 0 || !ctx->cstream || !ctx->cstream->weights) { ctx->err = "tap: the last batch was not a stream call with the colour vote on (cimbar_hip_set_stream_colour_vote)"; return CIMBAR_HIP_EINVAL; }
+			const size_t row = (size_t)NCELLS * sizeof(uint32_t), rows = out_bytes / row;
+			int occupied = 0;
+			HIPCHK(hipMemcpy(&occupied, ctx->cstream->words, sizeof(int), hipMemcpyDeviceToHost));
+			if (rows > (size_t)occupied) { ctx->err = "tap: more rows than the carry store has occupied slots"; return CIMBAR_HIP_EINVAL; }
+			if (rows) HIPCHK(hipMemcpy2D(out, row, ctx->cstream->weights, CS_WEIGHTS * sizeof(uint32_t), row, rows, hipMemcpyDeviceToHost));
+			return (int64_t)(rows * row);
 		}
 #ifdef FLOOD_PROF
 		case 100: {   // cycle counters of the flood kernel, per workgroup area (= per frame while the batch fits the grid). k_flood: 10 x u64 (pop,

@@ -22,7 +22,8 @@ TAP_GROUP_CELLS, TAP_GROUP_MARGIN, TAP_GROUPS = 10, 11, 12
 GROUP_OPEN = -2   # CIMBAR_HIP_GROUP_OPEN: the capture's group is still open at the end of a stream call
 TAP_COLOUR_MARGIN = 13
 TAP_SCAN_PATH = 14
-TAP_GROUP_COLOUR_MARGIN, TAP_GROUP_COLOUR_WEIGHTS = 15, 16   # the colour vote of the last combined batch (set_group_colour_vote)
+TAP_GROUP_COLOUR_MARGIN, TAP_GROUP_COLOUR_WEIGHTS = 15, 16   # the colour vote of the last combined batch (set_group_colour_vote / set_stream_colour_vote)
+TAP_STREAM_CARRY_WEIGHTS = 17   # the carried weights of the open group's members after a stream call with set_stream_colour_vote on
 # CIMBAR_HIP_COLOUR_MARGIN_SUGGESTED (include/cimbar_hip.h): the colour erasure threshold chosen on rendered frames (DESIGN_WIDENING.md)
 COLOUR_MARGIN_SUGGESTED = 32512
 
@@ -44,6 +45,7 @@ EXPORTS = (
     "cimbar_hip_rs_decode_erasures", "cimbar_hip_set_erasure_decode", "cimbar_hip_get_erasure_decode",
     "cimbar_hip_set_colour_erasure_decode", "cimbar_hip_get_colour_erasure_decode",
     "cimbar_hip_set_group_colour_vote", "cimbar_hip_get_group_colour_vote",
+    "cimbar_hip_set_stream_colour_vote", "cimbar_hip_get_stream_colour_vote",
     "cimbar_hip_decode_batch_combined", "cimbar_hip_scan_extract_decode_batch_combined_fmt",
     "cimbar_hip_decode_batch_combined_stream", "cimbar_hip_scan_extract_decode_batch_combined_stream_fmt", "cimbar_hip_combine_stream_reset",
     "cimbar_hip_auto_create", "cimbar_hip_auto_destroy", "cimbar_hip_auto_bufsize", "cimbar_hip_auto_last_error", "cimbar_hip_auto_reset_ccm",
@@ -202,6 +204,11 @@ def load_library(path=None):
         lib.cimbar_hip_set_group_colour_vote.restype = i32
         lib.cimbar_hip_get_group_colour_vote.argtypes = [vp, ctypes.POINTER(i32)]
         lib.cimbar_hip_get_group_colour_vote.restype = i32
+    if hasattr(lib, "cimbar_hip_set_stream_colour_vote"):   # (the same: tools/stream_colour_bench.py --lib)
+        lib.cimbar_hip_set_stream_colour_vote.argtypes = [vp, i32]
+        lib.cimbar_hip_set_stream_colour_vote.restype = i32
+        lib.cimbar_hip_get_stream_colour_vote.argtypes = [vp, ctypes.POINTER(i32)]
+        lib.cimbar_hip_get_stream_colour_vote.restype = i32
     lib.cimbar_hip_mode_bufsize.argtypes = [i32]
     lib.cimbar_hip_mode_bufsize.restype = i32
     lib.cimbar_hip_ctx_bufsize.argtypes = [vp]
@@ -808,6 +815,17 @@ class HipDecoder:
         self._check(self._lib.cimbar_hip_get_group_colour_vote(self._ctx, ctypes.byref(a)), "cimbar_hip_get_group_colour_vote")
         return bool(a.value)
 
+    def set_stream_colour_vote(self, on=True):
+        """cimbar_hip_set_stream_colour_vote: the colour vote (and, with set_colour_erasure_decode on, the group colour retry) in the stream
+        calls; set_group_colour_vote governs the plain combined calls only. A stream samples it in its first call after create /
+        combine_stream_reset; a call that finds it changed in mid-stream is refused. Modes 4 / 8 refuse it."""
+        self._check(self._lib.cimbar_hip_set_stream_colour_vote(self._ctx, int(bool(on))), "cimbar_hip_set_stream_colour_vote")
+
+    def get_stream_colour_vote(self):
+        a = ctypes.c_int()
+        self._check(self._lib.cimbar_hip_get_stream_colour_vote(self._ctx, ctypes.byref(a)), "cimbar_hip_get_stream_colour_vote")
+        return bool(a.value)
+
     def rs_decode_erasures(self, blocks, erasures):
         """Errors-and-erasures Reed-Solomon decode of caller-given blocks of this mode's code (cimbar_hip_rs_decode_erasures).
         blocks: (n, RS_BLOCK) uint8; erasures: a list of n sequences of byte positions (at most RS_BLOCK each, any count: more than
@@ -896,6 +914,7 @@ class HipDecoder:
             TAP_GROUP_CELLS: ((n, self.geo.NCELLS), np.uint8), TAP_GROUP_MARGIN: ((n, self.geo.NCELLS), np.uint16), TAP_GROUPS: ((n,), np.int32),
             TAP_COLOUR_MARGIN: ((n, self.geo.NCELLS), np.uint32), TAP_SCAN_PATH: ((n,), np.int32),
             TAP_GROUP_COLOUR_MARGIN: ((n, self.geo.NCELLS), np.uint32), TAP_GROUP_COLOUR_WEIGHTS: ((n, self.geo.NCELLS), np.uint32),
+            TAP_STREAM_CARRY_WEIGHTS: ((n, self.geo.NCELLS), np.uint32),
         }
         shape, dt = shapes[what]
         out = np.zeros(shape, dtype=dt)
