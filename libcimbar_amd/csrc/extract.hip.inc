@@ -388,7 +388,8 @@ __global__ __launch_bounds__(64) void k_scan_otsu(const uint32_t* __restrict__ h
 // X4: cv::warpPerspective(INTER_LINEAR, BORDER_CONSTANT 0) into a width x height RGB8 frame, four destination pixels per lane (their
 // 12 bytes leave as three aligned dword stores). minv: the already inverted matrix (destination -> source), 9 doubles per frame.
 // OpenCV evaluates the source position per 64-pixel block of a row as (X0 + M0*x1) with X0 taken at the block's left edge -- the same
-// association is kept here, it decides the last bit. width must be a multiple of 64 (it is 1024).
+// association is kept here, it decides the last bit. width must be a multiple of 4 (a lane's four pixels); it need not be one of 64: 1024 in
+// modes 68 / 67 / 4 / 8, 736 in mode 66, whose twelfth 64-column tile is half empty (OpenCV's last block of a row is 32 wide there, with the same X0).
 // FMT: the capture's pixel format. What cv::warpPerspective interpolates in the reference is the RGB image get_rgb made of the capture, so the
 // four taps are converted (capture formats above) and then blended; nothing of that image exists in memory here.
 // The two horizontally adjacent pixels (sx, sy), (sx + 1, sy) of an interior tap pair as R | G << 8 | B << 16 each:
