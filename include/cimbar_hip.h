@@ -331,6 +331,44 @@ int cimbar_hip_combine_stream_reset(cimbar_hip_ctx* ctx);
 int cimbar_hip_set_stream_colour_vote(cimbar_hip_ctx* ctx, int on);
 int cimbar_hip_get_stream_colour_vote(cimbar_hip_ctx* ctx, int* on);
 
+/* Torn-capture stitching. A camera's rolling shutter that crosses a display refresh shows frame A on one side of a line and frame B on the
+ * other; the next capture shows B, then C. The Reed-Solomon stream is interleaved over the two halves of the frame, so a torn capture alone
+ * delivers at most the chunks of the half its tear does not cross, while two consecutive torn captures together hold every cell of the frame
+ * they share. These calls decode a batch capture by capture exactly as cimbar_hip_decode_batch / cimbar_hip_scan_extract_decode_batch_fmt do
+ * (chunks, masks, status and the colour-correction carry equal theirs for the same input and settings), then, for every pair of consecutive
+ * captures k and k+1 of the batch:
+ *   lines      axis 0 (a horizontal tear): line(i) = cell i's grid row (y_i - offset) / 9, L = the grid's rows. axis 1 (the tear a phone
+ *              held at a right angle to the screen produces): line(i) = its grid column (x_i - offset) / 9, L = the grid's columns.
+ *              width(l) = the cells on line l, fewer on the lines that cross the anchors.
+ *   eq(i)      symbol and colour both equal in the two captures (the comparison of the group decode's agree(k, k+1))
+ *   flag(l)    cnt(l) * 1000 >= min_agree_permille * width(l), cnt(l) = the sum of eq over line l; min_agree_permille <= 0: 750
+ *   band       a = the lowest flagged line, b = the highest flagged line + 1, f = the flagged lines
+ *   candidate  both captures usable (capture path: extracted), f >= 1, b - a >= min_band (min_band <= 0: 2), 4 f >= 3 (b - a) -- a few
+ *              damaged lines inside the band are tolerated -- and a > 0 or b < L: a band over the whole frame means the two captures show one
+ *              frame, which is the group decode's case
+ *   split      s = (a + b) >> 1, the line farthest from both tears. Direction 0: cell i is capture k+1's if line(i) < s, else capture k's --
+ *              the later capture's low lines and the earlier capture's high lines show the shared frame. Direction 1 is the reverse, for a
+ *              sensor read the other way round. Symbol and colour are taken from the chosen capture as it decided them.
+ *   decode     both directions' cells go through the same Reed-Solomon decode and chunk bookkeeping as one frame (modes 4 / 8: the coupled
+ *              stream). No colour-correction matrix is derived, read or carried; nothing is voted, retried (the erasure settings do not
+ *              reach this decode) or filled in from the two captures, which show other frames.
+ *   schunks / smasks  2 (n - 1) slots of cimbar_hip_ctx_bufsize bytes / one mask word; pair k, direction d is slot 2k + d. smask is the
+ *              stitched decode's own mask, chunks outside it are zero, and so is everything of a pair that is no candidate. The wrong
+ *              direction yields chunks of a neighbouring frame or nothing: every chunk in any mask is a genuine chunk, and a sink
+ *              (cimbar_hip_deliver_chunks takes the same layout) drops the duplicates.
+ *   tears      (n - 1) x 4 int32 {a, b, s, f}, a = b = s = -1 for a pair that is no candidate; may be NULL
+ * Every output follows out_mem. Host outputs: synchronises and returns the number of candidate pairs. Device outputs: enqueues only, behind
+ * the per-capture decode on the same stream, and returns 0. n == 1: no pair, nothing stitched, returns 0. axis outside {0, 1}, min_band > L
+ * or a null required pointer: CIMBAR_HIP_EINVAL, checked before anything is enqueued. Pairs do not span two calls. Buffers, stream and errors
+ * otherwise as for cimbar_hip_decode_batch; no other call's behaviour depends on these. */
+int64_t cimbar_hip_decode_batch_stitched(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rgb_mem, int should_preprocess, int color_correction,
+                                         int axis, int min_agree_permille, int min_band, uint8_t* chunks, uint32_t* masks, uint8_t* schunks,
+                                         uint32_t* smasks, int32_t* tears, int out_mem, void* hip_stream);
+int64_t cimbar_hip_scan_extract_decode_batch_stitched_fmt(cimbar_hip_ctx* ctx, const uint8_t* img, unsigned width, unsigned height, int format, int n,
+                                                          int img_mem, int preprocess, int color_correction, int axis, int min_agree_permille,
+                                                          int min_band, uint8_t* chunks, uint32_t* masks, int* status, uint8_t* schunks,
+                                                          uint32_t* smasks, int32_t* tears, int out_mem, void* hip_stream);
+
 /* ---- chunk delivery: a batch's slots and masks -> what a fountain sink eats --------------------------------------------------------------
  * The batch entry points above report a frame's chunks in fixed slots plus one mask word. The reference's receive interface has another shape:
  * cimbard_scan_extract_decode returns the delivered chunks packed front to back (escrow_buffer_writer), and cimbard_fountain_decode(buf, size)
@@ -639,8 +677,13 @@ enum {
 	                                            colour dispute and for captures in no group (stream call: in no group that closed in the call) */
 	/* the carry store after the last batch, when that was a stream call of a stream with cimbar_hip_set_stream_colour_vote on (else
 	 * CIMBAR_HIP_EINVAL) */
-	CIMBAR_HIP_TAP_STREAM_CARRY_WEIGHTS = 17 /* rows * cells u32    : the carried weights of slots 0 .. rows - 1 (the open group's members in capture
+	CIMBAR_HIP_TAP_STREAM_CARRY_WEIGHTS = 17,/* rows * cells u32    : the carried weights of slots 0 .. rows - 1 (the open group's members in capture
 	                                            order), every cell filled; rows = out_bytes / (cells * 4), CIMBAR_HIP_EINVAL above the occupied slots */
+	/* the stitching of the last batch, when it was a stitched one (cimbar_hip_decode_batch_stitched / _scan_extract_decode_batch_stitched_fmt;
+	 * CIMBAR_HIP_EINVAL after any other batch) */
+	CIMBAR_HIP_TAP_STITCH_CELLS = 18, /* 2 (n - 1) * cells bytes: the stitched cell of slot 2k + d, colour << 4 | symbol; zero for the slots of a
+	                                     pair that is no candidate */
+	CIMBAR_HIP_TAP_STITCH_LINES = 19  /* (n - 1) * L u16        : cnt(l), the agreeing cells of pair k on line l of the call's axis */
 };
 int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_bytes);
 

@@ -42,6 +42,11 @@ struct cimbar_hip_ctx {
 	int gcv_stream_n = -1;                      // ... >= 0: a stream call of that many captures (CIMBAR_HIP_TAP_STREAM_CARRY_WEIGHTS describes its carry store)
 	DevBuf<uint32_t> d_gcm, d_gcw;              // the vote's margins [groups][NCELLS] and member weights [captures][NCELLS]; allocated by the first combined call with its setting on
 	std::unique_ptr<CombineStream> cstream;     // cimbar_hip_decode_batch_combined_stream / _scan_extract_decode_batch_combined_stream_fmt
+	// torn-capture stitching (cimbar_hip_decode_batch_stitched / _scan_extract_decode_batch_stitched_fmt, stitch.hip.inc): per pair slot, grown on demand
+	int stitch_n = 0, stitch_axis = 0;          // the last batch was a stitched one of stitch_n captures (> 0: the stitch taps describe it)
+	DevBuf<uint8_t> d_ssym, d_scol, d_srs_ok;   // [2 (n - 1)][NCELLS], [2 (n - 1)][ALL_BLOCKS]
+	DevBuf<uint32_t> d_slive; DevBuf<int32_t> d_stears; DevBuf<uint16_t> d_slines; DevBuf<int> d_sslots;   // [2 (n - 1)], [n - 1][4], [n - 1][L], 1 int
+	DevBuf<uint8_t> d_schunks; DevBuf<uint32_t> d_smasks;   // staging for host-memory stitch outputs
 	int wave_adapt = 1;               // CIMBAR_HIP_FLOOD_WAVE_ADAPT=0: run k_flood_wave in front of every exact replay, whatever it achieved before
 	bool wave_ran = false;            // k_flood_wave ran in the batch h_flagged describes
 	int wave_skip_left = 0;           // batches that still go straight to the exact replay (see enqueue)
@@ -51,6 +56,7 @@ struct cimbar_hip_ctx {
 	std::string err;
 	Tables tb{};                      // what the kernels take by value: filled by build_tables from the owners beside it
 	DevBuf<ushort2> tb_cell_xy; DevBuf<uint16_t> tb_stream_cell, tb_cell_grid, tb_ccm_grid; DevBuf<int16_t> tb_grid_cell, tb_cand;
+	DevBuf<uint8_t> tb_stitch_line;  // [2][NCELLS] the grid row and the grid column of every cell (k_stitch_pairs)
 	uint64_t tile_hashes[16] = {};   // as computed at create (also in c_tile)
 	int last_n = 0;
 	int scan_n = 0;                             // captures of the last anchor search (CIMBAR_HIP_TAP_SCAN_PATH describes it)
@@ -353,6 +359,13 @@ int build_tables(cimbar_hip_ctx* ctx)
 	}
 	HIPCHK(ctx->tb_ccm_grid.reserve(NHDR_CELLS));
 	HIPCHK(hipMemcpy(ctx->tb_ccm_grid, ccm_grid.data(), sizeof(uint16_t) * NHDR_CELLS, hipMemcpyHostToDevice));
+	std::vector<uint8_t> stitch_line((size_t)2 * NCELLS);
+	for (int i = 0; i < NCELLS; ++i) {
+		stitch_line[i] = (uint8_t)(((int)xy[i].y - OFFSET) / PITCH);
+		stitch_line[NCELLS + i] = (uint8_t)(((int)xy[i].x - OFFSET) / PITCH);
+	}
+	HIPCHK(ctx->tb_stitch_line.reserve(stitch_line.size()));
+	HIPCHK(hipMemcpy(ctx->tb_stitch_line, stitch_line.data(), stitch_line.size(), hipMemcpyHostToDevice));
 	HIPCHK(ctx->tb_cand.reserve((size_t)NCELLS * 12));
 	HIPCHK(hipMemcpy(ctx->tb_cell_xy, xy.data(), sizeof(ushort2) * NCELLS, hipMemcpyHostToDevice));
 	HIPCHK(hipMemcpy(ctx->tb_stream_cell, sc.data(), sizeof(uint16_t) * NCELLS, hipMemcpyHostToDevice));
@@ -486,6 +499,7 @@ int enqueue(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_rgb, int n, in
 {
 	cimbar_hip_ctx::ScratchSet& cur = ctx->cur();
 	ctx->grp_valid = false;   // (the group taps describe a combined batch only until the next batch of any kind)
+	ctx->stitch_n = 0;        // (... and the stitch taps a stitched one)
 	ctx->gcv_valid = false;
 	ctx->gcv_stream_n = -1;
 	// the colour retry (erasure.hip.inc) runs behind every chain that reports chunks; the set in use holds its margins
@@ -908,20 +922,26 @@ GroupOut group_out(cimbar_hip_ctx* ctx, const CombineArgs& cb, int out_mem)
 	return {ctx->d_gchunks, ctx->d_gmasks};
 }
 
+// the k_rs LIVE launches over `slots` slots of cells (combine.hip.inc, stitch.hip.inc): *n_live of them are decoded, those with a live flag, into
+// d_chunks / rs_ok
+void launch_live_rs(cimbar_hip_ctx* ctx, hipStream_t st, int slots, const uint8_t* sym, const uint8_t* col, uint8_t* rs_ok, const int* n_live,
+                    const uint32_t* live, uint8_t* d_chunks)
+{
+	if constexpr (LEGACY) {
+		hipLaunchKernelGGL((k_rs<CELL_BITS, false, true>), dim3((slots * ALL_BLOCKS + 3) / 4), dim3(256), 0, st, sym, ctx->tb, 0, slots, 0, d_chunks, rs_ok, 0,
+		                   col, n_live, live);
+	} else {
+		hipLaunchKernelGGL((k_rs<4, false, true>), dim3((slots * SYM_BLOCKS + 3) / 4), dim3(256), 0, st, sym, ctx->tb, 0, slots, 0, d_chunks, rs_ok, 0,
+		                   (const uint8_t*)nullptr, n_live, live);
+		hipLaunchKernelGGL((k_rs<2, false, true>), dim3((slots * COL_BLOCKS + 3) / 4), dim3(256), 0, st, col, ctx->tb, 0, slots, SYM_CHUNKS, d_chunks, rs_ok,
+		                   SYM_BLOCKS, (const uint8_t*)nullptr, n_live, live);
+	}
+}
+
 // the groups' Reed-Solomon pass over `slots` group slots (k_rs LIVE: see combine.hip.inc), from the combined cells into d_gchunks / d_grs_ok
 void launch_group_rs(cimbar_hip_ctx* ctx, hipStream_t st, int slots, uint8_t* d_gchunks)
 {
-	const int* ng = ctx->d_ngroups;
-	const uint32_t* disp = ctx->d_gdisp;
-	if constexpr (LEGACY) {
-		hipLaunchKernelGGL((k_rs<CELL_BITS, false, true>), dim3((slots * ALL_BLOCKS + 3) / 4), dim3(256), 0, st, ctx->d_gsym, ctx->tb, 0, slots, 0, d_gchunks,
-		                   ctx->d_grs_ok, 0, (const uint8_t*)ctx->d_gcol, ng, disp);
-	} else {
-		hipLaunchKernelGGL((k_rs<4, false, true>), dim3((slots * SYM_BLOCKS + 3) / 4), dim3(256), 0, st, ctx->d_gsym, ctx->tb, 0, slots, 0, d_gchunks,
-		                   ctx->d_grs_ok, 0, (const uint8_t*)nullptr, ng, disp);
-		hipLaunchKernelGGL((k_rs<2, false, true>), dim3((slots * COL_BLOCKS + 3) / 4), dim3(256), 0, st, ctx->d_gcol, ctx->tb, 0, slots, SYM_CHUNKS, d_gchunks,
-		                   ctx->d_grs_ok, SYM_BLOCKS, (const uint8_t*)nullptr, ng, disp);
-	}
+	launch_live_rs(ctx, st, slots, ctx->d_gsym, ctx->d_gcol, ctx->d_grs_ok, ctx->d_ngroups, ctx->d_gdisp, d_gchunks);
 }
 
 // G1-G4 behind a batch's per-capture decode, on the same stream; reads that decode's intermediates and outputs (d_chunks / d_masks), writes
@@ -1095,11 +1115,86 @@ int64_t finish_batch(cimbar_hip_ctx* ctx, hipStream_t st, int n, uint8_t* chunks
 	return (int64_t)total;
 }
 
+// ------------------------------------------------------------------------------------------------ torn-capture stitching (stitch.hip.inc)
+struct StitchArgs {
+	int axis, min_agree, min_band;
+	uint8_t* schunks; uint32_t* smasks; int32_t* tears;   // 2 (n - 1) slots; (n - 1) x 4 ints (may be nullptr)
+	std::vector<int32_t> h_tears;                         // host outputs: where the tear records land when the caller wants none
+};
+
+// the argument checks of the stitched entry points, before anything is enqueued
+int check_stitch(cimbar_hip_ctx* ctx, const char* who, int n, StitchArgs& sa)
+{
+	if (sa.axis != 0 && sa.axis != 1) { ctx->err = std::string(who) + ": axis must be 0 (grid rows) or 1 (grid columns)"; return CIMBAR_HIP_EINVAL; }
+	if (sa.min_band > stitch_lines(sa.axis)) { ctx->err = std::string(who) + ": min_band above the lines of the axis"; return CIMBAR_HIP_EINVAL; }
+	if (n > 1 && (!sa.schunks || !sa.smasks)) { ctx->err = std::string(who) + ": null schunks / smasks"; return CIMBAR_HIP_EINVAL; }
+	if (sa.min_agree <= 0) sa.min_agree = STITCH_AGREE_DEFAULT;
+	if (sa.min_band <= 0) sa.min_band = STITCH_BAND_DEFAULT;
+	return 0;
+}
+
+int ensure_stitch_capacity(cimbar_hip_ctx* ctx, int n)
+{
+	const size_t P = (size_t)n - 1, S = 2 * P;
+	HIPCHK(ctx->d_ssym.reserve(S * NCELLS));
+	HIPCHK(ctx->d_scol.reserve(S * NCELLS));
+	HIPCHK(ctx->d_srs_ok.reserve(S * ALL_BLOCKS));
+	HIPCHK(ctx->d_slive.reserve(S));
+	HIPCHK(ctx->d_stears.reserve(P * 4));
+	HIPCHK(ctx->d_slines.reserve(P * STITCH_LMAX));
+	HIPCHK(ctx->d_sslots.ensure(1));
+	HIPCHK(ctx->d_schunks.reserve(S * FRAME_BYTES));
+	HIPCHK(ctx->d_smasks.reserve(S));
+	return 0;
+}
+
+// S1, the Reed-Solomon pass over the 2 (n - 1) slots (launch_live_rs: the k_rs LIVE instances of the group decode, fed from the stitch scratch) and S2, behind
+// a batch's per-capture decode on the same stream (n > 1). Reads that decode's symbols and colours; writes the caller's buffers (device
+// outputs) or the context's staging, whose copies back to the host are enqueued here as well. d_status as for enqueue_combine.
+int enqueue_stitch(cimbar_hip_ctx* ctx, hipStream_t st, int n, const int* d_status, int stride, StitchArgs& sa, int out_mem)
+{
+	if (int r = ensure_stitch_capacity(ctx, n)) return r;
+	cimbar_hip_ctx::ScratchSet& cur = ctx->cur();
+	const int pairs = n - 1, slots = 2 * pairs;
+	const bool dev = out_mem == CIMBAR_HIP_MEM_DEVICE;
+	uint8_t* d_out = dev ? sa.schunks : ctx->d_schunks.get();
+	uint32_t* d_om = dev ? sa.smasks : ctx->d_smasks.get();
+	HIPCHK(hipMemsetAsync(ctx->d_sslots, 0, sizeof(int), st));
+	hipLaunchKernelGGL(k_stitch_pairs, dim3(pairs), dim3(256), 0, st, cur.d_symbols, cur.d_colors, n, d_status, stride, ctx->tb_stitch_line, sa.axis,
+	                   sa.min_agree, sa.min_band, ctx->d_stears, ctx->d_slines, ctx->d_slive, ctx->d_sslots, ctx->d_ssym, ctx->d_scol);
+	launch_live_rs(ctx, st, slots, ctx->d_ssym, ctx->d_scol, ctx->d_srs_ok, ctx->d_sslots, ctx->d_slive, d_out);
+	hipLaunchKernelGGL(k_stitch_end, dim3(slots), dim3(256), 0, st, ctx->d_slive, ctx->d_srs_ok, d_out, d_om);
+	HIPCHK(hipGetLastError());
+	if (dev) {
+		if (sa.tears) HIPCHK(hipMemcpyAsync(sa.tears, ctx->d_stears, sizeof(int32_t) * 4 * (size_t)pairs, hipMemcpyDeviceToDevice, st));
+	} else {
+		if (!sa.tears) { sa.h_tears.resize((size_t)pairs * 4); sa.tears = sa.h_tears.data(); }
+		HIPCHK(hipMemcpyAsync(sa.schunks, d_out, (size_t)slots * FRAME_BYTES, hipMemcpyDeviceToHost, st));
+		HIPCHK(hipMemcpyAsync(sa.smasks, d_om, sizeof(uint32_t) * (size_t)slots, hipMemcpyDeviceToHost, st));
+		HIPCHK(hipMemcpyAsync(sa.tears, ctx->d_stears, sizeof(int32_t) * 4 * (size_t)pairs, hipMemcpyDeviceToHost, st));
+	}
+	return 0;
+}
+
+// the end of a stitched call: finish_batch for the per-capture outputs; host outputs: the candidate pairs, read from the tear records
+int64_t finish_stitched(cimbar_hip_ctx* ctx, hipStream_t st, int n, uint8_t* chunks, uint32_t* masks, const uint8_t* d_chunks, const uint32_t* d_masks,
+                        int out_mem, const StitchArgs& sa)
+{
+	const int64_t r = finish_batch(ctx, st, n, chunks, masks, d_chunks, d_masks, out_mem, nullptr);
+	if (r < 0) return r;
+	ctx->stitch_n = n;
+	ctx->stitch_axis = sa.axis;
+	if (out_mem == CIMBAR_HIP_MEM_DEVICE || n < 2) return 0;
+	int64_t cand = 0;
+	for (int k = 0; k + 1 < n; ++k) cand += sa.tears[(size_t)k * 4] >= 0;
+	return cand;
+}
+
 int64_t decode_batch_impl(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rgb_mem, int should_preprocess, int color_correction, uint8_t* chunks,
-                          uint32_t* masks, int out_mem, void* hip_stream, CombineArgs* cb)
+                          uint32_t* masks, int out_mem, void* hip_stream, CombineArgs* cb, StitchArgs* sa = nullptr)
 {
 	const bool strm = cb && cb->stream;
-	const char* who = strm ? "decode_batch_combined_stream" : cb ? "decode_batch_combined" : "decode_batch";
+	const char* who = sa ? "decode_batch_stitched" : strm ? "decode_batch_combined_stream" : cb ? "decode_batch_combined" : "decode_batch";
 	// (a stream call may bring no capture at all: n == 0 with a flush closes the open group)
 	if (strm ? (n < 0 || (n > 0 && (!rgb || !chunks || !masks))) : (!rgb || !chunks || !masks || n <= 0)) { ctx->err = std::string(who) + ": null buffer or n <= 0"; return CIMBAR_HIP_EINVAL; }
 	if ((rgb_mem != CIMBAR_HIP_MEM_HOST && rgb_mem != CIMBAR_HIP_MEM_DEVICE) || (out_mem != CIMBAR_HIP_MEM_HOST && out_mem != CIMBAR_HIP_MEM_DEVICE)) {
@@ -1107,6 +1202,7 @@ int64_t decode_batch_impl(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rg
 		return CIMBAR_HIP_EINVAL;
 	}
 	if (cb) if (int r = check_combine(ctx, who, n, *cb)) return r;
+	if (sa) if (int r = check_stitch(ctx, who, n, *sa)) return r;
 	HIPCHK(hipSetDevice(ctx->device));
 	// NULL means what it means for any HIP launch -- the (legacy) null stream -- whenever a device buffer is involved, so the
 	// work is ordered after whatever produced the frames there; the all-host path synchronises anyway and uses its own stream
@@ -1131,6 +1227,10 @@ int64_t decode_batch_impl(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rg
 	}
 	if (cb)
 		if (int r = enqueue_combine(ctx, st, n, d_rgb, d_chunks, d_masks, nullptr, 0, *cb, out_mem)) return r;
+	if (sa) {
+		if (n > 1) if (int r = enqueue_stitch(ctx, st, n, nullptr, 0, *sa, out_mem)) return r;
+		return finish_stitched(ctx, st, n, chunks, masks, d_chunks, d_masks, out_mem, *sa);
+	}
 	return finish_batch(ctx, st, n, chunks, masks, d_chunks, d_masks, out_mem, cb);
 }
 
@@ -1159,6 +1259,15 @@ int64_t cimbar_hip_decode_batch_combined_stream(cimbar_hip_ctx* ctx, const uint8
 	if (!ctx) return CIMBAR_HIP_EINVAL;
 	CombineArgs cb{nullptr, min_agree_permille, max_group, groups_out, gchunks, gmasks, n_groups, true, flush, gsizes};
 	return decode_batch_impl(ctx, rgb, n, rgb_mem, should_preprocess, color_correction, chunks, masks, out_mem, hip_stream, &cb);
+}
+
+int64_t cimbar_hip_decode_batch_stitched(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rgb_mem, int should_preprocess, int color_correction,
+                                         int axis, int min_agree_permille, int min_band, uint8_t* chunks, uint32_t* masks, uint8_t* schunks,
+                                         uint32_t* smasks, int32_t* tears, int out_mem, void* hip_stream)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	StitchArgs sa{axis, min_agree_permille, min_band, schunks, smasks, tears, {}};
+	return decode_batch_impl(ctx, rgb, n, rgb_mem, should_preprocess, color_correction, chunks, masks, out_mem, hip_stream, nullptr, &sa);
 }
 
 // drop the open group and the fixed parameters: the next stream call starts a stream of its own
@@ -1674,10 +1783,10 @@ namespace {
 
 int64_t scan_extract_decode_impl(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsigned width, unsigned height, int format, int n, int rgb_mem,
                                  int preprocess, int color_correction, uint8_t* chunks, uint32_t* masks, int* status, int out_mem,
-                                 void* hip_stream, CombineArgs* cb)
+                                 void* hip_stream, CombineArgs* cb, StitchArgs* sa = nullptr)
 {
 	const bool strm = cb && cb->stream;
-	const char* who = strm ? "scan_extract_decode_batch_combined_stream" : cb ? "scan_extract_decode_batch_combined" : "scan_extract_decode_batch";
+	const char* who = sa ? "scan_extract_decode_batch_stitched" : strm ? "scan_extract_decode_batch_combined_stream" : cb ? "scan_extract_decode_batch_combined" : "scan_extract_decode_batch";
 	if (strm && n == 0) {   // (no capture: a flush closes the open group; no image argument is read)
 		if (out_mem != CIMBAR_HIP_MEM_HOST && out_mem != CIMBAR_HIP_MEM_DEVICE) { ctx->err = std::string(who) + ": out_mem must be CIMBAR_HIP_MEM_HOST or CIMBAR_HIP_MEM_DEVICE"; return CIMBAR_HIP_EINVAL; }
 		if (int r = check_combine(ctx, who, n, *cb)) return r;
@@ -1695,6 +1804,7 @@ int64_t scan_extract_decode_impl(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsign
 	int fmt; size_t cbytes;
 	if (int r = check_capture(ctx, who, width, height, format, &fmt, &cbytes)) return r;
 	if (cb) if (int r = check_combine(ctx, who, n, *cb)) return r;
+	if (sa) if (int r = check_stitch(ctx, who, n, *sa)) return r;
 	HIPCHK(hipSetDevice(ctx->device));
 	const bool any_device = rgb_mem == CIMBAR_HIP_MEM_DEVICE || out_mem == CIMBAR_HIP_MEM_DEVICE;
 	hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (any_device ? (hipStream_t)nullptr : ctx->stream);
@@ -1723,9 +1833,13 @@ int64_t scan_extract_decode_impl(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsign
 	if (strm) { if (int r = enqueue_combine_stream(ctx, st, n, ctx->d_ex_frames, d_chunks, d_masks, &ctx->d_scan_res[0].status, stride, *cb, out_mem)) return r; }
 	else if (cb)
 		if (int r = enqueue_combine(ctx, st, n, ctx->d_ex_frames, d_chunks, d_masks, &ctx->d_scan_res[0].status, stride, *cb, out_mem)) return r;
+	// ... nor any stitched pair
+	if (sa && n > 1)
+		if (int r = enqueue_stitch(ctx, st, n, &ctx->d_scan_res[0].status, stride, *sa, out_mem)) return r;
 	const hipMemcpyKind kind = out_mem == CIMBAR_HIP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
 	if (status) HIPCHK(hipMemcpy2DAsync(status, sizeof(int), &ctx->d_scan_res[0].status, sizeof(ScanResult), sizeof(int), (size_t)n, kind, st));
 	if (strm) return finish_stream(ctx, st, n, chunks, masks, d_chunks, d_masks, out_mem, *cb);
+	if (sa) return finish_stitched(ctx, st, n, chunks, masks, d_chunks, d_masks, out_mem, *sa);
 	return finish_batch(ctx, st, n, chunks, masks, d_chunks, d_masks, out_mem, cb);
 }
 
@@ -1747,6 +1861,16 @@ int64_t cimbar_hip_scan_extract_decode_batch_combined_fmt(cimbar_hip_ctx* ctx, c
 	if (!ctx) return CIMBAR_HIP_EINVAL;
 	CombineArgs cb{groups_in, min_agree_permille, max_group, groups_out, gchunks, gmasks, n_groups};
 	return scan_extract_decode_impl(ctx, rgb, width, height, format, n, rgb_mem, preprocess, color_correction, chunks, masks, status, out_mem, hip_stream, &cb);
+}
+
+int64_t cimbar_hip_scan_extract_decode_batch_stitched_fmt(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsigned width, unsigned height, int format, int n,
+                                                          int rgb_mem, int preprocess, int color_correction, int axis, int min_agree_permille,
+                                                          int min_band, uint8_t* chunks, uint32_t* masks, int* status, uint8_t* schunks,
+                                                          uint32_t* smasks, int32_t* tears, int out_mem, void* hip_stream)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	StitchArgs sa{axis, min_agree_permille, min_band, schunks, smasks, tears, {}};
+	return scan_extract_decode_impl(ctx, rgb, width, height, format, n, rgb_mem, preprocess, color_correction, chunks, masks, status, out_mem, hip_stream, nullptr, &sa);
 }
 
 int64_t cimbar_hip_scan_extract_decode_batch_combined_stream_fmt(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsigned width, unsigned height, int format,
@@ -2050,6 +2174,22 @@ int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_byte
 			} else {
 				for (size_t k = 0; k < n; ++k) if (grp[k] < 0 || (size_t)grp[k] >= G || !disp[grp[k]]) std::memset((uint32_t*)out + k * NCELLS, 0, (size_t)NCELLS * sizeof(uint32_t));
 			}
+			return (int64_t)bytes;
+		}
+		case CIMBAR_HIP_TAP_STITCH_CELLS:
+		case CIMBAR_HIP_TAP_STITCH_LINES: {
+			if (ctx->stitch_n <= 0) { ctx->err = "tap: the last batch was not a stitched one (cimbar_hip_decode_batch_stitched / _scan_extract_decode_batch_stitched_fmt)"; return CIMBAR_HIP_EINVAL; }
+			const size_t pairs = (size_t)ctx->stitch_n - 1, slots = 2 * pairs, L = (size_t)stitch_lines(ctx->stitch_axis);
+			bytes = what == CIMBAR_HIP_TAP_STITCH_LINES ? pairs * L * sizeof(uint16_t) : slots * NCELLS;
+			if (out_bytes < bytes) { ctx->err = "tap: buffer too small"; return CIMBAR_HIP_EINVAL; }
+			if (!bytes) return 0;
+			if (what == CIMBAR_HIP_TAP_STITCH_LINES) { HIPCHK(hipMemcpy(out, ctx->d_slines, bytes, hipMemcpyDeviceToHost)); return (int64_t)bytes; }
+			std::vector<uint8_t> col(bytes);
+			std::vector<uint32_t> lv(slots);
+			HIPCHK(hipMemcpy(out, ctx->d_ssym, bytes, hipMemcpyDeviceToHost));
+			HIPCHK(hipMemcpy(col.data(), ctx->d_scol, bytes, hipMemcpyDeviceToHost));
+			HIPCHK(hipMemcpy(lv.data(), ctx->d_slive, sizeof(uint32_t) * slots, hipMemcpyDeviceToHost));
+			for (size_t k = 0; k < bytes; ++k) ((uint8_t*)out)[k] = lv[k / NCELLS] ? (uint8_t)((col[k] << 4) | (((uint8_t*)out)[k] & 15u)) : (uint8_t)0;
 			return (int64_t)bytes;
 		}
 		case CIMBAR_HIP_TAP_STREAM_CARRY_WEIGHTS: {

@@ -106,6 +106,7 @@ struct Tables {
 #include "k4_frame.hip.inc"
 #include "erasure.hip.inc"
 #include "combine.hip.inc"
+#include "stitch.hip.inc"
 #include "k1_padded.hip.inc"
 #include "encode.hip.inc"
 #include "extract.hip.inc"

@@ -1,0 +1,159 @@
+// stitch.hip.inc -- part of cimbar_hip.hip (one translation unit; included inside its anonymous namespace, after combine.hip.inc).
+// S1-S2: torn-capture stitching -- a frame that two consecutive captures each show one side of, decoded from the cells of both
+// ------------------------------------------------------------------------------------------------ the rule
+// A rolling shutter that crosses a display refresh shows frame A on one side of a line and frame B on the other; the next capture shows B,
+// then C. The two captures agree where both show B. A batch is decoded capture by capture first (enqueue(), unchanged). Then, for
+// consecutive captures k and k+1 and the caller's axis:
+//   lines      axis 0: line(i) = cell i's grid row (y_i - OFFSET) / PITCH, L = DIM_Y; axis 1: its grid column (x_i - OFFSET) / PITCH, L = DIM_X.
+//              width(l) = the cells on line l (fewer on the lines that cross the anchors)
+//   eq(i)      symbol AND colour equal, with agreeing_cells' masks (combine.hip.inc)
+//   cnt(l)     = the sum of eq over line l; flag(l) = cnt(l) * 1000 >= min_agree_permille * width(l)   (min_agree_permille <= 0: 750)
+//   band       a = the lowest flagged line, b = the highest flagged line + 1, f = the flagged lines
+//   candidate  both captures usable, f >= 1, b - a >= min_band (min_band <= 0: 2), 4 f >= 3 (b - a) (a few damaged lines inside the band
+//              are tolerated), and a > 0 or b < L (a band over the whole frame is two captures of one frame: the group decode's case)
+//   split      s = (a + b) >> 1, the line farthest from both tears. Direction 0: cell i comes from capture k+1 if line(i) < s, else from
+//              capture k (the later capture's low lines and the earlier one's high lines show the shared frame); direction 1 is the
+//              reverse, for a sensor read the other way round. Symbol and colour are the chosen capture's own decisions.
+//   decode     slot 2k + d holds pair k, direction d. A candidate's two cell sets go through k_rs<.., LIVE> and the aligned_stream
+//              bookkeeping of one frame (group_end_body's cmask; modes 4 / 8: the coupled stream). No colour-correction matrix is
+//              derived, read or carried; nothing is filled in from the members (they show other frames); no vote, no erasure retry.
+//              smask = that decode's own mask; slots of chunks outside it are zero.
+// The wrong direction yields chunks of a neighbouring frame or nothing: every chunk in a mask is a genuine chunk, and a sink dedups.
+//   S1 k_stitch_pairs  one workgroup per pair: cnt, the tear record {a, b, s, f}, the two slots' live flags and, for a candidate, both
+//                      directions' stitched symbols and colours
+//   K3 k_rs            over 2 (n - 1) slots (LIVE: the workgroups past the last candidate and the wavefronts of a non-candidate return at once)
+//   S2 k_stitch_end    one workgroup per slot: the aligner walk, the mask, zeroes for undelivered chunks; all zeroes for a non-live slot
+constexpr int STITCH_AGREE_DEFAULT = 750, STITCH_BAND_DEFAULT = 2;
+constexpr int STITCH_LMAX = DIM_X > DIM_Y ? DIM_X : DIM_Y;
+static_assert(STITCH_LMAX <= 128, "the line flags fit two ballots");
+static_assert(TOP_W % 4 == 0 && DIM_X % 4 == 0 && TOP_CELLS % 4 == 0 && MID_CELLS % 4 == 0, "axis 0: every dword of cells lies on one grid row");
+
+__device__ __host__ constexpr int stitch_lines(int axis) { return axis == 0 ? DIM_Y : DIM_X; }
+__device__ __forceinline__ int stitch_width(int axis, int l)
+{
+	if (axis == 0) return (l < MARKER || l >= DIM_Y - MARKER) ? TOP_W : DIM_X;
+	return (l < MARKER || l >= DIM_X - MARKER) ? DIM_Y - 2 * MARKER : DIM_Y;
+}
+
+// S1. line_tab: [2][NCELLS] u8, the grid row and the grid column of every cell. status == nullptr: every capture usable, else the capture
+// path's extraction status, stride ints apart (> 0: usable). tears [n - 1][4], lines [n - 1][L] u16, live / ssym / scol per slot;
+// *n_slots (zeroed by the host) = the slots up to the last candidate's, for the Reed-Solomon launches: a batch without a candidate costs
+// them nothing but the launch. A non-candidate writes its record and cleared flags only.
+__global__ __launch_bounds__(256) void k_stitch_pairs(const uint8_t* __restrict__ symbols, const uint8_t* __restrict__ colors, int n,
+                                                      const int* __restrict__ status, int stride, const uint8_t* __restrict__ line_tab, int axis,
+                                                      int min_agree, int min_band, int32_t* __restrict__ tears, uint16_t* __restrict__ lines,
+                                                      uint32_t* __restrict__ live, int* __restrict__ n_slots, uint8_t* __restrict__ ssym,
+                                                      uint8_t* __restrict__ scol)
+{
+	const int k = blockIdx.x;
+	if (k + 1 >= n) return;
+	constexpr int W = NCELLS / 4;
+	constexpr uint32_t CM = 0x01010101u * (uint32_t)(NCOLORS - 1);
+	const int L = stitch_lines(axis);
+	__shared__ uint32_t s_cnt[128];
+	__shared__ int s_split;
+	if (threadIdx.x < 128) s_cnt[threadIdx.x] = 0;
+	__syncthreads();
+	const uint32_t* s0 = reinterpret_cast<const uint32_t*>(symbols + (size_t)k * NCELLS);
+	const uint32_t* c0 = reinterpret_cast<const uint32_t*>(colors + (size_t)k * NCELLS);
+	const uint32_t *s1 = s0 + W, *c1 = c0 + W;
+	const uint32_t* lt = reinterpret_cast<const uint32_t*>(line_tab + (size_t)axis * NCELLS);
+	for (int w = threadIdx.x; w < W; w += 256) {
+		const uint32_t x = ((s0[w] ^ s1[w]) & 0x0F0F0F0Fu) | ((c0[w] ^ c1[w]) & CM);
+		const uint32_t ids = lt[w];
+		const uint32_t e0 = (x & 0xFFu) == 0u, e1 = (x & 0xFF00u) == 0u, e2 = (x & 0xFF0000u) == 0u, e3 = (x >> 24) == 0u;
+		if (ids == (ids & 0xFFu) * 0x01010101u) {   // (axis 0: always)
+			const uint32_t c = e0 + e1 + e2 + e3;
+			if (c) atomicAdd(&s_cnt[ids & 0xFFu], c);
+		} else {
+			if (e0) atomicAdd(&s_cnt[ids & 0xFFu], 1u);
+			if (e1) atomicAdd(&s_cnt[(ids >> 8) & 0xFFu], 1u);
+			if (e2) atomicAdd(&s_cnt[(ids >> 16) & 0xFFu], 1u);
+			if (e3) atomicAdd(&s_cnt[ids >> 24], 1u);
+		}
+	}
+	__syncthreads();
+	if (threadIdx.x < 64) {
+		const int lane = threadIdx.x;
+		const bool usable = !status || (status[(size_t)k * stride] > 0 && status[(size_t)(k + 1) * stride] > 0);
+		bool fl[2];
+#pragma unroll
+		for (int h = 0; h < 2; ++h) {
+			const int l = lane + 64 * h;
+			const uint32_t c = l < L ? s_cnt[l] : 0u;
+			fl[h] = l < L && (unsigned long long)c * 1000ull >= (unsigned long long)min_agree * (unsigned long long)stitch_width(axis, l < L ? l : 0);
+			if (l < L) lines[(size_t)k * L + l] = (uint16_t)c;
+		}
+		const unsigned long long lo = __ballot(fl[0]), hi = __ballot(fl[1]);
+		if (lane == 0) {
+			const int f = (int)__popcll(lo) + (int)__popcll(hi);
+			int a = -1, b = -1, s = -1;
+			if (f >= 1) {
+				const int lowest = lo ? __ffsll((long long)lo) - 1 : 64 + __ffsll((long long)hi) - 1;
+				const int highest = hi ? 127 - __clzll((long long)hi) : 63 - __clzll((long long)lo);
+				const int bb = highest + 1;
+				if (usable && bb - lowest >= min_band && 4 * f >= 3 * (bb - lowest) && (lowest > 0 || bb < L)) { a = lowest; b = bb; s = (a + b) >> 1; }
+			}
+			int32_t* t = tears + (size_t)k * 4;
+			t[0] = a; t[1] = b; t[2] = s; t[3] = f;
+			live[2 * k] = live[2 * k + 1] = a >= 0 ? 1u : 0u;
+			if (a >= 0) atomicMax(n_slots, 2 * k + 2);
+			s_split = s;
+		}
+	}
+	__syncthreads();
+	const int s = s_split;
+	if (s < 0) return;
+	uint32_t* os0 = reinterpret_cast<uint32_t*>(ssym + (size_t)(2 * k) * NCELLS);
+	uint32_t* oc0 = reinterpret_cast<uint32_t*>(scol + (size_t)(2 * k) * NCELLS);
+	uint32_t *os1 = os0 + W, *oc1 = oc0 + W;
+	for (int w = threadIdx.x; w < W; w += 256) {
+		const uint32_t ids = lt[w];
+		// bytes whose line lies below the split: direction 0 takes them from capture k + 1, direction 1 from capture k
+		const uint32_t m = ((int)(ids & 0xFFu) < s ? 0xFFu : 0u) | ((int)((ids >> 8) & 0xFFu) < s ? 0xFF00u : 0u) |
+		                   ((int)((ids >> 16) & 0xFFu) < s ? 0xFF0000u : 0u) | ((int)(ids >> 24) < s ? 0xFF000000u : 0u);
+		const uint32_t a0 = s0[w], a1 = s1[w], b0 = c0[w], b1 = c1[w];
+		os0[w] = (a1 & m) | (a0 & ~m);
+		os1[w] = (a0 & m) | (a1 & ~m);
+		oc0[w] = (b1 & m) | (b0 & ~m);
+		oc1[w] = (b0 & m) | (b1 & ~m);
+	}
+}
+
+// S2: slot blockIdx.x of 2 (n - 1). Live: the aligned_stream bookkeeping over the slot's block flags, the symbol blocks then the colour
+// blocks with one state (group_end_body's cmask); smask = that mask, chunks outside it are zeroed. Not live: zero chunks, mask 0.
+__global__ __launch_bounds__(256) void k_stitch_end(const uint32_t* __restrict__ live, const uint8_t* __restrict__ rs_ok, uint8_t* __restrict__ schunks,
+                                                    uint32_t* __restrict__ smasks)
+{
+	const int g = blockIdx.x;
+	uint8_t* gc = schunks + (size_t)g * FRAME_BYTES;
+	if (!live[g]) {
+		for (int k = threadIdx.x; k < FRAME_BYTES; k += 256) gc[k] = 0;
+		if (threadIdx.x == 0) smasks[g] = 0;
+		return;
+	}
+	constexpr uint32_t FULL = (1u << CHUNKS) - 1u;
+	__shared__ uint32_t s_mask;
+	if (threadIdx.x < 64) {
+		const int lane = threadIdx.x;
+		const uint8_t* ok = rs_ok + (size_t)g * ALL_BLOCKS;
+		static_assert(ALL_BLOCKS <= 128, "block flags fit two ballots");
+		const unsigned long long lo = __ballot(lane < ALL_BLOCKS && ok[lane < ALL_BLOCKS ? lane : 0] != 0);
+		const unsigned long long hi = ALL_BLOCKS > 64 ? __ballot(64 + lane < ALL_BLOCKS && ok[64 + lane < ALL_BLOCKS ? 64 + lane : 0] != 0) : 0ull;
+		if (lane == 0) {
+			FrameState st = {0, 0, 0, 0};
+			uint8_t hdr[6] = {0, 0, 0, 0, 0, 0};
+			unsigned radio = 0;
+			for (int b = 0; b < ALL_BLOCKS; ++b) aligner_block(st, b, (int)(((b < 64 ? lo : hi) >> (b & 63)) & 1ull), nullptr, false, hdr, radio);
+			s_mask = st.mask & FULL;
+		}
+	}
+	__syncthreads();
+	const uint32_t mask = s_mask;
+	for (int j = 0; j < CHUNKS; ++j) {
+		if (mask & (1u << j)) continue;
+		uint8_t* dst = gc + (size_t)j * CHUNK;
+		for (int k = threadIdx.x; k < CHUNK; k += 256) dst[k] = 0;
+	}
+	if (threadIdx.x == 0) smasks[g] = mask;
+}

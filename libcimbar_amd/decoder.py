@@ -24,6 +24,7 @@ TAP_COLOUR_MARGIN = 13
 TAP_SCAN_PATH = 14
 TAP_GROUP_COLOUR_MARGIN, TAP_GROUP_COLOUR_WEIGHTS = 15, 16   # the colour vote of the last combined batch (set_group_colour_vote / set_stream_colour_vote)
 TAP_STREAM_CARRY_WEIGHTS = 17   # the carried weights of the open group's members after a stream call with set_stream_colour_vote on
+TAP_STITCH_CELLS, TAP_STITCH_LINES = 18, 19   # the stitching of the last stitched batch (decode_batch_stitched): n = its captures
 # CIMBAR_HIP_COLOUR_MARGIN_SUGGESTED (include/cimbar_hip.h): the colour erasure threshold chosen on rendered frames (DESIGN_WIDENING.md)
 COLOUR_MARGIN_SUGGESTED = 32512
 
@@ -51,6 +52,7 @@ EXPORTS = (
     "cimbar_hip_auto_create", "cimbar_hip_auto_destroy", "cimbar_hip_auto_bufsize", "cimbar_hip_auto_last_error", "cimbar_hip_auto_reset_ccm",
     "cimbar_hip_auto_get_ccm", "cimbar_hip_auto_set_ccm", "cimbar_hip_auto_scan_extract_decode_batch_fmt",
     "cimbar_hip_deliver_chunks", "cimbar_hip_delivery_reset", "cimbar_hip_delivery_stats",
+    "cimbar_hip_decode_batch_stitched", "cimbar_hip_scan_extract_decode_batch_stitched_fmt",
 )
 # cimbar_hip_deliver_chunks' flags
 DELIVER_DEDUP, DELIVER_REMEMBER, DELIVER_DROP_EMPTY = 1, 2, 4
@@ -167,6 +169,11 @@ def load_library(path=None):
     lib.cimbar_hip_scan_extract_decode_batch_combined_stream_fmt.argtypes = [vp, vp, u32, u32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp,
                                                                              vp, vp, vp, i32, vp]
     lib.cimbar_hip_scan_extract_decode_batch_combined_stream_fmt.restype = i64
+    lib.cimbar_hip_decode_batch_stitched.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp]
+    lib.cimbar_hip_decode_batch_stitched.restype = i64
+    lib.cimbar_hip_scan_extract_decode_batch_stitched_fmt.argtypes = [vp, vp, u32, u32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp,
+                                                                      i32, vp]
+    lib.cimbar_hip_scan_extract_decode_batch_stitched_fmt.restype = i64
     lib.cimbar_hip_combine_stream_reset.argtypes = [vp]
     lib.cimbar_hip_combine_stream_reset.restype = i32
     lib.cimbar_hip_auto_create.argtypes = [i32, vp, i32, ctypes.POINTER(vp)]
@@ -561,6 +568,51 @@ class HipDecoder:
             "cimbar_hip_scan_extract_decode_batch_combined_stream_fmt")
         return int(rc), chunks, masks, status, gout, gchunks, gmasks, gsizes
 
+    def _stitch_outputs(self, n):
+        geo = self.geo
+        p = max(n - 1, 0)
+        return (np.zeros((n, geo.CHUNKS_PER_FRAME, geo.CHUNK), dtype=np.uint8), np.zeros(n, dtype=np.uint32),
+                np.zeros((2 * p, geo.CHUNKS_PER_FRAME, geo.CHUNK), dtype=np.uint8), np.zeros(2 * p, dtype=np.uint32), np.zeros((p, 4), dtype=np.int32))
+
+    def decode_batch_stitched(self, frames, axis=0, min_agree_permille=0, min_band=0, should_preprocess=False, color_correction=2):
+        """Torn-capture stitching (cimbar_hip_decode_batch_stitched): frames as for decode_batch; axis 0 = a tear along a grid row, 1 = along
+        a grid column. Returns (candidate pairs, chunks, masks, schunks, smasks, tears): the per-capture results of decode_batch, 2 (n - 1)
+        slots of stitched chunks / masks (pair k, direction d at slot 2k + d) and the (n - 1, 4) tear records {a, b, s, f}."""
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        n = frames.shape[0]
+        if frames.shape[1:] != self.geo.FRAME_SHAPE:
+            raise CimbarHipError(f"decode_batch_stitched: frames must be (n,{self.geo.IMG_H},{self.geo.IMG_W},3) uint8")
+        chunks, masks, schunks, smasks, tears = self._stitch_outputs(n)
+        rc = self._check(self._lib.cimbar_hip_decode_batch_stitched(self._ctx, frames.ctypes.data, n, MEM_HOST, int(bool(should_preprocess)),
+                                                                    int(color_correction), int(axis), int(min_agree_permille), int(min_band),
+                                                                    chunks.ctypes.data, masks.ctypes.data, schunks.ctypes.data, smasks.ctypes.data,
+                                                                    tears.ctypes.data, MEM_HOST, None), "cimbar_hip_decode_batch_stitched")
+        return int(rc), chunks, masks, schunks, smasks, tears
+
+    def decode_batch_stitched_device(self, frames_ptr, n, chunks_ptr, masks_ptr, schunks_ptr, smasks_ptr, tears_ptr=None, axis=0,
+                                     min_agree_permille=0, min_band=0, should_preprocess=False, color_correction=2, stream=None):
+        """Device pointers in and out (layouts as in include/cimbar_hip.h; tears_ptr may be 0); enqueues on `stream` (None / 0 = the null
+        stream) and returns at once."""
+        vp = ctypes.c_void_p
+        return int(self._check(self._lib.cimbar_hip_decode_batch_stitched(self._ctx, vp(frames_ptr), int(n), MEM_DEVICE, int(bool(should_preprocess)),
+                                                                          int(color_correction), int(axis), int(min_agree_permille), int(min_band),
+                                                                          vp(chunks_ptr), vp(masks_ptr), vp(schunks_ptr or None), vp(smasks_ptr or None),
+                                                                          vp(tears_ptr or None), MEM_DEVICE, vp(stream) if stream else None),
+                               "cimbar_hip_decode_batch_stitched(device)"))
+
+    def scan_extract_decode_batch_stitched(self, captures, axis=0, min_agree_permille=0, min_band=0, preprocess=-1, color_correction=2,
+                                           size=None, fmt=3):
+        """The capture path with torn-capture stitching (cimbar_hip_scan_extract_decode_batch_stitched_fmt). Returns
+        (candidate pairs, chunks, masks, status, schunks, smasks, tears); a capture whose extraction failed is in no pair."""
+        captures, n, w, h, fmt = self._captures(captures, size, fmt)
+        chunks, masks, schunks, smasks, tears = self._stitch_outputs(n)
+        status = np.zeros(n, dtype=np.int32)
+        rc = self._check(self._lib.cimbar_hip_scan_extract_decode_batch_stitched_fmt(
+            self._ctx, captures.ctypes.data, w, h, fmt, n, MEM_HOST, int(preprocess), int(color_correction), int(axis), int(min_agree_permille),
+            int(min_band), chunks.ctypes.data, masks.ctypes.data, status.ctypes.data, schunks.ctypes.data, smasks.ctypes.data, tears.ctypes.data,
+            MEM_HOST, None), "cimbar_hip_scan_extract_decode_batch_stitched_fmt")
+        return int(rc), chunks, masks, status, schunks, smasks, tears
+
     def combine_stream_reset(self):
         """drop the open group and the stream's fixed min_agree_permille / max_group"""
         self._check(self._lib.cimbar_hip_combine_stream_reset(self._ctx), "cimbar_hip_combine_stream_reset")
@@ -915,10 +967,18 @@ class HipDecoder:
             TAP_COLOUR_MARGIN: ((n, self.geo.NCELLS), np.uint32), TAP_SCAN_PATH: ((n,), np.int32),
             TAP_GROUP_COLOUR_MARGIN: ((n, self.geo.NCELLS), np.uint32), TAP_GROUP_COLOUR_WEIGHTS: ((n, self.geo.NCELLS), np.uint32),
             TAP_STREAM_CARRY_WEIGHTS: ((n, self.geo.NCELLS), np.uint32),
+            # (n = the captures of the stitched batch; the lines tap has DIM_Y entries per pair on axis 0 and DIM_X on axis 1: tap_stitch_lines)
+            TAP_STITCH_CELLS: ((2 * max(n - 1, 0), self.geo.NCELLS), np.uint8),
         }
         shape, dt = shapes[what]
         out = np.zeros(shape, dtype=dt)
         self._check(self._lib.cimbar_hip_tap(self._ctx, what, out.ctypes.data, out.nbytes), "cimbar_hip_tap")
+        return out
+
+    def tap_stitch_lines(self, n, axis=0):
+        """TAP_STITCH_LINES of the last stitched batch of n captures on `axis`: (n - 1, L) uint16, the agreeing cells per line"""
+        out = np.zeros((max(n - 1, 0), self.geo.DIM_Y if axis == 0 else self.geo.DIM_X), dtype=np.uint16)
+        self._check(self._lib.cimbar_hip_tap(self._ctx, TAP_STITCH_LINES, out.ctypes.data, out.nbytes), "cimbar_hip_tap")
         return out
 
     def enable_timing(self, on=True):
