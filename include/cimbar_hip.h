@@ -359,8 +359,8 @@ int cimbar_hip_get_stream_colour_vote(cimbar_hip_ctx* ctx, int* on);
  *   tears      (n - 1) x 4 int32 {a, b, s, f}, a = b = s = -1 for a pair that is no candidate; may be NULL
  * Every output follows out_mem. Host outputs: synchronises and returns the number of candidate pairs. Device outputs: enqueues only, behind
  * the per-capture decode on the same stream, and returns 0. n == 1: no pair, nothing stitched, returns 0. axis outside {0, 1}, min_band > L
- * or a null required pointer: CIMBAR_HIP_EINVAL, checked before anything is enqueued. Pairs do not span two calls. Buffers, stream and errors
- * otherwise as for cimbar_hip_decode_batch; no other call's behaviour depends on these. */
+ * or a null required pointer: CIMBAR_HIP_EINVAL, checked before anything is enqueued. Pairs do not span two calls (the stream forms below
+ * carry the last capture). Buffers, stream and errors otherwise as for cimbar_hip_decode_batch; no other call's behaviour depends on these. */
 int64_t cimbar_hip_decode_batch_stitched(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rgb_mem, int should_preprocess, int color_correction,
                                          int axis, int min_agree_permille, int min_band, uint8_t* chunks, uint32_t* masks, uint8_t* schunks,
                                          uint32_t* smasks, int32_t* tears, int out_mem, void* hip_stream);
@@ -368,6 +368,39 @@ int64_t cimbar_hip_scan_extract_decode_batch_stitched_fmt(cimbar_hip_ctx* ctx, c
                                                           int img_mem, int preprocess, int color_correction, int axis, int min_agree_permille,
                                                           int min_band, uint8_t* chunks, uint32_t* masks, int* status, uint8_t* schunks,
                                                           uint32_t* smasks, int32_t* tears, int out_mem, void* hip_stream);
+
+/* Torn-capture stitching across calls. A live receiver hands over one capture per call, or a few, and a tear's two captures then arrive in two
+ * calls; these calls keep a copy of the last capture's decided cells on the device (symbols and colours, one byte per cell each, and one word
+ * saying whether the capture is usable) and hold the next stream call's first capture against it. Take a sequence of stitched-stream calls on
+ * one context that starts after cimbar_hip_create or cimbar_hip_stitch_stream_reset and uses one axis, min_agree_permille and min_band: it
+ * reports, in order, the pairs ONE cimbar_hip_decode_batch_stitched (or _scan_extract_decode_batch_stitched_fmt) call reports for the
+ * concatenation of the captures -- tears, schunks and smasks -- each pair in the call that holds its second capture. A pair closes with its
+ * second capture, so nothing is ever open and there is no flush.
+ *   rows       a call of n captures reports n pair rows: row 0 = (the carried capture, capture 0), row r = (capture r - 1, capture r); row r,
+ *              direction d is slot 2r + d. schunks: 2n slots of cimbar_hip_ctx_bufsize bytes, smasks: 2n words, tears: n x 4 int32 (may be NULL)
+ *   row 0 without a usable carry  (the first call after create or reset; capture path: the carried capture's extraction failed) is no
+ *              candidate: tears {-1, -1, -1, 0}, both slots zero, both masks 0
+ *   the rule   otherwise the one above, word for word: eq, flag, band, candidate, split, both directions, the decode and what smask means. No
+ *              matrix is derived, read or carried; no vote, no erasure retry
+ *   chunks / masks / status and the colour-correction carry are the plain call's for the same input
+ *   axis, min_agree_permille, min_band, should_preprocess, color_correction, n and the capture size may change from call to call: row 0 is
+ *              judged with the parameters of the call that reports it. Only the carry is state
+ * n <= 0, a null required pointer, axis outside {0, 1} or min_band > L: CIMBAR_HIP_EINVAL, checked before anything is enqueued, the carry left
+ * as it was. Host outputs: synchronises and returns the candidate rows of this call. Device outputs: enqueues only and returns 0; whether row 0
+ * has a usable partner is decided on the device from the carried word, nothing is read back. Other calls on the context may run between two
+ * stitched-stream calls (cimbar_hip_decode_batch, the plain stitched calls, the combined and combined-stream calls, delivery, the pipelined
+ * entry): they neither see nor disturb the carry. Consecutive stitched-stream calls are ordered against each other, whatever their hip_stream.
+ * The scratch of the stitched decode is shared with the plain stitched calls: a plain and a stream stitched call running at the same time on
+ * two streams are the caller's to order. The stitch taps after a stream call describe its n rows.
+ * cimbar_hip_stitch_stream_reset waits for the stitched-stream calls issued so far and forgets the carry. */
+int64_t cimbar_hip_decode_batch_stitched_stream(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rgb_mem, int should_preprocess, int color_correction,
+                                                int axis, int min_agree_permille, int min_band, uint8_t* chunks, uint32_t* masks, uint8_t* schunks,
+                                                uint32_t* smasks, int32_t* tears, int out_mem, void* hip_stream);
+int64_t cimbar_hip_scan_extract_decode_batch_stitched_stream_fmt(cimbar_hip_ctx* ctx, const uint8_t* img, unsigned width, unsigned height, int format,
+                                                                 int n, int img_mem, int preprocess, int color_correction, int axis,
+                                                                 int min_agree_permille, int min_band, uint8_t* chunks, uint32_t* masks, int* status,
+                                                                 uint8_t* schunks, uint32_t* smasks, int32_t* tears, int out_mem, void* hip_stream);
+int cimbar_hip_stitch_stream_reset(cimbar_hip_ctx* ctx);
 
 /* ---- chunk delivery: a batch's slots and masks -> what a fountain sink eats --------------------------------------------------------------
  * The batch entry points above report a frame's chunks in fixed slots plus one mask word. The reference's receive interface has another shape:
@@ -680,10 +713,14 @@ enum {
 	CIMBAR_HIP_TAP_STREAM_CARRY_WEIGHTS = 17,/* rows * cells u32    : the carried weights of slots 0 .. rows - 1 (the open group's members in capture
 	                                            order), every cell filled; rows = out_bytes / (cells * 4), CIMBAR_HIP_EINVAL above the occupied slots */
 	/* the stitching of the last batch, when it was a stitched one (cimbar_hip_decode_batch_stitched / _scan_extract_decode_batch_stitched_fmt;
-	 * CIMBAR_HIP_EINVAL after any other batch) */
+	 * CIMBAR_HIP_EINVAL after any other batch). After a stitched-stream call of n captures both describe its n rows: 2n * cells bytes and
+	 * n * L u16, row 0 first (zero counts where row 0 had no usable carry). */
 	CIMBAR_HIP_TAP_STITCH_CELLS = 18, /* 2 (n - 1) * cells bytes: the stitched cell of slot 2k + d, colour << 4 | symbol; zero for the slots of a
 	                                     pair that is no candidate */
-	CIMBAR_HIP_TAP_STITCH_LINES = 19  /* (n - 1) * L u16        : cnt(l), the agreeing cells of pair k on line l of the call's axis */
+	CIMBAR_HIP_TAP_STITCH_LINES = 19, /* (n - 1) * L u16        : cnt(l), the agreeing cells of pair k on line l of the call's axis */
+	/* what the stitched-stream calls carry: the last capture of the last such call (CIMBAR_HIP_EINVAL while nothing is carried: after create and
+	 * after cimbar_hip_stitch_stream_reset); does not depend on the last batch */
+	CIMBAR_HIP_TAP_STITCH_CARRY = 20  /* 2 * cells bytes        : the carried symbols, then the carried colours, by linear cell index */
 };
 int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_bytes);
 

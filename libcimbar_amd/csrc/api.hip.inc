@@ -284,6 +284,31 @@ int64_t cimbar_hip_scan_extract_decode_batch_stitched_fmt(cimbar_hip_ctx* ctx, c
 	                  min_agree_permille, min_band, chunks, masks, status, schunks, smasks, tears, out_mem, hip_stream);
 }
 
+int64_t cimbar_hip_decode_batch_stitched_stream(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rgb_mem, int should_preprocess, int color_correction,
+                                                int axis, int min_agree_permille, int min_band, uint8_t* chunks, uint32_t* masks, uint8_t* schunks,
+                                                uint32_t* smasks, int32_t* tears, int out_mem, void* hip_stream)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return CIMBAR_FWD(cimbar_hip_decode_batch_stitched_stream, rgb, n, rgb_mem, should_preprocess, color_correction, axis, min_agree_permille, min_band,
+	                  chunks, masks, schunks, smasks, tears, out_mem, hip_stream);
+}
+
+int64_t cimbar_hip_scan_extract_decode_batch_stitched_stream_fmt(cimbar_hip_ctx* ctx, const uint8_t* img, unsigned width, unsigned height, int format,
+                                                                 int n, int img_mem, int preprocess, int color_correction, int axis,
+                                                                 int min_agree_permille, int min_band, uint8_t* chunks, uint32_t* masks, int* status,
+                                                                 uint8_t* schunks, uint32_t* smasks, int32_t* tears, int out_mem, void* hip_stream)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return CIMBAR_FWD(cimbar_hip_scan_extract_decode_batch_stitched_stream_fmt, img, width, height, format, n, img_mem, preprocess, color_correction,
+	                  axis, min_agree_permille, min_band, chunks, masks, status, schunks, smasks, tears, out_mem, hip_stream);
+}
+
+int cimbar_hip_stitch_stream_reset(cimbar_hip_ctx* ctx)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return CIMBAR_FWD(cimbar_hip_stitch_stream_reset);
+}
+
 int cimbar_hip_combine_stream_reset(cimbar_hip_ctx* ctx)
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;

@@ -15,6 +15,19 @@ struct CombineStream {
 	CarryStore store() const { return CarryStore{symbols, colors, plane, drift, flood, chunks, masks, words, weights}; }
 };
 
+// what the stream calls of torn-capture stitching keep between calls (stitch.hip.inc, "the stream calls"): the last capture's decided cells
+// in two slots used in turn, one usable word per slot and the event that orders one stream call behind the one before. Nothing of it exists
+// until the first stitched-stream call.
+struct StitchStream {
+	DevBuf<uint8_t> symbols, colors;          // [2][SS_CELLS]
+	DevBuf<uint32_t> usable;                  // [2]
+	Event ev_last;                            // behind the last stitched-stream call's work: the next one, on whatever stream, starts after it
+	bool used = false;                        // ev_last has been recorded
+	bool carried = false;                     // slot `cur` holds the last capture of a stream call (CIMBAR_HIP_TAP_STITCH_CARRY describes it)
+	int cur = 0;                              // the slot the next call reads
+	StitchCarry carry() const { return StitchCarry{symbols, colors, usable, cur}; }
+};
+
 struct cimbar_hip_ctx {
 	int mode_tag = MODE_VAL;                  // FIRST member: api.hip.inc reads it through the opaque pointer to pick the namespace
 	int device = 0;
@@ -44,8 +57,10 @@ struct cimbar_hip_ctx {
 	std::unique_ptr<CombineStream> cstream;     // cimbar_hip_decode_batch_combined_stream / _scan_extract_decode_batch_combined_stream_fmt
 	// torn-capture stitching (cimbar_hip_decode_batch_stitched / _scan_extract_decode_batch_stitched_fmt, stitch.hip.inc): per pair slot, grown on demand
 	int stitch_n = 0, stitch_axis = 0;          // the last batch was a stitched one of stitch_n captures (> 0: the stitch taps describe it)
-	DevBuf<uint8_t> d_ssym, d_scol, d_srs_ok;   // [2 (n - 1)][NCELLS], [2 (n - 1)][ALL_BLOCKS]
-	DevBuf<uint32_t> d_slive; DevBuf<int32_t> d_stears; DevBuf<uint16_t> d_slines; DevBuf<int> d_sslots;   // [2 (n - 1)], [n - 1][4], [n - 1][L], 1 int
+	int stitch_rows = 0;                        // ... and reported that many pair rows: stitch_n - 1, a stream call stitch_n
+	DevBuf<uint8_t> d_ssym, d_scol, d_srs_ok;   // [2 rows][NCELLS], [2 rows][ALL_BLOCKS]
+	DevBuf<uint32_t> d_slive; DevBuf<int32_t> d_stears; DevBuf<uint16_t> d_slines; DevBuf<int> d_sslots;   // [2 rows], [rows][4], [rows][L], 1 int
+	std::unique_ptr<StitchStream> sstream;      // cimbar_hip_decode_batch_stitched_stream / _scan_extract_decode_batch_stitched_stream_fmt
 	DevBuf<uint8_t> d_schunks; DevBuf<uint32_t> d_smasks;   // staging for host-memory stitch outputs
 	int wave_adapt = 1;               // CIMBAR_HIP_FLOOD_WAVE_ADAPT=0: run k_flood_wave in front of every exact replay, whatever it achieved before
 	bool wave_ran = false;            // k_flood_wave ran in the batch h_flagged describes
@@ -1118,8 +1133,10 @@ int64_t finish_batch(cimbar_hip_ctx* ctx, hipStream_t st, int n, uint8_t* chunks
 // ------------------------------------------------------------------------------------------------ torn-capture stitching (stitch.hip.inc)
 struct StitchArgs {
 	int axis, min_agree, min_band;
-	uint8_t* schunks; uint32_t* smasks; int32_t* tears;   // 2 (n - 1) slots; (n - 1) x 4 ints (may be nullptr)
+	uint8_t* schunks; uint32_t* smasks; int32_t* tears;   // 2 rows slots; rows x 4 ints (may be nullptr)
 	std::vector<int32_t> h_tears;                         // host outputs: where the tear records land when the caller wants none
+	bool stream = false;                                  // a stream call: n rows, row 0 against the carried capture; else n - 1
+	int rows(int n) const { return stream ? n : n - 1; }
 };
 
 // the argument checks of the stitched entry points, before anything is enqueued
@@ -1127,15 +1144,15 @@ int check_stitch(cimbar_hip_ctx* ctx, const char* who, int n, StitchArgs& sa)
 {
 	if (sa.axis != 0 && sa.axis != 1) { ctx->err = std::string(who) + ": axis must be 0 (grid rows) or 1 (grid columns)"; return CIMBAR_HIP_EINVAL; }
 	if (sa.min_band > stitch_lines(sa.axis)) { ctx->err = std::string(who) + ": min_band above the lines of the axis"; return CIMBAR_HIP_EINVAL; }
-	if (n > 1 && (!sa.schunks || !sa.smasks)) { ctx->err = std::string(who) + ": null schunks / smasks"; return CIMBAR_HIP_EINVAL; }
+	if (sa.rows(n) > 0 && (!sa.schunks || !sa.smasks)) { ctx->err = std::string(who) + ": null schunks / smasks"; return CIMBAR_HIP_EINVAL; }
 	if (sa.min_agree <= 0) sa.min_agree = STITCH_AGREE_DEFAULT;
 	if (sa.min_band <= 0) sa.min_band = STITCH_BAND_DEFAULT;
 	return 0;
 }
 
-int ensure_stitch_capacity(cimbar_hip_ctx* ctx, int n)
+int ensure_stitch_capacity(cimbar_hip_ctx* ctx, int rows)
 {
-	const size_t P = (size_t)n - 1, S = 2 * P;
+	const size_t P = (size_t)rows, S = 2 * P;
 	HIPCHK(ctx->d_ssym.reserve(S * NCELLS));
 	HIPCHK(ctx->d_scol.reserve(S * NCELLS));
 	HIPCHK(ctx->d_srs_ok.reserve(S * ALL_BLOCKS));
@@ -1148,20 +1165,43 @@ int ensure_stitch_capacity(cimbar_hip_ctx* ctx, int n)
 	return 0;
 }
 
-// S1, the Reed-Solomon pass over the 2 (n - 1) slots (launch_live_rs: the k_rs LIVE instances of the group decode, fed from the stitch scratch) and S2, behind
-// a batch's per-capture decode on the same stream (n > 1). Reads that decode's symbols and colours; writes the caller's buffers (device
-// outputs) or the context's staging, whose copies back to the host are enqueued here as well. d_status as for enqueue_combine.
+// the start of a stitched-stream call, in front of its per-capture decode: the carry store (allocated by the first such call, nothing
+// carried) and the wait that puts the whole call behind the stitched-stream call before, whatever their streams
+int begin_stitch_stream(cimbar_hip_ctx* ctx, hipStream_t st)
+{
+	if (!ctx->sstream) ctx->sstream = std::make_unique<StitchStream>();
+	StitchStream& s = *ctx->sstream;
+	HIPCHK(s.ev_last.create());
+	HIPCHK(s.symbols.ensure((size_t)2 * SS_CELLS));
+	HIPCHK(s.colors.ensure((size_t)2 * SS_CELLS));
+	if (!s.usable) { HIPCHK(s.usable.ensure(2)); HIPCHK(hipMemset(s.usable, 0, sizeof(uint32_t) * 2)); }
+	if (s.used) HIPCHK(hipStreamWaitEvent(st, s.ev_last, 0));
+	return 0;
+}
+
+// S1, the Reed-Solomon pass over the 2 rows slots (launch_live_rs: the k_rs LIVE instances of the group decode, fed from the stitch scratch) and S2, behind
+// a batch's per-capture decode on the same stream (rows > 0: n - 1 pairs, a stream call n rows). Reads that decode's symbols and colours; writes the
+// caller's buffers (device outputs) or the context's staging, whose copies back to the host are enqueued here as well. d_status as for enqueue_combine.
+// A stream call (after begin_stitch_stream): S1 reads the carried capture from one slot and leaves its last capture in the other.
 int enqueue_stitch(cimbar_hip_ctx* ctx, hipStream_t st, int n, const int* d_status, int stride, StitchArgs& sa, int out_mem)
 {
-	if (int r = ensure_stitch_capacity(ctx, n)) return r;
+	const int pairs = sa.rows(n), slots = 2 * pairs;
+	if (int r = ensure_stitch_capacity(ctx, pairs)) return r;
 	cimbar_hip_ctx::ScratchSet& cur = ctx->cur();
-	const int pairs = n - 1, slots = 2 * pairs;
 	const bool dev = out_mem == CIMBAR_HIP_MEM_DEVICE;
 	uint8_t* d_out = dev ? sa.schunks : ctx->d_schunks.get();
 	uint32_t* d_om = dev ? sa.smasks : ctx->d_smasks.get();
 	HIPCHK(hipMemsetAsync(ctx->d_sslots, 0, sizeof(int), st));
-	hipLaunchKernelGGL(k_stitch_pairs, dim3(pairs), dim3(256), 0, st, cur.d_symbols, cur.d_colors, n, d_status, stride, ctx->tb_stitch_line, sa.axis,
-	                   sa.min_agree, sa.min_band, ctx->d_stears, ctx->d_slines, ctx->d_slive, ctx->d_sslots, ctx->d_ssym, ctx->d_scol);
+	if (sa.stream) {
+		StitchStream& s = *ctx->sstream;
+		hipLaunchKernelGGL(k_stitch_pairs_stream, dim3(pairs), dim3(256), 0, st, cur.d_symbols, cur.d_colors, n, d_status, stride, ctx->tb_stitch_line,
+		                   sa.axis, sa.min_agree, sa.min_band, ctx->d_stears, ctx->d_slines, ctx->d_slive, ctx->d_sslots, ctx->d_ssym, ctx->d_scol, s.carry());
+		HIPCHK(hipGetLastError());
+		s.cur ^= 1;   // (the slot that launch fills)
+		s.carried = true;
+	} else
+		hipLaunchKernelGGL(k_stitch_pairs, dim3(pairs), dim3(256), 0, st, cur.d_symbols, cur.d_colors, n, d_status, stride, ctx->tb_stitch_line, sa.axis,
+		                   sa.min_agree, sa.min_band, ctx->d_stears, ctx->d_slines, ctx->d_slive, ctx->d_sslots, ctx->d_ssym, ctx->d_scol);
 	launch_live_rs(ctx, st, slots, ctx->d_ssym, ctx->d_scol, ctx->d_srs_ok, ctx->d_sslots, ctx->d_slive, d_out);
 	hipLaunchKernelGGL(k_stitch_end, dim3(slots), dim3(256), 0, st, ctx->d_slive, ctx->d_srs_ok, d_out, d_om);
 	HIPCHK(hipGetLastError());
@@ -1176,17 +1216,23 @@ int enqueue_stitch(cimbar_hip_ctx* ctx, hipStream_t st, int n, const int* d_stat
 	return 0;
 }
 
-// the end of a stitched call: finish_batch for the per-capture outputs; host outputs: the candidate pairs, read from the tear records
+// the end of a stitched call: finish_batch for the per-capture outputs; host outputs: the candidate pairs, read from the tear records.
+// A stream call records the event the next one waits for, behind everything it enqueued.
 int64_t finish_stitched(cimbar_hip_ctx* ctx, hipStream_t st, int n, uint8_t* chunks, uint32_t* masks, const uint8_t* d_chunks, const uint32_t* d_masks,
                         int out_mem, const StitchArgs& sa)
 {
 	const int64_t r = finish_batch(ctx, st, n, chunks, masks, d_chunks, d_masks, out_mem, nullptr);
 	if (r < 0) return r;
 	ctx->stitch_n = n;
+	ctx->stitch_rows = sa.rows(n);
 	ctx->stitch_axis = sa.axis;
-	if (out_mem == CIMBAR_HIP_MEM_DEVICE || n < 2) return 0;
+	if (sa.stream) {
+		HIPCHK(hipEventRecord(ctx->sstream->ev_last, st));
+		ctx->sstream->used = true;
+	}
+	if (out_mem == CIMBAR_HIP_MEM_DEVICE) return 0;
 	int64_t cand = 0;
-	for (int k = 0; k + 1 < n; ++k) cand += sa.tears[(size_t)k * 4] >= 0;
+	for (int k = 0; k < sa.rows(n); ++k) cand += sa.tears[(size_t)k * 4] >= 0;
 	return cand;
 }
 
@@ -1194,7 +1240,7 @@ int64_t decode_batch_impl(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rg
                           uint32_t* masks, int out_mem, void* hip_stream, CombineArgs* cb, StitchArgs* sa = nullptr)
 {
 	const bool strm = cb && cb->stream;
-	const char* who = sa ? "decode_batch_stitched" : strm ? "decode_batch_combined_stream" : cb ? "decode_batch_combined" : "decode_batch";
+	const char* who = sa ? (sa->stream ? "decode_batch_stitched_stream" : "decode_batch_stitched") : strm ? "decode_batch_combined_stream" : cb ? "decode_batch_combined" : "decode_batch";
 	// (a stream call may bring no capture at all: n == 0 with a flush closes the open group)
 	if (strm ? (n < 0 || (n > 0 && (!rgb || !chunks || !masks))) : (!rgb || !chunks || !masks || n <= 0)) { ctx->err = std::string(who) + ": null buffer or n <= 0"; return CIMBAR_HIP_EINVAL; }
 	if ((rgb_mem != CIMBAR_HIP_MEM_HOST && rgb_mem != CIMBAR_HIP_MEM_DEVICE) || (out_mem != CIMBAR_HIP_MEM_HOST && out_mem != CIMBAR_HIP_MEM_DEVICE)) {
@@ -1213,6 +1259,7 @@ int64_t decode_batch_impl(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rg
 		if (int r = enqueue_combine_stream(ctx, st, 0, nullptr, nullptr, nullptr, nullptr, 0, *cb, out_mem)) return r;
 		return finish_stream(ctx, st, 0, chunks, masks, nullptr, nullptr, out_mem, *cb);
 	}
+	if (sa && sa->stream) if (int r = begin_stitch_stream(ctx, st)) return r;
 	if (int r = ensure_capacity(ctx, n)) return r;
 
 	const uint8_t* d_rgb = nullptr;
@@ -1228,7 +1275,7 @@ int64_t decode_batch_impl(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rg
 	if (cb)
 		if (int r = enqueue_combine(ctx, st, n, d_rgb, d_chunks, d_masks, nullptr, 0, *cb, out_mem)) return r;
 	if (sa) {
-		if (n > 1) if (int r = enqueue_stitch(ctx, st, n, nullptr, 0, *sa, out_mem)) return r;
+		if (sa->rows(n) > 0) if (int r = enqueue_stitch(ctx, st, n, nullptr, 0, *sa, out_mem)) return r;
 		return finish_stitched(ctx, st, n, chunks, masks, d_chunks, d_masks, out_mem, *sa);
 	}
 	return finish_batch(ctx, st, n, chunks, masks, d_chunks, d_masks, out_mem, cb);
@@ -1268,6 +1315,28 @@ int64_t cimbar_hip_decode_batch_stitched(cimbar_hip_ctx* ctx, const uint8_t* rgb
 	if (!ctx) return CIMBAR_HIP_EINVAL;
 	StitchArgs sa{axis, min_agree_permille, min_band, schunks, smasks, tears, {}};
 	return decode_batch_impl(ctx, rgb, n, rgb_mem, should_preprocess, color_correction, chunks, masks, out_mem, hip_stream, nullptr, &sa);
+}
+
+int64_t cimbar_hip_decode_batch_stitched_stream(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rgb_mem, int should_preprocess, int color_correction,
+                                                int axis, int min_agree_permille, int min_band, uint8_t* chunks, uint32_t* masks, uint8_t* schunks,
+                                                uint32_t* smasks, int32_t* tears, int out_mem, void* hip_stream)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	StitchArgs sa{axis, min_agree_permille, min_band, schunks, smasks, tears, {}, true};
+	return decode_batch_impl(ctx, rgb, n, rgb_mem, should_preprocess, color_correction, chunks, masks, out_mem, hip_stream, nullptr, &sa);
+}
+
+// wait for the stitched-stream calls issued so far and forget the carry: the next one's row 0 has no partner
+int cimbar_hip_stitch_stream_reset(cimbar_hip_ctx* ctx)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	if (!ctx->sstream) return 0;
+	StitchStream& s = *ctx->sstream;
+	HIPCHK(hipSetDevice(ctx->device));
+	if (s.used) HIPCHK(hipEventSynchronize(s.ev_last));
+	if (s.usable) HIPCHK(hipMemset(s.usable, 0, sizeof(uint32_t) * 2));
+	s.carried = false;
+	return 0;
 }
 
 // drop the open group and the fixed parameters: the next stream call starts a stream of its own
@@ -1786,7 +1855,7 @@ int64_t scan_extract_decode_impl(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsign
                                  void* hip_stream, CombineArgs* cb, StitchArgs* sa = nullptr)
 {
 	const bool strm = cb && cb->stream;
-	const char* who = sa ? "scan_extract_decode_batch_stitched" : strm ? "scan_extract_decode_batch_combined_stream" : cb ? "scan_extract_decode_batch_combined" : "scan_extract_decode_batch";
+	const char* who = sa ? (sa->stream ? "scan_extract_decode_batch_stitched_stream" : "scan_extract_decode_batch_stitched") : strm ? "scan_extract_decode_batch_combined_stream" : cb ? "scan_extract_decode_batch_combined" : "scan_extract_decode_batch";
 	if (strm && n == 0) {   // (no capture: a flush closes the open group; no image argument is read)
 		if (out_mem != CIMBAR_HIP_MEM_HOST && out_mem != CIMBAR_HIP_MEM_DEVICE) { ctx->err = std::string(who) + ": out_mem must be CIMBAR_HIP_MEM_HOST or CIMBAR_HIP_MEM_DEVICE"; return CIMBAR_HIP_EINVAL; }
 		if (int r = check_combine(ctx, who, n, *cb)) return r;
@@ -1809,6 +1878,7 @@ int64_t scan_extract_decode_impl(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsign
 	const bool any_device = rgb_mem == CIMBAR_HIP_MEM_DEVICE || out_mem == CIMBAR_HIP_MEM_DEVICE;
 	hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (any_device ? (hipStream_t)nullptr : ctx->stream);
 	if (int r = drain_pipeline_into(ctx, st)) return r;
+	if (sa && sa->stream) if (int r = begin_stitch_stream(ctx, st)) return r;
 	if (int r = extract_state(ctx, n)) return r;
 	if (int r = ensure_capacity(ctx, n)) return r;
 	const uint8_t* d_in = nullptr;
@@ -1834,7 +1904,7 @@ int64_t scan_extract_decode_impl(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsign
 	else if (cb)
 		if (int r = enqueue_combine(ctx, st, n, ctx->d_ex_frames, d_chunks, d_masks, &ctx->d_scan_res[0].status, stride, *cb, out_mem)) return r;
 	// ... nor any stitched pair
-	if (sa && n > 1)
+	if (sa && sa->rows(n) > 0)
 		if (int r = enqueue_stitch(ctx, st, n, &ctx->d_scan_res[0].status, stride, *sa, out_mem)) return r;
 	const hipMemcpyKind kind = out_mem == CIMBAR_HIP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
 	if (status) HIPCHK(hipMemcpy2DAsync(status, sizeof(int), &ctx->d_scan_res[0].status, sizeof(ScanResult), sizeof(int), (size_t)n, kind, st));
@@ -1870,6 +1940,16 @@ int64_t cimbar_hip_scan_extract_decode_batch_stitched_fmt(cimbar_hip_ctx* ctx, c
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;
 	StitchArgs sa{axis, min_agree_permille, min_band, schunks, smasks, tears, {}};
+	return scan_extract_decode_impl(ctx, rgb, width, height, format, n, rgb_mem, preprocess, color_correction, chunks, masks, status, out_mem, hip_stream, nullptr, &sa);
+}
+
+int64_t cimbar_hip_scan_extract_decode_batch_stitched_stream_fmt(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsigned width, unsigned height, int format,
+                                                                 int n, int rgb_mem, int preprocess, int color_correction, int axis,
+                                                                 int min_agree_permille, int min_band, uint8_t* chunks, uint32_t* masks, int* status,
+                                                                 uint8_t* schunks, uint32_t* smasks, int32_t* tears, int out_mem, void* hip_stream)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	StitchArgs sa{axis, min_agree_permille, min_band, schunks, smasks, tears, {}, true};
 	return scan_extract_decode_impl(ctx, rgb, width, height, format, n, rgb_mem, preprocess, color_correction, chunks, masks, status, out_mem, hip_stream, nullptr, &sa);
 }
 
@@ -2065,6 +2145,17 @@ int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_byte
 		for (size_t k = 0; k < m; ++k) ((int32_t*)out)[k] = status[k] < 0 ? 2 : (ovf[k] ? 1 : 0);
 		return (int64_t)(m * sizeof(int32_t));
 	}
+	if (what == CIMBAR_HIP_TAP_STITCH_CARRY) {
+		// what the next stitched-stream call's row 0 is held against: the carried symbols, then the carried colours
+		if (!ctx->sstream || !ctx->sstream->carried) { ctx->err = "tap: nothing is carried (no stitched-stream call since create / cimbar_hip_stitch_stream_reset)"; return CIMBAR_HIP_EINVAL; }
+		if (out_bytes < (size_t)2 * NCELLS) { ctx->err = "tap: buffer too small"; return CIMBAR_HIP_EINVAL; }
+		const StitchStream& s = *ctx->sstream;
+		HIPCHK(hipSetDevice(ctx->device));
+		HIPCHK(hipDeviceSynchronize());
+		HIPCHK(hipMemcpy(out, s.symbols + (size_t)s.cur * SS_CELLS, NCELLS, hipMemcpyDeviceToHost));
+		HIPCHK(hipMemcpy((uint8_t*)out + NCELLS, s.colors + (size_t)s.cur * SS_CELLS, NCELLS, hipMemcpyDeviceToHost));
+		return (int64_t)2 * NCELLS;
+	}
 	if (ctx->last_n <= 0) { ctx->err = "tap: no batch has been decoded on this context yet"; return CIMBAR_HIP_EINVAL; }
 	HIPCHK(hipSetDevice(ctx->device));
 	HIPCHK(hipDeviceSynchronize());
@@ -2178,8 +2269,8 @@ int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_byte
 		}
 		case CIMBAR_HIP_TAP_STITCH_CELLS:
 		case CIMBAR_HIP_TAP_STITCH_LINES: {
-			if (ctx->stitch_n <= 0) { ctx->err = "tap: the last batch was not a stitched one (cimbar_hip_decode_batch_stitched / _scan_extract_decode_batch_stitched_fmt)"; return CIMBAR_HIP_EINVAL; }
-			const size_t pairs = (size_t)ctx->stitch_n - 1, slots = 2 * pairs, L = (size_t)stitch_lines(ctx->stitch_axis);
+			if (ctx->stitch_n <= 0) { ctx->err = "tap: the last batch was not a stitched one (cimbar_hip_decode_batch_stitched / _scan_extract_decode_batch_stitched_fmt and their stream forms)"; return CIMBAR_HIP_EINVAL; }
+			const size_t pairs = (size_t)ctx->stitch_rows, slots = 2 * pairs, L = (size_t)stitch_lines(ctx->stitch_axis);
 			bytes = what == CIMBAR_HIP_TAP_STITCH_LINES ? pairs * L * sizeof(uint16_t) : slots * NCELLS;
 			if (out_bytes < bytes) { ctx->err = "tap: buffer too small"; return CIMBAR_HIP_EINVAL; }
 			if (!bytes) return 0;

@@ -23,6 +23,12 @@
 //                      directions' stitched symbols and colours
 //   K3 k_rs            over 2 (n - 1) slots (LIVE: the workgroups past the last candidate and the wavefronts of a non-candidate return at once)
 //   S2 k_stitch_end    one workgroup per slot: the aligner walk, the mask, zeroes for undelivered chunks; all zeroes for a non-live slot
+// ------------------------------------------------------------------------------------------------ the stream calls
+// cimbar_hip_decode_batch_stitched_stream / _scan_extract_decode_batch_stitched_stream_fmt: a call of n captures reports n rows, row 0 = (the last
+// capture of the stream call before, capture 0), row r = (capture r - 1, capture r); row r, direction d is slot 2r + d. A pair closes with its
+// second capture, so the carry is always one capture's decided cells and a word saying whether that capture is usable; nothing is ever open.
+// Row 0 without a usable carry (after create / reset, or a carried capture whose extraction failed) is a non-candidate {-1, -1, -1, 0} with
+// zero counts. Everything else is the rule above, through the same body: k_stitch_pairs_stream is its CARRY instance, K3 and S2 run over 2n slots.
 constexpr int STITCH_AGREE_DEFAULT = 750, STITCH_BAND_DEFAULT = 2;
 constexpr int STITCH_LMAX = DIM_X > DIM_Y ? DIM_X : DIM_Y;
 static_assert(STITCH_LMAX <= 128, "the line flags fit two ballots");
@@ -36,27 +42,70 @@ __device__ __forceinline__ int stitch_width(int axis, int l)
 }
 
 // S1. line_tab: [2][NCELLS] u8, the grid row and the grid column of every cell. status == nullptr: every capture usable, else the capture
-// path's extraction status, stride ints apart (> 0: usable). tears [n - 1][4], lines [n - 1][L] u16, live / ssym / scol per slot;
+// path's extraction status, stride ints apart (> 0: usable). tears [rows][4], lines [rows][L] u16, live / ssym / scol per slot;
 // *n_slots (zeroed by the host) = the slots up to the last candidate's, for the Reed-Solomon launches: a batch without a candidate costs
 // them nothing but the launch. A non-candidate writes its record and cleared flags only.
-__global__ __launch_bounds__(256) void k_stitch_pairs(const uint8_t* __restrict__ symbols, const uint8_t* __restrict__ colors, int n,
-                                                      const int* __restrict__ status, int stride, const uint8_t* __restrict__ line_tab, int axis,
-                                                      int min_agree, int min_band, int32_t* __restrict__ tears, uint16_t* __restrict__ lines,
-                                                      uint32_t* __restrict__ live, int* __restrict__ n_slots, uint8_t* __restrict__ ssym,
-                                                      uint8_t* __restrict__ scol)
+// The stream calls' carry (cimbar_hip_decode_batch_stitched_stream): the last capture of the stream call before, two slots used in turn. A call
+// reads slot `cur` and writes the other one, so the writer needs no place behind the readers; the host flips `cur` with every call.
+constexpr int SS_CELLS = (NCELLS + 15) & ~15;   // slot stride, bytes
+struct StitchCarry {
+	uint8_t* symbols; uint8_t* colors;   // [2][SS_CELLS]
+	uint32_t* usable;                    // [2] != 0: the slot holds a usable capture (0 after create / reset and for a capture whose extraction failed)
+	int cur;                             // the slot this call reads
+};
+
+// CARRY = false: workgroup k of n - 1 is the pair (capture k, capture k + 1). CARRY = true: workgroup r of n is the row (capture r - 1,
+// capture r), the carried capture for r = 0; the last row's workgroup leaves capture n - 1 as the next call's carry.
+template <bool CARRY>
+__device__ __forceinline__ void stitch_pairs_body(const uint8_t* __restrict__ symbols, const uint8_t* __restrict__ colors, int n,
+                                                  const int* __restrict__ status, int stride, const uint8_t* __restrict__ line_tab, int axis,
+                                                  int min_agree, int min_band, int32_t* __restrict__ tears, uint16_t* __restrict__ lines,
+                                                  uint32_t* __restrict__ live, int* __restrict__ n_slots, uint8_t* __restrict__ ssym,
+                                                  uint8_t* __restrict__ scol, const StitchCarry cy)
 {
 	const int k = blockIdx.x;
-	if (k + 1 >= n) return;
 	constexpr int W = NCELLS / 4;
 	constexpr uint32_t CM = 0x01010101u * (uint32_t)(NCOLORS - 1);
 	const int L = stitch_lines(axis);
+	const uint32_t *s0, *c0, *s1, *c1;
+	[[maybe_unused]] bool pair_usable = true;
+	if constexpr (CARRY) {
+		if (k >= n) return;
+		s1 = reinterpret_cast<const uint32_t*>(symbols + (size_t)k * NCELLS);
+		c1 = reinterpret_cast<const uint32_t*>(colors + (size_t)k * NCELLS);
+		const bool later_usable = !status || status[(size_t)k * stride] > 0;
+		if (k == n - 1) {   // the next call's carry, into the slot nobody reads in this call
+			uint32_t* ns = reinterpret_cast<uint32_t*>(cy.symbols + (size_t)(cy.cur ^ 1) * SS_CELLS);
+			uint32_t* nc = reinterpret_cast<uint32_t*>(cy.colors + (size_t)(cy.cur ^ 1) * SS_CELLS);
+			for (int w = threadIdx.x; w < W; w += 256) { ns[w] = s1[w]; nc[w] = c1[w]; }
+			if (threadIdx.x == 0) cy.usable[cy.cur ^ 1] = later_usable ? 1u : 0u;
+		}
+		if (k == 0) {
+			if (!cy.usable[cy.cur]) {   // nothing carried, or a capture whose extraction failed: a non-candidate without counts
+				if (threadIdx.x < L) lines[threadIdx.x] = 0;
+				if (threadIdx.x == 0) {
+					tears[0] = tears[1] = tears[2] = -1; tears[3] = 0;
+					live[0] = live[1] = 0u;
+				}
+				return;
+			}
+			s0 = reinterpret_cast<const uint32_t*>(cy.symbols + (size_t)cy.cur * SS_CELLS);
+			c0 = reinterpret_cast<const uint32_t*>(cy.colors + (size_t)cy.cur * SS_CELLS);
+			pair_usable = later_usable;
+		} else {
+			s0 = s1 - W; c0 = c1 - W;
+			pair_usable = later_usable && (!status || status[(size_t)(k - 1) * stride] > 0);
+		}
+	} else {
+		if (k + 1 >= n) return;
+		s0 = reinterpret_cast<const uint32_t*>(symbols + (size_t)k * NCELLS);
+		c0 = reinterpret_cast<const uint32_t*>(colors + (size_t)k * NCELLS);
+		s1 = s0 + W; c1 = c0 + W;
+	}
 	__shared__ uint32_t s_cnt[128];
 	__shared__ int s_split;
 	if (threadIdx.x < 128) s_cnt[threadIdx.x] = 0;
 	__syncthreads();
-	const uint32_t* s0 = reinterpret_cast<const uint32_t*>(symbols + (size_t)k * NCELLS);
-	const uint32_t* c0 = reinterpret_cast<const uint32_t*>(colors + (size_t)k * NCELLS);
-	const uint32_t *s1 = s0 + W, *c1 = c0 + W;
 	const uint32_t* lt = reinterpret_cast<const uint32_t*>(line_tab + (size_t)axis * NCELLS);
 	for (int w = threadIdx.x; w < W; w += 256) {
 		const uint32_t x = ((s0[w] ^ s1[w]) & 0x0F0F0F0Fu) | ((c0[w] ^ c1[w]) & CM);
@@ -75,7 +124,9 @@ __global__ __launch_bounds__(256) void k_stitch_pairs(const uint8_t* __restrict_
 	__syncthreads();
 	if (threadIdx.x < 64) {
 		const int lane = threadIdx.x;
-		const bool usable = !status || (status[(size_t)k * stride] > 0 && status[(size_t)(k + 1) * stride] > 0);
+		bool usable;
+		if constexpr (CARRY) usable = pair_usable;
+		else usable = !status || (status[(size_t)k * stride] > 0 && status[(size_t)(k + 1) * stride] > 0);
 		bool fl[2];
 #pragma unroll
 		for (int h = 0; h < 2; ++h) {
@@ -118,6 +169,24 @@ __global__ __launch_bounds__(256) void k_stitch_pairs(const uint8_t* __restrict_
 		oc0[w] = (b1 & m) | (b0 & ~m);
 		oc1[w] = (b0 & m) | (b1 & ~m);
 	}
+}
+
+__global__ __launch_bounds__(256) void k_stitch_pairs(const uint8_t* __restrict__ symbols, const uint8_t* __restrict__ colors, int n,
+                                                      const int* __restrict__ status, int stride, const uint8_t* __restrict__ line_tab, int axis,
+                                                      int min_agree, int min_band, int32_t* __restrict__ tears, uint16_t* __restrict__ lines,
+                                                      uint32_t* __restrict__ live, int* __restrict__ n_slots, uint8_t* __restrict__ ssym,
+                                                      uint8_t* __restrict__ scol)
+{
+	stitch_pairs_body<false>(symbols, colors, n, status, stride, line_tab, axis, min_agree, min_band, tears, lines, live, n_slots, ssym, scol, StitchCarry{});
+}
+
+__global__ __launch_bounds__(256) void k_stitch_pairs_stream(const uint8_t* __restrict__ symbols, const uint8_t* __restrict__ colors, int n,
+                                                             const int* __restrict__ status, int stride, const uint8_t* __restrict__ line_tab, int axis,
+                                                             int min_agree, int min_band, int32_t* __restrict__ tears, uint16_t* __restrict__ lines,
+                                                             uint32_t* __restrict__ live, int* __restrict__ n_slots, uint8_t* __restrict__ ssym,
+                                                             uint8_t* __restrict__ scol, const StitchCarry cy)
+{
+	stitch_pairs_body<true>(symbols, colors, n, status, stride, line_tab, axis, min_agree, min_band, tears, lines, live, n_slots, ssym, scol, cy);
 }
 
 // S2: slot blockIdx.x of 2 (n - 1). Live: the aligned_stream bookkeeping over the slot's block flags, the symbol blocks then the colour

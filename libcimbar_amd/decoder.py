@@ -25,6 +25,7 @@ TAP_SCAN_PATH = 14
 TAP_GROUP_COLOUR_MARGIN, TAP_GROUP_COLOUR_WEIGHTS = 15, 16   # the colour vote of the last combined batch (set_group_colour_vote / set_stream_colour_vote)
 TAP_STREAM_CARRY_WEIGHTS = 17   # the carried weights of the open group's members after a stream call with set_stream_colour_vote on
 TAP_STITCH_CELLS, TAP_STITCH_LINES = 18, 19   # the stitching of the last stitched batch (decode_batch_stitched): n = its captures
+TAP_STITCH_CARRY = 20   # the capture the stitched-stream calls carry (decode_batch_stitched_stream): tap_stitch_carry
 # CIMBAR_HIP_COLOUR_MARGIN_SUGGESTED (include/cimbar_hip.h): the colour erasure threshold chosen on rendered frames (DESIGN_WIDENING.md)
 COLOUR_MARGIN_SUGGESTED = 32512
 
@@ -53,6 +54,7 @@ EXPORTS = (
     "cimbar_hip_auto_get_ccm", "cimbar_hip_auto_set_ccm", "cimbar_hip_auto_scan_extract_decode_batch_fmt",
     "cimbar_hip_deliver_chunks", "cimbar_hip_delivery_reset", "cimbar_hip_delivery_stats",
     "cimbar_hip_decode_batch_stitched", "cimbar_hip_scan_extract_decode_batch_stitched_fmt",
+    "cimbar_hip_decode_batch_stitched_stream", "cimbar_hip_scan_extract_decode_batch_stitched_stream_fmt", "cimbar_hip_stitch_stream_reset",
 )
 # cimbar_hip_deliver_chunks' flags
 DELIVER_DEDUP, DELIVER_REMEMBER, DELIVER_DROP_EMPTY = 1, 2, 4
@@ -174,6 +176,12 @@ def load_library(path=None):
     lib.cimbar_hip_scan_extract_decode_batch_stitched_fmt.argtypes = [vp, vp, u32, u32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp,
                                                                       i32, vp]
     lib.cimbar_hip_scan_extract_decode_batch_stitched_fmt.restype = i64
+    lib.cimbar_hip_decode_batch_stitched_stream.argtypes = lib.cimbar_hip_decode_batch_stitched.argtypes
+    lib.cimbar_hip_decode_batch_stitched_stream.restype = i64
+    lib.cimbar_hip_scan_extract_decode_batch_stitched_stream_fmt.argtypes = lib.cimbar_hip_scan_extract_decode_batch_stitched_fmt.argtypes
+    lib.cimbar_hip_scan_extract_decode_batch_stitched_stream_fmt.restype = i64
+    lib.cimbar_hip_stitch_stream_reset.argtypes = [vp]
+    lib.cimbar_hip_stitch_stream_reset.restype = i32
     lib.cimbar_hip_combine_stream_reset.argtypes = [vp]
     lib.cimbar_hip_combine_stream_reset.restype = i32
     lib.cimbar_hip_auto_create.argtypes = [i32, vp, i32, ctypes.POINTER(vp)]
@@ -613,6 +621,60 @@ class HipDecoder:
             MEM_HOST, None), "cimbar_hip_scan_extract_decode_batch_stitched_fmt")
         return int(rc), chunks, masks, status, schunks, smasks, tears
 
+    def _stitch_stream_outputs(self, n):
+        geo = self.geo
+        return (np.zeros((n, geo.CHUNKS_PER_FRAME, geo.CHUNK), dtype=np.uint8), np.zeros(n, dtype=np.uint32),
+                np.zeros((2 * n, geo.CHUNKS_PER_FRAME, geo.CHUNK), dtype=np.uint8), np.zeros(2 * n, dtype=np.uint32), np.zeros((n, 4), dtype=np.int32))
+
+    def decode_batch_stitched_stream(self, frames, axis=0, min_agree_permille=0, min_band=0, should_preprocess=False, color_correction=2):
+        """Torn-capture stitching across calls (cimbar_hip_decode_batch_stitched_stream): as decode_batch_stitched, but a call of n frames
+        reports n pair rows -- row 0 is (the last frame of the stream call before, frame 0), row r is (frame r - 1, frame r). Returns
+        (candidate rows, chunks, masks, schunks, smasks, tears) with n / n / 2n / 2n / n rows; row r, direction d is slot 2r + d. Row 0 of
+        the first call after create or stitch_stream_reset is {-1, -1, -1, 0} with zero slots."""
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        n = frames.shape[0]
+        if frames.shape[1:] != self.geo.FRAME_SHAPE:
+            raise CimbarHipError(f"decode_batch_stitched_stream: frames must be (n,{self.geo.IMG_H},{self.geo.IMG_W},3) uint8")
+        chunks, masks, schunks, smasks, tears = self._stitch_stream_outputs(n)
+        rc = self._check(self._lib.cimbar_hip_decode_batch_stitched_stream(
+            self._ctx, frames.ctypes.data, n, MEM_HOST, int(bool(should_preprocess)), int(color_correction), int(axis), int(min_agree_permille),
+            int(min_band), chunks.ctypes.data, masks.ctypes.data, schunks.ctypes.data, smasks.ctypes.data, tears.ctypes.data, MEM_HOST, None),
+            "cimbar_hip_decode_batch_stitched_stream")
+        return int(rc), chunks, masks, schunks, smasks, tears
+
+    def decode_batch_stitched_stream_device(self, frames_ptr, n, chunks_ptr, masks_ptr, schunks_ptr, smasks_ptr, tears_ptr=None, axis=0,
+                                            min_agree_permille=0, min_band=0, should_preprocess=False, color_correction=2, stream=None):
+        """Device pointers in and out (2n stitched slots, n tear records; tears_ptr may be 0); enqueues on `stream` (None / 0 = the null
+        stream), behind the stitched-stream call before, and returns at once."""
+        vp = ctypes.c_void_p
+        return int(self._check(self._lib.cimbar_hip_decode_batch_stitched_stream(
+            self._ctx, vp(frames_ptr), int(n), MEM_DEVICE, int(bool(should_preprocess)), int(color_correction), int(axis), int(min_agree_permille),
+            int(min_band), vp(chunks_ptr), vp(masks_ptr), vp(schunks_ptr or None), vp(smasks_ptr or None), vp(tears_ptr or None), MEM_DEVICE,
+            vp(stream) if stream else None), "cimbar_hip_decode_batch_stitched_stream(device)"))
+
+    def scan_extract_decode_batch_stitched_stream(self, captures, axis=0, min_agree_permille=0, min_band=0, preprocess=-1, color_correction=2,
+                                                  size=None, fmt=3):
+        """The capture path of decode_batch_stitched_stream (cimbar_hip_scan_extract_decode_batch_stitched_stream_fmt). Returns
+        (candidate rows, chunks, masks, status, schunks, smasks, tears); a capture whose extraction failed is in no pair, carried or not."""
+        captures, n, w, h, fmt = self._captures(captures, size, fmt)
+        chunks, masks, schunks, smasks, tears = self._stitch_stream_outputs(n)
+        status = np.zeros(n, dtype=np.int32)
+        rc = self._check(self._lib.cimbar_hip_scan_extract_decode_batch_stitched_stream_fmt(
+            self._ctx, captures.ctypes.data, w, h, fmt, n, MEM_HOST, int(preprocess), int(color_correction), int(axis), int(min_agree_permille),
+            int(min_band), chunks.ctypes.data, masks.ctypes.data, status.ctypes.data, schunks.ctypes.data, smasks.ctypes.data, tears.ctypes.data,
+            MEM_HOST, None), "cimbar_hip_scan_extract_decode_batch_stitched_stream_fmt")
+        return int(rc), chunks, masks, status, schunks, smasks, tears
+
+    def stitch_stream_reset(self):
+        """forget the capture the stitched-stream calls carry: the next one's row 0 has no partner"""
+        self._check(self._lib.cimbar_hip_stitch_stream_reset(self._ctx), "cimbar_hip_stitch_stream_reset")
+
+    def tap_stitch_carry(self):
+        """TAP_STITCH_CARRY: (symbols (NCELLS,), colours (NCELLS,)) uint8 of the carried capture; raises while nothing is carried"""
+        out = np.zeros((2, self.geo.NCELLS), dtype=np.uint8)
+        self._check(self._lib.cimbar_hip_tap(self._ctx, TAP_STITCH_CARRY, out.ctypes.data, out.nbytes), "cimbar_hip_tap")
+        return out[0], out[1]
+
     def combine_stream_reset(self):
         """drop the open group and the stream's fixed min_agree_permille / max_group"""
         self._check(self._lib.cimbar_hip_combine_stream_reset(self._ctx), "cimbar_hip_combine_stream_reset")
@@ -975,9 +1037,16 @@ class HipDecoder:
         self._check(self._lib.cimbar_hip_tap(self._ctx, what, out.ctypes.data, out.nbytes), "cimbar_hip_tap")
         return out
 
-    def tap_stitch_lines(self, n, axis=0):
-        """TAP_STITCH_LINES of the last stitched batch of n captures on `axis`: (n - 1, L) uint16, the agreeing cells per line"""
-        out = np.zeros((max(n - 1, 0), self.geo.DIM_Y if axis == 0 else self.geo.DIM_X), dtype=np.uint16)
+    def tap_stitch_cells(self, n, stream=False):
+        """TAP_STITCH_CELLS of the last stitched batch of n captures: (2 (n - 1), NCELLS) uint8, colour << 4 | symbol; stream=True: (2n, NCELLS)"""
+        out = np.zeros((2 * (n if stream else max(n - 1, 0)), self.geo.NCELLS), dtype=np.uint8)
+        self._check(self._lib.cimbar_hip_tap(self._ctx, TAP_STITCH_CELLS, out.ctypes.data, out.nbytes), "cimbar_hip_tap")
+        return out
+
+    def tap_stitch_lines(self, n, axis=0, stream=False):
+        """TAP_STITCH_LINES of the last stitched batch of n captures on `axis`: (n - 1, L) uint16, the agreeing cells per line; stream=True:
+        that batch was a stitched-stream call, (n, L)"""
+        out = np.zeros((n if stream else max(n - 1, 0), self.geo.DIM_Y if axis == 0 else self.geo.DIM_X), dtype=np.uint16)
         self._check(self._lib.cimbar_hip_tap(self._ctx, TAP_STITCH_LINES, out.ctypes.data, out.nbytes), "cimbar_hip_tap")
         return out
 
