@@ -1,5 +1,6 @@
 """GPU: mode auto-detection (cimbar_hip_auto_scan_extract_decode_batch_fmt / AutoDecoder) bit-exact against the sequential model
-(tests/automode_model.py): accepted mode, chunks, mask, status per capture and the carried matrix after the call."""
+(tests/automode_model.py): accepted mode, chunks, mask, status per capture and the carried matrix after the call.
+The last tests walk k_auto_resolve past its first round of 1024 captures (resolve_case)."""
 import os
 import subprocess
 import sys
@@ -168,6 +169,132 @@ def test_convergence_from_a_wrong_guess():
             "from libcimbar_amd import AutoDecoder; "
             "cams = [AM.capture(m, 500 + k) for k, m in enumerate([68, 67, 66, 4, 8, 0, 68])]; "
             "[T.check(AutoDecoder(0, T.WEB + [8]), cams, 3, T.WEB + [8], cc=cc) for cc in (1, 2)]; print('ok')") % ROOT
+    env = dict(os.environ, CIMBAR_HIP_AUTO_GUESS_FIRST="1")
+    res = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert res.returncode == 0 and "ok" in res.stdout, res.stdout[-2000:] + res.stderr[-4000:]
+
+
+# ---- k_auto_resolve past its first round: one workgroup resolves 1024 captures a round and hands the newest deriving attempt (s_run) on
+ROUND = 1024
+RES_N = ROUND + 40
+# three casts; a mode-B capture under one derives a matrix from its fountain header, a legacy mode-4 capture derives none and its whole
+# result is the colour pass under the matrix in force: 4A decodes only with A's matrix, 4C with any but B's (checked on the model below)
+GAINS = dict(A=(0.6, 1.0, 0.45), B=(1.0, 0.55, 0.7), C=(0.5, 0.7, 1.0))
+RES_NAMES = ("68A", "68B", "66C", "4A", "4C", "blank")
+DERIVING, QUIET = (0, 1, 2), (3, 4, 5)                  # indices into RES_NAMES: mode-B captures; legacy and blank ones
+_res = {}
+
+
+def resolve_inputs():
+    """the distinct captures in format 12 and the two index sequences over them"""
+    if not _res:
+        def cap(mode, seed, gain):
+            return AM.capture(mode, 0, frame=CC.cast(AM.mode_frame(mode, seed), np.eye(3), np.array(GAINS[gain])))
+        cams = [cap(68, 700, "A"), cap(68, 702, "B"), cap(66, 703, "C"), cap(4, 701, "A"), cap(4, 705, "C"), AM.capture(0, 0)]
+        rng = np.random.default_rng(11)
+        quiet = lambda k: rng.choice(QUIET, k)                                  # noqa: E731
+        a = rng.integers(0, len(cams), RES_N)
+        # a: B's matrix from 1010, nothing derived up to 1022; 1023 derives A's under its own cast and 1024 (4A) lives on it; 1040 derives a
+        # third matrix, C's, in the second round, and 1041 (4A) meets that one, not the first round's
+        a[1005:] = quiet(RES_N - 1005)
+        a[[1010, 1023, 1024, 1040, 1041, 1042]] = [1, 0, 3, 2, 3, 4]
+        # b: B's matrix from 990, A's from 1000, and nothing derived from there to the end: the second round lives on the first round's last
+        b = rng.integers(0, len(cams), RES_N)
+        b[985:] = quiet(RES_N - 985)
+        b[[990, 1000, 1024, 1030]] = [1, 0, 3, 3]
+        _res.update(cams=cams, imgs=AM.to_format(cams, 12), seq=dict(a=a, b=b), memo={})
+    return _res
+
+
+def resolve_one(u, ccm_in, cand, cc):
+    """capture u of resolve_inputs() with the matrix ccm_in (the bytes of a CoCcm) carried in -> (result, the bytes of the matrix after);
+    an attempt's result depends only on (capture, matrix carried in), so repeats are looked up"""
+    import ctypes
+    r = resolve_inputs()
+    key = (int(u), ccm_in, tuple(cand), cc)
+    if key not in r["memo"]:
+        ccm = pyref.CoCcm()
+        ctypes.memmove(ctypes.addressof(ccm), ccm_in, ctypes.sizeof(ccm))
+        h, w = r["cams"][0].shape[:2]
+        res = AM.auto_decode(np.ascontiguousarray(r["imgs"][u]), w, h, 12, list(cand), ccm, cc=cc)
+        r["memo"][key] = (res, bytes(ccm))
+    return r["memo"][key]
+
+
+def resolve_model(idx, cand, cc):
+    """-> per capture (mode, status, chunks, mask), and the matrix in force before capture f (f = n: the one carried out)"""
+    trace, want = [bytes(pyref.CoCcm())], []
+    for u in idx:
+        res, after = resolve_one(u, trace[-1], cand, cc)
+        want.append(res)
+        trace.append(after)
+    return want, trace
+
+
+def resolve_shapes(name, idx, cand, want, trace):
+    """the hand-overs the sequence is there for, on the model's trace of the matrix in force (color_correction 2)"""
+    differs = lambda x, y: x[0] != y[0] or x[3] != y[3] or (x[0] and not np.array_equal(x[2], y[2]))    # noqa: E731
+    derived = [f for f in range(len(idx)) if trace[f + 1] != trace[f]]
+    assert all(idx[f] in DERIVING for f in derived)
+    if name == "a":
+        # boundary hand-over: 1023 derives under a cast of its own, 1024 derives nothing and its result is that matrix's doing
+        assert 1023 in derived and 1024 not in derived
+        assert want[1024][0] == 4 and want[1024][3] != 0 and differs(want[1024], resolve_one(idx[1024], trace[0], cand, 2)[0])
+        assert differs(want[1024], resolve_one(idx[1024], trace[1023], cand, 2)[0])
+        # second-round order: 1040 derives a third matrix, and 1041 decodes under it, not under the first round's
+        assert derived[-1] == 1040 and len({trace[1023], trace[1024], trace[1041]}) == 3 and trace[1042] == trace[1041]
+        assert differs(want[1041], resolve_one(idx[1041], trace[1024], cand, 2)[0])
+        assert derived[-1] >= ROUND                                        # the matrix carried out comes from the second round
+    else:
+        # long reach: the last derivation is capture 1000, and captures of the second round decode by it
+        assert derived[-1] == 1000 and trace[1001] != trace[1000] and all(u in QUIET for u in idx[1001:])
+        reach = [f for f in range(ROUND, len(idx)) if want[f][0] and differs(want[f], resolve_one(idx[f], trace[1000], cand, 2)[0])]
+        assert 1024 in reach and 1030 in reach
+        assert derived[-1] < ROUND                                         # ... and so does the matrix carried out
+
+
+def resolve_case(name, cc=2, order=None):
+    """one sequence through the device (the captures gathered there from the six distinct ones) against the model"""
+    import torch
+    from libcimbar_amd import AutoDecoder
+    r = resolve_inputs()
+    idx = r["seq"][name]
+    cand = WEB if order is None else order
+    want, trace = resolve_model(idx, cand, cc)
+    if cc == 2:
+        resolve_shapes(name, idx, cand, want, trace)
+    n = len(idx)
+    h, w = r["cams"][0].shape[:2]
+    dec = AutoDecoder(0, WEB)
+    d_in = torch.from_numpy(r["imgs"]).cuda()[torch.from_numpy(idx).cuda()].reshape(n, -1)
+    slots = torch.zeros((n, dec.slot), dtype=torch.uint8, device="cuda")
+    masks, modes, status = (torch.zeros(n, dtype=torch.int32, device="cuda") for _ in range(3))
+    torch.cuda.synchronize()
+    total = dec.scan_extract_decode_device(d_in.data_ptr(), w, h, n, slots.data_ptr(), masks.data_ptr(), modes.data_ptr(), status.data_ptr(),
+                                           preprocess=1, color_correction=cc, fmt=12, order=order)
+    torch.cuda.synchronize()
+    modes, masks, status, slots = modes.cpu().numpy(), masks.cpu().numpy().view(np.uint32), status.cpu().numpy(), slots.cpu().numpy()
+    for f in range(n):
+        m, s, ch, mk = want[f]
+        assert modes[f] == m and status[f] == s and masks[f] == mk, (f, modes[f], m, status[f], s, hex(int(masks[f])), hex(mk))
+        fb = ch.size if m else 0
+        if m:
+            assert (slots[f, :fb] == ch.reshape(-1)).all(), f
+        assert not slots[f, fb:].any(), f
+    assert total == sum(bin(int(x)).count("1") * (pyref.GEOMETRY[int(m)][3] if m else 0) for x, m in zip(masks, modes))
+    carried = pyref.CoCcm.from_buffer_copy(trace[-1])
+    active, mat = dec.get_ccm()
+    assert active == bool(carried.active) and (not active or (mat.reshape(-1) == np.array(list(carried.m), np.float32)).all())
+
+
+@pytest.mark.parametrize("name,cc,order", [("a", 2, None), ("b", 2, None), ("b", 1, None), ("a", 2, [4, 68, 66, 67])],
+                         ids=["a-cc2", "b-cc2", "b-cc1", "a-cc2-reordered"])
+def test_resolve_across_1024_captures(name, cc, order):
+    resolve_case(name, cc, order)
+
+
+def test_resolve_across_1024_captures_from_a_wrong_guess():
+    code = ("import sys; sys.path.insert(0, %r); from tests import test_gpu_automode as T; T.resolve_case('a'); print('ok')") % ROOT
     env = dict(os.environ, CIMBAR_HIP_AUTO_GUESS_FIRST="1")
     res = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert res.returncode == 0 and "ok" in res.stdout, res.stdout[-2000:] + res.stderr[-4000:]

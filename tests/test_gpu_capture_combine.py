@@ -22,6 +22,7 @@ from libcimbar_amd import framegen, geometry
 from tests import capture_formats as CF
 from tests import combine_model as CM
 from tests import frames as F
+from tests import group_walk_cases as GW
 
 pytestmark = pytest.mark.gpu
 
@@ -41,43 +42,9 @@ def _frames(mode, n, seed):
     return frames, payload.numpy().reshape(n, -1)
 
 
-def _disc(frame, cx, cy, r, kind, seed):
-    h, w, _ = frame.shape
-    yy, xx = np.mgrid[0:h, 0:w]
-    d = (yy - cy * h) ** 2 + (xx - cx * w) ** 2 <= (r * min(h, w)) ** 2
-    if kind == "white":
-        frame[d] = 255
-    elif kind == "black":
-        frame[d] = 0
-    else:
-        frame[d] = np.random.default_rng(seed).integers(0, 256, (int(d.sum()), 3), dtype=np.uint8)
-    return frame
-
-
-def _band(frame, x0, x1, kind, seed):
-    """a fill over columns [x0, x1) and rows [0.1, 0.9) of the frame (fractions; the corner anchors stay clean)"""
-    h, w, _ = frame.shape
-    ys, xs = slice(int(0.1 * h), int(0.9 * h)), slice(int(x0 * w), int(x1 * w))
-    if kind == "white":
-        frame[ys, xs] = 255
-    elif kind == "black":
-        frame[ys, xs] = 0
-    else:
-        frame[ys, xs] = np.random.default_rng(seed).integers(0, 256, frame[ys, xs].shape, dtype=np.uint8)
-    return frame
-
-
-# The interleave spreads each Reed-Solomon block over one half of the frame (top or bottom), so damage must reach both halves to cost a
-# capture every chunk. Two captures: discs on the middle row, left and right; three: the thirds of the frame's width.
-PLACES = [(0.30, 0.50), (0.70, 0.50)]
-R = 0.19
-KINDS = ("white", "black", "noise")
-
-
-def _damaged_group(frame, m, seed, kinds=KINDS):
-    if m == 2:
-        return [_disc(frame.copy(), cx, cy, R, kinds[(seed + c) % len(kinds)], seed * 10 + c) for c, (cx, cy) in enumerate(PLACES)]
-    return [_band(frame.copy(), c / m, (c + 1) / m, kinds[(seed + c) % len(kinds)], seed * 10 + c) for c in range(m)]
+# (the damage helpers live in tests/group_walk_cases.py, which builds its batches from them too)
+_disc, _band, _damaged_group = GW.disc, GW.band, GW.damaged_group
+PLACES, R, KINDS = GW.PLACES, GW.R, GW.KINDS
 
 
 def _sym_mask(geo):

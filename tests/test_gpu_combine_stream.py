@@ -25,6 +25,7 @@ from tests import capture_formats as CF
 from tests import combine_model as CM
 from tests import combine_stream_model as SM
 from tests import frames as F
+from tests import group_walk_cases as GW
 
 pytestmark = pytest.mark.gpu
 
@@ -228,7 +229,7 @@ def test_the_carry_is_a_copy():
 
 
 # ---- 3. model parity with a carried member
-AGREE_3 = 250          # per mille: below what two captures with a third of the frame damaged each share, 16 times what two different frames do
+AGREE_3 = GW.AGREE_3   # per mille: below what two captures with a third of the frame damaged each share, 16 times what two different frames do
 
 
 @pytest.mark.parametrize("cut", [(1, 2), (2, 1)], ids=["1x2", "2x1"])

@@ -109,7 +109,7 @@ def test_boundary_sizes(mode):
             p, s = both_paths(dec, dm.DeliveryModel, random_slots(mode, n, 2), np.full(n, full, np.uint32), flags)
             assert len(s) == n * per
     rng = np.random.default_rng(3)
-    for n in (65, 257):           # across a wavefront and across the workgroup's first pass in the scan
+    for n in (65, 257):           # across a wavefront and across four of the scan's sixteen (its rounds of 1024 frames: test_scan_rounds)
         masks = rng.integers(0, 1 << per, n, dtype=np.uint32)
         masks[rng.integers(0, n, n // 8)] = 0
         both_paths(dec, dm.DeliveryModel, random_slots(mode, n, 4), masks, ALL)
@@ -263,6 +263,75 @@ def remember_sequence(dec, run, mode=68):
 @pytest.mark.parametrize("mode", (68, 66))
 def test_remember(mode, path):
     remember_sequence(dec_for(mode), run_host if path == "host" else run_device, mode)
+
+
+
+# ---- k_deliver_scan past its first round: one workgroup of 16 wavefronts scans 1024 frames a round and hands `carry` to the next
+ROUND = 1024
+SCAN_SIZES = (1023, 1024, 1025, 2047, 2049, 3000)
+
+
+def scan_masks(mode, n, seed):
+    """test_boundary_sizes' random masks, no chunk on frames 1020 .. 1030 except every chunk of 1023 and 1024 (the last lane of a round, the
+    first of the next). Every wavefront 9 .. 15 of the first round keeps a chunk -- the slots of wsum[] nothing smaller reaches -- and every
+    later round starts with a carry."""
+    per, _ = shape_of(mode)
+    rng = np.random.default_rng(seed)
+    masks = rng.integers(0, 1 << per, n, dtype=np.uint32)
+    masks[rng.integers(0, n, n // 8)] = 0
+    masks[1020:1031] = 0
+    masks[1023:1025] = (1 << per) - 1
+    assert n >= ROUND - 1 and all(masks[64 * w:64 * w + 64].any() for w in range(9, 16))
+    assert masks[:ROUND].any()                       # what the second round is handed is not zero
+    return masks
+
+
+@pytest.mark.parametrize("n", SCAN_SIZES)
+@pytest.mark.parametrize("mode", (66, 68))
+def test_scan_rounds(mode, n):
+    dec = dec_for(mode)
+    per, cs = shape_of(mode)
+    chunks, masks = random_slots(mode, n, 20), scan_masks(mode, n, 21 + n)
+    for flags in (0, ALL):
+        _, s = both_paths(dec, dm.DeliveryModel, chunks, masks, flags)
+        assert len(s) == sum(bin(int(m)).count("1") for m in masks)           # (distinct headers, none empty: the masks alone decide)
+
+
+def test_scan_rounds_benchmark_batch():
+    """8192 frames of mode 68, 61 MB of slots: the batch benchmark config 4 delivers, eight rounds of the scan"""
+    dec = dec_for(68)
+    chunks, masks = random_slots(68, 8192, 22), scan_masks(68, 8192, 23)
+    for flags in (0, ALL):
+        both_paths(dec, dm.DeliveryModel, chunks, masks, flags)
+
+
+@pytest.mark.parametrize("path", ["host", "device"])
+@pytest.mark.parametrize("mode", (66, 68))
+def test_remember_across_scan_rounds(mode, path):
+    """two consecutive REMEMBER calls of 2049 and 3000 frames; a third of the second call's headers are the first call's"""
+    dec, run = dec_for(mode), run_host if path == "host" else run_device
+    per, cs = shape_of(mode)
+    R = dm.REMEMBER | dm.DROP_EMPTY
+    a, ma = random_slots(mode, 2049, 24), scan_masks(mode, 2049, 25)
+    b, mb = random_slots(mode, 3000, 26), scan_masks(mode, 3000, 27)
+    rng = np.random.default_rng(28)
+    fa, fb = a.reshape(-1, cs), b.reshape(-1, cs)
+    pick = rng.permutation(len(fb))[:len(fb) // 3]
+    fb[pick, :6] = fa[rng.integers(0, len(fa), len(pick)), :6]
+    m = dm.DeliveryModel()
+    dec.delivery_reset()
+    m.reset()
+    try:
+        counts = []
+        for chunks, masks in ((a, ma), (b, mb)):
+            want = m.deliver(chunks, masks, R)
+            check(run(dec, chunks, masks, R), want, cs)
+            assert dec.delivery_stats() == m.stats()
+            counts.append(len(want[1]))
+        assert counts[0] == sum(bin(int(x)).count("1") for x in ma) and 0 < counts[1] < sum(bin(int(x)).count("1") for x in mb)
+        assert m.stats() == (counts[0] + counts[1], 1 << 20, False)
+    finally:
+        dec.delivery_reset()
 
 
 def test_reset_refuses_a_capacity_out_of_range_and_unknown_flags():
