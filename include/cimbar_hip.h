@@ -720,7 +720,11 @@ enum {
 	CIMBAR_HIP_TAP_STITCH_LINES = 19, /* (n - 1) * L u16        : cnt(l), the agreeing cells of pair k on line l of the call's axis */
 	/* what the stitched-stream calls carry: the last capture of the last such call (CIMBAR_HIP_EINVAL while nothing is carried: after create and
 	 * after cimbar_hip_stitch_stream_reset); does not depend on the last batch */
-	CIMBAR_HIP_TAP_STITCH_CARRY = 20  /* 2 * cells bytes        : the carried symbols, then the carried colours, by linear cell index */
+	CIMBAR_HIP_TAP_STITCH_CARRY = 20, /* 2 * cells bytes        : the carried symbols, then the carried colours, by linear cell index */
+	/* the threshold kernel's second product, as it left it (the colour pass reads it where a cell has no drift) */
+	CIMBAR_HIP_TAP_CELL_MEANS = 21    /* n * grid slots u32     : r | g << 8 | b << 16, the inner-6x6 mean (Cell.h: channel sum / 36, remainder dropped) of
+	                                     every cell at its undrifted position, by grid slot row * columns + column (112 x 112 | 112 x 78 | 80 x 69
+	                                     slots, the four corner cut-outs included) */
 };
 int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_bytes);
 

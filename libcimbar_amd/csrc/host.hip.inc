@@ -2181,6 +2181,7 @@ int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_byte
 		case CIMBAR_HIP_TAP_DRIFT: src = cur.d_drift; bytes = n * NCELLS * 2; break;
 		case CIMBAR_HIP_TAP_RS_OK: src = cur.d_rs_ok; bytes = n * ALL_BLOCKS; break;
 		case CIMBAR_HIP_TAP_CCM: src = cur.d_ccm_used; bytes = n * 10 * sizeof(float); break;
+		case CIMBAR_HIP_TAP_CELL_MEANS: src = cur.d_cellmean; bytes = n * GRID_CELLS * sizeof(uint32_t); break;
 		case CIMBAR_HIP_TAP_FLOOD: {
 			bytes = n;
 			if (out_bytes < bytes) { ctx->err = "tap: buffer too small"; return CIMBAR_HIP_EINVAL; }

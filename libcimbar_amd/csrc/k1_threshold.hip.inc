@@ -245,6 +245,11 @@ __device__ __forceinline__ uint32_t box_row(uint32_t (&ring)[2 * RAD + 2][K1_NP]
 	else return ((M >> (16 - 2 * NP)) & (((1u << NP) - 1u) << NP)) | (M >> (32 - NP));   // bit 2NP-1-p = pixel p
 }
 
+// Between the prologue's row loads: keeps the compiler from interleaving the loads of different rows (it emits no instruction). The waits of the first
+// pass count loads in issue order, and where the prologue's order differs from the loop's the compiler has to wait for the stricter of the two in
+// every pass.
+__device__ __forceinline__ void row_order_fence() { asm volatile("" ::: "memory"); }
+
 template <int RAD, bool PRE, int ROWS = K1_CELLROWS>
 #ifndef K1_WAVES
 #define K1_WAVES 3
@@ -323,166 +328,176 @@ __global__ __launch_bounds__(256, PRE ? K1_PRE_WAVES : K1_WAVES) void k_threshol
 		load_row(src, yb < 0 ? 1 : (yb >= IMG_H ? IMG_H - 2 : yb), ro, d0);
 		load_row(src, y0, ro, d1);
 #pragma unroll
-		for (int k = 0; k < DEPTH; ++k) load_row(src, ahead(k), ro, buf[k]);
+		for (int k = 0; k < DEPTH; ++k) { load_row(src, ahead(k), ro, buf[k]); row_order_fence(); }
 		gray_T<K1_PPL>(d0, T); pairs_T<NP>(T, GR[3]); patch_reflect(GR[3], es);
 		gray_T<K1_PPL>(d1, T); pairs_T<NP>(T, GR[0]); patch_reflect(GR[0], es);
 #pragma unroll
 		for (int i = 0; i < NP; ++i) { GR[1][i] = 0; GR[2][i] = 0; }
 	} else {
 #pragma unroll
-		for (int k = 0; k < DEPTH; ++k) load_row(src, clampy(y_first + dir * k), ro, buf[k]);
+		for (int k = 0; k < DEPTH; ++k) { load_row(src, clampy(y_first + dir * k), ro, buf[k]); row_order_fence(); }
 	}
 
-	// Straight-line body: every unrolled step runs unconditionally (rows past the strip are clamped re-reads whose results
-	// are never stored), so the refill of a consumed buffer is an unconditional load into the same registers -- no phi,
-	// no copy, and the compiler's vmcnt waits only ever cover the oldest row in flight.
-	for (int t0 = 0; t0 < total; t0 += RING) {
+	// One row step. `s` (the step's place in a pass over the ring) is a constant wherever this is called, so the ring slot, the prefetch buffer and the
+	// gray-ring slots are fixed registers; the refill of the consumed buffer is an unconditional load.
+	auto step = [&](const int s, const int t) __attribute__((always_inline)) {
+		const int y = y_first + dir * t;
+		uint32_t (&d)[NDW] = buf[s % DEPTH];
+		uint32_t G[NP];
+		int yl = y;   // the image row held in d
+		if (PRE) {
+			yl = ahead(t);
+			uint32_t T[K1_PPL];
+			gray_T<K1_PPL>(d, T);
+			pairs_T<NP>(T, GR[(s + 1) & 3]);
+			patch_reflect(GR[(s + 1) & 3], es);
+			sharp_pairs(GR[(s + 3) & 3], GR[s & 3], GR[(s + 1) & 3], G);
+			if (bounded(y + dir) == bounded(y)) {
+				// the output row repeats (replicated border of the threshold source, or past the strip): re-seat the two
+				// rows behind so the next step sees the same neighbourhood. Only the image's first / last strip gets here.
 #pragma unroll
-		for (int s = 0; s < RING; ++s) {
-			const int t = t0 + s;
-#ifndef K1_NO_EARLY_EXIT
-			// the strip's rows are done: nothing after the loop reads what the remaining steps of this pass over the ring would compute (they used to run
-			// on clamped re-reads -- 2 of 24 steps of a short strip, 5 of 72 of a tall one -- for the sake of a branch-free body; a scalar compare and a
-			// branch out of the loop cost no vector issue slot, which is what the pipelined loop is short of, profiles/r05f)
-			if (t >= total) break;
-#endif
-			const int y = y_first + dir * t;
-			uint32_t (&d)[NDW] = buf[s % DEPTH];
-			uint32_t G[NP];
-			int yl = y;   // the image row held in d
-			if (PRE) {
-				yl = ahead(t);
-				uint32_t T[K1_PPL];
-				gray_T<K1_PPL>(d, T);
-				pairs_T<NP>(T, GR[(s + 1) & 3]);
-				patch_reflect(GR[(s + 1) & 3], es);
-				sharp_pairs(GR[(s + 3) & 3], GR[s & 3], GR[(s + 1) & 3], G);
-				if (bounded(y + dir) == bounded(y)) {
-					// the output row repeats (replicated border of the threshold source, or past the strip): re-seat the two
-					// rows behind so the next step sees the same neighbourhood. Only the image's first / last strip gets here.
-#pragma unroll
-					for (int i = 0; i < NP; ++i) { GR[(s + 1) & 3][i] = GR[s & 3][i]; GR[s & 3][i] = GR[(s + 3) & 3][i]; }
-				}
-			} else {
-				uint32_t T[K1_PPL];
-				gray_T<K1_PPL>(d, T);
-				pairs_T<NP>(T, G);
+				for (int i = 0; i < NP; ++i) { GR[(s + 1) & 3][i] = GR[s & 3][i]; GR[s & 3][i] = GR[(s + 3) & 3][i]; }
 			}
-			patch_edge(G, es);   // (a partial last lane: BORDER_REPLICATE of the row the box sums are taken of)
+		} else {
+			uint32_t T[K1_PPL];
+			gray_T<K1_PPL>(d, T);
+			pairs_T<NP>(T, G);
+		}
+		patch_edge(G, es);   // (a partial last lane: BORDER_REPLICATE of the row the box sums are taken of)
 
-			// colour column sums: rows 9r+9 .. 9r+14 are the inner rows of cell row r (cell top = 8 + 9r)
-			const bool in_grid = yl >= y_begin && yl < y_end && yl >= OFFSET + 1 && yl < OFFSET + DIM_Y * PITCH;
-			const int ph = in_grid ? (yl - OFFSET) % PITCH : 0;
+		// colour column sums: rows 9r+9 .. 9r+14 are the inner rows of cell row r (cell top = 8 + 9r)
+		const bool in_grid = yl >= y_begin && yl < y_end && yl >= OFFSET + 1 && yl < OFFSET + DIM_Y * PITCH;
+		const int ph = in_grid ? (yl - OFFSET) % PITCH : 0;
 #ifdef K1_PROBE_NOCOLOR      // (timing probe only: the colour column sums and their transpose compiled out -- what K1 would take with ~20 % less vector work)
-			if (false) {
+		if (false) {
 #else
-			if (ph >= 1 && ph <= 6) {
+		if (ph >= 1 && ph <= 6) {
 #endif
 #pragma unroll
-				for (int k = 0; k < NDW; ++k) {
-					acc_e[k] += d[k] & 0x00FF00FFu;
-					acc_o[k] += __builtin_amdgcn_perm(0u, d[k], 0x0c030c01u);   // (d >> 8) & 0x00FF00FF in one op
-				}
+			for (int k = 0; k < NDW; ++k) {
+				acc_e[k] += d[k] & 0x00FF00FFu;
+				acc_o[k] += __builtin_amdgcn_perm(0u, d[k], 0x0c030c01u);   // (d >> 8) & 0x00FF00FF in one op
 			}
-			// d is dead: refill it with the row DEPTH steps ahead
-			load_row(src, PRE ? ahead(t + DEPTH) : bounded(y + dir * DEPTH), ro, d);
+		}
+		// d is dead: refill it with the row DEPTH steps ahead
+		load_row(src, PRE ? ahead(t + DEPTH) : bounded(y + dir * DEPTH), ro, d);
 
 #ifdef K1_PROBE_NOCOLOR
-			if (false) {
+		if (false) {
 #else
-			if (ph == (dir > 0 ? 6 : 1)) {   // the cell row's last inner row in walking order
+		if (ph == (dir > 0 ? 6 : 1)) {   // the cell row's last inner row in walking order
 #endif
-				uint16_t* sc = s_col[wave];
-				uint32_t w[2 * NDW];
+			uint16_t* sc = s_col[wave];
+			uint32_t w[2 * NDW];
+#pragma unroll
+			for (int k = 0; k < NDW; ++k) {
+				w[2 * k] = (acc_e[k] & 0xFFFFu) | (acc_o[k] << 16);            // bytes 0,1 of dword k
+				w[2 * k + 1] = (acc_e[k] >> 16) | (acc_o[k] & 0xFFFF0000u);    // bytes 2,3
+				acc_e[k] = 0; acc_o[k] = 0;
+			}
+			if constexpr (K1_PPL == 16) {
+				// 16-byte stores: a lane's row is 96 bytes, so lanes l and l+4 share their banks whatever the width; eight 4-byte pairs per lane
+				// (what the compiler makes of 8-byte stores) cost four times the LDS cycles of six 16-byte ones (SQ_LDS_BANK_CONFLICT, profiles/r05m)
+				// (by hand: the optimiser takes a vector store of four computed words apart again and pairs the pieces as ds_write2_b32. LDS operations of
+				// one wavefront are issued and performed in order, so the reads below see these stores without the compiler knowing of them)
+				typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+				const uint32_t at = (uint32_t)(uintptr_t)(sc + 48 * lane);   // (a shared-memory address' low word is its LDS offset)
+#pragma unroll
+				for (int j = 0; j < NDW / 2; ++j) {
+					const u4 v = {w[4 * j], w[4 * j + 1], w[4 * j + 2], w[4 * j + 3]};
+					asm volatile("ds_write_b128 %0, %1 offset:%2" :: "v"(at), "v"(v), "n"(16 * j) : "memory");
+				}
+			} else {
+				// (12 pixels per lane: rows of 72 bytes -- 8-byte stores, whose 16 lanes per pass fall on 16 different bank pairs; as 4-byte pieces four lanes share a bank)
+				typedef uint32_t u2 __attribute__((ext_vector_type(2)));
+				const uint32_t at = (uint32_t)(uintptr_t)(sc + K1_PPL * 3 * lane);
 #pragma unroll
 				for (int k = 0; k < NDW; ++k) {
-					w[2 * k] = (acc_e[k] & 0xFFFFu) | (acc_o[k] << 16);            // bytes 0,1 of dword k
-					w[2 * k + 1] = (acc_e[k] >> 16) | (acc_o[k] & 0xFFFF0000u);    // bytes 2,3
-					acc_e[k] = 0; acc_o[k] = 0;
+					const u2 v = {w[2 * k], w[2 * k + 1]};
+					asm volatile("ds_write_b64 %0, %1 offset:%2" :: "v"(at), "v"(v), "n"(8 * k) : "memory");
 				}
-				if constexpr (K1_PPL == 16) {
-					// 16-byte stores: a lane's row is 96 bytes, so lanes l and l+4 share their banks whatever the width; eight 4-byte pairs per lane
-					// (what the compiler makes of 8-byte stores) cost four times the LDS cycles of six 16-byte ones (SQ_LDS_BANK_CONFLICT, profiles/r05m)
-					// (by hand: the optimiser takes a vector store of four computed words apart again and pairs the pieces as ds_write2_b32. LDS operations of
-					// one wavefront are issued and performed in order, so the reads below see these stores without the compiler knowing of them)
-					typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-					const uint32_t at = (uint32_t)(uintptr_t)(sc + 48 * lane);   // (a shared-memory address' low word is its LDS offset)
-#pragma unroll
-					for (int j = 0; j < NDW / 2; ++j) {
-						const u4 v = {w[4 * j], w[4 * j + 1], w[4 * j + 2], w[4 * j + 3]};
-						asm volatile("ds_write_b128 %0, %1 offset:%2" :: "v"(at), "v"(v), "n"(16 * j) : "memory");
-					}
-				} else {
-					// (12 pixels per lane: rows of 72 bytes -- 8-byte stores, whose 16 lanes per pass fall on 16 different bank pairs; as 4-byte pieces four lanes share a bank)
-					typedef uint32_t u2 __attribute__((ext_vector_type(2)));
-					const uint32_t at = (uint32_t)(uintptr_t)(sc + K1_PPL * 3 * lane);
-#pragma unroll
-					for (int k = 0; k < NDW; ++k) {
-						const u2 v = {w[2 * k], w[2 * k + 1]};
-						asm volatile("ds_write_b64 %0, %1 offset:%2" :: "v"(at), "v"(v), "n"(8 * k) : "memory");
-					}
-				}
-				__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-				__builtin_amdgcn_wave_barrier();
-				const int cell_row = (yl - OFFSET) / PITCH;
-#pragma unroll
-				for (int half = 0; half < 2; ++half) {
-					const int c = lane + 64 * half;
-					if (c < DIM_X) {
-						const uint16_t* src = sc + 3 * (PITCH * c + OFFSET + 1);   // first inner column of cell column c, as a row byte
-						uint32_t r = 0, gg = 0, b = 0;
-#pragma unroll
-						for (int k = 0; k < 6; ++k) { r += src[3 * k]; gg += src[3 * k + 1]; b += src[3 * k + 2]; }
-						cm[cell_row * DIM_X + c] = (r / 36u) | ((gg / 36u) << 8) | ((b / 36u) << 16);
-					}
-				}
-				__builtin_amdgcn_wave_barrier();
 			}
+			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+			__builtin_amdgcn_wave_barrier();
+			const int cell_row = (yl - OFFSET) / PITCH;
+#pragma unroll
+			for (int half = 0; half < 2; ++half) {
+				const int c = lane + 64 * half;
+				if (c < DIM_X) {
+					const uint16_t* src = sc + 3 * (PITCH * c + OFFSET + 1);   // first inner column of cell column c, as a row byte
+					uint32_t r = 0, gg = 0, b = 0;
+#pragma unroll
+					for (int k = 0; k < 6; ++k) { r += src[3 * k]; gg += src[3 * k + 1]; b += src[3 * k + 2]; }
+					cm[cell_row * DIM_X + c] = (r / 36u) | ((gg / 36u) << 8) | ((b / 36u) << 16);
+				}
+			}
+			__builtin_amdgcn_wave_barrier();
+		}
 
-			uint32_t bits = 0;
-			// (the first 2 RAD steps of a strip only fill the window: no row is complete yet, so the horizontal pass, the comparison and the bit gather
-			// below are not issued for them -- a wave-uniform branch, 4 of a strip's 22 / 67 steps)
-			const bool emit = t >= 2 * RAD;
-			switch (s) {   // SLOT must be a compile-time constant; `s` is one after unrolling
-				case 0: bits = box_row<RAD, 0>(ring, C, G, emit); break;
-				case 1: bits = box_row<RAD, 1>(ring, C, G, emit); break;
-				case 2: bits = box_row<RAD, 2>(ring, C, G, emit); break;
-				case 3: bits = box_row<RAD, 3>(ring, C, G, emit); break;
-				case 4: bits = box_row<RAD, 4>(ring, C, G, emit); break;
-				case 5: bits = box_row<RAD, 5>(ring, C, G, emit); break;
-				case 6: bits = box_row<RAD, 6 % RING>(ring, C, G, emit); break;
-				default: bits = box_row<RAD, 7 % RING>(ring, C, G, emit); break;
-			}
-			if (emit) {
-				uint32_t* orow = out + (size_t)(y - dir * RAD) * PLANE_ROW;   // the row whose window just completed
-				if constexpr (K1_PPL == 16) {
-					// gather the 8 x 16 bits of lanes 8k..8k+7 into lane 8k and store 16 bytes (columns 128k .. 128k+127 of the row)
-					const uint32_t nb = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)bits, 0xB1, 0xf, 0xf, true);   // lane^1
-					const uint32_t w0 = (lane & 1) ? ((nb << 16) | bits) : ((bits << 16) | nb);                        // word of lanes (2j,2j+1), in both
-					const uint32_t w1 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)w0, 0x4E, 0xf, 0xf, true);      // quad_perm:[2,3,0,1]: the quad's other word
-					// lanes 4q..4q+3: lane 4q has w0 = word(2q), w1 = word(2q+1). Bring the next quad's two words over (row_shl:4).
-					const uint32_t w2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)w0, 0x104, 0xf, 0xf, true);     // row_shl:4 -> lane l gets lane l+4
-					const uint32_t w3 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)w1, 0x104, 0xf, 0xf, true);
-					if (t < total && !(lane & 7)) {
-						uint4 v; v.x = w0; v.y = w1; v.z = w2; v.w = w3;
-						*reinterpret_cast<uint4*>(orow + (lane >> 3) * 4) = v;
-					}
-				} else {
-					// gather the 8 x 12 bits of lanes 8k..8k+7 into lane 8k and store 12 bytes (columns 96k .. 96k+95 of the row): pairs of lanes make
-					// 24 bits, pairs of pairs 48 (as 16 + 32), and the two quads of the group the three words
-					const uint32_t nb = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)bits, 0xB1, 0xf, 0xf, true);    // lane^1
-					const uint32_t c24 = (bits << 12) | nb;                                                             // lanes 2j: columns of lanes (2j, 2j+1)
-					const uint32_t o24 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)c24, 0x4E, 0xf, 0xf, true);    // quad_perm:[2,3,0,1]: the quad's other pair
-					const uint32_t hi16 = c24 >> 8, lo32 = (c24 << 24) | o24;                                           // lanes 4q: the quad's 48 columns
-					const uint32_t bh = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hi16, 0x104, 0xf, 0xf, true);   // row_shl:4 -> lane l gets lane l+4
-					const uint32_t bl = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)lo32, 0x104, 0xf, 0xf, true);
-					if (t < total && !(lane & 7)) {
-						struct __attribute__((packed, aligned(4))) W3 { uint32_t x, y, z; } v;
-						v.x = (hi16 << 16) | (lo32 >> 16); v.y = (lo32 << 16) | bh; v.z = bl;
-						*reinterpret_cast<W3*>(orow + (lane >> 3) * 3) = v;
-					}
+		uint32_t bits = 0;
+		// (the first 2 RAD steps of a strip only fill the window: no row is complete yet, so the horizontal pass, the comparison and the bit gather
+		// below are not issued for them -- a wave-uniform branch, 4 of a strip's 22 / 67 steps)
+		const bool emit = t >= 2 * RAD;
+		switch (s) {   // SLOT must be a compile-time constant; `s` is one after unrolling
+			case 0: bits = box_row<RAD, 0>(ring, C, G, emit); break;
+			case 1: bits = box_row<RAD, 1>(ring, C, G, emit); break;
+			case 2: bits = box_row<RAD, 2>(ring, C, G, emit); break;
+			case 3: bits = box_row<RAD, 3>(ring, C, G, emit); break;
+			case 4: bits = box_row<RAD, 4>(ring, C, G, emit); break;
+			case 5: bits = box_row<RAD, 5>(ring, C, G, emit); break;
+			case 6: bits = box_row<RAD, 6 % RING>(ring, C, G, emit); break;
+			default: bits = box_row<RAD, 7 % RING>(ring, C, G, emit); break;
+		}
+		if (emit) {
+			uint32_t* orow = out + (size_t)(y - dir * RAD) * PLANE_ROW;   // the row whose window just completed
+			if constexpr (K1_PPL == 16) {
+				// gather the 8 x 16 bits of lanes 8k..8k+7 into lane 8k and store 16 bytes (columns 128k .. 128k+127 of the row)
+				const uint32_t nb = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)bits, 0xB1, 0xf, 0xf, true);   // lane^1
+				const uint32_t w0 = (lane & 1) ? ((nb << 16) | bits) : ((bits << 16) | nb);                        // word of lanes (2j,2j+1), in both
+				const uint32_t w1 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)w0, 0x4E, 0xf, 0xf, true);      // quad_perm:[2,3,0,1]: the quad's other word
+				// lanes 4q..4q+3: lane 4q has w0 = word(2q), w1 = word(2q+1). Bring the next quad's two words over (row_shl:4).
+				const uint32_t w2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)w0, 0x104, 0xf, 0xf, true);     // row_shl:4 -> lane l gets lane l+4
+				const uint32_t w3 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)w1, 0x104, 0xf, 0xf, true);
+				if (!(lane & 7)) {
+					uint4 v; v.x = w0; v.y = w1; v.z = w2; v.w = w3;
+					*reinterpret_cast<uint4*>(orow + (lane >> 3) * 4) = v;
+				}
+			} else {
+				// gather the 8 x 12 bits of lanes 8k..8k+7 into lane 8k and store 12 bytes (columns 96k .. 96k+95 of the row): pairs of lanes make
+				// 24 bits, pairs of pairs 48 (as 16 + 32), and the two quads of the group the three words
+				const uint32_t nb = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)bits, 0xB1, 0xf, 0xf, true);    // lane^1
+				const uint32_t c24 = (bits << 12) | nb;                                                             // lanes 2j: columns of lanes (2j, 2j+1)
+				const uint32_t o24 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)c24, 0x4E, 0xf, 0xf, true);    // quad_perm:[2,3,0,1]: the quad's other pair
+				const uint32_t hi16 = c24 >> 8, lo32 = (c24 << 24) | o24;                                           // lanes 4q: the quad's 48 columns
+				const uint32_t bh = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hi16, 0x104, 0xf, 0xf, true);   // row_shl:4 -> lane l gets lane l+4
+				const uint32_t bl = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)lo32, 0x104, 0xf, 0xf, true);
+				if (!(lane & 7)) {
+					struct __attribute__((packed, aligned(4))) W3 { uint32_t x, y, z; } v;
+					v.x = (hi16 << 16) | (lo32 >> 16); v.y = (lo32 << 16) | bh; v.z = bl;
+					*reinterpret_cast<W3*>(orow + (lane >> 3) * 3) = v;
 				}
 			}
 		}
+	};
+	// FULL passes over the ring in a loop whose only exit is at its end, then the strip's last total % RING steps once more as straight-line code that
+	// returns when the rows are done (2 of 24 steps of a short strip, 5 of 72 of a tall one used to run on clamped re-reads; the surplus steps issue
+	// nothing now -- a scalar compare and a branch cost no vector issue slot, which is what the pipelined loop is short of, profiles/r05f).
+	// Why not an exit test per step inside the loop: the body has lane-divergent branches (the two stores), so the compiler structurizes the whole loop
+	// and routes every exit edge through a block it shares with the latch. The normal path then runs one such block per exit edge, each with a
+	// vmcnt(0) -- the prefetch queue drained once per pass -- and copies of the buffer registers (DESIGN.md section 3, K1). With its one exit the loop is
+	// straight-line: every step waits for the oldest row in flight only (vmcnt 3 DEPTH - 3 before its first use, 3 DEPTH before the last), step 0
+	// included, because the prologue above issues its rows in walking order and so enters the loop with the queue the back edge carries.
+	// (a strip holds at least one cell row, so there is always one full pass: the loop tests at its end, and no value has to survive around it)
+	static_assert(PITCH + 2 * RAD >= RING, "a strip's shortest walk covers a full pass over the ring");
+	int t0 = 0;
+	do {
+#pragma unroll
+		for (int s = 0; s < RING; ++s) step(s, t0 + s);
+		t0 += RING;
+	} while (t0 + RING <= total);
+#pragma unroll
+	for (int s = 0; s < RING - 1; ++s) {
+		if (t0 + s >= total) return;
+		step(s, t0 + s);
 	}
 }

@@ -26,6 +26,7 @@ TAP_GROUP_COLOUR_MARGIN, TAP_GROUP_COLOUR_WEIGHTS = 15, 16   # the colour vote o
 TAP_STREAM_CARRY_WEIGHTS = 17   # the carried weights of the open group's members after a stream call with set_stream_colour_vote on
 TAP_STITCH_CELLS, TAP_STITCH_LINES = 18, 19   # the stitching of the last stitched batch (decode_batch_stitched): n = its captures
 TAP_STITCH_CARRY = 20   # the capture the stitched-stream calls carry (decode_batch_stitched_stream): tap_stitch_carry
+TAP_CELL_MEANS = 21   # the threshold kernel's undrifted cell means, r | g << 8 | b << 16 by grid slot (row * DIM_X + column)
 # CIMBAR_HIP_COLOUR_MARGIN_SUGGESTED (include/cimbar_hip.h): the colour erasure threshold chosen on rendered frames (DESIGN_WIDENING.md)
 COLOUR_MARGIN_SUGGESTED = 32512
 
@@ -1031,6 +1032,7 @@ class HipDecoder:
             TAP_STREAM_CARRY_WEIGHTS: ((n, self.geo.NCELLS), np.uint32),
             # (n = the captures of the stitched batch; the lines tap has DIM_Y entries per pair on axis 0 and DIM_X on axis 1: tap_stitch_lines)
             TAP_STITCH_CELLS: ((2 * max(n - 1, 0), self.geo.NCELLS), np.uint8),
+            TAP_CELL_MEANS: ((n, self.geo.DIM_Y, self.geo.DIM_X), np.uint32),
         }
         shape, dt = shapes[what]
         out = np.zeros(shape, dtype=dt)
