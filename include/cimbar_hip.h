@@ -402,6 +402,30 @@ int64_t cimbar_hip_scan_extract_decode_batch_stitched_stream_fmt(cimbar_hip_ctx*
                                                                  uint8_t* schunks, uint32_t* smasks, int32_t* tears, int out_mem, void* hip_stream);
 int cimbar_hip_stitch_stream_reset(cimbar_hip_ctx* ctx);
 
+/* Torn-capture stitching strip by strip (1 after cimbar_hip_create: the rule above, bit for bit). A tear is a straight line on the sensor, so
+ * a receiver's roll and perspective put it on a slant in the deskewed frame. When the tear rises over m grid lines across the frame and the
+ * two tears lie g lines apart, no whole line reaches 750 once g falls below about 0.75 m, although every column still has g clean shared
+ * lines. With strips = S in 2..8 the frame is cut across the lines into S strips and the band is found in each. lines, L, eq,
+ * min_agree_permille and min_band are the ones above; for captures k, k+1 and the call's axis:
+ *   strip      across(i) = cell i's index on the other axis: axis 0 its grid column (x_i - offset) / 9 with A = the grid's columns, axis 1
+ *              its grid row with A = the grid's rows. strip(i) = across(i) * S / A in integers.
+ *   width(l, j) the cells of line l in strip j (positive for S <= 8 in every mode; checked once at cimbar_hip_create)
+ *   flag(l, j) cnt(l, j) * 1000 >= min_agree_permille * width(l, j), cnt(l, j) = the sum of eq over those cells
+ *   per strip  a_j = the lowest flagged line, b_j = the highest flagged line + 1, f_j = the flagged lines. Strip j is located iff f_j >= 1,
+ *              b_j - a_j >= min_band and 4 f_j >= 3 (b_j - a_j); its own split is (a_j + b_j) >> 1.
+ *   candidate  both captures usable, 2 * located >= S, and some located strip with a_j > 0 or b_j < L (every located strip spanning the whole
+ *              frame is the group decode's case, as above)
+ *   splits     a located strip keeps its own split as s_j; any other takes the split of the nearest located strip by index, the lower index
+ *              on a tie
+ *   cells      direction 0: cell i is capture k+1's if line(i) < s_strip(i), else capture k's; direction 1 the reverse
+ *   tears      {min a_j, max b_j over the located strips, s_(S >> 1), the sum of f_j over all strips}; no candidate: {-1, -1, -1, that sum}
+ * Slots, the decode, smask, zeroes for a pair that is no candidate and the return values are unchanged; host outputs still return the records
+ * with a >= 0. The four stitched entry points read the setting when they are called, so it may change between the calls of a stream: row 0
+ * is judged with the setting of the call that reports it, like axis. set: strips outside 1..8 is CIMBAR_HIP_EINVAL and changes nothing;
+ * every mode accepts 1..8. get: writes the setting to *strips and returns 0. For a hand-held receiver 4 to 8 is the advice. */
+int cimbar_hip_set_stitch_strips(cimbar_hip_ctx* ctx, int strips);
+int cimbar_hip_get_stitch_strips(cimbar_hip_ctx* ctx, int* strips);
+
 /* ---- chunk delivery: a batch's slots and masks -> what a fountain sink eats --------------------------------------------------------------
  * The batch entry points above report a frame's chunks in fixed slots plus one mask word. The reference's receive interface has another shape:
  * cimbard_scan_extract_decode returns the delivered chunks packed front to back (escrow_buffer_writer), and cimbard_fountain_decode(buf, size)
@@ -722,9 +746,14 @@ enum {
 	 * after cimbar_hip_stitch_stream_reset); does not depend on the last batch */
 	CIMBAR_HIP_TAP_STITCH_CARRY = 20, /* 2 * cells bytes        : the carried symbols, then the carried colours, by linear cell index */
 	/* the threshold kernel's second product, as it left it (the colour pass reads it where a cell has no drift) */
-	CIMBAR_HIP_TAP_CELL_MEANS = 21    /* n * grid slots u32     : r | g << 8 | b << 16, the inner-6x6 mean (Cell.h: channel sum / 36, remainder dropped) of
+	CIMBAR_HIP_TAP_CELL_MEANS = 21,   /* n * grid slots u32     : r | g << 8 | b << 16, the inner-6x6 mean (Cell.h: channel sum / 36, remainder dropped) of
 	                                     every cell at its undrifted position, by grid slot row * columns + column (112 x 112 | 112 x 78 | 80 x 69
 	                                     slots, the four corner cut-outs included) */
+	/* the strips of the last batch, when it was a stitched one that ran with cimbar_hip_set_stitch_strips = S above 1 (else CIMBAR_HIP_EINVAL);
+	 * rows = n - 1, after a stitched-stream call n. CIMBAR_HIP_TAP_STITCH_LINES of such a batch is cnt(l) = the sum of cnt(l, j) over j. */
+	CIMBAR_HIP_TAP_STITCH_STRIPS = 22,      /* rows * S * 4 int32: {a_j, b_j, s_j, f_j}; a_j = b_j = -1 for a strip that is not located, s_j = the
+	                                           resolved split, -1 in a pair that is no candidate */
+	CIMBAR_HIP_TAP_STITCH_STRIP_LINES = 23  /* rows * S * L u16  : cnt(l, j), the agreeing cells of line l in strip j */
 };
 int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_bytes);
 

@@ -309,6 +309,18 @@ int cimbar_hip_stitch_stream_reset(cimbar_hip_ctx* ctx)
 	return CIMBAR_FWD(cimbar_hip_stitch_stream_reset);
 }
 
+int cimbar_hip_set_stitch_strips(cimbar_hip_ctx* ctx, int strips)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return CIMBAR_FWD(cimbar_hip_set_stitch_strips, strips);
+}
+
+int cimbar_hip_get_stitch_strips(cimbar_hip_ctx* ctx, int* strips)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return CIMBAR_FWD(cimbar_hip_get_stitch_strips, strips);
+}
+
 int cimbar_hip_combine_stream_reset(cimbar_hip_ctx* ctx)
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;

@@ -61,6 +61,9 @@ struct cimbar_hip_ctx {
 	DevBuf<uint8_t> d_ssym, d_scol, d_srs_ok;   // [2 rows][NCELLS], [2 rows][ALL_BLOCKS]
 	DevBuf<uint32_t> d_slive; DevBuf<int32_t> d_stears; DevBuf<uint16_t> d_slines; DevBuf<int> d_sslots;   // [2 rows], [rows][4], [rows][L], 1 int
 	std::unique_ptr<StitchStream> sstream;      // cimbar_hip_decode_batch_stitched_stream / _scan_extract_decode_batch_stitched_stream_fmt
+	int stitch_strips = 1;                      // cimbar_hip_set_stitch_strips: 1 = whole lines (k_stitch_pairs), 2..8 = k_stitch_pairs_strips
+	int stitch_S = 1;                           // the strips of the last stitched batch (> 1: the strip taps describe it)
+	DevBuf<int32_t> d_sstrips; DevBuf<uint16_t> d_sstrip_lines;   // [rows][S][4], [rows][S][L]: allocated by the first stitched call with strips > 1
 	DevBuf<uint8_t> d_schunks; DevBuf<uint32_t> d_smasks;   // staging for host-memory stitch outputs
 	int wave_adapt = 1;               // CIMBAR_HIP_FLOOD_WAVE_ADAPT=0: run k_flood_wave in front of every exact replay, whatever it achieved before
 	bool wave_ran = false;            // k_flood_wave ran in the batch h_flagged describes
@@ -72,6 +75,7 @@ struct cimbar_hip_ctx {
 	Tables tb{};                      // what the kernels take by value: filled by build_tables from the owners beside it
 	DevBuf<ushort2> tb_cell_xy; DevBuf<uint16_t> tb_stream_cell, tb_cell_grid, tb_ccm_grid; DevBuf<int16_t> tb_grid_cell, tb_cand;
 	DevBuf<uint8_t> tb_stitch_line;  // [2][NCELLS] the grid row and the grid column of every cell (k_stitch_pairs)
+	DevBuf<uint16_t> tb_stitch_width;  // [2][STITCH_SMAX][STITCH_SMAX][128] width(l, j) by axis, S - 1, strip and line (k_stitch_pairs_strips)
 	uint64_t tile_hashes[16] = {};   // as computed at create (also in c_tile)
 	int last_n = 0;
 	int scan_n = 0;                             // captures of the last anchor search (CIMBAR_HIP_TAP_SCAN_PATH describes it)
@@ -381,6 +385,19 @@ int build_tables(cimbar_hip_ctx* ctx)
 	}
 	HIPCHK(ctx->tb_stitch_line.reserve(stitch_line.size()));
 	HIPCHK(hipMemcpy(ctx->tb_stitch_line, stitch_line.data(), stitch_line.size(), hipMemcpyHostToDevice));
+	// the strips of cimbar_hip_set_stitch_strips: every line has cells in every strip, or a strip's flags would be empty products
+	std::vector<uint16_t> stitch_width((size_t)2 * STITCH_SMAX * STITCH_SMAX * 128, 0);
+	for (int axis = 0; axis < 2; ++axis)
+		for (int S = 1; S <= STITCH_SMAX; ++S) {
+			uint16_t* wt = stitch_width.data() + (size_t)(axis * STITCH_SMAX + S - 1) * STITCH_SMAX * 128;
+			const int A = axis == 0 ? DIM_X : DIM_Y;
+			for (int i = 0; i < NCELLS; ++i) ++wt[(stitch_line[(size_t)(axis ^ 1) * NCELLS + i] * S / A) * 128 + stitch_line[(size_t)axis * NCELLS + i]];
+			for (int j = 0; j < S; ++j)
+				for (int l = 0; l < stitch_lines(axis); ++l)
+					if (!wt[j * 128 + l]) { ctx->err = "build_tables: a stitch strip without cells on a line"; return CIMBAR_HIP_EINVAL; }
+		}
+	HIPCHK(ctx->tb_stitch_width.reserve(stitch_width.size()));
+	HIPCHK(hipMemcpy(ctx->tb_stitch_width, stitch_width.data(), sizeof(uint16_t) * stitch_width.size(), hipMemcpyHostToDevice));
 	HIPCHK(ctx->tb_cand.reserve((size_t)NCELLS * 12));
 	HIPCHK(hipMemcpy(ctx->tb_cell_xy, xy.data(), sizeof(ushort2) * NCELLS, hipMemcpyHostToDevice));
 	HIPCHK(hipMemcpy(ctx->tb_stream_cell, sc.data(), sizeof(uint16_t) * NCELLS, hipMemcpyHostToDevice));
@@ -1136,6 +1153,7 @@ struct StitchArgs {
 	uint8_t* schunks; uint32_t* smasks; int32_t* tears;   // 2 rows slots; rows x 4 ints (may be nullptr)
 	std::vector<int32_t> h_tears;                         // host outputs: where the tear records land when the caller wants none
 	bool stream = false;                                  // a stream call: n rows, row 0 against the carried capture; else n - 1
+	int strips = 1;                                       // cimbar_hip_set_stitch_strips as the call found it (check_stitch)
 	int rows(int n) const { return stream ? n : n - 1; }
 };
 
@@ -1147,12 +1165,17 @@ int check_stitch(cimbar_hip_ctx* ctx, const char* who, int n, StitchArgs& sa)
 	if (sa.rows(n) > 0 && (!sa.schunks || !sa.smasks)) { ctx->err = std::string(who) + ": null schunks / smasks"; return CIMBAR_HIP_EINVAL; }
 	if (sa.min_agree <= 0) sa.min_agree = STITCH_AGREE_DEFAULT;
 	if (sa.min_band <= 0) sa.min_band = STITCH_BAND_DEFAULT;
+	sa.strips = ctx->stitch_strips;
 	return 0;
 }
 
-int ensure_stitch_capacity(cimbar_hip_ctx* ctx, int rows)
+int ensure_stitch_capacity(cimbar_hip_ctx* ctx, int rows, int strips)
 {
 	const size_t P = (size_t)rows, S = 2 * P;
+	if (strips > 1) {
+		HIPCHK(ctx->d_sstrips.reserve(P * STITCH_SMAX * 4));
+		HIPCHK(ctx->d_sstrip_lines.reserve(P * STITCH_SMAX * STITCH_LMAX));
+	}
 	HIPCHK(ctx->d_ssym.reserve(S * NCELLS));
 	HIPCHK(ctx->d_scol.reserve(S * NCELLS));
 	HIPCHK(ctx->d_srs_ok.reserve(S * ALL_BLOCKS));
@@ -1186,20 +1209,30 @@ int begin_stitch_stream(cimbar_hip_ctx* ctx, hipStream_t st)
 int enqueue_stitch(cimbar_hip_ctx* ctx, hipStream_t st, int n, const int* d_status, int stride, StitchArgs& sa, int out_mem)
 {
 	const int pairs = sa.rows(n), slots = 2 * pairs;
-	if (int r = ensure_stitch_capacity(ctx, pairs)) return r;
+	if (int r = ensure_stitch_capacity(ctx, pairs, sa.strips)) return r;
 	cimbar_hip_ctx::ScratchSet& cur = ctx->cur();
 	const bool dev = out_mem == CIMBAR_HIP_MEM_DEVICE;
 	uint8_t* d_out = dev ? sa.schunks : ctx->d_schunks.get();
 	uint32_t* d_om = dev ? sa.smasks : ctx->d_smasks.get();
 	HIPCHK(hipMemsetAsync(ctx->d_sslots, 0, sizeof(int), st));
+	const uint16_t* strip_width = ctx->tb_stitch_width + (size_t)(sa.axis * STITCH_SMAX + sa.strips - 1) * STITCH_SMAX * 128;
 	if (sa.stream) {
 		StitchStream& s = *ctx->sstream;
-		hipLaunchKernelGGL(k_stitch_pairs_stream, dim3(pairs), dim3(256), 0, st, cur.d_symbols, cur.d_colors, n, d_status, stride, ctx->tb_stitch_line,
-		                   sa.axis, sa.min_agree, sa.min_band, ctx->d_stears, ctx->d_slines, ctx->d_slive, ctx->d_sslots, ctx->d_ssym, ctx->d_scol, s.carry());
+		if (sa.strips > 1)
+			hipLaunchKernelGGL(k_stitch_pairs_strips_stream, dim3(pairs), dim3(256), 0, st, cur.d_symbols, cur.d_colors, n, d_status, stride,
+			                   ctx->tb_stitch_line, strip_width, sa.axis, sa.strips, sa.min_agree, sa.min_band, ctx->d_stears, ctx->d_slines, ctx->d_sstrips,
+			                   ctx->d_sstrip_lines, ctx->d_slive, ctx->d_sslots, ctx->d_ssym, ctx->d_scol, s.carry());
+		else
+			hipLaunchKernelGGL(k_stitch_pairs_stream, dim3(pairs), dim3(256), 0, st, cur.d_symbols, cur.d_colors, n, d_status, stride, ctx->tb_stitch_line,
+			                   sa.axis, sa.min_agree, sa.min_band, ctx->d_stears, ctx->d_slines, ctx->d_slive, ctx->d_sslots, ctx->d_ssym, ctx->d_scol, s.carry());
 		HIPCHK(hipGetLastError());
 		s.cur ^= 1;   // (the slot that launch fills)
 		s.carried = true;
-	} else
+	} else if (sa.strips > 1)
+		hipLaunchKernelGGL(k_stitch_pairs_strips, dim3(pairs), dim3(256), 0, st, cur.d_symbols, cur.d_colors, n, d_status, stride, ctx->tb_stitch_line,
+		                   strip_width, sa.axis, sa.strips, sa.min_agree, sa.min_band, ctx->d_stears, ctx->d_slines, ctx->d_sstrips, ctx->d_sstrip_lines,
+		                   ctx->d_slive, ctx->d_sslots, ctx->d_ssym, ctx->d_scol);
+	else
 		hipLaunchKernelGGL(k_stitch_pairs, dim3(pairs), dim3(256), 0, st, cur.d_symbols, cur.d_colors, n, d_status, stride, ctx->tb_stitch_line, sa.axis,
 		                   sa.min_agree, sa.min_band, ctx->d_stears, ctx->d_slines, ctx->d_slive, ctx->d_sslots, ctx->d_ssym, ctx->d_scol);
 	launch_live_rs(ctx, st, slots, ctx->d_ssym, ctx->d_scol, ctx->d_srs_ok, ctx->d_sslots, ctx->d_slive, d_out);
@@ -1226,6 +1259,7 @@ int64_t finish_stitched(cimbar_hip_ctx* ctx, hipStream_t st, int n, uint8_t* chu
 	ctx->stitch_n = n;
 	ctx->stitch_rows = sa.rows(n);
 	ctx->stitch_axis = sa.axis;
+	ctx->stitch_S = sa.strips;
 	if (sa.stream) {
 		HIPCHK(hipEventRecord(ctx->sstream->ev_last, st));
 		ctx->sstream->used = true;
@@ -2077,6 +2111,22 @@ int cimbar_hip_get_group_colour_vote(cimbar_hip_ctx* ctx, int* on)
 	return 0;
 }
 
+int cimbar_hip_set_stitch_strips(cimbar_hip_ctx* ctx, int strips)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	if (strips < 1 || strips > STITCH_SMAX) { ctx->err = "set_stitch_strips: strips must be 1 .. 8"; return CIMBAR_HIP_EINVAL; }
+	// (read when a stitched call is enqueued: calls already issued keep the setting they were issued with)
+	ctx->stitch_strips = strips;
+	return 0;
+}
+
+int cimbar_hip_get_stitch_strips(cimbar_hip_ctx* ctx, int* strips)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	if (strips) *strips = ctx->stitch_strips;
+	return 0;
+}
+
 int cimbar_hip_set_stream_colour_vote(cimbar_hip_ctx* ctx, int on)
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;
@@ -2282,6 +2332,16 @@ int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_byte
 			HIPCHK(hipMemcpy(col.data(), ctx->d_scol, bytes, hipMemcpyDeviceToHost));
 			HIPCHK(hipMemcpy(lv.data(), ctx->d_slive, sizeof(uint32_t) * slots, hipMemcpyDeviceToHost));
 			for (size_t k = 0; k < bytes; ++k) ((uint8_t*)out)[k] = lv[k / NCELLS] ? (uint8_t)((col[k] << 4) | (((uint8_t*)out)[k] & 15u)) : (uint8_t)0;
+			return (int64_t)bytes;
+		}
+		case CIMBAR_HIP_TAP_STITCH_STRIPS:
+		case CIMBAR_HIP_TAP_STITCH_STRIP_LINES: {
+			if (ctx->stitch_n <= 0 || ctx->stitch_S <= 1) { ctx->err = "tap: the last batch was not a stitched one with strips above 1 (cimbar_hip_set_stitch_strips)"; return CIMBAR_HIP_EINVAL; }
+			const size_t rows = (size_t)ctx->stitch_rows * (size_t)ctx->stitch_S, L = (size_t)stitch_lines(ctx->stitch_axis);
+			bytes = what == CIMBAR_HIP_TAP_STITCH_STRIPS ? rows * 4 * sizeof(int32_t) : rows * L * sizeof(uint16_t);
+			if (out_bytes < bytes) { ctx->err = "tap: buffer too small"; return CIMBAR_HIP_EINVAL; }
+			if (!bytes) return 0;
+			HIPCHK(hipMemcpy(out, what == CIMBAR_HIP_TAP_STITCH_STRIPS ? (const void*)ctx->d_sstrips.get() : (const void*)ctx->d_sstrip_lines.get(), bytes, hipMemcpyDeviceToHost));
 			return (int64_t)bytes;
 		}
 		case CIMBAR_HIP_TAP_STREAM_CARRY_WEIGHTS: {

@@ -29,6 +29,21 @@
 // second capture, so the carry is always one capture's decided cells and a word saying whether that capture is usable; nothing is ever open.
 // Row 0 without a usable carry (after create / reset, or a carried capture whose extraction failed) is a non-candidate {-1, -1, -1, 0} with
 // zero counts. Everything else is the rule above, through the same body: k_stitch_pairs_stream is its CARRY instance, K3 and S2 run over 2n slots.
+// ------------------------------------------------------------------------------------------------ strips (cimbar_hip_set_stitch_strips, S in 2..8)
+// A tear is a straight line of the sensor, so roll and perspective put it on a slant in the deskewed frame: with the two tears closer than
+// 3/4 of the slant's rise no whole line reaches 750, though every column still has its clean shared lines. The frame is cut across the
+// lines into S strips and the band is found strip by strip:
+//   strip      across(i) = the cell's index on the other axis (axis 0: its grid column, A = DIM_X; axis 1: its grid row, A = DIM_Y);
+//              strip(i) = across(i) * S / A. width(l, j) = the cells of line l in strip j (> 0 for S <= 8 in every mode: build_tables checks)
+//   flag(l, j) cnt(l, j) * 1000 >= min_agree_permille * width(l, j), cnt(l, j) = the sum of eq over those cells
+//   located    a_j, b_j, f_j as a, b, f above, of strip j's flags; located iff f_j >= 1, b_j - a_j >= min_band and 4 f_j >= 3 (b_j - a_j)
+//   candidate  both captures usable, 2 * located >= S, and some located strip with a_j > 0 or b_j < L
+//   splits     a located strip: s_j = (a_j + b_j) >> 1; any other takes the split of the nearest located strip by index, the lower one on a tie.
+//              Cell i is chosen as above with s_{strip(i)} for s.
+//   record     {min a_j, max b_j over the located strips, s_{S >> 1}, the sum of f_j}; a non-candidate {-1, -1, -1, the sum of f_j}
+// Slots, the Reed-Solomon pass, S2 and *n_slots are the ones above. S = 1 is k_stitch_pairs / k_stitch_pairs_stream themselves.
+//   S1 k_stitch_pairs_strips / k_stitch_pairs_strips_stream  the same workgroup per pair with cnt [8][128] in LDS; also the per-strip records
+//                      {a_j, b_j, s_j, f_j} and cnt(l, j) for the taps (lines stays cnt(l), the sum over the strips)
 constexpr int STITCH_AGREE_DEFAULT = 750, STITCH_BAND_DEFAULT = 2;
 constexpr int STITCH_LMAX = DIM_X > DIM_Y ? DIM_X : DIM_Y;
 static_assert(STITCH_LMAX <= 128, "the line flags fit two ballots");
@@ -187,6 +202,200 @@ __global__ __launch_bounds__(256) void k_stitch_pairs_stream(const uint8_t* __re
                                                              uint8_t* __restrict__ scol, const StitchCarry cy)
 {
 	stitch_pairs_body<true>(symbols, colors, n, status, stride, line_tab, axis, min_agree, min_band, tears, lines, live, n_slots, ssym, scol, cy);
+}
+
+// S1 with strips. strip_width: [STITCH_SMAX][128] u16, width(l, j) of the call's axis and S (build_tables). strips [rows][S][4]
+// {a_j, b_j, s_j, f_j}: a_j = b_j = -1 for a strip that is not located, s_j = its resolved split, -1 in a non-candidate;
+// strip_lines [rows][S][L] u16. Everything else as stitch_pairs_body, whose operand selection and carry hand-over this repeats.
+constexpr int STITCH_SMAX = 8;
+__device__ __forceinline__ uint32_t stitch_strip(int axis, uint32_t across, uint32_t S) 
+{
+	return axis == 0 ? across * S / (uint32_t)DIM_X : across * S / (uint32_t)DIM_Y;   // (divisions by constants)
+}
+
+template <bool CARRY>
+__device__ __forceinline__ void stitch_pairs_strips_body(const uint8_t* __restrict__ symbols, const uint8_t* __restrict__ colors, int n,
+                                                         const int* __restrict__ status, int stride, const uint8_t* __restrict__ line_tab,
+                                                         const uint16_t* __restrict__ strip_width, int axis, int S, int min_agree, int min_band,
+                                                         int32_t* __restrict__ tears, uint16_t* __restrict__ lines, int32_t* __restrict__ strips,
+                                                         uint16_t* __restrict__ strip_lines, uint32_t* __restrict__ live, int* __restrict__ n_slots,
+                                                         uint8_t* __restrict__ ssym, uint8_t* __restrict__ scol, const StitchCarry cy)
+{
+	const int k = blockIdx.x;
+	constexpr int W = NCELLS / 4;
+	constexpr uint32_t CM = 0x01010101u * (uint32_t)(NCOLORS - 1);
+	const int L = stitch_lines(axis);
+	const uint32_t *s0, *c0, *s1, *c1;
+	bool usable;
+	if constexpr (CARRY) {
+		if (k >= n) return;
+		s1 = reinterpret_cast<const uint32_t*>(symbols + (size_t)k * NCELLS);
+		c1 = reinterpret_cast<const uint32_t*>(colors + (size_t)k * NCELLS);
+		const bool later_usable = !status || status[(size_t)k * stride] > 0;
+		if (k == n - 1) {   // the next call's carry, into the slot nobody reads in this call
+			uint32_t* ns = reinterpret_cast<uint32_t*>(cy.symbols + (size_t)(cy.cur ^ 1) * SS_CELLS);
+			uint32_t* nc = reinterpret_cast<uint32_t*>(cy.colors + (size_t)(cy.cur ^ 1) * SS_CELLS);
+			for (int w = threadIdx.x; w < W; w += 256) { ns[w] = s1[w]; nc[w] = c1[w]; }
+			if (threadIdx.x == 0) cy.usable[cy.cur ^ 1] = later_usable ? 1u : 0u;
+		}
+		if (k == 0) {
+			if (!cy.usable[cy.cur]) {   // nothing carried, or a capture whose extraction failed: a non-candidate without counts
+				if (threadIdx.x < L) lines[threadIdx.x] = 0;
+				for (int e = threadIdx.x; e < S * L; e += 256) strip_lines[e] = 0;
+				if (threadIdx.x < S) {
+					int32_t* r = strips + (size_t)threadIdx.x * 4;
+					r[0] = r[1] = r[2] = -1; r[3] = 0;
+				}
+				if (threadIdx.x == 0) {
+					tears[0] = tears[1] = tears[2] = -1; tears[3] = 0;
+					live[0] = live[1] = 0u;
+				}
+				return;
+			}
+			s0 = reinterpret_cast<const uint32_t*>(cy.symbols + (size_t)cy.cur * SS_CELLS);
+			c0 = reinterpret_cast<const uint32_t*>(cy.colors + (size_t)cy.cur * SS_CELLS);
+			usable = later_usable;
+		} else {
+			s0 = s1 - W; c0 = c1 - W;
+			usable = later_usable && (!status || status[(size_t)(k - 1) * stride] > 0);
+		}
+	} else {
+		if (k + 1 >= n) return;
+		s0 = reinterpret_cast<const uint32_t*>(symbols + (size_t)k * NCELLS);
+		c0 = reinterpret_cast<const uint32_t*>(colors + (size_t)k * NCELLS);
+		s1 = s0 + W; c1 = c0 + W;
+		usable = !status || (status[(size_t)k * stride] > 0 && status[(size_t)(k + 1) * stride] > 0);
+	}
+	__shared__ uint32_t s_cnt[STITCH_SMAX * 128];   // [strip][line]
+	__shared__ int s_a[STITCH_SMAX], s_b[STITCH_SMAX], s_f[STITCH_SMAX], s_split[STITCH_SMAX];
+	__shared__ int s_cand;
+	for (int e = threadIdx.x; e < STITCH_SMAX * 128; e += 256) s_cnt[e] = 0;
+	__syncthreads();
+	const uint32_t* lt = reinterpret_cast<const uint32_t*>(line_tab + (size_t)axis * NCELLS);
+	const uint32_t* at = reinterpret_cast<const uint32_t*>(line_tab + (size_t)(axis ^ 1) * NCELLS);   // the other axis' row: across(i)
+	const uint32_t uS = (uint32_t)S;
+	for (int w = threadIdx.x; w < W; w += 256) {
+		const uint32_t x = ((s0[w] ^ s1[w]) & 0x0F0F0F0Fu) | ((c0[w] ^ c1[w]) & CM);
+		const uint32_t ids = lt[w], ac = at[w];
+		const uint32_t e0 = (x & 0xFFu) == 0u, e1 = (x & 0xFF00u) == 0u, e2 = (x & 0xFF0000u) == 0u, e3 = (x >> 24) == 0u;
+		const uint32_t j0 = stitch_strip(axis, ac & 0xFFu, uS), j1 = stitch_strip(axis, (ac >> 8) & 0xFFu, uS);
+		const uint32_t j2 = stitch_strip(axis, (ac >> 16) & 0xFFu, uS), j3 = stitch_strip(axis, ac >> 24, uS);
+		if (ids == (ids & 0xFFu) * 0x01010101u && j0 == j1 && j0 == j2 && j0 == j3) {   // the four cells share line and strip
+			const uint32_t c = e0 + e1 + e2 + e3;
+			if (c) atomicAdd(&s_cnt[j0 * 128u + (ids & 0xFFu)], c);
+		} else {
+			if (e0) atomicAdd(&s_cnt[j0 * 128u + (ids & 0xFFu)], 1u);
+			if (e1) atomicAdd(&s_cnt[j1 * 128u + ((ids >> 8) & 0xFFu)], 1u);
+			if (e2) atomicAdd(&s_cnt[j2 * 128u + ((ids >> 16) & 0xFFu)], 1u);
+			if (e3) atomicAdd(&s_cnt[j3 * 128u + (ids >> 24)], 1u);
+		}
+	}
+	__syncthreads();
+	if (threadIdx.x < 64) {
+		const int lane = threadIdx.x;
+		uint32_t tot[2] = {0u, 0u};
+		for (int j = 0; j < S; ++j) {   // (S is the same in every lane: the ballots see the whole wavefront)
+			bool fl[2];
+#pragma unroll
+			for (int h = 0; h < 2; ++h) {
+				const int l = lane + 64 * h;
+				const uint32_t c = l < L ? s_cnt[j * 128 + l] : 0u;
+				const uint32_t wd = l < L ? strip_width[j * 128 + l] : 0u;
+				fl[h] = l < L && (unsigned long long)c * 1000ull >= (unsigned long long)min_agree * (unsigned long long)wd;
+				if (l < L) strip_lines[((size_t)k * S + j) * L + l] = (uint16_t)c;
+				tot[h] += c;
+			}
+			const unsigned long long lo = __ballot(fl[0]), hi = __ballot(fl[1]);
+			if (lane == 0) {
+				const int f = (int)__popcll(lo) + (int)__popcll(hi);
+				int a = -1, b = -1;
+				if (f >= 1) {
+					const int lowest = lo ? __ffsll((long long)lo) - 1 : 64 + __ffsll((long long)hi) - 1;
+					const int highest = hi ? 127 - __clzll((long long)hi) : 63 - __clzll((long long)lo);
+					const int bb = highest + 1;
+					if (bb - lowest >= min_band && 4 * f >= 3 * (bb - lowest)) { a = lowest; b = bb; }
+				}
+				s_a[j] = a; s_b[j] = b; s_f[j] = f;
+			}
+		}
+#pragma unroll
+		for (int h = 0; h < 2; ++h) {
+			const int l = lane + 64 * h;
+			if (l < L) lines[(size_t)k * L + l] = (uint16_t)tot[h];
+		}
+		if (lane == 0) {
+			int located = 0, fsum = 0, amin = L, bmax = 0;
+			bool partial = false;
+			for (int j = 0; j < S; ++j) {
+				fsum += s_f[j];
+				if (s_a[j] < 0) continue;
+				++located;
+				amin = min(amin, s_a[j]); bmax = max(bmax, s_b[j]);
+				partial = partial || s_a[j] > 0 || s_b[j] < L;
+			}
+			const bool cand = usable && 2 * located >= S && partial;
+			for (int j = 0; j < S; ++j) {
+				int sj = -1;
+				if (cand) {
+					int from = j;   // the nearest located strip by index, the lower one on a tie
+					for (int d = 0; d < S; ++d) {
+						if (j - d >= 0 && s_a[j - d] >= 0) { from = j - d; break; }
+						if (j + d < S && s_a[j + d] >= 0) { from = j + d; break; }
+					}
+					sj = (s_a[from] + s_b[from]) >> 1;
+				}
+				s_split[j] = sj;
+				int32_t* r = strips + ((size_t)k * S + j) * 4;
+				r[0] = s_a[j]; r[1] = s_b[j]; r[2] = sj; r[3] = s_f[j];
+			}
+			int32_t* t = tears + (size_t)k * 4;
+			t[0] = cand ? amin : -1; t[1] = cand ? bmax : -1; t[2] = cand ? s_split[S >> 1] : -1; t[3] = fsum;
+			live[2 * k] = live[2 * k + 1] = cand ? 1u : 0u;
+			if (cand) atomicMax(n_slots, 2 * k + 2);
+			s_cand = cand ? 1 : 0;
+		}
+	}
+	__syncthreads();
+	if (!s_cand) return;
+	uint32_t* os0 = reinterpret_cast<uint32_t*>(ssym + (size_t)(2 * k) * NCELLS);
+	uint32_t* oc0 = reinterpret_cast<uint32_t*>(scol + (size_t)(2 * k) * NCELLS);
+	uint32_t *os1 = os0 + W, *oc1 = oc0 + W;
+	for (int w = threadIdx.x; w < W; w += 256) {
+		const uint32_t ids = lt[w], ac = at[w];
+		// bytes whose line lies below their strip's split: direction 0 takes them from capture k + 1, direction 1 from capture k
+		const uint32_t m = ((int)(ids & 0xFFu) < s_split[stitch_strip(axis, ac & 0xFFu, uS)] ? 0xFFu : 0u) |
+		                   ((int)((ids >> 8) & 0xFFu) < s_split[stitch_strip(axis, (ac >> 8) & 0xFFu, uS)] ? 0xFF00u : 0u) |
+		                   ((int)((ids >> 16) & 0xFFu) < s_split[stitch_strip(axis, (ac >> 16) & 0xFFu, uS)] ? 0xFF0000u : 0u) |
+		                   ((int)(ids >> 24) < s_split[stitch_strip(axis, ac >> 24, uS)] ? 0xFF000000u : 0u);
+		const uint32_t a0 = s0[w], a1 = s1[w], b0 = c0[w], b1 = c1[w];
+		os0[w] = (a1 & m) | (a0 & ~m);
+		os1[w] = (a0 & m) | (a1 & ~m);
+		oc0[w] = (b1 & m) | (b0 & ~m);
+		oc1[w] = (b0 & m) | (b1 & ~m);
+	}
+}
+
+__global__ __launch_bounds__(256) void k_stitch_pairs_strips(const uint8_t* __restrict__ symbols, const uint8_t* __restrict__ colors, int n,
+                                                             const int* __restrict__ status, int stride, const uint8_t* __restrict__ line_tab,
+                                                             const uint16_t* __restrict__ strip_width, int axis, int S, int min_agree, int min_band,
+                                                             int32_t* __restrict__ tears, uint16_t* __restrict__ lines, int32_t* __restrict__ strips,
+                                                             uint16_t* __restrict__ strip_lines, uint32_t* __restrict__ live, int* __restrict__ n_slots,
+                                                             uint8_t* __restrict__ ssym, uint8_t* __restrict__ scol)
+{
+	stitch_pairs_strips_body<false>(symbols, colors, n, status, stride, line_tab, strip_width, axis, S, min_agree, min_band, tears, lines, strips,
+	                                strip_lines, live, n_slots, ssym, scol, StitchCarry{});
+}
+
+__global__ __launch_bounds__(256) void k_stitch_pairs_strips_stream(const uint8_t* __restrict__ symbols, const uint8_t* __restrict__ colors, int n,
+                                                                    const int* __restrict__ status, int stride, const uint8_t* __restrict__ line_tab,
+                                                                    const uint16_t* __restrict__ strip_width, int axis, int S, int min_agree,
+                                                                    int min_band, int32_t* __restrict__ tears, uint16_t* __restrict__ lines,
+                                                                    int32_t* __restrict__ strips, uint16_t* __restrict__ strip_lines,
+                                                                    uint32_t* __restrict__ live, int* __restrict__ n_slots, uint8_t* __restrict__ ssym,
+                                                                    uint8_t* __restrict__ scol, const StitchCarry cy)
+{
+	stitch_pairs_strips_body<true>(symbols, colors, n, status, stride, line_tab, strip_width, axis, S, min_agree, min_band, tears, lines, strips,
+	                               strip_lines, live, n_slots, ssym, scol, cy);
 }
 
 // S2: slot blockIdx.x of 2 (n - 1). Live: the aligned_stream bookkeeping over the slot's block flags, the symbol blocks then the colour

@@ -25,6 +25,7 @@ TAP_SCAN_PATH = 14
 TAP_GROUP_COLOUR_MARGIN, TAP_GROUP_COLOUR_WEIGHTS = 15, 16   # the colour vote of the last combined batch (set_group_colour_vote / set_stream_colour_vote)
 TAP_STREAM_CARRY_WEIGHTS = 17   # the carried weights of the open group's members after a stream call with set_stream_colour_vote on
 TAP_STITCH_CELLS, TAP_STITCH_LINES = 18, 19   # the stitching of the last stitched batch (decode_batch_stitched): n = its captures
+TAP_STITCH_STRIPS, TAP_STITCH_STRIP_LINES = 22, 23   # the strips of the last stitched batch (set_stitch_strips above 1): tap_stitch_strips
 TAP_STITCH_CARRY = 20   # the capture the stitched-stream calls carry (decode_batch_stitched_stream): tap_stitch_carry
 TAP_CELL_MEANS = 21   # the threshold kernel's undrifted cell means, r | g << 8 | b << 16 by grid slot (row * DIM_X + column)
 # CIMBAR_HIP_COLOUR_MARGIN_SUGGESTED (include/cimbar_hip.h): the colour erasure threshold chosen on rendered frames (DESIGN_WIDENING.md)
@@ -56,6 +57,7 @@ EXPORTS = (
     "cimbar_hip_deliver_chunks", "cimbar_hip_delivery_reset", "cimbar_hip_delivery_stats",
     "cimbar_hip_decode_batch_stitched", "cimbar_hip_scan_extract_decode_batch_stitched_fmt",
     "cimbar_hip_decode_batch_stitched_stream", "cimbar_hip_scan_extract_decode_batch_stitched_stream_fmt", "cimbar_hip_stitch_stream_reset",
+    "cimbar_hip_set_stitch_strips", "cimbar_hip_get_stitch_strips",
 )
 # cimbar_hip_deliver_chunks' flags
 DELIVER_DEDUP, DELIVER_REMEMBER, DELIVER_DROP_EMPTY = 1, 2, 4
@@ -183,6 +185,11 @@ def load_library(path=None):
     lib.cimbar_hip_scan_extract_decode_batch_stitched_stream_fmt.restype = i64
     lib.cimbar_hip_stitch_stream_reset.argtypes = [vp]
     lib.cimbar_hip_stitch_stream_reset.restype = i32
+    if hasattr(lib, "cimbar_hip_set_stitch_strips"):   # (CIMBAR_HIP_LIB may name an older build for an A/B run)
+        lib.cimbar_hip_set_stitch_strips.argtypes = [vp, i32]
+        lib.cimbar_hip_set_stitch_strips.restype = i32
+        lib.cimbar_hip_get_stitch_strips.argtypes = [vp, ctypes.POINTER(i32)]
+        lib.cimbar_hip_get_stitch_strips.restype = i32
     lib.cimbar_hip_combine_stream_reset.argtypes = [vp]
     lib.cimbar_hip_combine_stream_reset.restype = i32
     lib.cimbar_hip_auto_create.argtypes = [i32, vp, i32, ctypes.POINTER(vp)]
@@ -669,6 +676,30 @@ class HipDecoder:
     def stitch_stream_reset(self):
         """forget the capture the stitched-stream calls carry: the next one's row 0 has no partner"""
         self._check(self._lib.cimbar_hip_stitch_stream_reset(self._ctx), "cimbar_hip_stitch_stream_reset")
+
+    def set_stitch_strips(self, strips):
+        """cimbar_hip_set_stitch_strips: the stitched calls find the shared band in `strips` strips across the lines (1 .. 8; 1, the
+        setting after create, is whole lines). Read by every stitched call when it is made."""
+        self._check(self._lib.cimbar_hip_set_stitch_strips(self._ctx, int(strips)), "cimbar_hip_set_stitch_strips")
+
+    def get_stitch_strips(self):
+        a = ctypes.c_int32(0)
+        self._check(self._lib.cimbar_hip_get_stitch_strips(self._ctx, ctypes.byref(a)), "cimbar_hip_get_stitch_strips")
+        return int(a.value)
+
+    def tap_stitch_strips(self, n, strips, stream=False):
+        """TAP_STITCH_STRIPS of the last stitched batch of n captures, which ran with `strips` above 1: (n - 1, strips, 4) int32
+        {a_j, b_j, s_j, f_j}; stream=True: (n, strips, 4)"""
+        out = np.zeros((n if stream else max(n - 1, 0), int(strips), 4), np.int32)
+        self._check(self._lib.cimbar_hip_tap(self._ctx, TAP_STITCH_STRIPS, out.ctypes.data, out.nbytes), "cimbar_hip_tap")
+        return out
+
+    def tap_stitch_strip_lines(self, n, strips, axis=0, stream=False):
+        """TAP_STITCH_STRIP_LINES of that batch on `axis`: (n - 1, strips, L) uint16, the agreeing cells of every line in every strip;
+        stream=True: (n, strips, L)"""
+        out = np.zeros((n if stream else max(n - 1, 0), int(strips), self.geo.DIM_Y if axis == 0 else self.geo.DIM_X), np.uint16)
+        self._check(self._lib.cimbar_hip_tap(self._ctx, TAP_STITCH_STRIP_LINES, out.ctypes.data, out.nbytes), "cimbar_hip_tap")
+        return out
 
     def tap_stitch_carry(self):
         """TAP_STITCH_CARRY: (symbols (NCELLS,), colours (NCELLS,)) uint8 of the carried capture; raises while nothing is carried"""
