@@ -753,7 +753,13 @@ enum {
 	 * rows = n - 1, after a stitched-stream call n. CIMBAR_HIP_TAP_STITCH_LINES of such a batch is cnt(l) = the sum of cnt(l, j) over j. */
 	CIMBAR_HIP_TAP_STITCH_STRIPS = 22,      /* rows * S * 4 int32: {a_j, b_j, s_j, f_j}; a_j = b_j = -1 for a strip that is not located, s_j = the
 	                                           resolved split, -1 in a pair that is no candidate */
-	CIMBAR_HIP_TAP_STITCH_STRIP_LINES = 23  /* rows * S * L u16  : cnt(l, j), the agreeing cells of line l in strip j */
+	CIMBAR_HIP_TAP_STITCH_STRIP_LINES = 23, /* rows * S * L u16  : cnt(l, j), the agreeing cells of line l in strip j */
+	/* what the stage in front of the anchor search left for the captures CIMBAR_HIP_TAP_SCAN_PATH describes (n = the captures of the last
+	 * search launch, w x h their size; CIMBAR_HIP_EINVAL before any search). Read them before the next call of the extractor stage:
+	 * cimbar_hip_scan_preprocess runs no search, but writes its own histograms and thresholds where these two taps read */
+	CIMBAR_HIP_TAP_SCAN_GRAY = 24,      /* n * w * h bytes     : the blurred gray plane the search read, row-major, capture after capture */
+	CIMBAR_HIP_TAP_SCAN_HIST = 25,      /* n * 256 u32         : the histogram of each plane */
+	CIMBAR_HIP_TAP_SCAN_THRESHOLD = 26  /* n int32             : the Otsu threshold of each histogram; the search reads gray > threshold */
 };
 int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_bytes);
 

@@ -79,6 +79,7 @@ struct cimbar_hip_ctx {
 	uint64_t tile_hashes[16] = {};   // as computed at create (also in c_tile)
 	int last_n = 0;
 	int scan_n = 0;                             // captures of the last anchor search (CIMBAR_HIP_TAP_SCAN_PATH describes it)
+	unsigned scan_w = 0, scan_h = 0;            // ... and their size (CIMBAR_HIP_TAP_SCAN_GRAY: scan_n planes of scan_w x scan_h in d_ex_gray)
 	DevBuf<uint8_t> d_rgb;            // staging for host-resident input
 	// the intermediates of a batch (grown on demand). A context has `pipe_depth` sets of them and as many streams: the pipelined entry point steps to the
 	// next set with every batch, so that several batches are in flight at once; every other call uses the set the newest batch used (cur())
@@ -1839,6 +1840,8 @@ int enqueue_scan(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_in, unsig
 	                   &ctx->d_scan_res[0].status, sizeof(ScanResult) / sizeof(int), n, ctx->d_ex_minv);
 	HIPCHK(hipGetLastError());
 	ctx->scan_n = n;
+	ctx->scan_w = width;
+	ctx->scan_h = height;
 	return 0;
 }
 
@@ -2194,6 +2197,18 @@ int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_byte
 		HIPCHK(hipMemcpy2D(status.data(), sizeof(int), &ctx->d_scan_res[0].status, sizeof(ScanResult), sizeof(int), m, hipMemcpyDeviceToHost));
 		for (size_t k = 0; k < m; ++k) ((int32_t*)out)[k] = status[k] < 0 ? 2 : (ovf[k] ? 1 : 0);
 		return (int64_t)(m * sizeof(int32_t));
+	}
+	if (what == CIMBAR_HIP_TAP_SCAN_GRAY || what == CIMBAR_HIP_TAP_SCAN_HIST || what == CIMBAR_HIP_TAP_SCAN_THRESHOLD) {
+		// what the stage in front of that search left: blurred gray planes, their histograms, the Otsu thresholds
+		if (ctx->scan_n <= 0) { ctx->err = "tap: no capture has been searched for anchors on this context yet"; return CIMBAR_HIP_EINVAL; }
+		const size_t m = (size_t)ctx->scan_n;
+		const void* src = what == CIMBAR_HIP_TAP_SCAN_GRAY ? (const void*)ctx->d_ex_gray : (what == CIMBAR_HIP_TAP_SCAN_HIST ? (const void*)ctx->d_ex_hist : (const void*)ctx->d_ex_thr);
+		const size_t bytes = what == CIMBAR_HIP_TAP_SCAN_GRAY ? m * ctx->scan_w * ctx->scan_h : (what == CIMBAR_HIP_TAP_SCAN_HIST ? m * 256 * sizeof(uint32_t) : m * sizeof(int32_t));
+		if (out_bytes < bytes) { ctx->err = "tap: buffer too small"; return CIMBAR_HIP_EINVAL; }
+		HIPCHK(hipSetDevice(ctx->device));
+		HIPCHK(hipDeviceSynchronize());
+		HIPCHK(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
+		return (int64_t)bytes;
 	}
 	if (what == CIMBAR_HIP_TAP_STITCH_CARRY) {
 		// what the next stitched-stream call's row 0 is held against: the carried symbols, then the carried colours

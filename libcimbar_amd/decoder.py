@@ -28,6 +28,7 @@ TAP_STITCH_CELLS, TAP_STITCH_LINES = 18, 19   # the stitching of the last stitch
 TAP_STITCH_STRIPS, TAP_STITCH_STRIP_LINES = 22, 23   # the strips of the last stitched batch (set_stitch_strips above 1): tap_stitch_strips
 TAP_STITCH_CARRY = 20   # the capture the stitched-stream calls carry (decode_batch_stitched_stream): tap_stitch_carry
 TAP_CELL_MEANS = 21   # the threshold kernel's undrifted cell means, r | g << 8 | b << 16 by grid slot (row * DIM_X + column)
+TAP_SCAN_GRAY, TAP_SCAN_HIST, TAP_SCAN_THRESHOLD = 24, 25, 26   # what the stage in front of the last anchor search produced: tap_scan
 # CIMBAR_HIP_COLOUR_MARGIN_SUGGESTED (include/cimbar_hip.h): the colour erasure threshold chosen on rendered frames (DESIGN_WIDENING.md)
 COLOUR_MARGIN_SUGGESTED = 32512
 
@@ -706,6 +707,16 @@ class HipDecoder:
         out = np.zeros((2, self.geo.NCELLS), dtype=np.uint8)
         self._check(self._lib.cimbar_hip_tap(self._ctx, TAP_STITCH_CARRY, out.ctypes.data, out.nbytes), "cimbar_hip_tap")
         return out[0], out[1]
+
+    def tap_scan(self, n, w, h):
+        """TAP_SCAN_GRAY / _HIST / _THRESHOLD of the last anchor search, which ran on n captures of w x h: (gray (n, h, w) uint8, the blurred
+        gray planes; hist (n, 256) uint32; thr (n,) int32). Raises before any search"""
+        gray, hist, thr = np.zeros((n, h, w), np.uint8), np.zeros((n, 256), np.uint32), np.zeros((n,), np.int32)
+        for what, out in ((TAP_SCAN_GRAY, gray), (TAP_SCAN_HIST, hist), (TAP_SCAN_THRESHOLD, thr)):
+            got = self._check(self._lib.cimbar_hip_tap(self._ctx, what, out.ctypes.data, out.nbytes), "cimbar_hip_tap")
+            if got != out.nbytes:
+                raise ValueError(f"tap_scan: the last search ran on captures of another size or count ({got} bytes, not {out.nbytes})")
+        return gray, hist, thr
 
     def combine_stream_reset(self):
         """drop the open group and the stream's fixed min_agree_permille / max_group"""
