@@ -542,7 +542,34 @@ int64_t cimbar_hip_scan_extract_decode_batch(cimbar_hip_ctx* ctx, const uint8_t*
  * cimbard_scan_extract_decode(img, w, h, format, buf, size) is then
  *   cimbar_hip_scan_extract_decode_batch_fmt(ctx, img, w, h, format, 1, CIMBAR_HIP_MEM_HOST, 1, 2, chunks, &mask, &status, CIMBAR_HIP_MEM_HOST, NULL)
  * (upstream always sharpens on this path: `bool shouldPreprocess = true`, cimbar_recv_js.cpp:166) with status 0 -> return -3 and the chunks
- * whose mask bit is set packed front to back (escrow_buffer_writer); INTEGRATION.md has the wrapper. */
+ * whose mask bit is set packed front to back (escrow_buffer_writer); INTEGRATION.md has the wrapper.
+ *
+ * Capture formats of native receivers. Those four are what a browser hands over; cv::VideoCapture, V4L2 and the Android camera deliver others,
+ * which the reference's native front ends convert on the host first (cv::cvtColor(COLOR_BGR2RGB), recv.cpp:139). Five more values of `format`,
+ * each defined by the cvtColor code that builds the same RGB image, converted as loaded like the four above:
+ *   21    NV21: NV12 with every chroma pair stored (V, U); width * height * 3 / 2, even width and height             (cv::COLOR_YUV2RGB_NV21)
+ *   422   YUYV / YUY2: width * height * 2; a row is width / 2 groups (Y0, U, Y1, V); the (U, V) pair serves the two pixels of its group
+ *         and no other row; even width, any height                                                                   (cv::COLOR_YUV2RGB_YUY2)
+ *   4221  UYVY: the same with the group stored (U, Y0, V, Y1)                                                        (cv::COLOR_YUV2RGB_UYVY)
+ *   30    BGR8: width * height * 3, stored B, G, R                                                                   (cv::COLOR_BGR2RGB)
+ *   40    BGRA8: width * height * 4, stored B, G, R, A; the alpha byte is dropped                                    (cv::COLOR_BGRA2RGB)
+ * The YUV ones use the same fixed-point BT.601 arithmetic as 12 / 420 (OpenCV runs 4:2:2 through the code of 4:2:0). A width or height the layout
+ * cannot hold: CIMBAR_HIP_EDIM, cimbar_hip_capture_bytes 0. Every value that is none of the nine stays RGB8. Every entry point that takes `format`
+ * takes them (the _fmt calls here, the combined / stitched / stream _fmt calls, cimbar_hip_auto_scan_extract_decode_batch_fmt, the undistort
+ * calls); libcimbar_recv_hip.so, being the reference's interface, keeps the reference's meaning (anything but 4 / 12 / 420 is RGB8).
+ * Not covered: row pitch / plane strides of padded camera and video-decoder surfaces (captures are densely packed), Bayer raw, 10-bit formats,
+ * the ingest library, cimbar_hip_decode_frame (RGB8 with a stride). */
+enum cimbar_hip_format {
+	CIMBAR_HIP_FMT_RGB = 3,
+	CIMBAR_HIP_FMT_RGBA = 4,
+	CIMBAR_HIP_FMT_NV12 = 12,
+	CIMBAR_HIP_FMT_I420 = 420,       /* as cv::COLOR_YUV420p2RGB reads it: see above */
+	CIMBAR_HIP_FMT_NV21 = 21,
+	CIMBAR_HIP_FMT_YUYV = 422,
+	CIMBAR_HIP_FMT_UYVY = 4221,
+	CIMBAR_HIP_FMT_BGR = 30,
+	CIMBAR_HIP_FMT_BGRA = 40
+};
 size_t cimbar_hip_capture_bytes(unsigned width, unsigned height, int format);
 int cimbar_hip_scan_preprocess_fmt(cimbar_hip_ctx* ctx, const uint8_t* img, unsigned width, unsigned height, int format, int n, int img_mem,
                                    uint8_t* binary, int* thresholds, int out_mem, void* hip_stream);

@@ -361,7 +361,7 @@ int64_t cimbar_hip_scan_extract_decode_batch(cimbar_hip_ctx* ctx, const uint8_t*
 size_t cimbar_hip_capture_bytes(unsigned width, unsigned height, int format)
 {
 	const int fmt = m68::capture_format(format);
-	if ((fmt == m68::FMT_NV12 || fmt == m68::FMT_I420) && ((width | height) & 1u)) return 0;
+	if (!m68::capture_dims_ok(width, height, fmt)) return 0;
 	return m68::capture_bytes(width, height, fmt);
 }
 

@@ -334,7 +334,7 @@ int64_t cimbar_hip_auto_scan_extract_decode_batch_fmt(cimbar_hip_auto* a, const 
 		if (idx[i] < 0 || dup) { a->err = std::string(who) + ": `order` must list distinct modes the object was created with"; return CIMBAR_HIP_EINVAL; }
 	}
 	const int fmt = m68::capture_format(format <= 0 ? 3 : format);
-	if ((fmt == m68::FMT_NV12 || fmt == m68::FMT_I420) && ((width | height) & 1u)) { a->err = std::string(who) + ": a 4:2:0 capture (format 12 / 420) needs an even width and height"; return CIMBAR_HIP_EDIM; }
+	if (!m68::capture_dims_ok(width, height, fmt)) { a->err = std::string(who) + m68::CAPTURE_DIMS_MSG; return CIMBAR_HIP_EDIM; }
 	const size_t cbytes = cimbar_hip_capture_bytes(width, height, format <= 0 ? 3 : format);
 	if ((uint64_t)width * height * 4 >= (1ull << 33) || cbytes >= ((size_t)1 << 31)) { a->err = std::string(who) + ": captures of 2 GiB or more are not supported"; return CIMBAR_HIP_EDIM; }
 	AUTOCHK(hipSetDevice(a->device));

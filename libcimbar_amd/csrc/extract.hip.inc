@@ -22,12 +22,39 @@ __device__ __forceinline__ int refl101(int i, int n)
 // [assumed-OpenCV] color_yuv.simd.hpp, BT.601 in 20-bit fixed point: c = saturate_cast<uchar>((max(0, Y - 16) * CY + cuv) >> 20) with
 //   ruv = 2^19 + CVR (V - 128), guv = 2^19 + CVG (V - 128) + CUG (U - 128), buv = 2^19 + CUB (U - 128); one (U, V) per 2x2 pixels.
 constexpr int FMT_RGB = 3, FMT_RGBA = 4, FMT_NV12 = 12, FMT_I420 = 420;
+// ---- the formats of native receivers (no reference front end takes them; each is defined by the cv::cvtColor code that makes the same RGB image):
+//   21 = NV21 (Android): NV12 with the chroma pair stored (V, U) -> COLOR_YUV2RGB_NV21
+//   422 = YUYV / YUY2, 4221 = UYVY (UVC webcams, capture cards; V4L2): 2 bytes per pixel, a row is w/2 groups (Y0, U, Y1, V) / (U, Y0, V, Y1); one
+//     (U, V) pair serves the two pixels of its group and no other row -> COLOR_YUV2RGB_YUY2 / _UYVY. [assumed-OpenCV] color_yuv.simd.hpp runs 4:2:2
+//     through the same uvToRGBuv / yRGBuvToRGBA as 4:2:0, so yuv_terms / yuv_rgb below are its arithmetic too
+//   30 = BGR, 40 = BGRA (cv::VideoCapture, cv::imread) -> COLOR_BGR2RGB / COLOR_BGRA2RGB: a channel permutation
+constexpr int FMT_NV21 = 21, FMT_YUYV = 422, FMT_UYVY = 4221, FMT_BGR = 30, FMT_BGRA = 40;
+static_assert(FMT_RGB == CIMBAR_HIP_FMT_RGB && FMT_RGBA == CIMBAR_HIP_FMT_RGBA && FMT_NV12 == CIMBAR_HIP_FMT_NV12 && FMT_I420 == CIMBAR_HIP_FMT_I420 &&
+              FMT_NV21 == CIMBAR_HIP_FMT_NV21 && FMT_YUYV == CIMBAR_HIP_FMT_YUYV && FMT_UYVY == CIMBAR_HIP_FMT_UYVY && FMT_BGR == CIMBAR_HIP_FMT_BGR &&
+              FMT_BGRA == CIMBAR_HIP_FMT_BGRA, "the values named in cimbar_hip.h");
 constexpr int YUV_CY = 1220542, YUV_CUB = 2116026, YUV_CUG = -409993, YUV_CVG = -852492, YUV_CVR = 1673527, YUV_SHIFT = 20;
-__host__ __device__ inline int capture_format(int f) { return (f == FMT_RGBA || f == FMT_NV12 || f == FMT_I420) ? f : FMT_RGB; }
+__host__ __device__ constexpr bool fmt_is_sp420(int f) { return f == FMT_NV12 || f == FMT_NV21; }            // Y plane + one plane of chroma pairs
+__host__ __device__ constexpr bool fmt_is_420(int f) { return fmt_is_sp420(f) || f == FMT_I420; }
+__host__ __device__ constexpr bool fmt_is_422(int f) { return f == FMT_YUYV || f == FMT_UYVY; }
+__host__ __device__ constexpr bool fmt_is_bgr(int f) { return f == FMT_BGR || f == FMT_BGRA; }              // stored B, G, R(, A)
+__host__ __device__ constexpr bool fmt_is_3byte(int f) { return f == FMT_RGB || f == FMT_BGR; }
+__host__ __device__ constexpr bool fmt_is_4byte(int f) { return f == FMT_RGBA || f == FMT_BGRA; }
+__host__ __device__ inline int capture_format(int f) { return (fmt_is_4byte(f) || fmt_is_420(f) || fmt_is_422(f) || f == FMT_BGR) ? f : FMT_RGB; }
 __host__ __device__ inline size_t capture_bytes(size_t w, size_t h, int fmt)
 {
-	return (fmt == FMT_NV12 || fmt == FMT_I420) ? w * h * 3 / 2 : w * h * (fmt == FMT_RGBA ? 4 : 3);
+	return fmt_is_420(fmt) ? w * h * 3 / 2 : w * h * (fmt_is_422(fmt) ? 2 : (fmt_is_4byte(fmt) ? 4 : 3));
 }
+// what a layout cannot hold: 4:2:0 an odd width or height, 4:2:2 an odd width (cv::cvtColor asserts)
+inline bool capture_dims_ok(unsigned w, unsigned h, int fmt) { return !((fmt_is_420(fmt) && ((w | h) & 1u)) || (fmt_is_422(fmt) && (w & 1u))); }
+constexpr const char* CAPTURE_DIMS_MSG = ": a 4:2:0 capture (format 12 / 21 / 420) needs an even width and height, a 4:2:2 capture (format 422 / 4221) an even width";
+// one 4:2:2 group (two pixels, four bytes) as loaded: the lumas and the chroma pair
+template <bool UYVY> __device__ __forceinline__ void yuv422_group(uint32_t g, uint32_t& y0, uint32_t& y1, uint32_t& u, uint32_t& v)
+{
+	if (UYVY) { u = g & 0xFFu; y0 = (g >> 8) & 0xFFu; v = (g >> 16) & 0xFFu; y1 = g >> 24; }
+	else { y0 = g & 0xFFu; u = (g >> 8) & 0xFFu; y1 = (g >> 16) & 0xFFu; v = g >> 24; }
+}
+// B | G << 8 | R << 16 (| A << 24) -> R | G << 8 | B << 16: one v_perm_b32, the top byte cleared
+__device__ __forceinline__ uint32_t swap_rb(uint32_t p) { return __builtin_amdgcn_perm(0u, p, 0x0C000102u); }
 // the chroma terms of one (U, V) pair with the luma offset folded in: c = (max(Y, 16) * CY + k.c) >> 20, then saturate
 struct YuvTerms { int r, g, b; };
 __device__ __forceinline__ YuvTerms yuv_terms(uint32_t u, uint32_t v)
@@ -48,22 +75,40 @@ __device__ __forceinline__ uint32_t yuv_rgb(uint32_t Y, const YuvTerms& k)
 	const uint32_t R = (uint32_t)(r < 0 ? 0 : (r > 255 ? 255 : r)), G = (uint32_t)(g < 0 ? 0 : (g > 255 ? 255 : g)), B = (uint32_t)(b < 0 ? 0 : (b > 255 ? 255 : b));
 	return R | (G << 8) | (B << 16);
 }
+// A pixel is R | G << 8 | B << 16 and nothing above -- but the compiler builds the two low bytes of yuv_rgb's result with v_ashr_pk_u8_i32, shift +
+// saturate + pack in one gfx950 instruction, and then ORs the result on as if its upper half were zero. It is not: in k_convert_roi R and G of every
+// fourth pixel came out wrong. The kernels that read a pixel through byte selects never see it; code that shifts a pixel into its neighbour makes
+// the value opaque and masks it, with this.
+__device__ __forceinline__ uint32_t px_clean(uint32_t v) { asm volatile("" : "+v"(v)); return v & 0xFFFFFFu; }
 // one pixel of a capture as R | G << 8 | B << 16, any format (the general path: borders, odd widths, the large blurs)
 __device__ __forceinline__ uint32_t capture_px(const uint8_t* __restrict__ src, int sw, int sh, int fmt, int x, int y)
 {
-	if (fmt == FMT_RGB) { const uint8_t* p = src + ((size_t)y * sw + x) * 3; return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16); }
-	if (fmt == FMT_RGBA) { uint32_t v; __builtin_memcpy(&v, src + ((size_t)y * sw + x) * 4, 4); return v & 0xFFFFFFu; }
+	if (fmt_is_3byte(fmt)) {
+		const uint8_t* p = src + ((size_t)y * sw + x) * 3;
+		const uint32_t c0 = p[0], c2 = p[2];
+		return (fmt == FMT_BGR ? c2 : c0) | ((uint32_t)p[1] << 8) | ((fmt == FMT_BGR ? c0 : c2) << 16);
+	}
+	if (fmt_is_4byte(fmt)) { uint32_t v; __builtin_memcpy(&v, src + ((size_t)y * sw + x) * 4, 4); return fmt == FMT_BGRA ? swap_rb(v) : v & 0xFFFFFFu; }
+	if (fmt_is_422(fmt)) {
+		uint32_t g, y0, y1, u, v;
+		__builtin_memcpy(&g, src + ((size_t)y * sw + (x & ~1)) * 2, 4);
+		if (fmt == FMT_UYVY) yuv422_group<true>(g, y0, y1, u, v); else yuv422_group<false>(g, y0, y1, u, v);
+		return yuv_rgb((x & 1) ? y1 : y0, yuv_terms(u, v));
+	}
 	const size_t plane = (size_t)sw * sh;
 	const uint32_t Y = src[(size_t)y * sw + x];
 	uint32_t u, v;
-	if (fmt == FMT_NV12) { const uint8_t* p = src + plane + (size_t)(y >> 1) * sw + (x & ~1); u = p[0]; v = p[1]; }
+	if (fmt_is_sp420(fmt)) { const uint8_t* p = src + plane + (size_t)(y >> 1) * sw + (x & ~1); const int iu = fmt == FMT_NV21; u = p[iu]; v = p[iu ^ 1]; }
 	else { const size_t ci = (size_t)(y >> 1) * (sw >> 1) + (x >> 1); v = src[plane + ci]; u = src[plane + (plane >> 2) + ci]; }
 	return yuv_rgb(Y, yuv_terms(u, v));
 }
-// cvtColor(RGB2GRAY) of a packed pixel, left as gray16_T leaves it (gray = byte 2 of the result)
+// cvtColor(RGB2GRAY) of a packed pixel, left as gray16_T leaves it (gray = byte 2 of the result). BGR: the pixel as a B, G, R(, A) capture stores it
+// -- the R and B weights change places in the constants, the instructions stay
+template <bool BGR = false>
 __device__ __forceinline__ uint32_t gray_T_of(uint32_t rgb)
 {
-	constexpr uint32_t LO2 = 140u | (70u << 8) | (46u << 16), HI = 76u | (150u << 8) | (29u << 16);
+	constexpr uint32_t LO2 = BGR ? 46u | (70u << 8) | (140u << 16) : 140u | (70u << 8) | (46u << 16);
+	constexpr uint32_t HI = BGR ? 29u | (150u << 8) | (76u << 16) : 76u | (150u << 8) | (29u << 16);
 	return (__builtin_amdgcn_udot4(rgb, HI, 0u, false) << 8) + __builtin_amdgcn_udot4(rgb, LO2, 32768u, false);
 }
 
@@ -83,7 +128,7 @@ template <int R> __device__ __forceinline__ constexpr int gauss_w(int i)
 	     : R == 4 ? (i == 4 ? 60 : ((i == 3 || i == 5) ? 51 : ((i == 2 || i == 6) ? 30 : ((i == 1 || i == 7) ? 13 : 4))))
 	              : K17[i <= 8 ? i : 16 - i];
 }
-// RGB3: the capture is RGB8 and is staged as described above; otherwise (RGBA / NV12 / 4:2:0 planes, `fmt`) the gray tile is built pixel by
+// RGB3: the capture is RGB8 and is staged as described above; otherwise (every other format, `fmt`) the gray tile is built pixel by
 // pixel through capture_px -- this kernel is only the general path (odd widths, the 9x9 / 17x17 blurs), the streaming one below is the fast one.
 template <int R, bool RGB3>
 __global__ __launch_bounds__(256) void k_scan_gray_blur(const uint8_t* __restrict__ rgb, int w, int h, int fmt, uint8_t* __restrict__ out,
@@ -212,21 +257,29 @@ __device__ __forceinline__ void load48(const uint8_t* __restrict__ p, uint32_t d
 // byte-aligned gray values gray16_T produces for RGB8.
 //   RGB8  3 x dwordx4 (48 bytes)                        RGBA  4 x dwordx4; one v_dot4 pair per pixel, the alpha byte meets a zero coefficient
 //   NV12  dwordx4 of Y + dwordx4 of the (U, V) row y/2  4:2:0 planes  dwordx4 of Y + dwordx2 from each chroma plane's row y/2
-// (widths are multiples of 16 and frames start 16-byte aligned on this path, so every one of those loads is naturally aligned)
-template <int FMT> struct RowRegs { static constexpr int N = FMT == FMT_RGB ? 12 : (FMT == FMT_RGBA ? 16 : 8); };
+//   NV21  NV12's loads (the pair's bytes change places when it is taken apart)     BGR / BGRA  the RGB / RGBA loads (the weights change places)
+//   YUYV / UYVY  2 x dwordx4: the lane's 16 pixels are 32 contiguous bytes, one dword = one chroma pair and its two lumas
+// (widths are multiples of 16 and frames start 16-byte aligned on this path, so every one of those loads is naturally aligned: 4:2:2 rows are 2w
+// and frames 2wh bytes, multiples of 32)
+template <int FMT> struct RowRegs { static constexpr int N = fmt_is_3byte(FMT) ? 12 : (fmt_is_4byte(FMT) ? 16 : 8); };
 template <int FMT>
 __device__ __forceinline__ void capture_row_load(const uint8_t* __restrict__ frame, int w, int h, int y, int cl, uint32_t (&d)[RowRegs<FMT>::N])
 {
-	if constexpr (FMT == FMT_RGB) load48(frame + ((size_t)y * w + (size_t)cl * 16) * 3, d);
-	else if constexpr (FMT == FMT_RGBA) {
+	if constexpr (fmt_is_3byte(FMT)) load48(frame + ((size_t)y * w + (size_t)cl * 16) * 3, d);
+	else if constexpr (fmt_is_4byte(FMT)) {
 		const uint4* q = reinterpret_cast<const uint4*>(frame + ((size_t)y * w + (size_t)cl * 16) * 4);
 #pragma unroll
 		for (int k = 0; k < 4; ++k) { const uint4 a = q[k]; d[4 * k] = a.x; d[4 * k + 1] = a.y; d[4 * k + 2] = a.z; d[4 * k + 3] = a.w; }
+	} else if constexpr (fmt_is_422(FMT)) {
+		const uint4* q = reinterpret_cast<const uint4*>(frame + ((size_t)y * w + (size_t)cl * 16) * 2);
+		const uint4 a = q[0], b = q[1];
+		d[0] = a.x; d[1] = a.y; d[2] = a.z; d[3] = a.w;
+		d[4] = b.x; d[5] = b.y; d[6] = b.z; d[7] = b.w;
 	} else {
 		const size_t plane = (size_t)w * h;
 		const uint4 a = *reinterpret_cast<const uint4*>(frame + (size_t)y * w + (size_t)cl * 16);
 		d[0] = a.x; d[1] = a.y; d[2] = a.z; d[3] = a.w;
-		if constexpr (FMT == FMT_NV12) {
+		if constexpr (fmt_is_sp420(FMT)) {
 			const uint4 c = *reinterpret_cast<const uint4*>(frame + plane + (size_t)(y >> 1) * w + (size_t)cl * 16);
 			d[4] = c.x; d[5] = c.y; d[6] = c.z; d[7] = c.w;
 		} else {
@@ -239,16 +292,27 @@ __device__ __forceinline__ void capture_row_load(const uint8_t* __restrict__ fra
 template <int FMT>
 __device__ __forceinline__ void capture_row_gray_T(const uint32_t (&d)[RowRegs<FMT>::N], uint32_t T[16])
 {
-	if constexpr (FMT == FMT_RGB) gray16_T(d, T);
-	else if constexpr (FMT == FMT_RGBA) {
+	if constexpr (fmt_is_3byte(FMT)) gray_T<16, FMT == FMT_BGR>(d, T);
+	else if constexpr (fmt_is_4byte(FMT)) {
 #pragma unroll
-		for (int p = 0; p < 16; ++p) T[p] = gray_T_of(d[p]);
+		for (int p = 0; p < 16; ++p) T[p] = gray_T_of<FMT == FMT_BGRA>(d[p]);
+	} else if constexpr (fmt_is_422(FMT)) {
+#pragma unroll
+		for (int c = 0; c < 8; ++c) {   // group c: pixels 2c, 2c+1 and their chroma pair in one dword
+			uint32_t y0, y1, u, v;
+			yuv422_group<FMT == FMT_UYVY>(d[c], y0, y1, u, v);
+			const YuvTerms k = yuv_terms(u, v);
+			T[2 * c] = gray_T_of(yuv_rgb(y0, k));
+			T[2 * c + 1] = gray_T_of(yuv_rgb(y1, k));
+		}
 	} else {
 #pragma unroll
 		for (int c = 0; c < 8; ++c) {   // chroma sample c serves pixels 2c, 2c+1
 			uint32_t u, v;
-			if constexpr (FMT == FMT_NV12) { const uint32_t uv = d[4 + (c >> 1)] >> (16 * (c & 1)); u = uv & 0xFFu; v = (uv >> 8) & 0xFFu; }
-			else { v = (d[4 + (c >> 2)] >> (8 * (c & 3))) & 0xFFu; u = (d[6 + (c >> 2)] >> (8 * (c & 3))) & 0xFFu; }
+			if constexpr (fmt_is_sp420(FMT)) {
+				const uint32_t uv = d[4 + (c >> 1)] >> (16 * (c & 1)), b0 = uv & 0xFFu, b1 = (uv >> 8) & 0xFFu;
+				u = FMT == FMT_NV21 ? b1 : b0; v = FMT == FMT_NV21 ? b0 : b1;
+			} else { v = (d[4 + (c >> 2)] >> (8 * (c & 3))) & 0xFFu; u = (d[6 + (c >> 2)] >> (8 * (c & 3))) & 0xFFu; }
 			const YuvTerms k = yuv_terms(u, v);
 #pragma unroll
 			for (int q = 0; q < 2; ++q) {
@@ -396,27 +460,41 @@ __global__ __launch_bounds__(64) void k_scan_otsu(const uint32_t* __restrict__ h
 template <int FMT>
 __device__ __forceinline__ void capture_pair(const uint8_t* __restrict__ src, int sw, int sh, int sx, int sy, uint32_t& p0, uint32_t& p1)
 {
-	if constexpr (FMT == FMT_RGB) {
+	if constexpr (fmt_is_3byte(FMT)) {
 		// six contiguous bytes: one 8-byte load (the caller keeps sx <= sw - 3, so it never leaves the frame). Offsets fit 32 bits (the host
-		// refuses captures of 2^31 bytes or more).
+		// refuses captures of 2^31 bytes or more). BGR / BGRA taps stay as stored: the blend is per channel, so remap_bilinear exchanges the
+		// channels of its result, once per output pixel.
 		uint2 r;
 		__builtin_memcpy(&r, src + (uint32_t)(sy * sw + sx) * 3u, 8);
 		p0 = r.x & 0xFFFFFFu;
 		p1 = (r.x >> 24) | ((r.y & 0xFFFFu) << 8);
-	} else if constexpr (FMT == FMT_RGBA) {
+	} else if constexpr (fmt_is_4byte(FMT)) {
 		uint2 r;
 		__builtin_memcpy(&r, src + (size_t)(uint32_t)(sy * sw + sx) * 4u, 8);
 		p0 = r.x & 0xFFFFFFu;
 		p1 = r.y & 0xFFFFFFu;
+	} else if constexpr (fmt_is_422(FMT)) {
+		// the group of column sx & ~1 and the one after it: eight bytes of one row. sx even: both pixels in the first group (sx <= sw - 4, the width
+		// being even: the second group is still inside the row); sx odd: the first group's second pixel and the second group's first, each with
+		// its own chroma pair (2 sx + 6 <= 2 sw).
+		uint2 g;
+		__builtin_memcpy(&g, src + (uint32_t)(sy * sw + (sx & ~1)) * 2u, 8);
+		uint32_t y0, y1, u, v, z0, z1, u1, v1;
+		yuv422_group<FMT == FMT_UYVY>(g.x, y0, y1, u, v);
+		yuv422_group<FMT == FMT_UYVY>(g.y, z0, z1, u1, v1);
+		const YuvTerms k0 = yuv_terms(u, v), k1 = (sx & 1) ? yuv_terms(u1, v1) : k0;
+		p0 = yuv_rgb((sx & 1) ? y1 : y0, k0);
+		p1 = yuv_rgb((sx & 1) ? z0 : y1, k1);
 	} else {
 		const uint32_t plane = (uint32_t)sw * (uint32_t)sh;
 		uint16_t yy;
 		__builtin_memcpy(&yy, src + (uint32_t)(sy * sw + sx), 2);
 		YuvTerms k0, k1;
-		if constexpr (FMT == FMT_NV12) {
-			// the (U, V) pairs of columns sx & ~1 and (sx & ~1) + 2: four bytes (sx <= sw - 3 keeps them inside the row)
+		if constexpr (fmt_is_sp420(FMT)) {
+			// the chroma pairs of columns sx & ~1 and (sx & ~1) + 2: four bytes (sx <= sw - 3 keeps them inside the row); NV12 stores (U, V), NV21 (V, U)
 			uint32_t uv;
 			__builtin_memcpy(&uv, src + plane + (uint32_t)((sy >> 1) * sw + (sx & ~1)), 4);
+			if constexpr (FMT == FMT_NV21) uv = __builtin_amdgcn_perm(0u, uv, 0x02030001u);
 			k0 = yuv_terms(uv & 0xFFu, (uv >> 8) & 0xFFu);
 			k1 = (sx & 1) ? yuv_terms((uv >> 16) & 0xFFu, uv >> 24) : k0;
 		} else {
@@ -473,7 +551,9 @@ __device__ __forceinline__ uint32_t remap_bilinear(const uint8_t* __restrict__ s
 			const uint32_t ra = __builtin_amdgcn_udot4(__builtin_amdgcn_perm(a1p, a0p, sel), wx, 0u, false);
 			const uint32_t rb = __builtin_amdgcn_udot4(__builtin_amdgcn_perm(b1p, b0p, sel), wx, 0u, false);
 			const uint32_t S = __builtin_amdgcn_udot2(us2w{(unsigned short)ra, (unsigned short)rb}, wy, 512u, false);
-			v |= (S >> 10) << (8 * c);
+			// (BGR / BGRA: the taps are as stored, channel c of them is channel 2 - c of the output -- the permutation commutes with the
+			// per-channel blend, so it is this constant shift, once per output pixel, and not a v_perm per tap)
+			v |= (S >> 10) << (8 * (fmt_is_bgr(FMT) ? 2 - c : c));
 		}
 	} else if (sx >= -1 && sx < sw && sy >= -1 && sy < sh) {   // border: taps outside read as 0 (BORDER_CONSTANT)
 		const int w00 = (32 - fx) * (32 - fy) * 32, w01 = fx * (32 - fy) * 32, w10 = (32 - fx) * fy * 32, w11 = fx * fy * 32;
@@ -536,7 +616,8 @@ __global__ __launch_bounds__(256) void k_warp(const uint8_t* __restrict__ rgb, i
 // RGB8 scratch (same geometry, only the box is written), and k_warp<3> reads that. The box: the four corners of the destination frame through the
 // inverted matrix (a projective map takes the square to a convex quadrilateral as long as the denominator keeps its sign: every tap lies inside the
 // corners' bounding box), two pixels of margin for the fixed-point rounding and the +1 taps; any corner with a non-positive or non-finite denominator
-// makes it the whole capture. One thread = 8 x 2 pixels (four 2x2 chroma blocks).
+// makes it the whole capture. One thread = 8 x 2 pixels (four 2x2 chroma blocks; in 4:2:2, where rows share no chroma, two rows of four groups).
+// NV21 is NV12 with the pair's bytes exchanged on load.
 // the box of one capture: {x0, y0, x1, y1} inclusive, or the whole capture (see above); one lane per capture
 __global__ __launch_bounds__(64) void k_roi_boxes(const double* __restrict__ minv, int n, int sw, int sh, int width, int height, int4* __restrict__ boxes)
 {
@@ -565,7 +646,7 @@ __global__ __launch_bounds__(64) void k_roi_boxes(const double* __restrict__ min
 template <int FMT>
 __global__ __launch_bounds__(256) void k_convert_roi(const uint8_t* __restrict__ cap, int sw, int sh, const int4* __restrict__ boxes, uint8_t* __restrict__ rgb_out)
 {
-	static_assert(FMT == FMT_NV12 || FMT == FMT_I420, "only the 4:2:0 formats are converted ahead of the warp");
+	static_assert(fmt_is_420(FMT) || fmt_is_422(FMT), "only the YUV formats are converted ahead of the warp");
 	const int f = blockIdx.z;
 	const int4 box = boxes[f];
 	const int bx0 = box.x, by0 = box.y, bx1 = box.z, by1 = box.w;
@@ -579,13 +660,43 @@ __global__ __launch_bounds__(256) void k_convert_roi(const uint8_t* __restrict__
 	if ((sw & 7) == 0) {
 		// the fast path (every camera size): 8 + 8 luma bytes and the 8 chroma bytes under them as aligned 8-byte (4:2:0 planes: 4-byte) loads, the two rows'
 		// 24 RGB bytes each as three aligned 8-byte stores
+		auto store_row = [&](int yy, const uint32_t (&p)[8]) {
+			// eight pixels R | G << 8 | B << 16 -> 24 bytes
+			uint2 a, bq, c;
+			a.x = p[0] | (p[1] << 24); a.y = (p[1] >> 8) | (p[2] << 16);
+			bq.x = (p[2] >> 16) | (p[3] << 8); bq.y = p[4] | (p[5] << 24);
+			c.x = (p[5] >> 8) | (p[6] << 16); c.y = (p[6] >> 16) | (p[7] << 8);
+			uint2* o = reinterpret_cast<uint2*>(out + ((size_t)yy * sw + x) * 3);
+			o[0] = a; o[1] = bq; o[2] = c;
+		};
+		if constexpr (fmt_is_422(FMT)) {
+			// 4:2:2: a row's eight pixels are four groups, 16 contiguous bytes; the two rows share nothing
+#pragma unroll
+			for (int r = 0; r < 2; ++r) {
+				if (y + r >= sh) break;
+				uint4 g;
+				__builtin_memcpy(&g, src + ((size_t)(y + r) * sw + x) * 2, 16);
+				const uint32_t gw[4] = {g.x, g.y, g.z, g.w};
+				uint32_t px[8];
+#pragma unroll
+				for (int q = 0; q < 4; ++q) {
+					uint32_t y0, y1, u, v;
+					yuv422_group<FMT == FMT_UYVY>(gw[q], y0, y1, u, v);
+					const YuvTerms k = yuv_terms(u, v);
+					px[2 * q] = px_clean(yuv_rgb(y0, k)); px[2 * q + 1] = px_clean(yuv_rgb(y1, k));
+				}
+				store_row(y + r, px);
+			}
+			return;
+		}
 		uint2 y0v, y1v;
 		__builtin_memcpy(&y0v, src + (size_t)y * sw + x, 8);
 		if (y + 1 < sh) __builtin_memcpy(&y1v, src + (size_t)(y + 1) * sw + x, 8); else y1v = y0v;
 		uint32_t uu[4], vv[4];
-		if constexpr (FMT == FMT_NV12) {
+		if constexpr (fmt_is_sp420(FMT)) {
 			uint2 c;
 			__builtin_memcpy(&c, src + plane + (size_t)(y >> 1) * sw + x, 8);
+			if constexpr (FMT == FMT_NV21) { c.x = __builtin_amdgcn_perm(0u, c.x, 0x02030001u); c.y = __builtin_amdgcn_perm(0u, c.y, 0x02030001u); }   // (V, U) -> (U, V)
 			uu[0] = c.x & 0xFFu; vv[0] = (c.x >> 8) & 0xFFu; uu[1] = (c.x >> 16) & 0xFFu; vv[1] = c.x >> 24;
 			uu[2] = c.y & 0xFFu; vv[2] = (c.y >> 8) & 0xFFu; uu[3] = (c.y >> 16) & 0xFFu; vv[3] = c.y >> 24;
 		} else {
@@ -597,28 +708,14 @@ __global__ __launch_bounds__(256) void k_convert_roi(const uint8_t* __restrict__
 			for (int q = 0; q < 4; ++q) { uu[q] = (cu >> (8 * q)) & 0xFFu; vv[q] = (cv >> (8 * q)) & 0xFFu; }
 		}
 		uint32_t px0[8], px1[8];
-		// (a pixel is R | G << 8 | B << 16 and nothing above: the compiler builds the two low bytes with v_ashr_pk_u8_i32, shift + saturate + pack in one
-		// gfx950 instruction, and then ORs the result on as if its upper half were zero -- it is not: R and G of every fourth pixel came out wrong. The
-		// kernels that read a pixel through byte selects never see it; here the bytes are shifted into their neighbours, so the value is made opaque
-		// and masked.)
-		auto clean = [](uint32_t v) { asm volatile("" : "+v"(v)); return v & 0xFFFFFFu; };
 #pragma unroll
 		for (int q = 0; q < 4; ++q) {
 			const YuvTerms k = yuv_terms(uu[q], vv[q]);
 			const uint32_t w0 = q < 2 ? y0v.x : y0v.y, w1 = q < 2 ? y1v.x : y1v.y;
 			const int sft = 16 * (q & 1);
-			px0[2 * q] = clean(yuv_rgb((w0 >> sft) & 0xFFu, k)); px0[2 * q + 1] = clean(yuv_rgb((w0 >> (sft + 8)) & 0xFFu, k));
-			px1[2 * q] = clean(yuv_rgb((w1 >> sft) & 0xFFu, k)); px1[2 * q + 1] = clean(yuv_rgb((w1 >> (sft + 8)) & 0xFFu, k));
+			px0[2 * q] = px_clean(yuv_rgb((w0 >> sft) & 0xFFu, k)); px0[2 * q + 1] = px_clean(yuv_rgb((w0 >> (sft + 8)) & 0xFFu, k));
+			px1[2 * q] = px_clean(yuv_rgb((w1 >> sft) & 0xFFu, k)); px1[2 * q + 1] = px_clean(yuv_rgb((w1 >> (sft + 8)) & 0xFFu, k));
 		}
-		auto store_row = [&](int yy, const uint32_t (&p)[8]) {
-			// eight pixels R | G << 8 | B << 16 -> 24 bytes
-			uint2 a, bq, c;
-			a.x = p[0] | (p[1] << 24); a.y = (p[1] >> 8) | (p[2] << 16);
-			bq.x = (p[2] >> 16) | (p[3] << 8); bq.y = p[4] | (p[5] << 24);
-			c.x = (p[5] >> 8) | (p[6] << 16); c.y = (p[6] >> 16) | (p[7] << 8);
-			uint2* o = reinterpret_cast<uint2*>(out + ((size_t)yy * sw + x) * 3);
-			o[0] = a; o[1] = bq; o[2] = c;
-		};
 		store_row(y, px0);
 		if (y + 1 < sh) store_row(y + 1, px1);
 		return;
@@ -628,15 +725,16 @@ __global__ __launch_bounds__(256) void k_convert_roi(const uint8_t* __restrict__
 	for (int q = 0; q < 4; ++q) {
 		const int xx = x + 2 * q;
 		if (2 * q >= npx) break;
-		uint32_t u, v;
-		if constexpr (FMT == FMT_NV12) { const uint8_t* p = src + plane + (size_t)(y >> 1) * sw + xx; u = p[0]; v = p[1]; }
-		else { const size_t ci = (size_t)(y >> 1) * (sw >> 1) + (xx >> 1); v = src[plane + ci]; u = src[plane + (plane >> 2) + ci]; }
+		uint32_t u = 0, v = 0;
+		if constexpr (fmt_is_sp420(FMT)) { const uint8_t* p = src + plane + (size_t)(y >> 1) * sw + xx; u = p[FMT == FMT_NV21]; v = p[FMT != FMT_NV21]; }
+		else if constexpr (FMT == FMT_I420) { const size_t ci = (size_t)(y >> 1) * (sw >> 1) + (xx >> 1); v = src[plane + ci]; u = src[plane + (plane >> 2) + ci]; }
 		const YuvTerms k = yuv_terms(u, v);
 #pragma unroll
 		for (int r = 0; r < 2; ++r) {
 			if (y + r >= sh) break;
-			const uint8_t* yr = src + (size_t)(y + r) * sw + xx;
-			const uint32_t p0 = yuv_rgb(yr[0], k), p1 = yuv_rgb(yr[1], k);
+			uint32_t p0, p1;
+			if constexpr (fmt_is_422(FMT)) { p0 = capture_px(src, sw, sh, FMT, xx, y + r); p1 = capture_px(src, sw, sh, FMT, xx + 1, y + r); }
+			else { const uint8_t* yr = src + (size_t)(y + r) * sw + xx; p0 = yuv_rgb(yr[0], k); p1 = yuv_rgb(yr[1], k); }
 			uint8_t* o = out + ((size_t)(y + r) * sw + xx) * 3;
 			o[0] = (uint8_t)p0; o[1] = (uint8_t)(p0 >> 8); o[2] = (uint8_t)(p0 >> 16);
 			o[3] = (uint8_t)p1; o[4] = (uint8_t)(p1 >> 8); o[5] = (uint8_t)(p1 >> 16);

@@ -125,7 +125,7 @@ struct cimbar_hip_ctx {
 	int k1_tall = -1;                 // CIMBAR_HIP_K1_STRIPS=short|tall|auto: which instance of the plain threshold kernel a launch takes (auto: tall inside the pipelined loop for batches of K1_TALL_MIN frames and more)
 	int k1_lds_pad = 0;               // CIMBAR_HIP_K1_LDS_PAD: dynamic LDS bytes reserved per K1 workgroup (an occupancy cap for experiments: 30000 -> two workgroups per CU)
 	size_t warp_scratch = (size_t)4 << 30;   // CIMBAR_HIP_WARP_SCRATCH_MB: what the two-pass warp may hold of converted captures at a time (it goes through a batch in passes of that many captures, at most WARP_CHUNK)
-	int warp_twopass = 1;             // CIMBAR_HIP_WARP_TWOPASS=0: NV12 / 4:2:0 captures are converted inside the warp kernel, tap by tap, instead of once per source pixel ahead of it
+	int warp_twopass = 1;             // CIMBAR_HIP_WARP_TWOPASS=0: YUV captures (12 / 21 / 420 / 422 / 4221) are converted inside the warp kernel, tap by tap, instead of once per source pixel ahead of it
 	DevBuf<int4> d_ex_box;            // ... and the box of every capture (k_roi_boxes)
 	DevBuf<uint8_t> d_ex_rgb;         // ... the capture-shaped RGB8 scratch of that conversion, WARP_CHUNK captures at a time
 	int frame_stage = 0;              // CIMBAR_HIP_FRAME_STAGE=1: pageable frames go through the context's own page-locked staging instead of the runtime's
@@ -1611,6 +1611,22 @@ int cimbar_hip_decode_frame(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsigned wi
 // ---- extractor stage -------------------------------------------------------------------------------------------------------------
 namespace {
 
+// one call per capture format, the format as a compile-time constant (F::value): every kernel that reads a capture is a template on it
+template <class Fn>
+void for_capture_format(int fmt, Fn&& fn)
+{
+	switch (fmt) {
+	case FMT_RGBA: fn(std::integral_constant<int, FMT_RGBA>{}); break;
+	case FMT_NV12: fn(std::integral_constant<int, FMT_NV12>{}); break;
+	case FMT_I420: fn(std::integral_constant<int, FMT_I420>{}); break;
+	case FMT_NV21: fn(std::integral_constant<int, FMT_NV21>{}); break;
+	case FMT_YUYV: fn(std::integral_constant<int, FMT_YUYV>{}); break;
+	case FMT_UYVY: fn(std::integral_constant<int, FMT_UYVY>{}); break;
+	case FMT_BGR: fn(std::integral_constant<int, FMT_BGR>{}); break;
+	case FMT_BGRA: fn(std::integral_constant<int, FMT_BGRA>{}); break;
+	default: fn(std::integral_constant<int, FMT_RGB>{}); break;
+	}
+}
 // X1 for n captures: the streaming kernel where the rows can be loaded and stored as aligned 16-byte pieces, else the tiled one
 template <int FMT>
 void launch_gray_blur_rows(hipStream_t st, unsigned unit, const dim3& g, const uint8_t* d_in, unsigned width, unsigned height, int lanes_out, uint8_t* d_out, uint32_t* d_hist)
@@ -1633,10 +1649,7 @@ void launch_gray_blur(hipStream_t st, unsigned unit, int fmt, const uint8_t* d_i
 		const int groups = (int)width / 16, nb = (groups + 61) / 62, lanes_out = (groups + nb - 1) / nb;   // <= 62 column groups per wavefront + 2 halo lanes
 		const int strips = ((int)height + X1S_ROWS - 1) / X1S_ROWS;
 		const dim3 g(nb, (strips + 3) / 4, n);
-		if (fmt == FMT_RGBA) launch_gray_blur_rows<FMT_RGBA>(st, unit, g, d_in, width, height, lanes_out, d_out, d_hist);
-		else if (fmt == FMT_NV12) launch_gray_blur_rows<FMT_NV12>(st, unit, g, d_in, width, height, lanes_out, d_out, d_hist);
-		else if (fmt == FMT_I420) launch_gray_blur_rows<FMT_I420>(st, unit, g, d_in, width, height, lanes_out, d_out, d_hist);
-		else launch_gray_blur_rows<FMT_RGB>(st, unit, g, d_in, width, height, lanes_out, d_out, d_hist);
+		for_capture_format(fmt, [&](auto F) { launch_gray_blur_rows<decltype(F)::value>(st, unit, g, d_in, width, height, lanes_out, d_out, d_hist); });
 		return;
 	}
 	const dim3 g((width + X1_TW - 1) / X1_TW, (height + X1_TH * X1_TILES - 1) / (X1_TH * X1_TILES), n);
@@ -1649,18 +1662,17 @@ void launch_warp(hipStream_t st, int fmt, const uint8_t* d_in, unsigned width, u
 {
 	static const int xcd_order = [] { const char* v = std::getenv("CIMBAR_HIP_WARP_ORDER"); return v ? std::atoi(v) : 1; }();
 	const dim3 g((IMG_W + 63) / 64, (IMG_H + 16 * WARP_ROWS - 1) / (16 * WARP_ROWS), n);
-	if (fmt == FMT_RGBA) hipLaunchKernelGGL((k_warp<FMT_RGBA>), g, dim3(256), 0, st, d_in, (int)width, (int)height, d_minv, d_out, IMG_W, IMG_H, xcd_order);
-	else if (fmt == FMT_NV12) hipLaunchKernelGGL((k_warp<FMT_NV12>), g, dim3(256), 0, st, d_in, (int)width, (int)height, d_minv, d_out, IMG_W, IMG_H, xcd_order);
-	else if (fmt == FMT_I420) hipLaunchKernelGGL((k_warp<FMT_I420>), g, dim3(256), 0, st, d_in, (int)width, (int)height, d_minv, d_out, IMG_W, IMG_H, xcd_order);
-	else hipLaunchKernelGGL((k_warp<FMT_RGB>), g, dim3(256), 0, st, d_in, (int)width, (int)height, d_minv, d_out, IMG_W, IMG_H, xcd_order);
+	for_capture_format(fmt, [&](auto F) { hipLaunchKernelGGL((k_warp<decltype(F)::value>), g, dim3(256), 0, st, d_in, (int)width, (int)height, d_minv, d_out, IMG_W, IMG_H, xcd_order); });
 }
 
-// X4 for a context: 4:2:0 captures go through k_convert_roi + k_warp<3> (WARP_CHUNK captures at a time through one capture-shaped scratch), everything
-// else -- and everything with CIMBAR_HIP_WARP_TWOPASS=0 -- through the warp kernel of its own format
+// X4 for a context: YUV captures (4:2:0: 12 / 21 / 420; 4:2:2: 422 / 4221) go through k_convert_roi + k_warp<3> (WARP_CHUNK captures at a time through
+// one capture-shaped scratch), everything else -- and everything with CIMBAR_HIP_WARP_TWOPASS=0 -- through the warp kernel of its own format.
+// (4:2:2 as well: per 256 1080p YUYV captures the extract call takes 2.20 ms this way and 2.44 ms with the conversion inside the warp, the same ratio
+// as NV12's -- tools/capture_formats_bench.py, profiles/capture_formats_bench.json)
 constexpr int WARP_CHUNK = 512;
 int launch_warp_ctx(cimbar_hip_ctx* ctx, hipStream_t st, int fmt, const uint8_t* d_in, unsigned width, unsigned height, int n, const double* d_minv, uint8_t* d_out)
 {
-	if (!ctx->warp_twopass || (fmt != FMT_NV12 && fmt != FMT_I420)) { launch_warp(st, fmt, d_in, width, height, n, d_minv, d_out); return 0; }
+	if (!ctx->warp_twopass || !(fmt_is_420(fmt) || fmt_is_422(fmt))) { launch_warp(st, fmt, d_in, width, height, n, d_minv, d_out); return 0; }
 	const size_t per = (size_t)width * height * 3, cbytes = capture_bytes(width, height, fmt);
 	// captures per pass: WARP_CHUNK, fewer where that many converted captures would not fit the scratch allowance (4 GiB: 512 x 1080p = 3.2 GB; 4K captures go 171 at a time)
 	const size_t fit = ctx->warp_scratch / per;
@@ -1673,19 +1685,26 @@ int launch_warp_ctx(cimbar_hip_ctx* ctx, hipStream_t st, int fmt, const uint8_t*
 	for (int lo = 0; lo < n; lo += chunk) {
 		const int m = n - lo < chunk ? n - lo : chunk;
 		const dim3 gc((width + 127) / 128, (height + 31) / 32, m);
-		if (fmt == FMT_NV12) hipLaunchKernelGGL((k_convert_roi<FMT_NV12>), gc, dim3(256), 0, st, d_in + (size_t)lo * cbytes, (int)width, (int)height, ctx->d_ex_box + lo, ctx->d_ex_rgb);
-		else hipLaunchKernelGGL((k_convert_roi<FMT_I420>), gc, dim3(256), 0, st, d_in + (size_t)lo * cbytes, (int)width, (int)height, ctx->d_ex_box + lo, ctx->d_ex_rgb);
+		auto convert = [&](auto F) { hipLaunchKernelGGL((k_convert_roi<decltype(F)::value>), gc, dim3(256), 0, st, d_in + (size_t)lo * cbytes, (int)width, (int)height, ctx->d_ex_box + lo, ctx->d_ex_rgb); };
+		switch (fmt) {
+		case FMT_NV12: convert(std::integral_constant<int, FMT_NV12>{}); break;
+		case FMT_NV21: convert(std::integral_constant<int, FMT_NV21>{}); break;
+		case FMT_YUYV: convert(std::integral_constant<int, FMT_YUYV>{}); break;
+		case FMT_UYVY: convert(std::integral_constant<int, FMT_UYVY>{}); break;
+		default: convert(std::integral_constant<int, FMT_I420>{}); break;
+		}
 		launch_warp(st, FMT_RGB, ctx->d_ex_rgb, width, height, m, d_minv + (size_t)lo * 9, d_out + (size_t)lo * FRAME_RGB);
 	}
 	return 0;
 }
 
 // the `format` argument as the reference reads it: <= 0 is 3 (cimbar_recv_js.cpp:150-151), 4 / 12 / 420 are get_rgb's cases, everything else its
-// default (RGB8). The 4:2:0 layouts cannot hold an odd width or height (cv::cvtColor asserts; the reference would throw): EDIM.
+// default (RGB8) -- but for the five values of native receivers (21 / 422 / 4221 / 30 / 40, extract.hip.inc). The 4:2:0 layouts cannot hold an odd
+// width or height, the 4:2:2 ones no odd width (cv::cvtColor asserts; the reference would throw): EDIM.
 int check_capture(cimbar_hip_ctx* ctx, const char* who, unsigned width, unsigned height, int format, int* fmt, size_t* bytes)
 {
 	*fmt = capture_format(format);
-	if ((*fmt == FMT_NV12 || *fmt == FMT_I420) && ((width | height) & 1u)) { ctx->err = std::string(who) + ": a 4:2:0 capture (format 12 / 420) needs an even width and height"; return CIMBAR_HIP_EDIM; }
+	if (!capture_dims_ok(width, height, *fmt)) { ctx->err = std::string(who) + CAPTURE_DIMS_MSG; return CIMBAR_HIP_EDIM; }
 	*bytes = capture_bytes(width, height, *fmt);
 	if ((uint64_t)width * height * 4 >= (1ull << 33) || *bytes >= ((size_t)1 << 31)) { ctx->err = std::string(who) + ": captures of 2 GiB or more are not supported (the kernels address a capture with 32-bit offsets)"; return CIMBAR_HIP_EDIM; }
 	return 0;
@@ -2520,10 +2539,7 @@ void launch_undistort(hipStream_t st, int fmt, const uint8_t* d_in, unsigned wid
 	static const int xcd_order = [] { const char* v = std::getenv("CIMBAR_HIP_WARP_ORDER"); return v ? std::atoi(v) : 1; }();
 	const dim3 g((width + 63) / 64, (height + 16 * UD_ROWS - 1) / (16 * UD_ROWS), m);
 	const int W = (int)width, H = (int)height;
-	if (fmt == FMT_RGBA) hipLaunchKernelGGL((k_undistort<FMT_RGBA>), g, dim3(256), 0, st, d_in, W, H, d_xt, P, d_k1, d_ok, d_out, xcd_order);
-	else if (fmt == FMT_NV12) hipLaunchKernelGGL((k_undistort<FMT_NV12>), g, dim3(256), 0, st, d_in, W, H, d_xt, P, d_k1, d_ok, d_out, xcd_order);
-	else if (fmt == FMT_I420) hipLaunchKernelGGL((k_undistort<FMT_I420>), g, dim3(256), 0, st, d_in, W, H, d_xt, P, d_k1, d_ok, d_out, xcd_order);
-	else hipLaunchKernelGGL((k_undistort<FMT_RGB>), g, dim3(256), 0, st, d_in, W, H, d_xt, P, d_k1, d_ok, d_out, xcd_order);
+	for_capture_format(fmt, [&](auto F) { hipLaunchKernelGGL((k_undistort<decltype(F)::value>), g, dim3(256), 0, st, d_in, W, H, d_xt, P, d_k1, d_ok, d_out, xcd_order); });
 }
 
 // the argument checks the three entry points share; *st = the stream the call runs on

@@ -93,10 +93,12 @@ __device__ __forceinline__ void load_row(const RowSrc<12>& src, int r, const Row
 // (9798 = 76*128+70, 19235 = 150*128+35, 3735 = 29*128+23) and the low dot product is doubled, so that
 //   T = (hi_dot << 8) + 2*lo_dot + 32768 = 2 * (R*9798 + G*19235 + B*3735 + 16384)   and   gray = T >> 16 = byte 2 of T.
 // Leaving the result byte-aligned lets one v_perm_b32 pack two pixels into a u16 pair.
-template <int PPL>
+// BGR (captures stored B, G, R: extract.hip.inc): the R and B coefficients change places, nothing else.
+template <int PPL, bool BGR = false>
 __device__ __forceinline__ void gray_T(const uint32_t* d, uint32_t* T)
 {
-	constexpr uint32_t LO2 = 140u | (70u << 8) | (46u << 16), HI = 76u | (150u << 8) | (29u << 16);
+	constexpr uint32_t LO2 = BGR ? 46u | (70u << 8) | (140u << 16) : 140u | (70u << 8) | (46u << 16);
+	constexpr uint32_t HI = BGR ? 29u | (150u << 8) | (76u << 16) : 76u | (150u << 8) | (29u << 16);
 	constexpr int NDW = PPL * 3 / 4;
 #pragma unroll
 	for (int p = 0; p < PPL; ++p) {

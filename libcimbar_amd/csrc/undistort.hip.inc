@@ -192,7 +192,7 @@ __global__ __launch_bounds__(256) void k_undistort(const uint8_t* __restrict__ i
 		uint32_t px[4];
 #pragma unroll
 		for (int k = 0; k < 4; ++k) {
-			if (!ok) { px[k] = k < nx ? capture_px(src, w, h, FMT, x0 + k, y) : 0u; continue; }
+			if (!ok) { px[k] = k < nx ? px_clean(capture_px(src, w, h, FMT, x0 + k, y)) : 0u; continue; }   // (px_clean: the pixels are shifted into each other below)
 			// initUndistortRectifyMap's per-pixel body (undistort.simd.hpp, the scalar tail), identity tilt, k4..k6 = s1..s4 = 0: the denominator
 			// 1 + ((k6 r2 + k5) r2 + k4) r2 is exactly 1 and the s terms add zeros
 			const double x = xs[k];

@@ -360,21 +360,28 @@ def comm_destroy(comm):
 _ERR = {-1: "EINVAL", -2: "EDIM", -3: "ENODEVICE", -4: "EHIP", -5: "ENOMEM"}
 
 
+# the C ABI's `format` values (include/cimbar_hip.h, enum cimbar_hip_format): the reference's four, and the formats of native receivers
+FMT_RGB, FMT_RGBA, FMT_NV12, FMT_I420 = 3, 4, 12, 420
+FMT_NV21, FMT_YUYV, FMT_UYVY, FMT_BGR, FMT_BGRA = 21, 422, 4221, 30, 40
+_SHAPED = {FMT_RGB: 3, FMT_BGR: 3, FMT_RGBA: 4, FMT_BGRA: 4}     # formats an (n, h, w, channels) array describes by itself
+
+
 def _captures(lib, captures, size, fmt):
-    """RGB8 captures as an (n,h,w,3) array, or -- with size=(w,h) and the C ABI's `fmt` (3 RGB, 4 RGBA, 12 NV12, 420) -- n captures of
+    """RGB8 captures as an (n,h,w,3) array (BGR8 with fmt=30; RGBA8 / BGRA8 as (n,h,w,4) with fmt=4 / 40), or -- with size=(w,h) and the C ABI's
+    `fmt` (FMT_*: 3 RGB, 4 RGBA, 12 NV12, 420, 21 NV21, 422 YUYV, 4221 UYVY, 30 BGR, 40 BGRA) -- n captures of
     cimbar_hip_capture_bytes(w, h, fmt) bytes each as an (n, bytes) array. Returns (array, n, w, h, fmt)."""
     captures = np.ascontiguousarray(captures, dtype=np.uint8)
     if size is None:
         fmt = int(fmt) if int(fmt) > 0 else 3          # (<= 0 means RGB to the C ABI as well, cimbar_recv_js.cpp:150-151)
-        if fmt == 4 and captures.ndim == 4 and captures.shape[3] == 4:
+        if _SHAPED.get(fmt) == 4 and captures.ndim == 4 and captures.shape[3] == 4:
             n, h, w = captures.shape[:3]
-            return captures, n, w, h, 4
-        if fmt != 3:
+            return captures, n, w, h, fmt
+        if _SHAPED.get(fmt) != 3:
             raise CimbarHipError(f"captures in format {fmt} need size=(w, h): the array's shape does not say what the frame is")
         if captures.ndim != 4 or captures.shape[3] != 3:
-            raise CimbarHipError(f"RGB captures are an (n, h, w, 3) array, got {captures.shape}")
+            raise CimbarHipError(f"{'BGR' if fmt == FMT_BGR else 'RGB'} captures are an (n, h, w, 3) array, got {captures.shape}")
         n, h, w = captures.shape[:3]
-        return captures, n, w, h, 3
+        return captures, n, w, h, fmt
     w, h = size
     per = int(lib.cimbar_hip_capture_bytes(w, h, int(fmt)))
     if per == 0 or captures.size % per:

@@ -117,9 +117,17 @@ unsigned cimbard_get_report(unsigned char* buff, unsigned maxlen)
 	return len;
 }
 
+// `format` as the reference's get_rgb reads it (cimbar_recv_js.cpp:94-120): 4, 12 and 420 are its cases, every other value is RGB8. libcimbar_hip
+// gives five more values a meaning of its own (CIMBAR_HIP_FMT_NV21 / YUYV / UYVY / BGR / BGRA); this interface is the reference's and keeps the
+// reference's meaning, so they are RGB8 here as they always were. The native formats are reached through cimbar_hip_* only.
+static int reference_format(int format)
+{
+	return (format == CIMBAR_HIP_FMT_RGBA || format == CIMBAR_HIP_FMT_NV12 || format == CIMBAR_HIP_FMT_I420) ? format : CIMBAR_HIP_FMT_RGB;
+}
+
 int cimbard_scan_extract_decode(const unsigned char* imgdata, unsigned imgw, unsigned imgh, int format, unsigned char* bufspace, unsigned bufsize)
 {
-	if (format <= 0) format = 3;
+	format = reference_format(format);
 	if (imgw == 0 || imgh == 0) return -1;
 	const int mode = g_mode.load();
 	const int frame_bytes = cimbar_hip_mode_bufsize(mode);
@@ -153,7 +161,7 @@ int cimbard_hip_scan_extract_decode_auto(const unsigned char* imgdata, unsigned 
                                          unsigned bufsize, int* mode_out)
 {
 	if (mode_out) *mode_out = 0;
-	if (format <= 0) format = 3;
+	format = reference_format(format);
 	if (imgw == 0 || imgh == 0) return -1;
 	if (bufsize < (unsigned)cimbar_hip_mode_bufsize(68)) return -2;   // 7500: the largest cimbard_get_bufsize of 66 68 67 4
 	if (!imgdata || !bufspace) { t_dec.report = "null buffer"; return -4; }
