@@ -187,6 +187,27 @@ int cimbar_hip_set_ccm(cimbar_hip_ctx* ctx, const float m9[9]);
 int cimbar_hip_set_erasure_decode(cimbar_hip_ctx* ctx, int sym_distance, int colour_margin, int max_erasures);
 int cimbar_hip_get_erasure_decode(cimbar_hip_ctx* ctx, int* sym_distance, int* colour_margin, int* max_erasures);
 
+/* The relaxed flood (off after cimbar_hip_create; modes 68 / 67 / 66). A frame that leaves the parallel symbol pass and that the certifying pass
+ * does not settle is normally replayed in the reference's exact flood order, 12 400 dependent steps. With threshold >= 0 such a frame is flooded
+ * in parallel rounds instead: a round decodes every offered cell whose best offer has a priority (its neighbour's match distance) of at most
+ * max(threshold, the smallest priority on offer), each at the drift of the best offer it holds, smallest (priority, offering cell) first. That is
+ * the reference's rule without its tie order, so symbols and drift may differ from the reference's in single cells. The result of a frame is
+ * accepted when every one of its symbol RS blocks decodes; with fallback != 0 every other frame is replayed exactly inside the same call, and
+ * its outputs are then the default policy's byte for byte. An accepted frame's colour pass reads at the relaxed drift, so its colour chunks may
+ * differ from the default policy's in either direction.
+ *   threshold : -1 turns it off (nothing extra is launched); 0 .. 32 turns it on. CIMBAR_HIP_RELAXED_FLOOD_SUGGESTED (12) is the value of the
+ *               table in DESIGN_WIDENING.md "Relaxed flood": the exact flood's quality in 40 .. 1 000 rounds; 24 and more degrade on shifted and
+ *               rescaled frames, 0 .. 8 need thousands of rounds on noisy ones. Anything else is CIMBAR_HIP_EINVAL
+ *   fallback  : != 0: frames with a failing symbol block take the exact replay (and the symbol RS pass runs a second time over the batch)
+ * Modes 4 and 8 refuse threshold >= 0 (EINVAL): their one RS stream is decoded after the colour pass, so there is nothing to check the flood
+ * against. Takes effect for batches issued after the call. get: writes the two values, returns 1 if on, 0 if off.
+ * stats: out[0] frames flooded in rounds, [1] of those, frames whose symbol blocks all decoded, [2] frames handed to the exact replay (0 without
+ * fallback), [3] rounds in total; cumulative over the batches issued since the last cimbar_hip_set_relaxed_flood, which clears them. */
+#define CIMBAR_HIP_RELAXED_FLOOD_SUGGESTED 12
+int cimbar_hip_set_relaxed_flood(cimbar_hip_ctx* ctx, int threshold, int fallback);
+int cimbar_hip_get_relaxed_flood(cimbar_hip_ctx* ctx, int* threshold, int* fallback);
+int cimbar_hip_relaxed_flood_stats(cimbar_hip_ctx* ctx, int64_t out[4]);
+
 /* Colour erasure decoding (off after cimbar_hip_create; independent of cimbar_hip_set_erasure_decode: either, both or neither may be on). With
  * colour_margin > 0 the same entry points retry the COLOUR chunks a frame's mask lacks, after the symbol retry where that runs. A cell's
  * confidence is the classifier's margin: (second-smallest) - (smallest) squared distance of CimbDecoder::get_best_color, computed from the
@@ -727,9 +748,11 @@ enum {
 	CIMBAR_HIP_TAP_COLORS = 2,     /* n * 12400 bytes : colour (0..3) by linear cell index */
 	CIMBAR_HIP_TAP_DRIFT = 3,      /* n * 12400 * 2 int8: accumulated (dx,dy) at which each cell's colour is read */
 	CIMBAR_HIP_TAP_RS_OK = 4,      /* n * 60 bytes    : 1 = libcorrect-equivalent decode returned > 0, per RS block */
-	CIMBAR_HIP_TAP_FLOOD = 5,      /* n bytes         : 1 = frame needed the exact flood-order pass */
+	CIMBAR_HIP_TAP_FLOOD = 5,      /* n bytes         : 1 = frame left the parallel pass: a flood pass decoded it (CIMBAR_HIP_TAP_FLOOD_PATH says which:
+	                                  the exact flood-order replay, the certified batch flood or, with cimbar_hip_set_relaxed_flood, the rounds) */
 	CIMBAR_HIP_TAP_CCM = 6,        /* n * 10 floats   : 3x3 matrix used for the colour pass + active flag */
-	CIMBAR_HIP_TAP_FLOOD_PATH = 7, /* n bytes         : 0 = parallel pass was exact, 1 = exact flood replay, 2 = certified batch flood */
+	CIMBAR_HIP_TAP_FLOOD_PATH = 7, /* n bytes         : 0 = parallel pass was exact, 1 = exact flood replay, 2 = certified batch flood,
+	                                  3 = flooded in rounds, accepted (cimbar_hip_set_relaxed_flood; without its fallback: flooded in rounds) */
 	CIMBAR_HIP_TAP_FLOOD_INFO = 8, /* n u32           : what the batch-parallel flood made of a flagged frame: low byte 0 = certified, 1..4 = the rule
 	                                  that declined it, 5 = out of super-rounds; bits 8..15 the super-round; bits 16.. cells decoded by then.
 	                                  0xFFFFFFFF for frames that were never flagged, and for every frame of a batch in which the pass did not
@@ -786,7 +809,11 @@ enum {
 	 * cimbar_hip_scan_preprocess runs no search, but writes its own histograms and thresholds where these two taps read */
 	CIMBAR_HIP_TAP_SCAN_GRAY = 24,      /* n * w * h bytes     : the blurred gray plane the search read, row-major, capture after capture */
 	CIMBAR_HIP_TAP_SCAN_HIST = 25,      /* n * 256 u32         : the histogram of each plane */
-	CIMBAR_HIP_TAP_SCAN_THRESHOLD = 26  /* n int32             : the Otsu threshold of each histogram; the search reads gray > threshold */
+	CIMBAR_HIP_TAP_SCAN_THRESHOLD = 26, /* n int32             : the Otsu threshold of each histogram; the search reads gray > threshold */
+	/* the relaxed flood of the last batch (cimbar_hip_set_relaxed_flood) */
+	CIMBAR_HIP_TAP_FLOOD_ROUNDS = 27    /* n u32               : rounds | cells decoded << 16 of every frame flooded in rounds -- also of one that was
+	                                       then handed to the exact replay (CIMBAR_HIP_TAP_FLOOD_PATH 1); 0 for every other frame, and for every
+	                                       frame of a batch that ran with the setting off */
 };
 int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_bytes);
 

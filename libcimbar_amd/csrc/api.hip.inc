@@ -194,6 +194,24 @@ int cimbar_hip_get_colour_erasure_decode(cimbar_hip_ctx* ctx, int* colour_margin
 	return CIMBAR_FWD(cimbar_hip_get_colour_erasure_decode, colour_margin, max_erasures);
 }
 
+int cimbar_hip_set_relaxed_flood(cimbar_hip_ctx* ctx, int threshold, int fallback)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return CIMBAR_FWD(cimbar_hip_set_relaxed_flood, threshold, fallback);
+}
+
+int cimbar_hip_get_relaxed_flood(cimbar_hip_ctx* ctx, int* threshold, int* fallback)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return CIMBAR_FWD(cimbar_hip_get_relaxed_flood, threshold, fallback);
+}
+
+int cimbar_hip_relaxed_flood_stats(cimbar_hip_ctx* ctx, int64_t out[4])
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return CIMBAR_FWD(cimbar_hip_relaxed_flood_stats, out);
+}
+
 int cimbar_hip_set_group_colour_vote(cimbar_hip_ctx* ctx, int on)
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;

@@ -37,7 +37,7 @@ struct cimbar_hip_ctx {
 	Event ev_k1, ev_join, ev_mid[8];
 	int tail_split = 1, tail_parts = 2;
 	PinnedBuf<uint32_t> h_flagged;    // written by k_count_flagged at the end of every ordinary batch: [0] frames that left the parallel path, [1] frames of that batch,
-	                                  // [2] frames the exact replay had to take.
+	                                  // [2] frames the exact replay (or, with the relaxed flood on, k_flood_rounds) had to take.
 	int er_sym = 0, er_col = -1, er_max = -1;   // cimbar_hip_set_erasure_decode: off while er_sym <= 0 (k_erasure_frame is then never launched)
 	int ec_margin = 0, ec_max = -1;             // cimbar_hip_set_colour_erasure_decode: off while ec_margin <= 0 (k_colour_erasure_frame is then never launched)
 	bool cm_valid = false;                      // the last batch ran the colour retry (CIMBAR_HIP_TAP_COLOUR_MARGIN describes it)
@@ -89,7 +89,8 @@ struct cimbar_hip_ctx {
 		DevBuf<uint32_t> d_plane, d_cellmean;
 		DevBuf<uint8_t> d_symbols, d_colors;
 		DevBuf<int8_t> d_drift;
-		DevBuf<uint32_t> d_flood;         // [cap] frame flags, then [cap] what k_flood_wave made of the frame (CIMBAR_HIP_TAP_FLOOD_INFO); zeroed when it grows
+		DevBuf<uint32_t> d_flood;         // [cap] frame flags, then [cap] what k_flood_wave made of the frame (CIMBAR_HIP_TAP_FLOOD_INFO), then [cap] what k_flood_rounds did
+		                                  // (CIMBAR_HIP_TAP_FLOOD_ROUNDS); zeroed when it grows
 		DevBuf<uint8_t> d_rs_ok;
 		DevBuf<FrameState> d_states;
 		DevBuf<float> d_ccm_frames, d_ccm_used;
@@ -170,6 +171,11 @@ struct cimbar_hip_ctx {
 	int flood_dense = -1;             // exact replay at eight frames per CU (k_flood3<HEAP_LDS8, true>): -1 = where a launch has more frames than four per CU hold,
 	                                  // 0 = never, 1 = always (CIMBAR_HIP_FLOOD_DENSE)
 	int flood_wave = 1;               // run k_flood_wave in front of k_flood (CIMBAR_HIP_FLOOD_WAVE=0 turns it off: exact replay for every flagged frame)
+	// the relaxed flood (cimbar_hip_set_relaxed_flood, k2d_floodrounds.hip.inc): off while rf_threshold < 0 -- enqueue() then launches what it always did
+	int rf_threshold = -1, rf_fallback = 0;
+	int rf_grid = FR_GRID;            // workgroups of k_flood_rounds (CIMBAR_HIP_ROUNDS_GRID lowers it: a workgroup then walks several frames)
+	bool rf_valid = false;            // the last batch ran with the setting on (CIMBAR_HIP_TAP_FLOOD_ROUNDS describes it)
+	DevBuf<unsigned long long> d_rf_stats;   // [4] cimbar_hip_relaxed_flood_stats; allocated by the setter
 	// timing
 	bool timing = false;
 	static constexpr int NSTAGE = 8;
@@ -447,8 +453,8 @@ int ensure_capacity(cimbar_hip_ctx* ctx, int n)
 	HIPCHK(cur.d_symbols.reserve(N * NCELLS));
 	HIPCHK(cur.d_colors.reserve(N * NCELLS));
 	HIPCHK(cur.d_drift.reserve(N * NCELLS * 2));
-	HIPCHK(cur.d_flood.reserve(2 * N));
-	HIPCHK(hipMemset(cur.d_flood, 0, sizeof(uint32_t) * 2 * N));
+	HIPCHK(cur.d_flood.reserve(3 * N));
+	HIPCHK(hipMemset(cur.d_flood, 0, sizeof(uint32_t) * 3 * N));
 	HIPCHK(cur.d_rs_ok.reserve(N * ALL_BLOCKS));
 	HIPCHK(cur.d_states.reserve(N));
 	HIPCHK(cur.d_ccm_frames.reserve(N * 10));
@@ -608,27 +614,28 @@ int enqueue(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_rgb, int n, in
 		}
 	}
 	if (counted) ctx->wave_ran = run_wave;
+	const bool relaxed = !LEGACY && ctx->rf_threshold >= 0 && ctx->d_rf_stats && !(ctx->dbg_skip & 2);
+	ctx->rf_valid = relaxed;
 	auto tail = [&](hipStream_t s, int fa, int m, int part) -> hipError_t {
 		// part 0: up to k_frame_mid, part 1: the rest
 		if (part == 0) {
 			if (!(ctx->dbg_skip & 1)) hipLaunchKernelGGL(k_symbols, dim3(K2_BLOCKS, m), dim3(256), 0, s, cur.d_plane, ctx->tb, cur.d_symbols, cur.d_flood, fa);
 			if (hipError_t e = (s == st ? mark() : hipSuccess)) return e;
-			{
-				// the two halves of a split batch may run their flood kernels at the same time: each gets its own half of the spill areas
-				const int areas = pipe ? FLOOD_GRID / ctx->pipe_depth : (split ? FLOOD_GRID / 2 : FLOOD_GRID);
-				const int area0 = pipe ? ctx->pipe_set * areas : ((split && s != st) ? FLOOD_GRID / 2 : 0);
-				if (run_wave && !(ctx->dbg_skip & 2)) {
-					// first the batch-parallel pass for frames whose flood provably does not depend on the tie order (it clears their flag to 2)
-					const int wareas = pipe ? FW_GRID / ctx->pipe_depth : (split ? FW_GRID / 2 : FW_GRID);
-					const int warea0 = pipe ? ctx->pipe_set * wareas : ((split && s != st) ? FW_GRID / 2 : 0);
-					hipLaunchKernelGGL(k_flood_wave, dim3(m < wareas ? m : wareas), dim3(256), 0, s, cur.d_plane, ctx->tb, ctx->d_fw_queue, cur.d_flood,
-					                   cur.d_symbols, cur.d_drift, fa, m, warea0, cur.d_flood + cur.cap);
-				} else if (ctx->flood_wave && !(ctx->dbg_skip & 2)) {
-					// skipped by the scheduler: CIMBAR_HIP_TAP_FLOOD_INFO must not show what the pass said about some earlier batch
-					if (hipError_t e = hipMemsetAsync(cur.d_flood + cur.cap + fa, 0xFF, sizeof(uint32_t) * (size_t)m, s)) return e;
-				}
-				const int counter = pipe ? ctx->pipe_set : ((split && s != st) ? 1 : 0);          // (launches that may overlap use different frame counters)
-				auto exact_flood = [&](const uint32_t* flags) {
+			// the two halves of a split batch may run their flood kernels at the same time: each gets its own half of the spill areas
+			const int areas = pipe ? FLOOD_GRID / ctx->pipe_depth : (split ? FLOOD_GRID / 2 : FLOOD_GRID);
+			const int area0 = pipe ? ctx->pipe_set * areas : ((split && s != st) ? FLOOD_GRID / 2 : 0);
+			if (run_wave && !(ctx->dbg_skip & 2)) {
+				// first the batch-parallel pass for frames whose flood provably does not depend on the tie order (it clears their flag to 2)
+				const int wareas = pipe ? FW_GRID / ctx->pipe_depth : (split ? FW_GRID / 2 : FW_GRID);
+				const int warea0 = pipe ? ctx->pipe_set * wareas : ((split && s != st) ? FW_GRID / 2 : 0);
+				hipLaunchKernelGGL(k_flood_wave, dim3(m < wareas ? m : wareas), dim3(256), 0, s, cur.d_plane, ctx->tb, ctx->d_fw_queue, cur.d_flood,
+				                   cur.d_symbols, cur.d_drift, fa, m, warea0, cur.d_flood + cur.cap);
+			} else if (ctx->flood_wave && !(ctx->dbg_skip & 2)) {
+				// skipped by the scheduler: CIMBAR_HIP_TAP_FLOOD_INFO must not show what the pass said about some earlier batch
+				if (hipError_t e = hipMemsetAsync(cur.d_flood + cur.cap + fa, 0xFF, sizeof(uint32_t) * (size_t)m, s)) return e;
+			}
+			const int counter = pipe ? ctx->pipe_set : ((split && s != st) ? 1 : 0);          // (launches that may overlap use different frame counters)
+			auto exact_flood = [&](const uint32_t* flags) {
 				// three frames per CU while the batch fits, four (smaller LDS heap) beyond that
 				const int areas3 = areas * FLOOD_GRID3 / FLOOD_GRID;
 				// a launch with fewer workgroups than frames hands the rest out through the counter pair sc.next[2 * counter ..]: zeroed HERE, in stream
@@ -645,16 +652,21 @@ int enqueue(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_rgb, int n, in
 					hipLaunchKernelGGL((k_flood3<HEAP_LDS, false>), dim3(m), dim3(128), 0, s, cur.d_plane, ctx->tb, ctx->flood, flags, cur.d_symbols, cur.d_drift, fa, m, area0, counter);
 				else
 					hipLaunchKernelGGL((k_flood3<HEAP_LDS4, false>), hand_out(m < areas ? m : areas), dim3(128), 0, s, cur.d_plane, ctx->tb, ctx->flood, flags, cur.d_symbols, cur.d_drift, fa, m, area0, counter);
-				};
-				exact_flood(cur.d_flood);
-				if (ctx->flood_verify && ctx->flood_wave && !(ctx->dbg_skip & 2)) {
-					// CIMBAR_HIP_FLOOD_VERIFY: what k_flood_wave certified (flag 2) is set aside, the same frames are replayed exactly, and the two
-					// results are compared cell by cell (symbol and drifted position). The exact result is what stays -- a wrong certificate would be
-					// counted (cimbar_hip_flood_verify_totals, CIMBAR_HIP_TAP_FLOOD_VERIFY) AND repaired.
-					hipLaunchKernelGGL(k_verify_begin, dim3(m), dim3(256), 0, s, cur.d_flood, cur.d_symbols, cur.d_drift, ctx->d_vflag, ctx->d_vsym, ctx->d_vdrift, fa, ctx->vcap);
-					exact_flood(ctx->d_vflag);
-					hipLaunchKernelGGL(k_verify_end, dim3(m), dim3(256), 0, s, cur.d_symbols, cur.d_drift, ctx->d_vflag, ctx->d_vsym, ctx->d_vdrift, fa, ctx->vcap, ctx->d_vtotals);
-				}
+			};
+			// The relaxed flood (cimbar_hip_set_relaxed_flood): the frames still flagged 1 are flooded in threshold rounds (flag 3) instead of
+			// replayed; what the symbol streams' RS pass makes of them decides below whether they stay that way.
+			if (relaxed) {
+				if (hipError_t e = hipMemsetAsync(cur.d_flood + 2 * cur.cap + fa, 0, sizeof(uint32_t) * (size_t)m, s)) return e;
+				hipLaunchKernelGGL(k_flood_rounds, dim3(m < ctx->rf_grid ? m : ctx->rf_grid), dim3(FR_THREADS), 0, s, cur.d_plane, ctx->tb, cur.d_flood, cur.d_symbols,
+				                   cur.d_drift, fa, m, (uint32_t)ctx->rf_threshold, cur.d_flood + 2 * cur.cap);
+			} else exact_flood(cur.d_flood);
+			if (ctx->flood_verify && ctx->flood_wave && !(ctx->dbg_skip & 2)) {
+				// CIMBAR_HIP_FLOOD_VERIFY: what k_flood_wave certified (flag 2) is set aside, the same frames are replayed exactly, and the two
+				// results are compared cell by cell (symbol and drifted position). The exact result is what stays -- a wrong certificate would be
+				// counted (cimbar_hip_flood_verify_totals, CIMBAR_HIP_TAP_FLOOD_VERIFY) AND repaired.
+				hipLaunchKernelGGL(k_verify_begin, dim3(m), dim3(256), 0, s, cur.d_flood, cur.d_symbols, cur.d_drift, ctx->d_vflag, ctx->d_vsym, ctx->d_vdrift, fa, ctx->vcap);
+				exact_flood(ctx->d_vflag);
+				hipLaunchKernelGGL(k_verify_end, dim3(m), dim3(256), 0, s, cur.d_symbols, cur.d_drift, ctx->d_vflag, ctx->d_vsym, ctx->d_vdrift, fa, ctx->vcap, ctx->d_vtotals);
 			}
 			if (hipError_t e = (s == st ? mark() : hipSuccess)) return e;
 			// (legacy modes have ONE stream, decoded after the colour pass; the stage-time slot stays so that the names keep their meaning)
@@ -663,6 +675,16 @@ int enqueue(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_rgb, int n, in
 			else
 #endif
 			if (!LEGACY && !(ctx->dbg_skip & 4)) hipLaunchKernelGGL((k_rs<4>), dim3((m * SYM_BLOCKS + 3) / 4), dim3(256), 0, s, cur.d_symbols, ctx->tb, fa, m, 0, d_chunks, cur.d_rs_ok, 0);
+			if (relaxed) {
+				// acceptance: a frame flooded in rounds keeps its result iff every symbol block decoded. With fallback on, the others go back to flag 1,
+				// the exact replay takes them -- inside this call, in front of everything that reads symbols, drift or flags -- and the RS pass runs once
+				// more over the part (it rewrites the same bytes for the frames that did not change: 40 blocks per frame of clean-path work).
+				hipLaunchKernelGGL(k_rounds_check, dim3((m + 255) / 256), dim3(256), 0, s, cur.d_flood, cur.d_rs_ok, cur.d_flood + 2 * cur.cap, fa, m, ctx->rf_fallback, ctx->d_rf_stats);
+				if (ctx->rf_fallback) {
+					exact_flood(cur.d_flood);
+					hipLaunchKernelGGL((k_rs<4>), dim3((m * SYM_BLOCKS + 3) / 4), dim3(256), 0, s, cur.d_symbols, ctx->tb, fa, m, 0, d_chunks, cur.d_rs_ok, 0);
+				}
+			}
 			if (hipError_t e = (s == st ? mark() : hipSuccess)) return e;
 			if (!(ctx->dbg_skip & 8)) hipLaunchKernelGGL(k_frame_mid, dim3(m), dim3(64), 0, s, d_rgb, cur.d_cellmean, ctx->tb, d_chunks, cur.d_rs_ok, cc, cur.d_states, cur.d_ccm_frames, fa, plain);
 			return s == st ? mark() : hipSuccess;
@@ -816,6 +838,7 @@ int cimbar_hip_create(int device, int mode_val, cimbar_hip_ctx** out)
 	if (const char* v = std::getenv("CIMBAR_HIP_FLOOD_VERIFY")) ctx->flood_verify = std::atoi(v) != 0;
 	if (const char* v = std::getenv("CIMBAR_HIP_FLOOD_DENSE")) ctx->flood_dense = std::atoi(v);
 	if (const char* v = std::getenv("CIMBAR_HIP_FLOOD_DENSE_GRID")) { int k = std::atoi(v); if (k >= 4 && k <= FLOOD_DENSE_PER * FLOOD_GRID) ctx->flood_dense_grid = k; }
+	if (const char* v = std::getenv("CIMBAR_HIP_ROUNDS_GRID")) { int k = std::atoi(v); if (k >= 1 && k <= FR_GRID) ctx->rf_grid = k; }
 #ifdef CIMBAR_PROBES
 	if (const char* v = std::getenv("CIMBAR_HIP_DEBUG_SKIP")) ctx->dbg_skip = std::atoi(v);
 #endif
@@ -2117,6 +2140,45 @@ int cimbar_hip_get_colour_erasure_decode(cimbar_hip_ctx* ctx, int* colour_margin
 	return ctx->ec_margin > 0 ? 1 : 0;
 }
 
+int cimbar_hip_set_relaxed_flood(cimbar_hip_ctx* ctx, int threshold, int fallback)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	if (threshold < -1 || threshold > FR_THRESHOLD_MAX) { ctx->err = "set_relaxed_flood: threshold -1 (off) or 0 .. 32"; return CIMBAR_HIP_EINVAL; }
+	if (LEGACY && threshold >= 0) { ctx->err = "set_relaxed_flood: modes 4 and 8 decode their one RS stream after the colour pass; there is nothing to check a relaxed flood against"; return CIMBAR_HIP_EINVAL; }
+	HIPCHK(hipSetDevice(ctx->device));
+	if (threshold >= 0 && !ctx->d_rf_stats) HIPCHK(ctx->d_rf_stats.reserve(4));
+	if (ctx->d_rf_stats) {
+		// (the counts of batches still in flight belong to the old setting)
+		HIPCHK(hipDeviceSynchronize());
+		HIPCHK(hipMemset(ctx->d_rf_stats, 0, 4 * sizeof(unsigned long long)));
+	}
+	// (read when a batch is enqueued: batches already issued keep the setting they were issued with)
+	ctx->rf_threshold = threshold;
+	ctx->rf_fallback = threshold >= 0 && fallback ? 1 : 0;
+	return 0;
+}
+
+int cimbar_hip_get_relaxed_flood(cimbar_hip_ctx* ctx, int* threshold, int* fallback)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	if (threshold) *threshold = ctx->rf_threshold;
+	if (fallback) *fallback = ctx->rf_fallback;
+	return ctx->rf_threshold >= 0 ? 1 : 0;
+}
+
+int cimbar_hip_relaxed_flood_stats(cimbar_hip_ctx* ctx, int64_t out[4])
+{
+	if (!ctx || !out) return CIMBAR_HIP_EINVAL;
+	for (int k = 0; k < 4; ++k) out[k] = 0;
+	if (!ctx->d_rf_stats) return 0;
+	unsigned long long t[4];
+	HIPCHK(hipSetDevice(ctx->device));
+	HIPCHK(hipDeviceSynchronize());
+	HIPCHK(hipMemcpy(t, ctx->d_rf_stats, sizeof t, hipMemcpyDeviceToHost));
+	for (int k = 0; k < 4; ++k) out[k] = (int64_t)t[k];
+	return 0;
+}
+
 int cimbar_hip_set_group_colour_vote(cimbar_hip_ctx* ctx, int on)
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;
@@ -2281,6 +2343,13 @@ int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_byte
 			HIPCHK(hipMemcpy(fl.data(), cur.d_flood, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
 			HIPCHK(hipMemcpy(out, cur.d_flood + cur.cap, bytes, hipMemcpyDeviceToHost));
 			for (size_t k = 0; k < n; ++k) if (!fl[k]) ((uint32_t*)out)[k] = 0xFFFFFFFFu;   // frame never flagged: the batch-parallel flood did not look at it
+			return (int64_t)bytes;
+		}
+		case CIMBAR_HIP_TAP_FLOOD_ROUNDS: {
+			bytes = n * sizeof(uint32_t);
+			if (out_bytes < bytes) { ctx->err = "tap: buffer too small"; return CIMBAR_HIP_EINVAL; }
+			if (!ctx->rf_valid) { std::memset(out, 0, bytes); return (int64_t)bytes; }   // the batch ran without the relaxed flood: no frame took rounds
+			HIPCHK(hipMemcpy(out, cur.d_flood + 2 * cur.cap, bytes, hipMemcpyDeviceToHost));
 			return (int64_t)bytes;
 		}
 		case CIMBAR_HIP_TAP_FLOOD_PATH: {

@@ -441,7 +441,9 @@ constexpr int HEAP_LDS4 = HEAP_LDS < CIMBAR_HEAP_LDS4 ? HEAP_LDS : CIMBAR_HEAP_L
 #endif
 constexpr int HEAP_LDS8 = HEAP_LDS < CIMBAR_HEAP_LDS8 ? 63 : CIMBAR_HEAP_LDS8;   // (the spill-test build: one block in LDS, every deeper access global)
 constexpr int FLOOD_DENSE_PER = 2;                       // dense workgroups (and spill areas) per ordinary one
-// flood_flag[f]: 0 = the parallel pass (k_symbols) was exact; 1 = needs the exact replay; 2 = settled by k_flood_wave
+// flood_flag[f]: 0 = the parallel pass (k_symbols) was exact; 1 = needs the exact replay; 2 = settled by k_flood_wave; 3 = flooded in rounds by
+// k_flood_rounds (k2d_floodrounds.hip.inc; only with cimbar_hip_set_relaxed_flood on -- k_rounds_check may set it back to 1). Whoever reads the
+// flag to learn "does this frame have drift?" tests != 0.
 //
 // The replay kernel is k_flood3 below. Its two predecessors are gone (round 4): k_flood, one wavefront per frame running flood_step above
 // for all 12 400 cells (24-34 ms per frame: ~620 dependent instructions per step), and k_flood2, which split the step over two wavefronts

@@ -310,7 +310,7 @@ __global__ __launch_bounds__(256) void k_verify_end(const uint8_t* __restrict__ 
 	}
 }
 
-// how many frames of the batch left the parallel pass (flag 1 or 2) and how many of those needed the exact replay (flag 1), into pinned host
+// how many frames of the batch left the parallel pass (flag 1 or 2) and how many of those the certifying pass did not settle (flag 1 or 3), into pinned host
 // memory: inputs of enqueue()'s scheduling decisions ("split the chain or not", "is the certifying pass worth running")
 __global__ __launch_bounds__(256) void k_count_flagged(const uint32_t* __restrict__ flood_flag, int n, uint32_t* __restrict__ host_out)
 {
@@ -318,7 +318,7 @@ __global__ __launch_bounds__(256) void k_count_flagged(const uint32_t* __restric
 	if (threadIdx.x == 0) { s_n = 0; s_x = 0; }
 	__syncthreads();
 	uint32_t c = 0, x = 0;
-	for (int f = threadIdx.x; f < n; f += 256) { const uint32_t fl = flood_flag[f]; c += fl != 0u ? 1u : 0u; x += fl == 1u ? 1u : 0u; }
+	for (int f = threadIdx.x; f < n; f += 256) { const uint32_t fl = flood_flag[f]; c += fl != 0u ? 1u : 0u; x += (fl == 1u || fl == 3u) ? 1u : 0u; }   // (3: flooded in rounds -- not certified either)
 	if (c) atomicAdd(&s_n, c);
 	if (x) atomicAdd(&s_x, x);
 	__syncthreads();

@@ -102,6 +102,7 @@ struct Tables {
 #include "k2_symbols.hip.inc"
 #include "k2b_flood.hip.inc"
 #include "k2c_floodwave.hip.inc"
+#include "k2d_floodrounds.hip.inc"
 #include "k3_rs.hip.inc"
 #include "k4_frame.hip.inc"
 #include "erasure.hip.inc"

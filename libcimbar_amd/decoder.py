@@ -31,6 +31,9 @@ TAP_CELL_MEANS = 21   # the threshold kernel's undrifted cell means, r | g << 8 
 TAP_SCAN_GRAY, TAP_SCAN_HIST, TAP_SCAN_THRESHOLD = 24, 25, 26   # what the stage in front of the last anchor search produced: tap_scan
 # CIMBAR_HIP_COLOUR_MARGIN_SUGGESTED (include/cimbar_hip.h): the colour erasure threshold chosen on rendered frames (DESIGN_WIDENING.md)
 COLOUR_MARGIN_SUGGESTED = 32512
+TAP_FLOOD_ROUNDS = 27   # the relaxed flood of the last batch (set_relaxed_flood): rounds | cells decoded << 16 per frame flooded in rounds
+# CIMBAR_HIP_RELAXED_FLOOD_SUGGESTED (include/cimbar_hip.h): the threshold of the table in DESIGN_WIDENING.md "Relaxed flood"
+RELAXED_FLOOD_SUGGESTED = 12
 
 # every symbol include/cimbar_hip.h declares (tests/test_capi_symbols.py checks the header against this list and the .so)
 EXPORTS = (
@@ -59,6 +62,7 @@ EXPORTS = (
     "cimbar_hip_decode_batch_stitched", "cimbar_hip_scan_extract_decode_batch_stitched_fmt",
     "cimbar_hip_decode_batch_stitched_stream", "cimbar_hip_scan_extract_decode_batch_stitched_stream_fmt", "cimbar_hip_stitch_stream_reset",
     "cimbar_hip_set_stitch_strips", "cimbar_hip_get_stitch_strips",
+    "cimbar_hip_set_relaxed_flood", "cimbar_hip_get_relaxed_flood", "cimbar_hip_relaxed_flood_stats",
 )
 # cimbar_hip_deliver_chunks' flags
 DELIVER_DEDUP, DELIVER_REMEMBER, DELIVER_DROP_EMPTY = 1, 2, 4
@@ -219,6 +223,12 @@ def load_library(path=None):
     lib.cimbar_hip_set_erasure_decode.restype = i32
     lib.cimbar_hip_get_erasure_decode.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32)]
     lib.cimbar_hip_get_erasure_decode.restype = i32
+    lib.cimbar_hip_set_relaxed_flood.argtypes = [vp, i32, i32]
+    lib.cimbar_hip_set_relaxed_flood.restype = i32
+    lib.cimbar_hip_get_relaxed_flood.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    lib.cimbar_hip_get_relaxed_flood.restype = i32
+    lib.cimbar_hip_relaxed_flood_stats.argtypes = [vp, ctypes.POINTER(i64)]
+    lib.cimbar_hip_relaxed_flood_stats.restype = i32
     lib.cimbar_hip_set_colour_erasure_decode.argtypes = [vp, i32, i32]
     lib.cimbar_hip_set_colour_erasure_decode.restype = i32
     lib.cimbar_hip_get_colour_erasure_decode.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]
@@ -969,6 +979,23 @@ class HipDecoder:
                          "cimbar_hip_get_colour_erasure_decode")
         return bool(rc), a.value, b.value
 
+    def set_relaxed_flood(self, threshold, fallback=True):
+        """cimbar_hip_set_relaxed_flood: threshold -1 = off (the default), 0 .. 32 = flagged frames are flooded in threshold rounds and kept
+        where every symbol RS block decodes; fallback: every other frame takes the exact replay inside the same call. Modes 4 / 8 refuse it."""
+        self._check(self._lib.cimbar_hip_set_relaxed_flood(self._ctx, int(threshold), int(bool(fallback))), "cimbar_hip_set_relaxed_flood")
+
+    def get_relaxed_flood(self):
+        """(on, threshold, fallback)"""
+        a, b = ctypes.c_int(), ctypes.c_int()
+        rc = self._check(self._lib.cimbar_hip_get_relaxed_flood(self._ctx, ctypes.byref(a), ctypes.byref(b)), "cimbar_hip_get_relaxed_flood")
+        return bool(rc), a.value, bool(b.value)
+
+    def relaxed_flood_stats(self):
+        """(frames flooded in rounds, accepted, handed to the exact replay, rounds in total) since the last set_relaxed_flood"""
+        out = (ctypes.c_int64 * 4)()
+        self._check(self._lib.cimbar_hip_relaxed_flood_stats(self._ctx, out), "cimbar_hip_relaxed_flood_stats")
+        return tuple(int(x) for x in out)
+
     def set_group_colour_vote(self, on=True):
         """cimbar_hip_set_group_colour_vote: the combined calls settle a disputed colour by the members' classifier margins instead of by
         plurality; with set_colour_erasure_decode on as well, the group's missing colour chunks are retried. Modes 4 / 8 refuse it."""
@@ -1074,7 +1101,7 @@ class HipDecoder:
         shapes = {
             TAP_BITPLANE: ((n, self.geo.IMG_W * self.geo.IMG_H // 8), np.uint8), TAP_SYMBOLS: ((n, self.geo.NCELLS), np.uint8),
             TAP_COLORS: ((n, self.geo.NCELLS), np.uint8), TAP_DRIFT: ((n, self.geo.NCELLS, 2), np.int8),
-            TAP_RS_OK: ((n, self.geo.BLOCKS), np.uint8), TAP_FLOOD: ((n,), np.uint8), TAP_CCM: ((n, 10), np.float32), TAP_FLOOD_PATH: ((n,), np.uint8), TAP_FLOOD_INFO: ((n,), np.uint32), TAP_FLOOD_VERIFY: ((n,), np.uint32),
+            TAP_RS_OK: ((n, self.geo.BLOCKS), np.uint8), TAP_FLOOD: ((n,), np.uint8), TAP_CCM: ((n, 10), np.float32), TAP_FLOOD_PATH: ((n,), np.uint8), TAP_FLOOD_INFO: ((n,), np.uint32), TAP_FLOOD_VERIFY: ((n,), np.uint32), TAP_FLOOD_ROUNDS: ((n,), np.uint32),
             TAP_GROUP_CELLS: ((n, self.geo.NCELLS), np.uint8), TAP_GROUP_MARGIN: ((n, self.geo.NCELLS), np.uint16), TAP_GROUPS: ((n,), np.int32),
             TAP_COLOUR_MARGIN: ((n, self.geo.NCELLS), np.uint32), TAP_SCAN_PATH: ((n,), np.int32),
             TAP_GROUP_COLOUR_MARGIN: ((n, self.geo.NCELLS), np.uint32), TAP_GROUP_COLOUR_WEIGHTS: ((n, self.geo.NCELLS), np.uint32),
