@@ -447,6 +447,60 @@ int cimbar_hip_stitch_stream_reset(cimbar_hip_ctx* ctx);
 int cimbar_hip_set_stitch_strips(cimbar_hip_ctx* ctx, int strips);
 int cimbar_hip_get_stitch_strips(cimbar_hip_ctx* ctx, int* strips);
 
+/* ---- repeat-capture skipping: one decode per displayed frame ------------------------------------------------------------------------------
+ * A camera films the display faster than it changes, so every frame arrives as a run of two to four near-identical captures, and the calls
+ * above decode each of them in full. These two calls find the runs IN FRONT of the decode, decode one capture of each run, and decode the
+ * others only where that one came back incomplete. Opt-in; no other call's behaviour depends on them. Modes 68 / 67 / 66 (the signature was
+ * checked on their palette: four ink colours on black); modes 4 and 8: CIMBAR_HIP_EINVAL.
+ *   signature  cell c of a usable capture's deskewed frame, nominal top-left (x, y) (no drift): R_c, G_c, B_c = the channel sums over pixel
+ *              rows y + 2 .. y + 5 and columns x .. x + 7, S_c = R_c + G_c + B_c; R_A, B_A, S_A = the sums of R_c, B_c, S_c over the frame's
+ *              cells; sig_c = [R_c S_A > S_c R_A] | [B_c S_A > S_c B_A] << 1. Strict comparisons, unsigned 64-bit arithmetic. The frame is
+ *              read as handed in, or as the warp wrote it; sharpening plays no part. (CIMBAR_HIP_TAP_REPEAT_SIG)
+ *   agreement  agree(k, k + 1) = the cells with equal sig (CIMBAR_HIP_TAP_REPEAT_AGREE)
+ *   runs       capture k starts a new run when it is the first; when agree(k - 1, k) * 1000 < min_agree_permille * cells (<= 0: 900; above
+ *              1000: CIMBAR_HIP_EINVAL); when the run before it already has max_run members (<= 0: 4; above 8: CIMBAR_HIP_EINVAL); or
+ *              when capture k - 1 or k is unusable (capture path only: its extraction failed). An unusable capture is in no run: runs_out
+ *              and roles -1, mask 0, zeroed slot, as in the plain call. Runs are numbered from 0 in capture order and do not span calls.
+ *   representative  member (len - 1) / 2 of a run: the first of two, the second of three or four. The reasoning -- on an LCD the first capture
+ *              after a switch tends to ghost and the last may catch the next switch -- is a guess; nobody has measured it.
+ *   pass 1     the representatives are decoded in capture order, exactly as one plain call would decode them
+ *   pass 2     the other members of every run whose representative's mask is not full are decoded in capture order, again exactly as one
+ *              plain call; if there are none, no second pass runs
+ *   roles      per capture: CIMBAR_HIP_ONCE_REPRESENTATIVE (1), _FALLBACK (2: decoded in pass 2), _SKIPPED (0), _UNUSABLE (-1)
+ *   chunks / masks  of a decoded capture: what the plain call delivers for it, bit for bit; of a skipped one: mask 0 and a zeroed slot.
+ *              Capture path: status is the plain call's for every capture -- extraction runs for all of them
+ *   contract   list 1 = the representatives, list 2 = the pass-2 members. The per-capture results of list 1, then of list 2, are the
+ *              results of two consecutive plain calls -- cimbar_hip_decode_batch on those frames, resp.
+ *              cimbar_hip_scan_extract_decode_batch_fmt on those captures -- on a context in the same state: the colour-correction carry
+ *              (cimbar_hip_get_ccm afterwards) and the erasure, colour-erasure and relaxed-flood settings in force included
+ *   per run    n slots, zero at and above the run count: rmasks[r] = the OR of the members' masks; rchunks[r] chunk j from the representative
+ *              where it delivered it, else from the lowest-index member that did, else zeros; *n_runs = the run count. One run is one
+ *              displayed frame: this is the row to hand to cimbar_hip_deliver_chunks
+ *   runs_out, roles, rchunks, rmasks, n_runs  may each be NULL. Every output follows out_mem.
+ *   synchronisation  the host needs the length of list 1, and then of list 2, to size the decode launches: each call reads a 4-byte count
+ *              back after the run walk and (unless every capture is its own run) again after pass 1 -- at most two stream synchronisations
+ *              in the middle of the call, device outputs included. After that a device-output call enqueues the rest and returns 0; a
+ *              host-output call synchronises and returns the run count. This is the one place where these calls differ from "only enqueues".
+ *   known limit  two different frames whose colour streams are equal are taken for repeats, and the second is dropped (an uncompressed file
+ *              of constant bytes can do that). A fountain receiver survives a dropped frame; a caller who cannot accept the limit uses the
+ *              plain or the combined calls.
+ * Buffers, stream and errors otherwise as for cimbar_hip_decode_batch / cimbar_hip_scan_extract_decode_batch_fmt; a null chunks or masks,
+ * n <= 0 or a parameter out of range is CIMBAR_HIP_EINVAL, checked before anything is enqueued. Not covered: runs across calls, the
+ * pipelined and frame-async entry points, the combined / stitched calls, the undistort path and the auto-detection objects. */
+enum {
+	CIMBAR_HIP_ONCE_UNUSABLE = -1,
+	CIMBAR_HIP_ONCE_SKIPPED = 0,
+	CIMBAR_HIP_ONCE_REPRESENTATIVE = 1,
+	CIMBAR_HIP_ONCE_FALLBACK = 2
+};
+int64_t cimbar_hip_decode_batch_once(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rgb_mem, int should_preprocess, int color_correction,
+                                     int min_agree_permille, int max_run, uint8_t* chunks, uint32_t* masks, int* runs_out, int* roles,
+                                     uint8_t* rchunks, uint32_t* rmasks, int* n_runs, int out_mem, void* hip_stream);
+int64_t cimbar_hip_scan_extract_decode_batch_once_fmt(cimbar_hip_ctx* ctx, const uint8_t* img, unsigned width, unsigned height, int format, int n,
+                                                      int img_mem, int preprocess, int color_correction, int min_agree_permille, int max_run,
+                                                      uint8_t* chunks, uint32_t* masks, int* status, int* runs_out, int* roles, uint8_t* rchunks,
+                                                      uint32_t* rmasks, int* n_runs, int out_mem, void* hip_stream);
+
 /* ---- chunk delivery: a batch's slots and masks -> what a fountain sink eats --------------------------------------------------------------
  * The batch entry points above report a frame's chunks in fixed slots plus one mask word. The reference's receive interface has another shape:
  * cimbard_scan_extract_decode returns the delivered chunks packed front to back (escrow_buffer_writer), and cimbard_fountain_decode(buf, size)
@@ -811,9 +865,13 @@ enum {
 	CIMBAR_HIP_TAP_SCAN_HIST = 25,      /* n * 256 u32         : the histogram of each plane */
 	CIMBAR_HIP_TAP_SCAN_THRESHOLD = 26, /* n int32             : the Otsu threshold of each histogram; the search reads gray > threshold */
 	/* the relaxed flood of the last batch (cimbar_hip_set_relaxed_flood) */
-	CIMBAR_HIP_TAP_FLOOD_ROUNDS = 27    /* n u32               : rounds | cells decoded << 16 of every frame flooded in rounds -- also of one that was
+	CIMBAR_HIP_TAP_FLOOD_ROUNDS = 27,   /* n u32              : rounds | cells decoded << 16 of every frame flooded in rounds -- also of one that was
 	                                       then handed to the exact replay (CIMBAR_HIP_TAP_FLOOD_PATH 1); 0 for every other frame, and for every
 	                                       frame of a batch that ran with the setting off */
+	/* the grouping of the last once-call (cimbar_hip_decode_batch_once / _scan_extract_decode_batch_once_fmt; n = its captures;
+	 * CIMBAR_HIP_EINVAL before any) */
+	CIMBAR_HIP_TAP_REPEAT_SIG = 28,     /* n * cells bytes     : sig_c, 0..3, by linear cell index */
+	CIMBAR_HIP_TAP_REPEAT_AGREE = 29    /* (n - 1) u32         : agree(k, k + 1) */
 };
 int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_bytes);
 

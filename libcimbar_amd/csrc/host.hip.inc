@@ -65,6 +65,14 @@ struct cimbar_hip_ctx {
 	int stitch_S = 1;                           // the strips of the last stitched batch (> 1: the strip taps describe it)
 	DevBuf<int32_t> d_sstrips; DevBuf<uint16_t> d_sstrip_lines;   // [rows][S][4], [rows][S][L]: allocated by the first stitched call with strips > 1
 	DevBuf<uint8_t> d_schunks; DevBuf<uint32_t> d_smasks;   // staging for host-memory stitch outputs
+	// repeat-capture skipping (cimbar_hip_decode_batch_once / _scan_extract_decode_batch_once_fmt, repeat.hip.inc): per capture, grown on demand;
+	// the gathered frames and their results are sized by the longer of a call's two lists
+	int rp_n = 0;                               // the last once-call had that many captures (> 0: the repeat taps describe it)
+	DevBuf<ushort4> d_rp_sums; DevBuf<uint8_t> d_rp_sig; DevBuf<uint32_t> d_rp_agree;   // [n][NCELLS], [n][NCELLS], [n]
+	DevBuf<int> d_rp_runs, d_rp_mem, d_rp_count, d_rp_roles, d_rp_list, d_rp_sel;        // [n], [n][GMAX], [n], [n], [2][n] lists 1 and 2, [list] scan status
+	DevBuf<int> d_rp_words; PinnedBuf<int> h_rp_words;                                   // [0] runs = the length of list 1, [1] the length of list 2
+	DevBuf<uint8_t> d_rp_frames, d_rp_chunks; DevBuf<uint32_t> d_rp_masks;               // [list] gathered frames and what their decode delivered
+	DevBuf<uint8_t> d_rp_rchunks; DevBuf<uint32_t> d_rp_rmasks;                          // staging for host-memory run outputs
 	int wave_adapt = 1;               // CIMBAR_HIP_FLOOD_WAVE_ADAPT=0: run k_flood_wave in front of every exact replay, whatever it achieved before
 	bool wave_ran = false;            // k_flood_wave ran in the batch h_flagged describes
 	int wave_skip_left = 0;           // batches that still go straight to the exact replay (see enqueue)
@@ -2050,6 +2058,197 @@ int64_t cimbar_hip_scan_extract_decode_batch(cimbar_hip_ctx* ctx, const uint8_t*
 	return cimbar_hip_scan_extract_decode_batch_fmt(ctx, rgb, width, height, FMT_RGB, n, rgb_mem, preprocess, color_correction, chunks, masks, status, out_mem, hip_stream);
 }
 
+namespace {
+
+// ------------------------------------------------------------------------------------------------ repeat-capture skipping (repeat.hip.inc)
+struct OnceArgs {
+	int min_agree, max_run;   // resolved by check_once (900 / 4 for <= 0)
+	int* runs_out; int* roles; uint8_t* rchunks; uint32_t* rmasks; int* n_runs;   // each may be nullptr
+};
+
+// the argument checks of the once entry points, before anything is enqueued
+int check_once(cimbar_hip_ctx* ctx, const char* who, OnceArgs& oa)
+{
+	if (LEGACY) { ctx->err = std::string(who) + ": modes 4 and 8 are not covered; the ink signature was checked on the palettes of modes 68 / 67 / 66"; return CIMBAR_HIP_EINVAL; }
+	if (oa.min_agree > 1000) { ctx->err = std::string(who) + ": min_agree_permille above 1000"; return CIMBAR_HIP_EINVAL; }
+	if (oa.max_run > GMAX) { ctx->err = std::string(who) + ": max_run above 8"; return CIMBAR_HIP_EINVAL; }
+	if (oa.min_agree <= 0) oa.min_agree = RP_AGREE_DEFAULT;
+	if (oa.max_run <= 0) oa.max_run = RP_RUN_DEFAULT;
+	return 0;
+}
+
+// room for the gathered frames of a list of `len` captures and for what their decode delivers
+int ensure_once_list(cimbar_hip_ctx* ctx, int len)
+{
+	HIPCHK(ctx->d_rp_frames.reserve((size_t)len * FRAME_RGB));
+	HIPCHK(ctx->d_rp_chunks.reserve((size_t)len * FRAME_BYTES));
+	HIPCHK(ctx->d_rp_masks.reserve((size_t)len));
+	HIPCHK(ctx->d_rp_sel.reserve((size_t)len));
+	return 0;
+}
+
+// the 4-byte count d_rp_words[which], read back behind everything enqueued on `st` so far
+int once_read_count(cimbar_hip_ctx* ctx, hipStream_t st, int which, int* out)
+{
+	HIPCHK(hipMemcpyAsync(ctx->h_rp_words + which, ctx->d_rp_words + which, sizeof(int), hipMemcpyDeviceToHost, st));
+	HIPCHK(hipStreamSynchronize(st));
+	*out = ((volatile int*)ctx->h_rp_words.get())[which];
+	return 0;
+}
+
+// Everything behind the input: n device-resident frames d_frames (the caller's, or the warp's), d_status = the capture path's extraction status
+// (stride ints apart; nullptr: every frame usable, sharpening by `pre`). R1-R5 and G2, the read-back of the run count, pass 1, the read-back
+// of list 2's length, pass 2, R8 and the outputs. pre / guess as scan_extract_decode_impl resolves them.
+int64_t once_impl(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_frames, int n, const int* d_status, int stride, int pre, bool guess, int cc,
+                  uint8_t* chunks, uint32_t* masks, const OnceArgs& oa, int out_mem)
+{
+	const size_t N = (size_t)n;
+	const bool dev = out_mem == CIMBAR_HIP_MEM_DEVICE, capture = d_status != nullptr;
+	HIPCHK(ctx->d_rp_sums.reserve(N * NCELLS));
+	HIPCHK(ctx->d_rp_sig.reserve(N * NCELLS));
+	HIPCHK(ctx->d_rp_agree.reserve(N));
+	HIPCHK(ctx->d_rp_runs.reserve(N));
+	HIPCHK(ctx->d_rp_mem.reserve(N * GMAX));
+	HIPCHK(ctx->d_rp_count.reserve(N));
+	HIPCHK(ctx->d_rp_roles.reserve(N));
+	HIPCHK(ctx->d_rp_list.reserve(2 * N));
+	HIPCHK(ctx->d_rp_words.ensure(2));
+	HIPCHK(ctx->h_rp_words.ensure(2));
+	// host-bound per-capture results go through the staging every batch call uses; it must hold all n slots whatever the passes' sizes
+	HIPCHK(ctx->d_chunks.reserve(N * FRAME_BYTES));
+	HIPCHK(ctx->d_masks.reserve(N));
+	uint8_t* d_chunks = dev ? chunks : ctx->d_chunks.get();
+	uint32_t* d_masks = dev ? masks : ctx->d_masks.get();
+	ctx->rp_n = 0;
+
+	hipLaunchKernelGGL(k_repeat_sums, dim3(DIM_Y, n), dim3(256), 0, st, d_frames, ctx->tb, ctx->d_rp_sums);
+	hipLaunchKernelGGL(k_repeat_sig, dim3(n), dim3(256), 0, st, ctx->d_rp_sums, ctx->d_rp_sig);
+	if (n > 1) hipLaunchKernelGGL(k_repeat_agree, dim3(n - 1), dim3(256), 0, st, ctx->d_rp_sig, n, ctx->d_rp_agree);
+	HIPCHK(hipMemsetAsync(ctx->d_rp_count, 0, sizeof(int) * N, st));
+	HIPCHK(hipMemsetAsync(ctx->d_rp_words, 0, sizeof(int) * 2, st));
+	hipLaunchKernelGGL(k_group_walk, dim3(1), dim3(64), 0, st, ctx->d_rp_agree, n, d_status, stride, (const int*)nullptr, oa.min_agree, oa.max_run,
+	                   ctx->d_rp_runs, ctx->d_rp_mem, ctx->d_rp_count, ctx->d_rp_words);
+	hipLaunchKernelGGL(k_repeat_lists, dim3((n + 255) / 256), dim3(256), 0, st, ctx->d_rp_runs, ctx->d_rp_mem, ctx->d_rp_count, n, ctx->d_rp_roles, ctx->d_rp_list);
+	HIPCHK(hipGetLastError());
+	int len1 = 0, len2 = 0;
+	if (int r = once_read_count(ctx, st, 0, &len1)) return r;
+	if (len1 < 0 || len1 > n) { ctx->err = "decode_batch_once: the run count read back is out of range"; return CIMBAR_HIP_EHIP; }
+
+	// one decode pass over `len` listed captures: gather, enqueue() as one plain batch of the entry point's kind, scatter
+	auto pass = [&](const int* d_list, int len) -> int {
+		if (int r = ensure_once_list(ctx, len)) return r;
+		if (int r = ensure_capacity(ctx, len)) return r;
+		hipLaunchKernelGGL(k_repeat_gather, dim3(96, len), dim3(256), 0, st, d_frames, d_list, ctx->d_rp_frames, guess ? d_status : (const int*)nullptr, stride, ctx->d_rp_sel);
+		ctx->no_split_once = capture;
+		const int er = enqueue(ctx, st, ctx->d_rp_frames, len, pre, cc, ctx->d_rp_chunks, ctx->d_rp_masks, 0, false, guess ? ctx->d_rp_sel.get() : nullptr, 1);
+		ctx->no_split_once = false;
+		if (er) return er;
+		hipLaunchKernelGGL(k_repeat_scatter, dim3(len), dim3(256), 0, st, d_list, ctx->d_rp_chunks, ctx->d_rp_masks, d_chunks, d_masks);
+		HIPCHK(hipGetLastError());
+		return 0;
+	};
+	if (len1 == n) {
+		// every capture is its own run: pass 1 decodes the input in place, and there is nobody for a pass 2
+		if (int r = ensure_capacity(ctx, n)) return r;
+		ctx->no_split_once = capture;
+		const int er = enqueue(ctx, st, d_frames, n, pre, cc, d_chunks, d_masks, 0, false, guess ? d_status : nullptr, stride);
+		ctx->no_split_once = false;
+		if (er) return er;
+	} else {
+		hipLaunchKernelGGL(k_repeat_clear, dim3(n), dim3(256), 0, st, ctx->d_rp_roles, d_chunks, d_masks);
+		if (len1 > 0) {
+			if (int r = pass(ctx->d_rp_list, len1)) return r;
+			hipLaunchKernelGGL(k_repeat_lists2, dim3(1), dim3(64), 0, st, ctx->d_rp_runs, ctx->d_rp_masks, n, ctx->d_rp_roles, ctx->d_rp_list + n, ctx->d_rp_words + 1);
+			HIPCHK(hipGetLastError());
+			if (int r = once_read_count(ctx, st, 1, &len2)) return r;
+			if (len2 < 0 || len2 > n - len1) { ctx->err = "decode_batch_once: the fallback count read back is out of range"; return CIMBAR_HIP_EHIP; }
+			if (len2 > 0) if (int r = pass(ctx->d_rp_list + n, len2)) return r;
+		}
+	}
+	uint8_t* d_rchunks = oa.rchunks;
+	uint32_t* d_rmasks = oa.rmasks;
+	if (!dev) {
+		if (oa.rchunks) { HIPCHK(ctx->d_rp_rchunks.reserve(N * FRAME_BYTES)); d_rchunks = ctx->d_rp_rchunks; }
+		if (oa.rmasks) { HIPCHK(ctx->d_rp_rmasks.reserve(N)); d_rmasks = ctx->d_rp_rmasks; }
+	}
+	if (d_rchunks || d_rmasks)
+		hipLaunchKernelGGL(k_repeat_end, dim3(n), dim3(256), 0, st, ctx->d_rp_mem, ctx->d_rp_count, ctx->d_rp_words, d_chunks, d_masks, d_rchunks, d_rmasks);
+	HIPCHK(hipGetLastError());
+	const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+	if (oa.runs_out) HIPCHK(hipMemcpyAsync(oa.runs_out, ctx->d_rp_runs, sizeof(int) * N, kind, st));
+	if (oa.roles) HIPCHK(hipMemcpyAsync(oa.roles, ctx->d_rp_roles, sizeof(int) * N, kind, st));
+	ctx->rp_n = n;
+	if (dev) {
+		if (oa.n_runs) HIPCHK(hipMemcpyAsync(oa.n_runs, ctx->d_rp_words, sizeof(int), kind, st));
+		return 0;
+	}
+	HIPCHK(hipMemcpyAsync(chunks, d_chunks, N * FRAME_BYTES, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipMemcpyAsync(masks, d_masks, sizeof(uint32_t) * N, hipMemcpyDeviceToHost, st));
+	if (oa.rchunks) HIPCHK(hipMemcpyAsync(oa.rchunks, d_rchunks, N * FRAME_BYTES, hipMemcpyDeviceToHost, st));
+	if (oa.rmasks) HIPCHK(hipMemcpyAsync(oa.rmasks, d_rmasks, sizeof(uint32_t) * N, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipStreamSynchronize(st));
+	if (oa.n_runs) *oa.n_runs = len1;
+	return len1;
+}
+
+}  // namespace
+
+int64_t cimbar_hip_decode_batch_once(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rgb_mem, int should_preprocess, int color_correction,
+                                     int min_agree_permille, int max_run, uint8_t* chunks, uint32_t* masks, int* runs_out, int* roles,
+                                     uint8_t* rchunks, uint32_t* rmasks, int* n_runs, int out_mem, void* hip_stream)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	const char* who = "decode_batch_once";
+	OnceArgs oa{min_agree_permille, max_run, runs_out, roles, rchunks, rmasks, n_runs};
+	if (int r = check_once(ctx, who, oa)) return r;
+	if (!rgb || !chunks || !masks || n <= 0) { ctx->err = std::string(who) + ": null buffer or n <= 0"; return CIMBAR_HIP_EINVAL; }
+	if ((rgb_mem != CIMBAR_HIP_MEM_HOST && rgb_mem != CIMBAR_HIP_MEM_DEVICE) || (out_mem != CIMBAR_HIP_MEM_HOST && out_mem != CIMBAR_HIP_MEM_DEVICE)) {
+		ctx->err = std::string(who) + ": rgb_mem / out_mem must be CIMBAR_HIP_MEM_HOST or CIMBAR_HIP_MEM_DEVICE";
+		return CIMBAR_HIP_EINVAL;
+	}
+	HIPCHK(hipSetDevice(ctx->device));
+	const bool any_device = rgb_mem == CIMBAR_HIP_MEM_DEVICE || out_mem == CIMBAR_HIP_MEM_DEVICE;
+	hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (any_device ? (hipStream_t)nullptr : ctx->stream);
+	if (int r = drain_pipeline_into(ctx, st)) return r;
+	const uint8_t* d_rgb = nullptr;
+	if (int r = stage_input(ctx, st, ctx->d_rgb, rgb, (size_t)n * FRAME_RGB, rgb_mem, &d_rgb)) return r;
+	return once_impl(ctx, st, d_rgb, n, nullptr, 0, should_preprocess, false, color_correction, chunks, masks, oa, out_mem);
+}
+
+int64_t cimbar_hip_scan_extract_decode_batch_once_fmt(cimbar_hip_ctx* ctx, const uint8_t* img, unsigned width, unsigned height, int format, int n,
+                                                      int img_mem, int preprocess, int color_correction, int min_agree_permille, int max_run,
+                                                      uint8_t* chunks, uint32_t* masks, int* status, int* runs_out, int* roles, uint8_t* rchunks,
+                                                      uint32_t* rmasks, int* n_runs, int out_mem, void* hip_stream)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	const char* who = "scan_extract_decode_batch_once";
+	OnceArgs oa{min_agree_permille, max_run, runs_out, roles, rchunks, rmasks, n_runs};
+	if (int r = check_once(ctx, who, oa)) return r;
+	if (!img || !chunks || !masks || n <= 0 || width < 8 || height < 8) { ctx->err = std::string(who) + ": null buffer, n <= 0 or a capture smaller than 8x8"; return CIMBAR_HIP_EINVAL; }
+	if ((img_mem != CIMBAR_HIP_MEM_HOST && img_mem != CIMBAR_HIP_MEM_DEVICE) || (out_mem != CIMBAR_HIP_MEM_HOST && out_mem != CIMBAR_HIP_MEM_DEVICE)) {
+		ctx->err = std::string(who) + ": img_mem / out_mem must be CIMBAR_HIP_MEM_HOST or CIMBAR_HIP_MEM_DEVICE";
+		return CIMBAR_HIP_EINVAL;
+	}
+	int fmt; size_t cbytes;
+	if (int r = check_capture(ctx, who, width, height, format, &fmt, &cbytes)) return r;
+	HIPCHK(hipSetDevice(ctx->device));
+	const bool any_device = img_mem == CIMBAR_HIP_MEM_DEVICE || out_mem == CIMBAR_HIP_MEM_DEVICE;
+	hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (any_device ? (hipStream_t)nullptr : ctx->stream);
+	if (int r = drain_pipeline_into(ctx, st)) return r;
+	if (int r = extract_state(ctx, n)) return r;
+	const uint8_t* d_in = nullptr;
+	if (int r = stage_input(ctx, st, ctx->d_ex_in, img, cbytes * n, img_mem, &d_in)) return r;
+	HIPCHK(ctx->d_ex_frames.reserve((size_t)n * FRAME_RGB));
+	// extraction runs for every capture, repeats included: the runs are found on the deskewed frames
+	if (int r = enqueue_scan(ctx, st, d_in, width, height, fmt, n)) return r;
+	if (int r = launch_warp_ctx(ctx, st, fmt, d_in, width, height, n, ctx->d_ex_minv, ctx->d_ex_frames)) return r;
+	const hipMemcpyKind kind = out_mem == CIMBAR_HIP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+	if (status) HIPCHK(hipMemcpy2DAsync(status, sizeof(int), &ctx->d_scan_res[0].status, sizeof(ScanResult), sizeof(int), (size_t)n, kind, st));
+	const bool guess = preprocess != 0 && preprocess != 1;
+	return once_impl(ctx, st, ctx->d_ex_frames, n, &ctx->d_scan_res[0].status, (int)(sizeof(ScanResult) / sizeof(int)), preprocess == 1 ? 1 : 0, guess,
+	                 color_correction, chunks, masks, oa, out_mem);
+}
+
 int cimbar_hip_set_template(cimbar_hip_ctx* ctx, const uint8_t* rgb_template, int mem)
 {
 	if (!ctx || !rgb_template) return CIMBAR_HIP_EINVAL;
@@ -2301,6 +2500,17 @@ int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_byte
 		HIPCHK(hipMemcpy(out, s.symbols + (size_t)s.cur * SS_CELLS, NCELLS, hipMemcpyDeviceToHost));
 		HIPCHK(hipMemcpy((uint8_t*)out + NCELLS, s.colors + (size_t)s.cur * SS_CELLS, NCELLS, hipMemcpyDeviceToHost));
 		return (int64_t)2 * NCELLS;
+	}
+	if (what == CIMBAR_HIP_TAP_REPEAT_SIG || what == CIMBAR_HIP_TAP_REPEAT_AGREE) {
+		// what the last once-call grouped its captures by (its n, not the length of the list its last pass decoded)
+		if (ctx->rp_n <= 0) { ctx->err = "tap: no once-call has run on this context yet (cimbar_hip_decode_batch_once / _scan_extract_decode_batch_once_fmt)"; return CIMBAR_HIP_EINVAL; }
+		const size_t m = (size_t)ctx->rp_n;
+		const size_t bytes = what == CIMBAR_HIP_TAP_REPEAT_SIG ? m * NCELLS : (m - 1) * sizeof(uint32_t);
+		if (out_bytes < bytes) { ctx->err = "tap: buffer too small"; return CIMBAR_HIP_EINVAL; }
+		HIPCHK(hipSetDevice(ctx->device));
+		HIPCHK(hipDeviceSynchronize());
+		if (bytes) HIPCHK(hipMemcpy(out, what == CIMBAR_HIP_TAP_REPEAT_SIG ? (const void*)ctx->d_rp_sig.get() : (const void*)ctx->d_rp_agree.get(), bytes, hipMemcpyDeviceToHost));
+		return (int64_t)bytes;
 	}
 	if (ctx->last_n <= 0) { ctx->err = "tap: no batch has been decoded on this context yet"; return CIMBAR_HIP_EINVAL; }
 	HIPCHK(hipSetDevice(ctx->device));

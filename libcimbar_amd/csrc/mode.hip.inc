@@ -108,6 +108,7 @@ struct Tables {
 #include "erasure.hip.inc"
 #include "combine.hip.inc"
 #include "stitch.hip.inc"
+#include "repeat.hip.inc"
 #include "k1_padded.hip.inc"
 #include "encode.hip.inc"
 #include "extract.hip.inc"

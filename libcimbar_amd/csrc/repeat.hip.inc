@@ -1,0 +1,218 @@
+// repeat.hip.inc -- part of cimbar_hip.hip (one translation unit; included inside its anonymous namespace, after stitch.hip.inc).
+// R1-R8: repeat-capture skipping -- a run of captures that show one displayed frame is decoded once, the rest only if that decode is incomplete
+// ------------------------------------------------------------------------------------------------ the rule
+// A camera films the display faster than it changes, so every frame arrives as a run of near-identical captures. The combined calls find such
+// runs from the DECODED cells; cimbar_hip_decode_batch_once / _scan_extract_decode_batch_once_fmt find them in front of the decode, from a
+// signature of the ink colours that needs no symbol, no drift and no colour matrix (modes 68 / 67 / 66: four palette colours on black):
+//   sums       cell c of a frame, nominal top-left (x, y) = cell_xy[c]: R_c, G_c, B_c = the channel sums over pixel rows y + 2 .. y + 5 and
+//              columns x .. x + 7 (32 pixels), S_c = R_c + G_c + B_c. Rows 3..4 alone would not do: some tiles have no ink there.
+//   totals     R_A, B_A, S_A = the sums of R_c, B_c, S_c over the frame's NCELLS cells
+//   sig_c      [R_c S_A > S_c R_A] | [B_c S_A > S_c B_A] << 1 -- "redder than the frame" and "bluer than the frame"; strict, unsigned 64 bit
+//              (the products stay below 2^43). The frame is read as handed in, or as the warp wrote it: sharpening plays no part.
+//   agree      agree(k, k + 1) = the cells with equal sig
+//   runs       k_group_walk's walk (combine.hip.inc) over that agree array: capture k starts a run when it is the first, when
+//              agree(k - 1, k) * 1000 < min_agree_permille * NCELLS, when the run before it already has max_run members, or when capture
+//              k - 1 or k is unusable (capture path: extraction failed). An unusable capture is in no run.
+//   rep        member (len - 1) / 2 of a run: the first of two, the second of three or four
+//   pass 1     the representatives, gathered in capture order, through enqueue() as one plain batch
+//   pass 2     the other members of every run whose representative's mask is not full, likewise; no such member: no second pass
+//   per run    rmask = the OR of the members' masks; chunk j from the representative where it delivered it, else from the lowest-index
+//              member that did, else zeros
+//   R1 k_repeat_sums     (cell rows x frames) workgroups: the four needed pixel rows of a cell row, 16 bytes per lane, through LDS to (R, S, B)
+//   R2 k_repeat_sig      one workgroup per frame: the totals by a fixed-order block reduction (no atomics), then sig, one byte per cell
+//   R3 k_repeat_agree    one workgroup per adjacent pair
+//   G2 k_group_walk      as it is
+//   R4 k_repeat_lists    roles and list 1 (the representatives) from the walk's members; R5 k_repeat_lists2: list 2 from list 1's masks
+//   R6 k_repeat_gather   listed frames (capture path: and their scan status, for the per-frame sharpen choice) into a context-owned buffer
+//   R7 k_repeat_clear / k_repeat_scatter   zeroes for what no pass has decoded yet; a pass's chunks and masks back into capture slots
+//   R8 k_repeat_end      the per-run fill
+// The host reads the length of list 1, and then of list 2, back to size the decode launches (host.hip.inc, once_impl).
+constexpr int RP_AGREE_DEFAULT = 900, RP_RUN_DEFAULT = 4;
+constexpr int RP_ROW0 = 2, RP_ROWS = 4;                                  // pixel rows y + 2 .. y + 5 of a cell
+constexpr int RP_ROW_BYTES = IMG_W * 3, RP_ROW_VEC = RP_ROW_BYTES / 16;   // 3072 | 2208 bytes: 192 | 138 16-byte loads
+constexpr int RP_LOADS = (RP_ROWS * RP_ROW_VEC + 255) / 256;             // per lane: 3
+static_assert(RP_ROW_BYTES % 16 == 0 && FRAME_RGB % 16 == 0, "pixel rows start on 16-byte boundaries");
+static_assert(2 * DIM_X <= 256, "two lanes per cell of a cell row");
+static_assert(OFFSET + PITCH * (DIM_Y - 1) + RP_ROW0 + RP_ROWS <= IMG_H && OFFSET + PITCH * (DIM_X - 1) + 8 <= IMG_W, "the last cell's rows and columns lie inside the frame");
+
+enum { RP_ROLE_UNUSABLE = CIMBAR_HIP_ONCE_UNUSABLE, RP_ROLE_SKIPPED = CIMBAR_HIP_ONCE_SKIPPED, RP_ROLE_REP = CIMBAR_HIP_ONCE_REPRESENTATIVE, RP_ROLE_FALLBACK = CIMBAR_HIP_ONCE_FALLBACK };
+
+// R1: workgroup (cr, f) reads pixel rows OFFSET + PITCH cr + 2 .. + 5 of frame f whole -- 4 x RP_ROW_VEC coalesced 16-byte loads -- into LDS;
+// then lanes 2c and 2c + 1 sum two of the four rows of grid column c each. sums[f][cell] = {R, S, B, 0}, by linear cell index; the grid
+// slots inside the corner cut-outs (grid_cell < 0) are dropped.
+__global__ __launch_bounds__(256) void k_repeat_sums(const uint8_t* __restrict__ rgb, Tables tb, ushort4* __restrict__ sums)
+{
+	__shared__ __attribute__((aligned(16))) uint8_t s_px[RP_ROWS][RP_ROW_BYTES];
+	const int cr = blockIdx.x, f = blockIdx.y, t = threadIdx.x;
+	const uint8_t* frame = rgb + (size_t)f * FRAME_RGB + (size_t)(OFFSET + PITCH * cr + RP_ROW0) * RP_ROW_BYTES;
+	uint4 v[RP_LOADS];
+#pragma unroll
+	for (int i = 0; i < RP_LOADS; ++i) {
+		const int idx = t + 256 * i;
+		if (idx < RP_ROWS * RP_ROW_VEC) v[i] = reinterpret_cast<const uint4*>(frame)[idx];   // (the four rows are consecutive in memory)
+	}
+#pragma unroll
+	for (int i = 0; i < RP_LOADS; ++i) {
+		const int idx = t + 256 * i;
+		if (idx < RP_ROWS * RP_ROW_VEC) reinterpret_cast<uint4*>(&s_px[0][0])[idx] = v[i];
+	}
+	__syncthreads();
+	const int c = t >> 1, h = t & 1;
+	uint32_t r = 0, g = 0, b = 0;
+	if (c < DIM_X) {
+		const int x0 = (OFFSET + PITCH * c) * 3;
+#pragma unroll
+		for (int row = 0; row < 2; ++row) {
+			const uint8_t* p = &s_px[2 * h + row][x0];
+#pragma unroll
+			for (int px = 0; px < 8; ++px) { r += p[3 * px]; g += p[3 * px + 1]; b += p[3 * px + 2]; }
+		}
+	}
+	r += __shfl_xor(r, 1); g += __shfl_xor(g, 1); b += __shfl_xor(b, 1);
+	if (c < DIM_X && h == 0) {
+		const int cell = tb.grid_cell[cr * DIM_X + c];
+		if (cell >= 0) sums[(size_t)f * NCELLS + cell] = make_ushort4((unsigned short)r, (unsigned short)(r + g + b), (unsigned short)b, 0);
+	}
+}
+
+// R2: one workgroup per frame. The totals are sums of integers below 2^29 in a fixed order; sig[f][cell] in 0..3.
+__global__ __launch_bounds__(256) void k_repeat_sig(const ushort4* __restrict__ sums, uint8_t* __restrict__ sig)
+{
+	const int f = blockIdx.x;
+	const ushort4* s = sums + (size_t)f * NCELLS;
+	uint32_t r = 0, t = 0, b = 0;
+	for (int c = threadIdx.x; c < NCELLS; c += 256) { const ushort4 v = s[c]; r += v.x; t += v.y; b += v.z; }
+	for (int o = 32; o >= 1; o >>= 1) { r += __shfl_xor(r, o); t += __shfl_xor(t, o); b += __shfl_xor(b, o); }
+	__shared__ uint32_t s_part[3][4];
+	if ((threadIdx.x & 63) == 0) { s_part[0][threadIdx.x >> 6] = r; s_part[1][threadIdx.x >> 6] = t; s_part[2][threadIdx.x >> 6] = b; }
+	__syncthreads();
+	const unsigned long long RA = (unsigned long long)s_part[0][0] + s_part[0][1] + s_part[0][2] + s_part[0][3];
+	const unsigned long long SA = (unsigned long long)s_part[1][0] + s_part[1][1] + s_part[1][2] + s_part[1][3];
+	const unsigned long long BA = (unsigned long long)s_part[2][0] + s_part[2][1] + s_part[2][2] + s_part[2][3];
+	for (int c = threadIdx.x; c < NCELLS; c += 256) {
+		const ushort4 v = s[c];
+		const uint32_t red = (unsigned long long)v.x * SA > (unsigned long long)v.y * RA ? 1u : 0u;
+		const uint32_t blue = (unsigned long long)v.z * SA > (unsigned long long)v.y * BA ? 2u : 0u;
+		sig[(size_t)f * NCELLS + c] = (uint8_t)(red | blue);
+	}
+}
+
+// R3: one workgroup per pair (k, k + 1), k < n - 1: the cells with equal sig
+__global__ __launch_bounds__(256) void k_repeat_agree(const uint8_t* __restrict__ sig, int n, uint32_t* __restrict__ agree)
+{
+	const int k = blockIdx.x;
+	if (k + 1 >= n) return;
+	const uint32_t* a = reinterpret_cast<const uint32_t*>(sig + (size_t)k * NCELLS);
+	const uint32_t* b = a + NCELLS / 4;
+	uint32_t cnt = 0;
+	for (int w = threadIdx.x; w < NCELLS / 4; w += 256) {
+		const uint32_t x = a[w] ^ b[w];
+		cnt += ((x & 0xFFu) == 0u) + ((x & 0xFF00u) == 0u) + ((x & 0xFF0000u) == 0u) + ((x >> 24) == 0u);
+	}
+	for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o);
+	__shared__ uint32_t s_part[4];
+	if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = cnt;
+	__syncthreads();
+	if (threadIdx.x == 0) agree[k] = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+}
+
+// the representative of run r: member (len - 1) / 2
+__device__ __forceinline__ int repeat_rep(const int* __restrict__ rmem, const int* __restrict__ rcount, int r) { return rmem[(size_t)r * GMAX + (rcount[r] - 1) / 2]; }
+
+// R4: one lane per capture. roles[k] = -1 in no run, 1 the representative of its run, else 0; list1[r] = the representative of run r (the runs
+// are numbered in capture order, so list 1 is in capture order too)
+__global__ __launch_bounds__(256) void k_repeat_lists(const int* __restrict__ runs, const int* __restrict__ rmem, const int* __restrict__ rcount, int n,
+                                                      int* __restrict__ roles, int* __restrict__ list1)
+{
+	const int k = blockIdx.x * 256 + threadIdx.x;
+	if (k >= n) return;
+	const int r = runs[k];
+	if (r < 0) { roles[k] = RP_ROLE_UNUSABLE; return; }
+	const bool rep = repeat_rep(rmem, rcount, r) == k;
+	roles[k] = rep ? RP_ROLE_REP : RP_ROLE_SKIPPED;
+	if (rep) list1[r] = k;
+}
+
+// R5: one wavefront, 64 captures per step. A skipped capture whose run's representative came back with an incomplete mask (rep_masks[r]: pass
+// 1's masks, by run) takes role 2 and joins list 2, in capture order; *count2 = its length.
+__global__ __launch_bounds__(64) void k_repeat_lists2(const int* __restrict__ runs, const uint32_t* __restrict__ rep_masks, int n, int* __restrict__ roles,
+                                                      int* __restrict__ list2, int* __restrict__ count2)
+{
+	const int lane = threadIdx.x;
+	const unsigned long long below = (1ull << lane) - 1ull;
+	constexpr uint32_t FULL = (1u << CHUNKS) - 1u;
+	int base = 0;
+	for (int k0 = 0; k0 < n; k0 += 64) {
+		const int k = k0 + lane;
+		bool take = false;
+		if (k < n && roles[k] == RP_ROLE_SKIPPED) take = (rep_masks[runs[k]] & FULL) != FULL;
+		const unsigned long long tb = __ballot(take);
+		if (take) { roles[k] = RP_ROLE_FALLBACK; list2[base + (int)__popcll(tb & below)] = k; }
+		base += (int)__popcll(tb);
+	}
+	if (lane == 0) *count2 = base;
+}
+
+// R6: frame list[j] -> dst frame j, j = blockIdx.y; sel_out[j] = that capture's scan status (status == nullptr: none)
+__global__ __launch_bounds__(256) void k_repeat_gather(const uint8_t* __restrict__ rgb, const int* __restrict__ list, uint8_t* __restrict__ dst,
+                                                       const int* __restrict__ status, int stride, int* __restrict__ sel_out)
+{
+	const int j = blockIdx.y, k = list[j];
+	const uint4* s = reinterpret_cast<const uint4*>(rgb + (size_t)k * FRAME_RGB);
+	uint4* d = reinterpret_cast<uint4*>(dst + (size_t)j * FRAME_RGB);
+	constexpr int VEC = (int)(FRAME_RGB / 16);
+	for (int i = blockIdx.x * 256 + threadIdx.x; i < VEC; i += gridDim.x * 256) d[i] = s[i];
+	if (status && blockIdx.x == 0 && threadIdx.x == 0) sel_out[j] = status[(size_t)k * stride];
+}
+
+// R7: one workgroup per capture: everything but a representative is zero until a pass delivers it
+__global__ __launch_bounds__(256) void k_repeat_clear(const int* __restrict__ roles, uint8_t* __restrict__ chunks, uint32_t* __restrict__ masks)
+{
+	const int k = blockIdx.x;
+	if (roles[k] == RP_ROLE_REP) return;
+	if (threadIdx.x == 0) masks[k] = 0;
+	for (int i = threadIdx.x; i < FRAME_BYTES; i += 256) chunks[(size_t)k * FRAME_BYTES + i] = 0;
+}
+
+// ... and a pass's results, by list position j = blockIdx.x, into the slots of the captures they belong to
+__global__ __launch_bounds__(256) void k_repeat_scatter(const int* __restrict__ list, const uint8_t* __restrict__ src_chunks, const uint32_t* __restrict__ src_masks,
+                                                        uint8_t* __restrict__ chunks, uint32_t* __restrict__ masks)
+{
+	const int j = blockIdx.x, k = list[j];
+	if (threadIdx.x == 0) masks[k] = src_masks[j];
+	for (int i = threadIdx.x; i < FRAME_BYTES; i += 256) chunks[(size_t)k * FRAME_BYTES + i] = src_chunks[(size_t)j * FRAME_BYTES + i];
+}
+
+// R8: one workgroup per run slot r < n; slots at or above *nruns are zero. rchunks / rmasks may each be nullptr.
+__global__ __launch_bounds__(256) void k_repeat_end(const int* __restrict__ rmem, const int* __restrict__ rcount, const int* __restrict__ nruns,
+                                                    const uint8_t* __restrict__ chunks, const uint32_t* __restrict__ masks, uint8_t* __restrict__ rchunks,
+                                                    uint32_t* __restrict__ rmasks)
+{
+	const int r = blockIdx.x;
+	__shared__ int s_src[CHUNKS];
+	const bool live = r < *nruns;
+	if (threadIdx.x < CHUNKS) {
+		int src = -1;
+		if (live) {
+			const int cnt = rcount[r], rep = repeat_rep(rmem, rcount, r);
+			if ((masks[rep] >> threadIdx.x) & 1u) src = rep;
+			else
+				for (int m = 0; m < cnt && src < 0; ++m) {
+					const int k = rmem[(size_t)r * GMAX + m];
+					if ((masks[k] >> threadIdx.x) & 1u) src = k;
+				}
+		}
+		s_src[threadIdx.x] = src;
+	}
+	__syncthreads();
+	if (rmasks && threadIdx.x == 0) {
+		uint32_t m = 0;
+		if (live) for (int j = 0; j < rcount[r]; ++j) m |= masks[rmem[(size_t)r * GMAX + j]];
+		rmasks[r] = m;
+	}
+	if (!rchunks) return;
+	for (int i = threadIdx.x; i < FRAME_BYTES; i += 256) {
+		const int src = s_src[i / CHUNK];
+		rchunks[(size_t)r * FRAME_BYTES + i] = src >= 0 ? chunks[(size_t)src * FRAME_BYTES + i] : (uint8_t)0;
+	}
+}

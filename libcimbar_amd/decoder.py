@@ -34,6 +34,9 @@ COLOUR_MARGIN_SUGGESTED = 32512
 TAP_FLOOD_ROUNDS = 27   # the relaxed flood of the last batch (set_relaxed_flood): rounds | cells decoded << 16 per frame flooded in rounds
 # CIMBAR_HIP_RELAXED_FLOOD_SUGGESTED (include/cimbar_hip.h): the threshold of the table in DESIGN_WIDENING.md "Relaxed flood"
 RELAXED_FLOOD_SUGGESTED = 12
+TAP_REPEAT_SIG, TAP_REPEAT_AGREE = 28, 29   # the grouping of the last once-call (decode_batch_once): tap_repeat_sig / tap_repeat_agree
+# CIMBAR_HIP_ONCE_*: a capture's role in a once-call
+ONCE_UNUSABLE, ONCE_SKIPPED, ONCE_REPRESENTATIVE, ONCE_FALLBACK = -1, 0, 1, 2
 
 # every symbol include/cimbar_hip.h declares (tests/test_capi_symbols.py checks the header against this list and the .so)
 EXPORTS = (
@@ -63,6 +66,7 @@ EXPORTS = (
     "cimbar_hip_decode_batch_stitched_stream", "cimbar_hip_scan_extract_decode_batch_stitched_stream_fmt", "cimbar_hip_stitch_stream_reset",
     "cimbar_hip_set_stitch_strips", "cimbar_hip_get_stitch_strips",
     "cimbar_hip_set_relaxed_flood", "cimbar_hip_get_relaxed_flood", "cimbar_hip_relaxed_flood_stats",
+    "cimbar_hip_decode_batch_once", "cimbar_hip_scan_extract_decode_batch_once_fmt",
 )
 # cimbar_hip_deliver_chunks' flags
 DELIVER_DEDUP, DELIVER_REMEMBER, DELIVER_DROP_EMPTY = 1, 2, 4
@@ -195,6 +199,12 @@ def load_library(path=None):
         lib.cimbar_hip_set_stitch_strips.restype = i32
         lib.cimbar_hip_get_stitch_strips.argtypes = [vp, ctypes.POINTER(i32)]
         lib.cimbar_hip_get_stitch_strips.restype = i32
+    if hasattr(lib, "cimbar_hip_decode_batch_once"):   # (CIMBAR_HIP_LIB may name an older build for an A/B run)
+        lib.cimbar_hip_decode_batch_once.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp]
+        lib.cimbar_hip_decode_batch_once.restype = i64
+        lib.cimbar_hip_scan_extract_decode_batch_once_fmt.argtypes = [vp, vp, u32, u32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                                      i32, vp]
+        lib.cimbar_hip_scan_extract_decode_batch_once_fmt.restype = i64
     lib.cimbar_hip_combine_stream_reset.argtypes = [vp]
     lib.cimbar_hip_combine_stream_reset.restype = i32
     lib.cimbar_hip_auto_create.argtypes = [i32, vp, i32, ctypes.POINTER(vp)]
@@ -646,6 +656,56 @@ class HipDecoder:
             int(min_band), chunks.ctypes.data, masks.ctypes.data, status.ctypes.data, schunks.ctypes.data, smasks.ctypes.data, tears.ctypes.data,
             MEM_HOST, None), "cimbar_hip_scan_extract_decode_batch_stitched_fmt")
         return int(rc), chunks, masks, status, schunks, smasks, tears
+
+    def _once_outputs(self, n):
+        geo = self.geo
+        return (np.zeros((n, geo.CHUNKS_PER_FRAME, geo.CHUNK), dtype=np.uint8), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.int32),
+                np.zeros(n, dtype=np.int32), np.zeros((n, geo.CHUNKS_PER_FRAME, geo.CHUNK), dtype=np.uint8), np.zeros(n, dtype=np.uint32))
+
+    def decode_batch_once(self, frames, min_agree_permille=0, max_run=0, should_preprocess=False, color_correction=2):
+        """Repeat-capture skipping (cimbar_hip_decode_batch_once): frames as for decode_batch. Runs of captures of one displayed frame are found
+        from an ink-colour signature in front of the decode; one member of each run is decoded, the others only if that one is incomplete.
+        Returns (n_runs, chunks, masks, runs, roles, rchunks, rmasks): per capture its chunks / mask (zero for a skipped one), its run and its
+        role (ONCE_*), and n slots of run chunks / masks (zero from n_runs on)."""
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        n = frames.shape[0]
+        if frames.shape[1:] != self.geo.FRAME_SHAPE:
+            raise CimbarHipError(f"decode_batch_once: frames must be (n,{self.geo.IMG_H},{self.geo.IMG_W},3) uint8")
+        chunks, masks, runs, roles, rchunks, rmasks = self._once_outputs(n)
+        n_runs = ctypes.c_int(0)
+        rc = self._check(self._lib.cimbar_hip_decode_batch_once(self._ctx, frames.ctypes.data, n, MEM_HOST, int(bool(should_preprocess)),
+                                                                int(color_correction), int(min_agree_permille), int(max_run), chunks.ctypes.data,
+                                                                masks.ctypes.data, runs.ctypes.data, roles.ctypes.data, rchunks.ctypes.data,
+                                                                rmasks.ctypes.data, ctypes.addressof(n_runs), MEM_HOST, None),
+                         "cimbar_hip_decode_batch_once")
+        assert rc == n_runs.value
+        return int(rc), chunks, masks, runs, roles, rchunks, rmasks
+
+    def decode_batch_once_device(self, frames_ptr, n, chunks_ptr, masks_ptr, runs_ptr=None, roles_ptr=None, rchunks_ptr=None, rmasks_ptr=None,
+                                 n_runs_ptr=None, min_agree_permille=0, max_run=0, should_preprocess=False, color_correction=2, stream=None):
+        """Device pointers in and out (layouts as in include/cimbar_hip.h; the five run outputs may each be 0). Synchronises `stream` (None / 0 =
+        the null stream) at most twice to size its decode passes, enqueues the rest and returns 0."""
+        vp = ctypes.c_void_p
+        return int(self._check(self._lib.cimbar_hip_decode_batch_once(self._ctx, vp(frames_ptr), int(n), MEM_DEVICE, int(bool(should_preprocess)),
+                                                                      int(color_correction), int(min_agree_permille), int(max_run), vp(chunks_ptr),
+                                                                      vp(masks_ptr), vp(runs_ptr or None), vp(roles_ptr or None),
+                                                                      vp(rchunks_ptr or None), vp(rmasks_ptr or None), vp(n_runs_ptr or None),
+                                                                      MEM_DEVICE, vp(stream) if stream else None),
+                               "cimbar_hip_decode_batch_once(device)"))
+
+    def scan_extract_decode_batch_once(self, captures, min_agree_permille=0, max_run=0, preprocess=-1, color_correction=2, size=None, fmt=3):
+        """The capture path with repeat-capture skipping (cimbar_hip_scan_extract_decode_batch_once_fmt). Returns
+        (n_runs, chunks, masks, status, runs, roles, rchunks, rmasks); a capture whose extraction failed is in no run (run and role -1)."""
+        captures, n, w, h, fmt = self._captures(captures, size, fmt)
+        chunks, masks, runs, roles, rchunks, rmasks = self._once_outputs(n)
+        status = np.zeros(n, dtype=np.int32)
+        n_runs = ctypes.c_int(0)
+        rc = self._check(self._lib.cimbar_hip_scan_extract_decode_batch_once_fmt(
+            self._ctx, captures.ctypes.data, w, h, fmt, n, MEM_HOST, int(preprocess), int(color_correction), int(min_agree_permille), int(max_run),
+            chunks.ctypes.data, masks.ctypes.data, status.ctypes.data, runs.ctypes.data, roles.ctypes.data, rchunks.ctypes.data, rmasks.ctypes.data,
+            ctypes.addressof(n_runs), MEM_HOST, None), "cimbar_hip_scan_extract_decode_batch_once_fmt")
+        assert rc == n_runs.value
+        return int(rc), chunks, masks, status, runs, roles, rchunks, rmasks
 
     def _stitch_stream_outputs(self, n):
         geo = self.geo
@@ -1126,6 +1186,19 @@ class HipDecoder:
         that batch was a stitched-stream call, (n, L)"""
         out = np.zeros((n if stream else max(n - 1, 0), self.geo.DIM_Y if axis == 0 else self.geo.DIM_X), dtype=np.uint16)
         self._check(self._lib.cimbar_hip_tap(self._ctx, TAP_STITCH_LINES, out.ctypes.data, out.nbytes), "cimbar_hip_tap")
+        return out
+
+    def tap_repeat_sig(self, n):
+        """TAP_REPEAT_SIG of the last once-call of n captures: (n, NCELLS) uint8, the ink signature 0..3 of every cell"""
+        out = np.zeros((n, self.geo.NCELLS), dtype=np.uint8)
+        self._check(self._lib.cimbar_hip_tap(self._ctx, TAP_REPEAT_SIG, out.ctypes.data, out.nbytes), "cimbar_hip_tap")
+        return out
+
+    def tap_repeat_agree(self, n):
+        """TAP_REPEAT_AGREE of the last once-call of n captures: (n - 1,) uint32, the cells of equal signature in captures k and k + 1"""
+        out = np.zeros(max(n - 1, 0), dtype=np.uint32)
+        if n > 1:
+            self._check(self._lib.cimbar_hip_tap(self._ctx, TAP_REPEAT_AGREE, out.ctypes.data, out.nbytes), "cimbar_hip_tap")
         return out
 
     def enable_timing(self, on=True):
