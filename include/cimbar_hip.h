@@ -485,8 +485,9 @@ int cimbar_hip_get_stitch_strips(cimbar_hip_ctx* ctx, int* strips);
  *              of constant bytes can do that). A fountain receiver survives a dropped frame; a caller who cannot accept the limit uses the
  *              plain or the combined calls.
  * Buffers, stream and errors otherwise as for cimbar_hip_decode_batch / cimbar_hip_scan_extract_decode_batch_fmt; a null chunks or masks,
- * n <= 0 or a parameter out of range is CIMBAR_HIP_EINVAL, checked before anything is enqueued. Not covered: runs across calls, the
- * pipelined and frame-async entry points, the combined / stitched calls, the undistort path and the auto-detection objects. */
+ * n <= 0 or a parameter out of range is CIMBAR_HIP_EINVAL, checked before anything is enqueued. Runs across calls: the _once_stream calls
+ * below. Not covered: the pipelined and frame-async entry points, the combined / stitched calls, the undistort path and the auto-detection
+ * objects. */
 enum {
 	CIMBAR_HIP_ONCE_UNUSABLE = -1,
 	CIMBAR_HIP_ONCE_SKIPPED = 0,
@@ -500,6 +501,58 @@ int64_t cimbar_hip_scan_extract_decode_batch_once_fmt(cimbar_hip_ctx* ctx, const
                                                       int img_mem, int preprocess, int color_correction, int min_agree_permille, int max_run,
                                                       uint8_t* chunks, uint32_t* masks, int* status, int* runs_out, int* roles, uint8_t* rchunks,
                                                       uint32_t* rmasks, int* n_runs, int out_mem, void* hip_stream);
+
+/* ---- repeat-capture skipping across calls: the open run is carried from call to call -------------------------------------------------------
+ * A live receiver hands over one capture (or a few) per call, so a run of repeats spans calls. The two _once_stream calls are the calls above
+ * with one piece of state on the device: what the previous once-stream call on this context left. Signature, agree, min_agree_permille,
+ * max_run, roles and usability are exactly those of the plain once-calls; modes 4 and 8: CIMBAR_HIP_EINVAL.
+ *   carry      the signature of the previous call's last capture; one word saying whether that capture was usable; and, if it was, the open
+ *              run it belongs to: len = its members so far, over all calls; P = the OR of the masks its decoded members delivered; its chunk
+ *              row, filled as rchunks is. After cimbar_hip_create or cimbar_hip_once_stream_reset nothing is carried. The carry sits in two
+ *              slots used in turn: a call reads one and writes the other, and they change roles only when the call returns its result, so a
+ *              call that returns an error leaves the carry as it was. (CIMBAR_HIP_TAP_REPEAT_CARRY)
+ *   walk       capture k continues the run of its predecessor (k = 0: the carried capture's run) if and only if both are usable,
+ *              agree * 1000 >= min_agree_permille * cells, and that run has fewer than max_run members, counting those of earlier calls.
+ *              Otherwise a usable capture starts a run and an unusable one is in no run. Runs are numbered from 0 in the call's capture
+ *              order; *continued = 1 if run 0 continues the carried run, else 0. Over any split of a capture sequence into calls the run
+ *              boundaries are those ONE plain once-call reports for the concatenation with the same two parameters.
+ *   segment    a run's members in this call. P of the continued run's segment is the carried mask, P of every other segment is 0. The
+ *              representative of a segment is its member (seg_len - 1) / 2.
+ *   pass 1     for every segment whose P is not full: its representative, in capture order. A segment whose P is full decodes nothing: all
+ *              its members are CIMBAR_HIP_ONCE_SKIPPED.
+ *   pass 2     for every segment with P | (its representative's mask) not full: its other members, in capture order; none: no second pass
+ *   contract   as above: the per-capture results of list 1, then of list 2, are the results of two consecutive plain calls on a context in
+ *              the same state; a skipped or unusable capture has mask 0 and a zeroed slot; capture path: extraction runs for every capture
+ *              and status is the plain call's
+ *   per run    n slots, zero at and above the run count: rmasks[r] = P | the OR of the members' masks; rchunks[r] chunk j from the carried row
+ *              where P has bit j, else from the representative where it delivered it, else from the lowest-index member that did, else
+ *              zeros. The row is cumulative over the run's calls: handed to cimbar_hip_deliver_chunks with CIMBAR_HIP_DELIVER_DEDUP and
+ *              _REMEMBER, each chunk reaches the sink once.
+ *   new carry  the call's last capture: its signature and its usable word; if it is usable, its run: len = (the carried len if the run is the
+ *              continued one, else 0) + seg_len, P = rmasks of that run, the row = rchunks of that run
+ *   no flush   a run is reported in every call it has members in, so nothing is ever open from the caller's side
+ *   parameters min_agree_permille, max_run, should_preprocess / preprocess, color_correction, n and the capture size may change from call to
+ *              call: capture 0 is judged with the parameters of the call that holds it
+ *   one call   directly after create or reset reports, in every output, what the plain once-call reports for the same input; *continued = 0
+ *   synchronisation  as above: the length of list 1 is read back after the walk and, if list 1 is neither empty nor all n captures, the
+ *              length of list 2 after pass 1. A call whose list 1 is empty enqueues no decode at all.
+ *   ordering   consecutive once-stream calls are ordered against each other whatever their hip_stream. Other calls on the context neither
+ *              see nor disturb the carry, but the scratch of the run search is shared with the plain once-calls: running one of each at the
+ *              same time on two streams is the caller's to order.
+ *   continued  may be NULL; it follows out_mem. Everything else as for the plain once-calls, the known limit included. Arguments are checked
+ *              before anything is enqueued.
+ * cimbar_hip_once_stream_reset waits for the once-stream calls issued so far and forgets the carry.
+ * Not covered: the pipelined and frame-async entry points, composing with the combined / stitched calls, the undistort path, the
+ * auto-detection objects, a variant without read-backs. */
+int64_t cimbar_hip_decode_batch_once_stream(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rgb_mem, int should_preprocess, int color_correction,
+                                            int min_agree_permille, int max_run, uint8_t* chunks, uint32_t* masks, int* runs_out, int* roles,
+                                            uint8_t* rchunks, uint32_t* rmasks, int* n_runs, int* continued, int out_mem, void* hip_stream);
+int64_t cimbar_hip_scan_extract_decode_batch_once_stream_fmt(cimbar_hip_ctx* ctx, const uint8_t* img, unsigned width, unsigned height, int format, int n,
+                                                             int img_mem, int preprocess, int color_correction, int min_agree_permille, int max_run,
+                                                             uint8_t* chunks, uint32_t* masks, int* status, int* runs_out, int* roles,
+                                                             uint8_t* rchunks, uint32_t* rmasks, int* n_runs, int* continued, int out_mem,
+                                                             void* hip_stream);
+int cimbar_hip_once_stream_reset(cimbar_hip_ctx* ctx);
 
 /* ---- chunk delivery: a batch's slots and masks -> what a fountain sink eats --------------------------------------------------------------
  * The batch entry points above report a frame's chunks in fixed slots plus one mask word. The reference's receive interface has another shape:
@@ -869,9 +922,14 @@ enum {
 	                                       then handed to the exact replay (CIMBAR_HIP_TAP_FLOOD_PATH 1); 0 for every other frame, and for every
 	                                       frame of a batch that ran with the setting off */
 	/* the grouping of the last once-call (cimbar_hip_decode_batch_once / _scan_extract_decode_batch_once_fmt; n = its captures;
-	 * CIMBAR_HIP_EINVAL before any) */
+	 * CIMBAR_HIP_EINVAL before any). After a once-stream call (cimbar_hip_decode_batch_once_stream / _scan_extract_decode_batch_once_stream_fmt)
+	 * they describe its n captures, and _AGREE has n entries: entry 0 is capture 0 against the carried capture (0 when the carry is
+	 * unusable or nothing is carried), entry k is agree(k - 1, k). */
 	CIMBAR_HIP_TAP_REPEAT_SIG = 28,     /* n * cells bytes     : sig_c, 0..3, by linear cell index */
-	CIMBAR_HIP_TAP_REPEAT_AGREE = 29    /* (n - 1) u32         : agree(k, k + 1) */
+	CIMBAR_HIP_TAP_REPEAT_AGREE = 29,   /* (n - 1) u32         : agree(k, k + 1); after a once-stream call n u32 */
+	/* what the once-stream calls carry: the last capture of the last such call (CIMBAR_HIP_EINVAL while nothing is carried: after create and
+	 * after cimbar_hip_once_stream_reset); does not depend on the last batch */
+	CIMBAR_HIP_TAP_REPEAT_CARRY = 30    /* cells bytes + 3 u32 : the carried signature, then {usable, len, P}; len and P are 0 when usable is */
 };
 int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_bytes);
 

@@ -340,6 +340,32 @@ int64_t cimbar_hip_scan_extract_decode_batch_once_fmt(cimbar_hip_ctx* ctx, const
 	                  min_agree_permille, max_run, chunks, masks, status, runs_out, roles, rchunks, rmasks, n_runs, out_mem, hip_stream);
 }
 
+int64_t cimbar_hip_decode_batch_once_stream(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rgb_mem, int should_preprocess, int color_correction,
+                                            int min_agree_permille, int max_run, uint8_t* chunks, uint32_t* masks, int* runs_out, int* roles,
+                                            uint8_t* rchunks, uint32_t* rmasks, int* n_runs, int* continued, int out_mem, void* hip_stream)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return CIMBAR_FWD(cimbar_hip_decode_batch_once_stream, rgb, n, rgb_mem, should_preprocess, color_correction, min_agree_permille, max_run, chunks,
+	                  masks, runs_out, roles, rchunks, rmasks, n_runs, continued, out_mem, hip_stream);
+}
+
+int64_t cimbar_hip_scan_extract_decode_batch_once_stream_fmt(cimbar_hip_ctx* ctx, const uint8_t* img, unsigned width, unsigned height, int format, int n,
+                                                             int img_mem, int preprocess, int color_correction, int min_agree_permille, int max_run,
+                                                             uint8_t* chunks, uint32_t* masks, int* status, int* runs_out, int* roles,
+                                                             uint8_t* rchunks, uint32_t* rmasks, int* n_runs, int* continued, int out_mem,
+                                                             void* hip_stream)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return CIMBAR_FWD(cimbar_hip_scan_extract_decode_batch_once_stream_fmt, img, width, height, format, n, img_mem, preprocess, color_correction,
+	                  min_agree_permille, max_run, chunks, masks, status, runs_out, roles, rchunks, rmasks, n_runs, continued, out_mem, hip_stream);
+}
+
+int cimbar_hip_once_stream_reset(cimbar_hip_ctx* ctx)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return CIMBAR_FWD(cimbar_hip_once_stream_reset);
+}
+
 int cimbar_hip_stitch_stream_reset(cimbar_hip_ctx* ctx)
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;

@@ -28,6 +28,20 @@ struct StitchStream {
 	StitchCarry carry() const { return StitchCarry{symbols, colors, usable, cur}; }
 };
 
+// what the once-stream calls of repeat-capture skipping keep between calls (repeat.hip.inc, "runs across calls"): the last capture's
+// signature, words and run row in two slots used in turn, the words of the call in flight and the event that orders one once-stream call
+// behind the one before. Nothing of it exists until the first once-stream call.
+struct OnceStream {
+	DevBuf<uint8_t> sig, row;                 // [2][RP_CARRY_SIG], [2][RP_CARRY_ROW]
+	DevBuf<uint32_t> words;                   // [2][RP_CARRY_WORDS]
+	DevBuf<int> cw; PinnedBuf<int> h_cw;      // [RP_CALL_WORDS] of the call in flight, and where their read-backs land
+	Event ev_last;                            // behind the last once-stream call's work: the next one, on whatever stream, starts after it
+	bool used = false;                        // ev_last has been recorded
+	bool carried = false;                     // slot `cur` holds the last capture of a once-stream call (CIMBAR_HIP_TAP_REPEAT_CARRY describes it)
+	int cur = 0;                              // the slot the next call reads
+	RepeatCarry carry() const { return RepeatCarry{sig, words, row, cur}; }
+};
+
 struct cimbar_hip_ctx {
 	int mode_tag = MODE_VAL;                  // FIRST member: api.hip.inc reads it through the opaque pointer to pick the namespace
 	int device = 0;
@@ -68,6 +82,8 @@ struct cimbar_hip_ctx {
 	// repeat-capture skipping (cimbar_hip_decode_batch_once / _scan_extract_decode_batch_once_fmt, repeat.hip.inc): per capture, grown on demand;
 	// the gathered frames and their results are sized by the longer of a call's two lists
 	int rp_n = 0;                               // the last once-call had that many captures (> 0: the repeat taps describe it)
+	bool rp_stream = false;                     // ... and was a once-stream call (its agreement has rp_n entries, entry 0 against the carry)
+	std::unique_ptr<OnceStream> ostream;        // cimbar_hip_decode_batch_once_stream / _scan_extract_decode_batch_once_stream_fmt
 	DevBuf<ushort4> d_rp_sums; DevBuf<uint8_t> d_rp_sig; DevBuf<uint32_t> d_rp_agree;   // [n][NCELLS], [n][NCELLS], [n]
 	DevBuf<int> d_rp_runs, d_rp_mem, d_rp_count, d_rp_roles, d_rp_list, d_rp_sel;        // [n], [n][GMAX], [n], [n], [2][n] lists 1 and 2, [list] scan status
 	DevBuf<int> d_rp_words; PinnedBuf<int> h_rp_words;                                   // [0] runs = the length of list 1, [1] the length of list 2
@@ -2064,6 +2080,8 @@ namespace {
 struct OnceArgs {
 	int min_agree, max_run;   // resolved by check_once (900 / 4 for <= 0)
 	int* runs_out; int* roles; uint8_t* rchunks; uint32_t* rmasks; int* n_runs;   // each may be nullptr
+	bool stream = false;      // a once-stream call: run 0 may continue the run the call before left (after begin_once_stream)
+	int* continued = nullptr; // ... and whether it does (may be nullptr)
 };
 
 // the argument checks of the once entry points, before anything is enqueued
@@ -2087,13 +2105,38 @@ int ensure_once_list(cimbar_hip_ctx* ctx, int len)
 	return 0;
 }
 
-// the 4-byte count d_rp_words[which], read back behind everything enqueued on `st` so far
-int once_read_count(cimbar_hip_ctx* ctx, hipStream_t st, int which, int* out)
+// the 4-byte count d_words[which] (h_words: its page-locked mirror), read back behind everything enqueued on `st` so far
+int once_read_count(cimbar_hip_ctx* ctx, hipStream_t st, const int* d_words, int* h_words, int which, int* out)
 {
-	HIPCHK(hipMemcpyAsync(ctx->h_rp_words + which, ctx->d_rp_words + which, sizeof(int), hipMemcpyDeviceToHost, st));
+	HIPCHK(hipMemcpyAsync(h_words + which, d_words + which, sizeof(int), hipMemcpyDeviceToHost, st));
 	HIPCHK(hipStreamSynchronize(st));
-	*out = ((volatile int*)ctx->h_rp_words.get())[which];
+	*out = ((volatile int*)h_words)[which];
 	return 0;
+}
+
+// the start of a once-stream call, behind its argument checks: the carry store (allocated by the first such call, nothing carried) and the
+// wait that puts the whole call behind the once-stream call before, whatever their streams
+int begin_once_stream(cimbar_hip_ctx* ctx, hipStream_t st)
+{
+	if (!ctx->ostream) ctx->ostream = std::make_unique<OnceStream>();
+	OnceStream& s = *ctx->ostream;
+	HIPCHK(s.ev_last.create());
+	HIPCHK(s.sig.ensure((size_t)2 * RP_CARRY_SIG));
+	HIPCHK(s.row.ensure((size_t)2 * RP_CARRY_ROW));
+	HIPCHK(s.cw.ensure(RP_CALL_WORDS));
+	HIPCHK(s.h_cw.ensure(RP_CALL_WORDS));
+	if (!s.words) { HIPCHK(s.words.ensure((size_t)2 * RP_CARRY_WORDS)); HIPCHK(hipMemset(s.words, 0, sizeof(uint32_t) * 2 * RP_CARRY_WORDS)); }
+	if (s.used) HIPCHK(hipStreamWaitEvent(st, s.ev_last, 0));
+	return 0;
+}
+
+// the end of a once-stream call, failed or not: the event the next one waits for, behind whatever this one enqueued
+int64_t end_once_stream(cimbar_hip_ctx* ctx, hipStream_t st, int64_t rc)
+{
+	OnceStream& s = *ctx->ostream;
+	if (hipEventRecord(s.ev_last, st) == hipSuccess) s.used = true;
+	else if (rc >= 0) { ctx->err = "once_stream: hipEventRecord failed"; return CIMBAR_HIP_EHIP; }
+	return rc;
 }
 
 // Everything behind the input: n device-resident frames d_frames (the caller's, or the warp's), d_status = the capture path's extraction status
@@ -2120,18 +2163,32 @@ int64_t once_impl(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_frames, 
 	uint8_t* d_chunks = dev ? chunks : ctx->d_chunks.get();
 	uint32_t* d_masks = dev ? masks : ctx->d_masks.get();
 	ctx->rp_n = 0;
+	// a once-stream call: the carry it reads, and its own words (list 1 may be shorter than the run count)
+	OnceStream* os = oa.stream ? ctx->ostream.get() : nullptr;
+	const RepeatCarry cy = os ? os->carry() : RepeatCarry{};
+	int* d_words = os ? os->cw.get() : ctx->d_rp_words.get();
+	int* h_words = os ? os->h_cw.get() : ctx->h_rp_words.get();
+	const int w_len1 = os ? (int)RPC_LEN1 : 0, w_len2 = os ? (int)RPC_LEN2 : 1;
 
 	hipLaunchKernelGGL(k_repeat_sums, dim3(DIM_Y, n), dim3(256), 0, st, d_frames, ctx->tb, ctx->d_rp_sums);
 	hipLaunchKernelGGL(k_repeat_sig, dim3(n), dim3(256), 0, st, ctx->d_rp_sums, ctx->d_rp_sig);
-	if (n > 1) hipLaunchKernelGGL(k_repeat_agree, dim3(n - 1), dim3(256), 0, st, ctx->d_rp_sig, n, ctx->d_rp_agree);
-	HIPCHK(hipMemsetAsync(ctx->d_rp_count, 0, sizeof(int) * N, st));
-	HIPCHK(hipMemsetAsync(ctx->d_rp_words, 0, sizeof(int) * 2, st));
-	hipLaunchKernelGGL(k_group_walk, dim3(1), dim3(64), 0, st, ctx->d_rp_agree, n, d_status, stride, (const int*)nullptr, oa.min_agree, oa.max_run,
-	                   ctx->d_rp_runs, ctx->d_rp_mem, ctx->d_rp_count, ctx->d_rp_words);
-	hipLaunchKernelGGL(k_repeat_lists, dim3((n + 255) / 256), dim3(256), 0, st, ctx->d_rp_runs, ctx->d_rp_mem, ctx->d_rp_count, n, ctx->d_rp_roles, ctx->d_rp_list);
+	if (os) {
+		hipLaunchKernelGGL(k_repeat_agree_stream, dim3(n), dim3(256), 0, st, ctx->d_rp_sig, cy, ctx->d_rp_agree);
+		hipLaunchKernelGGL(k_repeat_walk_stream, dim3(1), dim3(64), 0, st, ctx->d_rp_agree, n, d_status, stride, oa.min_agree, oa.max_run, cy, ctx->d_rp_runs,
+		                   ctx->d_rp_mem, ctx->d_rp_count, d_words);
+		hipLaunchKernelGGL(k_repeat_lists_stream, dim3((n + 255) / 256), dim3(256), 0, st, ctx->d_rp_runs, ctx->d_rp_mem, ctx->d_rp_count, n, d_words, ctx->d_rp_roles,
+		                   ctx->d_rp_list);
+	} else {
+		if (n > 1) hipLaunchKernelGGL(k_repeat_agree, dim3(n - 1), dim3(256), 0, st, ctx->d_rp_sig, n, ctx->d_rp_agree);
+		HIPCHK(hipMemsetAsync(ctx->d_rp_count, 0, sizeof(int) * N, st));
+		HIPCHK(hipMemsetAsync(ctx->d_rp_words, 0, sizeof(int) * 2, st));
+		hipLaunchKernelGGL(k_group_walk, dim3(1), dim3(64), 0, st, ctx->d_rp_agree, n, d_status, stride, (const int*)nullptr, oa.min_agree, oa.max_run,
+		                   ctx->d_rp_runs, ctx->d_rp_mem, ctx->d_rp_count, ctx->d_rp_words);
+		hipLaunchKernelGGL(k_repeat_lists, dim3((n + 255) / 256), dim3(256), 0, st, ctx->d_rp_runs, ctx->d_rp_mem, ctx->d_rp_count, n, ctx->d_rp_roles, ctx->d_rp_list);
+	}
 	HIPCHK(hipGetLastError());
 	int len1 = 0, len2 = 0;
-	if (int r = once_read_count(ctx, st, 0, &len1)) return r;
+	if (int r = once_read_count(ctx, st, d_words, h_words, w_len1, &len1)) return r;
 	if (len1 < 0 || len1 > n) { ctx->err = "decode_batch_once: the run count read back is out of range"; return CIMBAR_HIP_EHIP; }
 
 	// one decode pass over `len` listed captures: gather, enqueue() as one plain batch of the entry point's kind, scatter
@@ -2158,9 +2215,12 @@ int64_t once_impl(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_frames, 
 		hipLaunchKernelGGL(k_repeat_clear, dim3(n), dim3(256), 0, st, ctx->d_rp_roles, d_chunks, d_masks);
 		if (len1 > 0) {
 			if (int r = pass(ctx->d_rp_list, len1)) return r;
-			hipLaunchKernelGGL(k_repeat_lists2, dim3(1), dim3(64), 0, st, ctx->d_rp_runs, ctx->d_rp_masks, n, ctx->d_rp_roles, ctx->d_rp_list + n, ctx->d_rp_words + 1);
+			if (os)
+				hipLaunchKernelGGL(k_repeat_lists2_stream, dim3(1), dim3(64), 0, st, ctx->d_rp_runs, ctx->d_rp_masks, n, cy, ctx->d_rp_roles, ctx->d_rp_list + n, d_words);
+			else
+				hipLaunchKernelGGL(k_repeat_lists2, dim3(1), dim3(64), 0, st, ctx->d_rp_runs, ctx->d_rp_masks, n, ctx->d_rp_roles, ctx->d_rp_list + n, ctx->d_rp_words + 1);
 			HIPCHK(hipGetLastError());
-			if (int r = once_read_count(ctx, st, 1, &len2)) return r;
+			if (int r = once_read_count(ctx, st, d_words, h_words, w_len2, &len2)) return r;
 			if (len2 < 0 || len2 > n - len1) { ctx->err = "decode_batch_once: the fallback count read back is out of range"; return CIMBAR_HIP_EHIP; }
 			if (len2 > 0) if (int r = pass(ctx->d_rp_list + n, len2)) return r;
 		}
@@ -2171,35 +2231,46 @@ int64_t once_impl(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_frames, 
 		if (oa.rchunks) { HIPCHK(ctx->d_rp_rchunks.reserve(N * FRAME_BYTES)); d_rchunks = ctx->d_rp_rchunks; }
 		if (oa.rmasks) { HIPCHK(ctx->d_rp_rmasks.reserve(N)); d_rmasks = ctx->d_rp_rmasks; }
 	}
-	if (d_rchunks || d_rmasks)
+	if (os) {
+		if (d_rchunks || d_rmasks)
+			hipLaunchKernelGGL(k_repeat_end_stream, dim3(n), dim3(256), 0, st, ctx->d_rp_mem, ctx->d_rp_count, d_words, d_chunks, d_masks, cy, d_rchunks, d_rmasks);
+		// the call's last kernel: it writes the slot this call does not read, and the slots change roles only where the call returns its result
+		hipLaunchKernelGGL(k_repeat_carry, dim3(1), dim3(256), 0, st, ctx->d_rp_sig, ctx->d_rp_runs, ctx->d_rp_mem, ctx->d_rp_count, d_words, d_chunks, d_masks, n, cy);
+	} else if (d_rchunks || d_rmasks)
 		hipLaunchKernelGGL(k_repeat_end, dim3(n), dim3(256), 0, st, ctx->d_rp_mem, ctx->d_rp_count, ctx->d_rp_words, d_chunks, d_masks, d_rchunks, d_rmasks);
 	HIPCHK(hipGetLastError());
 	const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
 	if (oa.runs_out) HIPCHK(hipMemcpyAsync(oa.runs_out, ctx->d_rp_runs, sizeof(int) * N, kind, st));
 	if (oa.roles) HIPCHK(hipMemcpyAsync(oa.roles, ctx->d_rp_roles, sizeof(int) * N, kind, st));
-	ctx->rp_n = n;
+	auto done = [&]() {
+		ctx->rp_n = n;
+		ctx->rp_stream = os != nullptr;
+		if (os) { os->cur ^= 1; os->carried = true; }
+	};
 	if (dev) {
-		if (oa.n_runs) HIPCHK(hipMemcpyAsync(oa.n_runs, ctx->d_rp_words, sizeof(int), kind, st));
+		if (oa.n_runs) HIPCHK(hipMemcpyAsync(oa.n_runs, d_words + (os ? (int)RPC_RUNS : 0), sizeof(int), kind, st));
+		if (os && oa.continued) HIPCHK(hipMemcpyAsync(oa.continued, d_words + RPC_CONT, sizeof(int), kind, st));
+		done();
 		return 0;
 	}
 	HIPCHK(hipMemcpyAsync(chunks, d_chunks, N * FRAME_BYTES, hipMemcpyDeviceToHost, st));
 	HIPCHK(hipMemcpyAsync(masks, d_masks, sizeof(uint32_t) * N, hipMemcpyDeviceToHost, st));
 	if (oa.rchunks) HIPCHK(hipMemcpyAsync(oa.rchunks, d_rchunks, N * FRAME_BYTES, hipMemcpyDeviceToHost, st));
 	if (oa.rmasks) HIPCHK(hipMemcpyAsync(oa.rmasks, d_rmasks, sizeof(uint32_t) * N, hipMemcpyDeviceToHost, st));
+	if (os) HIPCHK(hipMemcpyAsync(h_words, d_words, sizeof(int) * RP_CALL_WORDS, hipMemcpyDeviceToHost, st));
 	HIPCHK(hipStreamSynchronize(st));
-	if (oa.n_runs) *oa.n_runs = len1;
-	return len1;
+	done();
+	const int n_runs = os ? ((volatile int*)h_words)[RPC_RUNS] : len1;
+	if (oa.n_runs) *oa.n_runs = n_runs;
+	if (os && oa.continued) *oa.continued = ((volatile int*)h_words)[RPC_CONT];
+	return n_runs;
 }
 
-}  // namespace
-
-int64_t cimbar_hip_decode_batch_once(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rgb_mem, int should_preprocess, int color_correction,
-                                     int min_agree_permille, int max_run, uint8_t* chunks, uint32_t* masks, int* runs_out, int* roles,
-                                     uint8_t* rchunks, uint32_t* rmasks, int* n_runs, int out_mem, void* hip_stream)
+// the frame entry points: oa as the caller gave it (check_once resolves the two parameters)
+int64_t decode_batch_once_impl(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rgb_mem, int should_preprocess, int color_correction, uint8_t* chunks,
+                               uint32_t* masks, OnceArgs oa, int out_mem, void* hip_stream)
 {
-	if (!ctx) return CIMBAR_HIP_EINVAL;
-	const char* who = "decode_batch_once";
-	OnceArgs oa{min_agree_permille, max_run, runs_out, roles, rchunks, rmasks, n_runs};
+	const char* who = oa.stream ? "decode_batch_once_stream" : "decode_batch_once";
 	if (int r = check_once(ctx, who, oa)) return r;
 	if (!rgb || !chunks || !masks || n <= 0) { ctx->err = std::string(who) + ": null buffer or n <= 0"; return CIMBAR_HIP_EINVAL; }
 	if ((rgb_mem != CIMBAR_HIP_MEM_HOST && rgb_mem != CIMBAR_HIP_MEM_DEVICE) || (out_mem != CIMBAR_HIP_MEM_HOST && out_mem != CIMBAR_HIP_MEM_DEVICE)) {
@@ -2210,19 +2281,22 @@ int64_t cimbar_hip_decode_batch_once(cimbar_hip_ctx* ctx, const uint8_t* rgb, in
 	const bool any_device = rgb_mem == CIMBAR_HIP_MEM_DEVICE || out_mem == CIMBAR_HIP_MEM_DEVICE;
 	hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (any_device ? (hipStream_t)nullptr : ctx->stream);
 	if (int r = drain_pipeline_into(ctx, st)) return r;
-	const uint8_t* d_rgb = nullptr;
-	if (int r = stage_input(ctx, st, ctx->d_rgb, rgb, (size_t)n * FRAME_RGB, rgb_mem, &d_rgb)) return r;
-	return once_impl(ctx, st, d_rgb, n, nullptr, 0, should_preprocess, false, color_correction, chunks, masks, oa, out_mem);
+	// (a stream call waits for the one before in front of the staging copy: the call before may still be decoding out of d_rgb)
+	if (oa.stream) if (int r = begin_once_stream(ctx, st)) return r;
+	const int64_t rc = [&]() -> int64_t {
+		const uint8_t* d_rgb = nullptr;
+		if (int r = stage_input(ctx, st, ctx->d_rgb, rgb, (size_t)n * FRAME_RGB, rgb_mem, &d_rgb)) return r;
+		return once_impl(ctx, st, d_rgb, n, nullptr, 0, should_preprocess, false, color_correction, chunks, masks, oa, out_mem);
+	}();
+	return oa.stream ? end_once_stream(ctx, st, rc) : rc;
 }
 
-int64_t cimbar_hip_scan_extract_decode_batch_once_fmt(cimbar_hip_ctx* ctx, const uint8_t* img, unsigned width, unsigned height, int format, int n,
-                                                      int img_mem, int preprocess, int color_correction, int min_agree_permille, int max_run,
-                                                      uint8_t* chunks, uint32_t* masks, int* status, int* runs_out, int* roles, uint8_t* rchunks,
-                                                      uint32_t* rmasks, int* n_runs, int out_mem, void* hip_stream)
+// ... and the capture entry points
+int64_t scan_extract_decode_batch_once_impl(cimbar_hip_ctx* ctx, const uint8_t* img, unsigned width, unsigned height, int format, int n, int img_mem,
+                                            int preprocess, int color_correction, uint8_t* chunks, uint32_t* masks, int* status, OnceArgs oa, int out_mem,
+                                            void* hip_stream)
 {
-	if (!ctx) return CIMBAR_HIP_EINVAL;
-	const char* who = "scan_extract_decode_batch_once";
-	OnceArgs oa{min_agree_permille, max_run, runs_out, roles, rchunks, rmasks, n_runs};
+	const char* who = oa.stream ? "scan_extract_decode_batch_once_stream" : "scan_extract_decode_batch_once";
 	if (int r = check_once(ctx, who, oa)) return r;
 	if (!img || !chunks || !masks || n <= 0 || width < 8 || height < 8) { ctx->err = std::string(who) + ": null buffer, n <= 0 or a capture smaller than 8x8"; return CIMBAR_HIP_EINVAL; }
 	if ((img_mem != CIMBAR_HIP_MEM_HOST && img_mem != CIMBAR_HIP_MEM_DEVICE) || (out_mem != CIMBAR_HIP_MEM_HOST && out_mem != CIMBAR_HIP_MEM_DEVICE)) {
@@ -2235,18 +2309,77 @@ int64_t cimbar_hip_scan_extract_decode_batch_once_fmt(cimbar_hip_ctx* ctx, const
 	const bool any_device = img_mem == CIMBAR_HIP_MEM_DEVICE || out_mem == CIMBAR_HIP_MEM_DEVICE;
 	hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (any_device ? (hipStream_t)nullptr : ctx->stream);
 	if (int r = drain_pipeline_into(ctx, st)) return r;
-	if (int r = extract_state(ctx, n)) return r;
-	const uint8_t* d_in = nullptr;
-	if (int r = stage_input(ctx, st, ctx->d_ex_in, img, cbytes * n, img_mem, &d_in)) return r;
-	HIPCHK(ctx->d_ex_frames.reserve((size_t)n * FRAME_RGB));
-	// extraction runs for every capture, repeats included: the runs are found on the deskewed frames
-	if (int r = enqueue_scan(ctx, st, d_in, width, height, fmt, n)) return r;
-	if (int r = launch_warp_ctx(ctx, st, fmt, d_in, width, height, n, ctx->d_ex_minv, ctx->d_ex_frames)) return r;
-	const hipMemcpyKind kind = out_mem == CIMBAR_HIP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-	if (status) HIPCHK(hipMemcpy2DAsync(status, sizeof(int), &ctx->d_scan_res[0].status, sizeof(ScanResult), sizeof(int), (size_t)n, kind, st));
-	const bool guess = preprocess != 0 && preprocess != 1;
-	return once_impl(ctx, st, ctx->d_ex_frames, n, &ctx->d_scan_res[0].status, (int)(sizeof(ScanResult) / sizeof(int)), preprocess == 1 ? 1 : 0, guess,
-	                 color_correction, chunks, masks, oa, out_mem);
+	if (oa.stream) if (int r = begin_once_stream(ctx, st)) return r;
+	const int64_t rc = [&]() -> int64_t {
+		if (int r = extract_state(ctx, n)) return r;
+		const uint8_t* d_in = nullptr;
+		if (int r = stage_input(ctx, st, ctx->d_ex_in, img, cbytes * n, img_mem, &d_in)) return r;
+		HIPCHK(ctx->d_ex_frames.reserve((size_t)n * FRAME_RGB));
+		// extraction runs for every capture, repeats included: the runs are found on the deskewed frames
+		if (int r = enqueue_scan(ctx, st, d_in, width, height, fmt, n)) return r;
+		if (int r = launch_warp_ctx(ctx, st, fmt, d_in, width, height, n, ctx->d_ex_minv, ctx->d_ex_frames)) return r;
+		const hipMemcpyKind kind = out_mem == CIMBAR_HIP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+		if (status) HIPCHK(hipMemcpy2DAsync(status, sizeof(int), &ctx->d_scan_res[0].status, sizeof(ScanResult), sizeof(int), (size_t)n, kind, st));
+		const bool guess = preprocess != 0 && preprocess != 1;
+		return once_impl(ctx, st, ctx->d_ex_frames, n, &ctx->d_scan_res[0].status, (int)(sizeof(ScanResult) / sizeof(int)), preprocess == 1 ? 1 : 0, guess,
+		                 color_correction, chunks, masks, oa, out_mem);
+	}();
+	return oa.stream ? end_once_stream(ctx, st, rc) : rc;
+}
+
+}  // namespace
+
+int64_t cimbar_hip_decode_batch_once(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rgb_mem, int should_preprocess, int color_correction,
+                                     int min_agree_permille, int max_run, uint8_t* chunks, uint32_t* masks, int* runs_out, int* roles,
+                                     uint8_t* rchunks, uint32_t* rmasks, int* n_runs, int out_mem, void* hip_stream)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return decode_batch_once_impl(ctx, rgb, n, rgb_mem, should_preprocess, color_correction, chunks, masks,
+	                              OnceArgs{min_agree_permille, max_run, runs_out, roles, rchunks, rmasks, n_runs}, out_mem, hip_stream);
+}
+
+int64_t cimbar_hip_scan_extract_decode_batch_once_fmt(cimbar_hip_ctx* ctx, const uint8_t* img, unsigned width, unsigned height, int format, int n,
+                                                      int img_mem, int preprocess, int color_correction, int min_agree_permille, int max_run,
+                                                      uint8_t* chunks, uint32_t* masks, int* status, int* runs_out, int* roles, uint8_t* rchunks,
+                                                      uint32_t* rmasks, int* n_runs, int out_mem, void* hip_stream)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return scan_extract_decode_batch_once_impl(ctx, img, width, height, format, n, img_mem, preprocess, color_correction, chunks, masks, status,
+	                                           OnceArgs{min_agree_permille, max_run, runs_out, roles, rchunks, rmasks, n_runs}, out_mem, hip_stream);
+}
+
+int64_t cimbar_hip_decode_batch_once_stream(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rgb_mem, int should_preprocess, int color_correction,
+                                            int min_agree_permille, int max_run, uint8_t* chunks, uint32_t* masks, int* runs_out, int* roles,
+                                            uint8_t* rchunks, uint32_t* rmasks, int* n_runs, int* continued, int out_mem, void* hip_stream)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return decode_batch_once_impl(ctx, rgb, n, rgb_mem, should_preprocess, color_correction, chunks, masks,
+	                              OnceArgs{min_agree_permille, max_run, runs_out, roles, rchunks, rmasks, n_runs, true, continued}, out_mem, hip_stream);
+}
+
+int64_t cimbar_hip_scan_extract_decode_batch_once_stream_fmt(cimbar_hip_ctx* ctx, const uint8_t* img, unsigned width, unsigned height, int format, int n,
+                                                             int img_mem, int preprocess, int color_correction, int min_agree_permille, int max_run,
+                                                             uint8_t* chunks, uint32_t* masks, int* status, int* runs_out, int* roles,
+                                                             uint8_t* rchunks, uint32_t* rmasks, int* n_runs, int* continued, int out_mem,
+                                                             void* hip_stream)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return scan_extract_decode_batch_once_impl(ctx, img, width, height, format, n, img_mem, preprocess, color_correction, chunks, masks, status,
+	                                           OnceArgs{min_agree_permille, max_run, runs_out, roles, rchunks, rmasks, n_runs, true, continued}, out_mem,
+	                                           hip_stream);
+}
+
+// wait for the once-stream calls issued so far and forget the carry: the next one's capture 0 starts a run
+int cimbar_hip_once_stream_reset(cimbar_hip_ctx* ctx)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	if (!ctx->ostream) return 0;
+	OnceStream& s = *ctx->ostream;
+	HIPCHK(hipSetDevice(ctx->device));
+	if (s.used) HIPCHK(hipEventSynchronize(s.ev_last));
+	if (s.words) HIPCHK(hipMemset(s.words, 0, sizeof(uint32_t) * 2 * RP_CARRY_WORDS));
+	s.carried = false;
+	return 0;
 }
 
 int cimbar_hip_set_template(cimbar_hip_ctx* ctx, const uint8_t* rgb_template, int mem)
@@ -2501,11 +2634,23 @@ int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_byte
 		HIPCHK(hipMemcpy((uint8_t*)out + NCELLS, s.colors + (size_t)s.cur * SS_CELLS, NCELLS, hipMemcpyDeviceToHost));
 		return (int64_t)2 * NCELLS;
 	}
+	if (what == CIMBAR_HIP_TAP_REPEAT_CARRY) {
+		// what the next once-stream call's capture 0 is held against: the carried signature, then {usable, len, P}
+		if (!ctx->ostream || !ctx->ostream->carried) { ctx->err = "tap: nothing is carried (no once-stream call since create / cimbar_hip_once_stream_reset)"; return CIMBAR_HIP_EINVAL; }
+		const size_t bytes = (size_t)NCELLS + 3 * sizeof(uint32_t);
+		if (out_bytes < bytes) { ctx->err = "tap: buffer too small"; return CIMBAR_HIP_EINVAL; }
+		const OnceStream& s = *ctx->ostream;
+		HIPCHK(hipSetDevice(ctx->device));
+		HIPCHK(hipDeviceSynchronize());
+		HIPCHK(hipMemcpy(out, s.sig + (size_t)s.cur * RP_CARRY_SIG, NCELLS, hipMemcpyDeviceToHost));
+		HIPCHK(hipMemcpy((uint8_t*)out + NCELLS, s.words + (size_t)s.cur * RP_CARRY_WORDS, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+		return (int64_t)bytes;
+	}
 	if (what == CIMBAR_HIP_TAP_REPEAT_SIG || what == CIMBAR_HIP_TAP_REPEAT_AGREE) {
 		// what the last once-call grouped its captures by (its n, not the length of the list its last pass decoded)
 		if (ctx->rp_n <= 0) { ctx->err = "tap: no once-call has run on this context yet (cimbar_hip_decode_batch_once / _scan_extract_decode_batch_once_fmt)"; return CIMBAR_HIP_EINVAL; }
 		const size_t m = (size_t)ctx->rp_n;
-		const size_t bytes = what == CIMBAR_HIP_TAP_REPEAT_SIG ? m * NCELLS : (m - 1) * sizeof(uint32_t);
+		const size_t bytes = what == CIMBAR_HIP_TAP_REPEAT_SIG ? m * NCELLS : (ctx->rp_stream ? m : m - 1) * sizeof(uint32_t);   // (a once-stream call: entry 0 against the carry)
 		if (out_bytes < bytes) { ctx->err = "tap: buffer too small"; return CIMBAR_HIP_EINVAL; }
 		HIPCHK(hipSetDevice(ctx->device));
 		HIPCHK(hipDeviceSynchronize());

@@ -27,6 +27,7 @@
 //   R7 k_repeat_clear / k_repeat_scatter   zeroes for what no pass has decoded yet; a pass's chunks and masks back into capture slots
 //   R8 k_repeat_end      the per-run fill
 // The host reads the length of list 1, and then of list 2, back to size the decode launches (host.hip.inc, once_impl).
+// The once-stream calls carry the last capture's run from call to call: "runs across calls" at the end of this file.
 constexpr int RP_AGREE_DEFAULT = 900, RP_RUN_DEFAULT = 4;
 constexpr int RP_ROW0 = 2, RP_ROWS = 4;                                  // pixel rows y + 2 .. y + 5 of a cell
 constexpr int RP_ROW_BYTES = IMG_W * 3, RP_ROW_VEC = RP_ROW_BYTES / 16;   // 3072 | 2208 bytes: 192 | 138 16-byte loads
@@ -184,6 +185,7 @@ __global__ __launch_bounds__(256) void k_repeat_scatter(const int* __restrict__ 
 }
 
 // R8: one workgroup per run slot r < n; slots at or above *nruns are zero. rchunks / rmasks may each be nullptr.
+// (The once-stream calls restate this fill with the carried row in front, in repeat_fill_row below: a change to the rule goes to both.)
 __global__ __launch_bounds__(256) void k_repeat_end(const int* __restrict__ rmem, const int* __restrict__ rcount, const int* __restrict__ nruns,
                                                     const uint8_t* __restrict__ chunks, const uint32_t* __restrict__ masks, uint8_t* __restrict__ rchunks,
                                                     uint32_t* __restrict__ rmasks)
@@ -215,4 +217,253 @@ __global__ __launch_bounds__(256) void k_repeat_end(const int* __restrict__ rmem
 		const int src = s_src[i / CHUNK];
 		rchunks[(size_t)r * FRAME_BYTES + i] = src >= 0 ? chunks[(size_t)src * FRAME_BYTES + i] : (uint8_t)0;
 	}
+}
+
+// ------------------------------------------------------------------------------------------------ runs across calls (the once-stream calls)
+// cimbar_hip_decode_batch_once_stream / _scan_extract_decode_batch_once_stream_fmt carry the run the last capture of a call belongs to into
+// the next call. The carry lives on the device in two slots used in turn (a call reads slot `cur` and k_repeat_carry writes the other):
+//   sig     the signature of the call's last capture
+//   words   {usable, len, P}: that capture was usable; the members of its run so far, over all calls; the OR of the masks its decoded
+//           members delivered. len and P are 0 for an unusable capture; all three are 0 after create and after cimbar_hip_once_stream_reset
+//   row     the run's chunk row, filled as rchunks is
+// A run's SEGMENT is its members in this call. Run 0 may continue the carried run (cw[RPC_CONT]); then its segment's P is the carried P, every
+// other segment's P is 0. List 1 holds the representative of every segment whose P is not full, list 2 the other members of every segment
+// with P | (its representative's mask) not full.
+//   R3s k_repeat_agree_stream  n rows: agree[0] against the carried signature (0 where the carry is unusable), agree[k] = agree(k - 1, k)
+//   G2r k_repeat_walk_stream   k_group_walk's walk seeded with the carried run's length and usable word; the member counts without atomics
+//   R4s k_repeat_lists_stream / R5s k_repeat_lists2_stream / R8s k_repeat_end_stream   as R4 / R5 / R8, honouring P and the carried row
+//   R9  k_repeat_carry         the new carry, into the other slot
+constexpr int RP_CARRY_SIG = (NCELLS + 15) & ~15, RP_CARRY_ROW = (FRAME_BYTES + 15) & ~15;   // slot strides, bytes
+enum { RPW_USABLE = 0, RPW_LEN = 1, RPW_P = 2, RP_CARRY_WORDS = 4 };                          // a slot's words
+enum { RPC_RUNS = 0, RPC_LEN2 = 1, RPC_CONT = 2, RPC_LEN1 = 3, RP_CALL_WORDS = 4 };           // a call's words: runs, |list 2|, continued, |list 1|
+constexpr uint32_t RP_FULL = (1u << CHUNKS) - 1u;
+static_assert(NCELLS % 4 == 0, "signatures are compared a word at a time");
+struct RepeatCarry {
+	uint8_t* sig;      // [2][RP_CARRY_SIG]
+	uint32_t* words;   // [2][RP_CARRY_WORDS]
+	uint8_t* row;      // [2][RP_CARRY_ROW]
+	int cur;           // the slot this call reads
+};
+
+// the P of run r's segment
+__device__ __forceinline__ uint32_t repeat_seg_p(const RepeatCarry& cy, const int* __restrict__ cw, int r)
+{
+	return (r == 0 && cw[RPC_CONT]) ? cy.words[cy.cur * RP_CARRY_WORDS + RPW_P] : 0u;
+}
+
+// R3s: one workgroup per capture k < n: the cells with equal sig in capture k and its predecessor (k = 0: the carried capture)
+__global__ __launch_bounds__(256) void k_repeat_agree_stream(const uint8_t* __restrict__ sig, RepeatCarry cy, uint32_t* __restrict__ agree)
+{
+	const int k = blockIdx.x;
+	const bool live = k > 0 || cy.words[cy.cur * RP_CARRY_WORDS + RPW_USABLE] != 0u;
+	const uint32_t* b = reinterpret_cast<const uint32_t*>(sig + (size_t)k * NCELLS);
+	const uint32_t* a = k > 0 ? b - NCELLS / 4 : reinterpret_cast<const uint32_t*>(cy.sig + (size_t)cy.cur * RP_CARRY_SIG);
+	uint32_t cnt = 0;
+	if (live)
+		for (int w = threadIdx.x; w < NCELLS / 4; w += 256) {
+			const uint32_t x = a[w] ^ b[w];
+			cnt += ((x & 0xFFu) == 0u) + ((x & 0xFF00u) == 0u) + ((x & 0xFF0000u) == 0u) + ((x >> 24) == 0u);
+		}
+	for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o);
+	__shared__ uint32_t s_part[4];
+	if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = cnt;
+	__syncthreads();
+	if (threadIdx.x == 0) agree[k] = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+}
+
+// G2r: one wavefront, 64 captures per step, as k_group_walk (groups_in == nullptr) with these differences. agree has n entries, agree[k]
+// against capture k's predecessor. Capture 0 continues the carried run when the carried capture and it are usable, agree[0] reaches the
+// threshold and the carried run has fewer than max_run members (cont); the walk then behaves as if that run had started len captures in
+// front of capture 0, so that its members of earlier calls count toward max_run. Without cont, capture 0 breaks as the first capture of a
+// plain call does. A run's member count is written by the head of the run behind it (the members in front of that head minus those in front
+// of the run), the last run's by lane 0 at the end: no atomics, nothing to zero.
+//   runs[k], rmem, rcount   as k_group_walk's groups, gmem, gcount, over the members in this call
+//   cw                      RPC_RUNS, RPC_CONT, RPC_LEN1 = the runs minus a continued run 0 whose carried P is full, RPC_LEN2 = 0
+__global__ __launch_bounds__(64) void k_repeat_walk_stream(const uint32_t* __restrict__ agree, int n, const int* __restrict__ status, int stride,
+                                                           int min_agree, int max_run, RepeatCarry cy, int* __restrict__ runs, int* __restrict__ rmem,
+                                                           int* __restrict__ rcount, int* __restrict__ cw)
+{
+	const int lane = threadIdx.x;
+	const unsigned long long below = (1ull << lane) - 1ull, upto = below | (1ull << lane);
+	const unsigned long long need = (unsigned long long)min_agree * NCELLS;
+	const uint32_t* w = cy.words + cy.cur * RP_CARRY_WORDS;
+	const bool cu = w[RPW_USABLE] != 0u;
+	const int L = cu ? (int)w[RPW_LEN] : 0;
+	const bool u0 = !status || status[0] > 0;
+	const bool cont = cu && u0 && (unsigned long long)agree[0] * 1000ull >= need && L < max_run;
+	int run_carry = cont ? -L : 0, starts_carry = cont ? 1 : 0, mem_carry = 0, base_carry = 0, prev_id = -1, top = -1;
+	bool prev_u = cu;
+	auto fetch = [&](int k, uint32_t& a, int& st) {
+		a = k < n ? agree[k] : 0u;
+		st = (status && k < n) ? status[(size_t)k * stride] : 1;
+	};
+	uint32_t a_cur; int st_cur;
+	fetch(lane, a_cur, st_cur);
+	for (int k0 = 0; k0 < n; k0 += 64) {
+		const int k = k0 + lane;
+		uint32_t a_nxt; int st_nxt;
+		fetch(k + 64, a_nxt, st_nxt);
+		const bool in = k < n;
+		const bool u = in && st_cur > 0;
+		const unsigned long long ub = __ballot(u);
+		const bool u_prev = lane == 0 ? prev_u : ((ub >> (lane - 1)) & 1ull) != 0;
+		const bool brk = in && ((k == 0 && !cont) || !u_prev || (unsigned long long)a_cur * 1000ull < need);
+		const unsigned long long bb = __ballot(brk) & upto;
+		const int run = bb ? k0 + 63 - __clzll(bb) : run_carry;          // the latest break at or before k (cont: the carried run's virtual start)
+		const bool start = u && (k - run) % max_run == 0;
+		const unsigned long long sb = __ballot(start);
+		const int id = u ? starts_carry + (int)__popcll(sb & upto) - 1 : -1;
+		run_carry = __shfl(run, 63);
+		starts_carry += (int)__popcll(sb);
+		const int id_prev_lane = __shfl(id, lane > 0 ? lane - 1 : 0);
+		const int id_prev = lane == 0 ? prev_id : id_prev_lane;
+		const bool head = id >= 0 && (k == 0 || id_prev != id);
+		const bool member = id >= 0;
+		const unsigned long long mb = __ballot(member), hb = __ballot(head) & upto;
+		const int before = mem_carry + (int)__popcll(mb & below);           // members of the call in front of capture k
+		const int hl = hb ? 63 - __clzll(hb) : lane;
+		const int at_head = __shfl(before, hl);
+		const int base = hb ? at_head : base_carry;                          // members in front of k's run
+		const int base_prev_lane = __shfl(base, lane > 0 ? lane - 1 : 0);
+		const int base_prev = lane == 0 ? base_carry : base_prev_lane;       // members in front of the run before k's, where k heads one
+		if (in) runs[k] = id;
+		if (member) rmem[(size_t)id * GMAX + (before - base)] = k;
+		if (head && id > 0) rcount[id - 1] = before - base_prev;
+		top = id > top ? id : top;
+		prev_id = __shfl(id, 63);
+		prev_u = __shfl((int)u, 63) != 0;
+		mem_carry += (int)__popcll(mb);
+		base_carry = __shfl(base, 63);
+		a_cur = a_nxt; st_cur = st_nxt;
+	}
+	for (int o = 32; o >= 1; o >>= 1) { const int t = __shfl_xor(top, o); top = t > top ? t : top; }
+	if (lane == 0) {
+		if (top >= 0) rcount[top] = mem_carry - base_carry;
+		const bool skip0 = cont && (w[RPW_P] & RP_FULL) == RP_FULL;
+		cw[RPC_RUNS] = top + 1;
+		cw[RPC_LEN2] = 0;
+		cw[RPC_CONT] = cont ? 1 : 0;
+		cw[RPC_LEN1] = top + 1 - (skip0 ? 1 : 0);
+	}
+}
+
+// R4s: one lane per capture, as R4; the members of a continued run 0 whose carried P is full are all skipped, and list 1 starts at run 1
+__global__ __launch_bounds__(256) void k_repeat_lists_stream(const int* __restrict__ runs, const int* __restrict__ rmem, const int* __restrict__ rcount, int n,
+                                                             const int* __restrict__ cw, int* __restrict__ roles, int* __restrict__ list1)
+{
+	const int k = blockIdx.x * 256 + threadIdx.x;
+	if (k >= n) return;
+	const int r = runs[k];
+	if (r < 0) { roles[k] = RP_ROLE_UNUSABLE; return; }
+	const int off = cw[RPC_RUNS] - cw[RPC_LEN1];
+	const bool rep = r >= off && repeat_rep(rmem, rcount, r) == k;
+	roles[k] = rep ? RP_ROLE_REP : RP_ROLE_SKIPPED;
+	if (rep) list1[r - off] = k;
+}
+
+// R5s: as R5. rep_masks holds pass 1's masks by list position, run r at r - off; run 0's carried P counts as delivered.
+__global__ __launch_bounds__(64) void k_repeat_lists2_stream(const int* __restrict__ runs, const uint32_t* __restrict__ rep_masks, int n, RepeatCarry cy,
+                                                             int* __restrict__ roles, int* __restrict__ list2, int* __restrict__ cw)
+{
+	const int lane = threadIdx.x;
+	const unsigned long long below = (1ull << lane) - 1ull;
+	const int off = cw[RPC_RUNS] - cw[RPC_LEN1];
+	int base = 0;
+	for (int k0 = 0; k0 < n; k0 += 64) {
+		const int k = k0 + lane;
+		bool take = false;
+		if (k < n && roles[k] == RP_ROLE_SKIPPED) {
+			const int r = runs[k];
+			if (r >= off) take = ((rep_masks[r - off] | repeat_seg_p(cy, cw, r)) & RP_FULL) != RP_FULL;
+		}
+		const unsigned long long tb = __ballot(take);
+		if (take) { roles[k] = RP_ROLE_FALLBACK; list2[base + (int)__popcll(tb & below)] = k; }
+		base += (int)__popcll(tb);
+	}
+	if (lane == 0) cw[RPC_LEN2] = base;
+}
+
+// The row of run r by one workgroup of 256 (live: r is a run of this call): chunk j from the carried row where the segment's P has bit j, else
+// from the representative where it delivered it, else from the lowest-index member that did, else zeros; *out_mask = P | the OR of the
+// members' masks. out_row / out_mask may each be nullptr. s_src: CHUNKS ints of LDS.
+__device__ __forceinline__ void repeat_fill_row(int r, bool live, const int* __restrict__ rmem, const int* __restrict__ rcount, const uint8_t* __restrict__ chunks,
+                                                const uint32_t* __restrict__ masks, const RepeatCarry& cy, const int* __restrict__ cw, uint8_t* __restrict__ out_row,
+                                                uint32_t* __restrict__ out_mask, int* s_src)
+{
+	const uint32_t P = live ? repeat_seg_p(cy, cw, r) : 0u;
+	if (threadIdx.x < CHUNKS) {
+		int src = -1;
+		if (live) {
+			const int cnt = rcount[r], rep = repeat_rep(rmem, rcount, r);
+			if ((P >> threadIdx.x) & 1u) src = -2;
+			else if ((masks[rep] >> threadIdx.x) & 1u) src = rep;
+			else
+				for (int m = 0; m < cnt && src == -1; ++m) {
+					const int k = rmem[(size_t)r * GMAX + m];
+					if ((masks[k] >> threadIdx.x) & 1u) src = k;
+				}
+		}
+		s_src[threadIdx.x] = src;
+	}
+	__syncthreads();
+	if (out_mask && threadIdx.x == 0) {
+		uint32_t m = P;
+		if (live) for (int j = 0; j < rcount[r]; ++j) m |= masks[rmem[(size_t)r * GMAX + j]];
+		*out_mask = m;
+	}
+	if (!out_row) return;
+	const uint8_t* carried = cy.row + (size_t)cy.cur * RP_CARRY_ROW;
+	// (one workgroup moves the row, so its time is load latency: every load of a lane is issued before its first store, which nothing lets
+	// the compiler do across the stores of a plain copy loop)
+	constexpr int PER = (FRAME_BYTES + 255) / 256;
+	uint8_t v[PER];
+#pragma unroll
+	for (int j = 0; j < PER; ++j) {
+		const int i = threadIdx.x + 256 * j;
+		uint8_t b = 0;
+		if (i < FRAME_BYTES) {
+			const int src = s_src[i / CHUNK];
+			if (src >= 0) b = chunks[(size_t)src * FRAME_BYTES + i];
+			else if (src == -2) b = carried[i];
+		}
+		v[j] = b;
+	}
+#pragma unroll
+	for (int j = 0; j < PER; ++j) {
+		const int i = threadIdx.x + 256 * j;
+		if (i < FRAME_BYTES) out_row[i] = v[j];
+	}
+}
+
+// R8s: one workgroup per run slot r < n; slots at or above the run count are zero. rchunks / rmasks may each be nullptr.
+__global__ __launch_bounds__(256) void k_repeat_end_stream(const int* __restrict__ rmem, const int* __restrict__ rcount, const int* __restrict__ cw,
+                                                           const uint8_t* __restrict__ chunks, const uint32_t* __restrict__ masks, RepeatCarry cy,
+                                                           uint8_t* __restrict__ rchunks, uint32_t* __restrict__ rmasks)
+{
+	const int r = blockIdx.x;
+	__shared__ int s_src[CHUNKS];
+	repeat_fill_row(r, r < cw[RPC_RUNS], rmem, rcount, chunks, masks, cy, cw, rchunks ? rchunks + (size_t)r * FRAME_BYTES : nullptr, rmasks ? rmasks + r : nullptr, s_src);
+}
+
+// R9: one workgroup. The other slot takes the call's last capture: its signature, whether it is in a run, and if so that run's length over
+// all calls, its mask and its row (what R8s reports for it).
+__global__ __launch_bounds__(256) void k_repeat_carry(const uint8_t* __restrict__ sig, const int* __restrict__ runs, const int* __restrict__ rmem,
+                                                      const int* __restrict__ rcount, const int* __restrict__ cw, const uint8_t* __restrict__ chunks,
+                                                      const uint32_t* __restrict__ masks, int n, RepeatCarry cy)
+{
+	const int to = cy.cur ^ 1, r = runs[n - 1];
+	__shared__ int s_src[CHUNKS];
+	const uint32_t* s = reinterpret_cast<const uint32_t*>(sig + (size_t)(n - 1) * NCELLS);
+	uint32_t* d = reinterpret_cast<uint32_t*>(cy.sig + (size_t)to * RP_CARRY_SIG);
+	for (int i = threadIdx.x; i < NCELLS / 4; i += 256) d[i] = s[i];
+	uint32_t* w = cy.words + to * RP_CARRY_WORDS;
+	if (r < 0) {
+		if (threadIdx.x == 0) { w[RPW_USABLE] = 0u; w[RPW_LEN] = 0u; w[RPW_P] = 0u; }
+		return;
+	}
+	if (threadIdx.x == 0) {
+		w[RPW_USABLE] = 1u;
+		w[RPW_LEN] = (uint32_t)(((r == 0 && cw[RPC_CONT]) ? (int)cy.words[cy.cur * RP_CARRY_WORDS + RPW_LEN] : 0) + rcount[r]);
+	}
+	repeat_fill_row(r, true, rmem, rcount, chunks, masks, cy, cw, cy.row + (size_t)to * RP_CARRY_ROW, w + RPW_P, s_src);
 }

@@ -35,6 +35,7 @@ TAP_FLOOD_ROUNDS = 27   # the relaxed flood of the last batch (set_relaxed_flood
 # CIMBAR_HIP_RELAXED_FLOOD_SUGGESTED (include/cimbar_hip.h): the threshold of the table in DESIGN_WIDENING.md "Relaxed flood"
 RELAXED_FLOOD_SUGGESTED = 12
 TAP_REPEAT_SIG, TAP_REPEAT_AGREE = 28, 29   # the grouping of the last once-call (decode_batch_once): tap_repeat_sig / tap_repeat_agree
+TAP_REPEAT_CARRY = 30   # what the once-stream calls carry (decode_batch_once_stream): tap_repeat_carry
 # CIMBAR_HIP_ONCE_*: a capture's role in a once-call
 ONCE_UNUSABLE, ONCE_SKIPPED, ONCE_REPRESENTATIVE, ONCE_FALLBACK = -1, 0, 1, 2
 
@@ -67,6 +68,7 @@ EXPORTS = (
     "cimbar_hip_set_stitch_strips", "cimbar_hip_get_stitch_strips",
     "cimbar_hip_set_relaxed_flood", "cimbar_hip_get_relaxed_flood", "cimbar_hip_relaxed_flood_stats",
     "cimbar_hip_decode_batch_once", "cimbar_hip_scan_extract_decode_batch_once_fmt",
+    "cimbar_hip_decode_batch_once_stream", "cimbar_hip_scan_extract_decode_batch_once_stream_fmt", "cimbar_hip_once_stream_reset",
 )
 # cimbar_hip_deliver_chunks' flags
 DELIVER_DEDUP, DELIVER_REMEMBER, DELIVER_DROP_EMPTY = 1, 2, 4
@@ -205,6 +207,14 @@ def load_library(path=None):
         lib.cimbar_hip_scan_extract_decode_batch_once_fmt.argtypes = [vp, vp, u32, u32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp,
                                                                       i32, vp]
         lib.cimbar_hip_scan_extract_decode_batch_once_fmt.restype = i64
+    if hasattr(lib, "cimbar_hip_decode_batch_once_stream"):   # (likewise)
+        lib.cimbar_hip_decode_batch_once_stream.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]
+        lib.cimbar_hip_decode_batch_once_stream.restype = i64
+        lib.cimbar_hip_scan_extract_decode_batch_once_stream_fmt.argtypes = [vp, vp, u32, u32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp,
+                                                                             vp, vp, vp, i32, vp]
+        lib.cimbar_hip_scan_extract_decode_batch_once_stream_fmt.restype = i64
+        lib.cimbar_hip_once_stream_reset.argtypes = [vp]
+        lib.cimbar_hip_once_stream_reset.restype = i32
     lib.cimbar_hip_combine_stream_reset.argtypes = [vp]
     lib.cimbar_hip_combine_stream_reset.restype = i32
     lib.cimbar_hip_auto_create.argtypes = [i32, vp, i32, ctypes.POINTER(vp)]
@@ -707,6 +717,62 @@ class HipDecoder:
         assert rc == n_runs.value
         return int(rc), chunks, masks, status, runs, roles, rchunks, rmasks
 
+    def decode_batch_once_stream(self, frames, min_agree_permille=0, max_run=0, should_preprocess=False, color_correction=2):
+        """Repeat-capture skipping across calls (cimbar_hip_decode_batch_once_stream): as decode_batch_once, but run 0 may continue the run
+        the last frame of the once-stream call before belongs to, and a run whose earlier calls already delivered every chunk decodes
+        nothing. Returns (n_runs, continued, chunks, masks, runs, roles, rchunks, rmasks); rchunks / rmasks of a continued run are cumulative
+        over its calls."""
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        n = frames.shape[0]
+        if frames.shape[1:] != self.geo.FRAME_SHAPE:
+            raise CimbarHipError(f"decode_batch_once_stream: frames must be (n,{self.geo.IMG_H},{self.geo.IMG_W},3) uint8")
+        chunks, masks, runs, roles, rchunks, rmasks = self._once_outputs(n)
+        n_runs, continued = ctypes.c_int(0), ctypes.c_int(-1)
+        rc = self._check(self._lib.cimbar_hip_decode_batch_once_stream(
+            self._ctx, frames.ctypes.data, n, MEM_HOST, int(bool(should_preprocess)), int(color_correction), int(min_agree_permille), int(max_run),
+            chunks.ctypes.data, masks.ctypes.data, runs.ctypes.data, roles.ctypes.data, rchunks.ctypes.data, rmasks.ctypes.data,
+            ctypes.addressof(n_runs), ctypes.addressof(continued), MEM_HOST, None), "cimbar_hip_decode_batch_once_stream")
+        assert rc == n_runs.value
+        return int(rc), int(continued.value), chunks, masks, runs, roles, rchunks, rmasks
+
+    def decode_batch_once_stream_device(self, frames_ptr, n, chunks_ptr, masks_ptr, runs_ptr=None, roles_ptr=None, rchunks_ptr=None, rmasks_ptr=None,
+                                        n_runs_ptr=None, continued_ptr=None, min_agree_permille=0, max_run=0, should_preprocess=False,
+                                        color_correction=2, stream=None):
+        """Device pointers in and out (the six run outputs may each be 0). Behind the once-stream call before, whatever its stream;
+        synchronises `stream` (None / 0 = the null stream) at most twice to size its decode passes, enqueues the rest and returns 0."""
+        vp = ctypes.c_void_p
+        return int(self._check(self._lib.cimbar_hip_decode_batch_once_stream(
+            self._ctx, vp(frames_ptr), int(n), MEM_DEVICE, int(bool(should_preprocess)), int(color_correction), int(min_agree_permille), int(max_run),
+            vp(chunks_ptr), vp(masks_ptr), vp(runs_ptr or None), vp(roles_ptr or None), vp(rchunks_ptr or None), vp(rmasks_ptr or None),
+            vp(n_runs_ptr or None), vp(continued_ptr or None), MEM_DEVICE, vp(stream) if stream else None),
+            "cimbar_hip_decode_batch_once_stream(device)"))
+
+    def scan_extract_decode_batch_once_stream(self, captures, min_agree_permille=0, max_run=0, preprocess=-1, color_correction=2, size=None, fmt=3):
+        """The capture path of decode_batch_once_stream (cimbar_hip_scan_extract_decode_batch_once_stream_fmt). Returns
+        (n_runs, continued, chunks, masks, status, runs, roles, rchunks, rmasks); a capture whose extraction failed is in no run, carried or
+        not."""
+        captures, n, w, h, fmt = self._captures(captures, size, fmt)
+        chunks, masks, runs, roles, rchunks, rmasks = self._once_outputs(n)
+        status = np.zeros(n, dtype=np.int32)
+        n_runs, continued = ctypes.c_int(0), ctypes.c_int(-1)
+        rc = self._check(self._lib.cimbar_hip_scan_extract_decode_batch_once_stream_fmt(
+            self._ctx, captures.ctypes.data, w, h, fmt, n, MEM_HOST, int(preprocess), int(color_correction), int(min_agree_permille), int(max_run),
+            chunks.ctypes.data, masks.ctypes.data, status.ctypes.data, runs.ctypes.data, roles.ctypes.data, rchunks.ctypes.data, rmasks.ctypes.data,
+            ctypes.addressof(n_runs), ctypes.addressof(continued), MEM_HOST, None), "cimbar_hip_scan_extract_decode_batch_once_stream_fmt")
+        assert rc == n_runs.value
+        return int(rc), int(continued.value), chunks, masks, status, runs, roles, rchunks, rmasks
+
+    def once_stream_reset(self):
+        """forget what the once-stream calls carry: the next one's first capture starts a run"""
+        self._check(self._lib.cimbar_hip_once_stream_reset(self._ctx), "cimbar_hip_once_stream_reset")
+
+    def tap_repeat_carry(self):
+        """TAP_REPEAT_CARRY: (sig (NCELLS,) uint8, usable, len, P) of the capture the once-stream calls carry; raises while nothing is carried"""
+        out = np.zeros(self.geo.NCELLS + 12, dtype=np.uint8)
+        self._check(self._lib.cimbar_hip_tap(self._ctx, TAP_REPEAT_CARRY, out.ctypes.data, out.nbytes), "cimbar_hip_tap")
+        usable, length, p = (int(v) for v in out[self.geo.NCELLS:].copy().view(np.uint32))
+        return out[:self.geo.NCELLS].copy(), usable, length, p
+
     def _stitch_stream_outputs(self, n):
         geo = self.geo
         return (np.zeros((n, geo.CHUNKS_PER_FRAME, geo.CHUNK), dtype=np.uint8), np.zeros(n, dtype=np.uint32),
@@ -1194,10 +1260,11 @@ class HipDecoder:
         self._check(self._lib.cimbar_hip_tap(self._ctx, TAP_REPEAT_SIG, out.ctypes.data, out.nbytes), "cimbar_hip_tap")
         return out
 
-    def tap_repeat_agree(self, n):
-        """TAP_REPEAT_AGREE of the last once-call of n captures: (n - 1,) uint32, the cells of equal signature in captures k and k + 1"""
-        out = np.zeros(max(n - 1, 0), dtype=np.uint32)
-        if n > 1:
+    def tap_repeat_agree(self, n, stream=False):
+        """TAP_REPEAT_AGREE of the last once-call of n captures: (n - 1,) uint32, the cells of equal signature in captures k and k + 1;
+        stream=True, after a once-stream call: (n,), entry 0 against the carried capture (0 when the carry is unusable)"""
+        out = np.zeros(n if stream else max(n - 1, 0), dtype=np.uint32)
+        if out.size:
             self._check(self._lib.cimbar_hip_tap(self._ctx, TAP_REPEAT_AGREE, out.ctypes.data, out.nbytes), "cimbar_hip_tap")
         return out
 
