@@ -194,7 +194,10 @@ int cimbar_hip_get_erasure_decode(cimbar_hip_ctx* ctx, int* sym_distance, int* c
  * the reference's rule without its tie order, so symbols and drift may differ from the reference's in single cells. The result of a frame is
  * accepted when every one of its symbol RS blocks decodes; with fallback != 0 every other frame is replayed exactly inside the same call, and
  * its outputs are then the default policy's byte for byte. An accepted frame's colour pass reads at the relaxed drift, so its colour chunks may
- * differ from the default policy's in either direction.
+ * differ from the default policy's in either direction. Whether the certifying pass settles a frame is not a function of the frame alone: it
+ * declines on the first rule that fires, and on frames with large flat areas (a saturated disc of glare) that can depend on the order in which
+ * its lanes queued tied cells. The default policy's outputs are the same either way; with the relaxed flood on, such a frame is flooded exactly
+ * in one run and in rounds in another, so its CIMBAR_HIP_TAP_FLOOD_PATH, the stats below and an accepted frame's colour chunks may vary.
  *   threshold : -1 turns it off (nothing extra is launched); 0 .. 32 turns it on. CIMBAR_HIP_RELAXED_FLOOD_SUGGESTED (12) is the value of the
  *               table in DESIGN_WIDENING.md "Relaxed flood": the exact flood's quality in 40 .. 1 000 rounds; 24 and more degrade on shifted and
  *               rescaled frames, 0 .. 8 need thousands of rounds on noisy ones. Anything else is CIMBAR_HIP_EINVAL
