@@ -489,8 +489,9 @@ int cimbar_hip_get_stitch_strips(cimbar_hip_ctx* ctx, int* strips);
  *              plain or the combined calls.
  * Buffers, stream and errors otherwise as for cimbar_hip_decode_batch / cimbar_hip_scan_extract_decode_batch_fmt; a null chunks or masks,
  * n <= 0 or a parameter out of range is CIMBAR_HIP_EINVAL, checked before anything is enqueued. Runs across calls: the _once_stream calls
- * below. Not covered: the pipelined and frame-async entry points, the combined / stitched calls, the undistort path and the auto-detection
- * objects. */
+ * below. A run that stays incomplete after pass 2 is given up here; cimbar_hip_set_once_rescue (below) decodes it once more from all its
+ * members' cells, as the combined calls decode a group. Not covered: the pipelined and frame-async entry points, the combined calls' colour
+ * vote and stream forms, the stitched calls, the undistort path and the auto-detection objects. */
 enum {
 	CIMBAR_HIP_ONCE_UNUSABLE = -1,
 	CIMBAR_HIP_ONCE_SKIPPED = 0,
@@ -504,6 +505,39 @@ int64_t cimbar_hip_scan_extract_decode_batch_once_fmt(cimbar_hip_ctx* ctx, const
                                                       int img_mem, int preprocess, int color_correction, int min_agree_permille, int max_run,
                                                       uint8_t* chunks, uint32_t* masks, int* status, int* runs_out, int* roles, uint8_t* rchunks,
                                                       uint32_t* rmasks, int* n_runs, int out_mem, void* hip_stream);
+
+/* Run rescue (off after cimbar_hip_create): a third pass of the two once-calls above, over exactly the runs the first two leave incomplete.
+ * The combined calls deliver a frame whose captures are each damaged somewhere else, at the price of decoding every capture; the once-calls
+ * decode one capture per run but only OR the members' masks. With the setting on, and at least one of rchunks / rmasks not NULL, after pass 2:
+ *   tried      a run is tried when it has at least two members, all of them decoded, and the OR of their masks is not full. All members are
+ *              decoded exactly when the representative's mask was not full (pass 2 then took the rest). A run of one is never tried, nor
+ *              a run whose representative or whose pass-2 members completed it. No tried run in a call: the rescue launches no decode.
+ *   group      a tried run's members, in capture order, are one group of cimbar_hip_decode_batch_combined: the combined cells are its
+ *              -- per cell the symbol vote over 2 d_c(t) - [t == s_c] and the colour plurality with its two tie-breaks -- taken from each
+ *              member's bit plane, symbols, colours, drift and flood flag as the pass that decoded it left them. The representatives'
+ *              cells are kept on the device across pass 2 (about 0.18 MB per run that may need them, mode 68). No colour-correction
+ *              matrix is derived, read or carried.
+ *   decode     Reed-Solomon over the combined cells and the chunk bookkeeping as in the combined call; with
+ *              cimbar_hip_set_erasure_decode on, its symbol-erasure retry as well
+ *   row        rmasks[r] = the combined decode's mask | the members' masks | the chunks the retry added; rchunks[r] chunk j = the combined
+ *              decode's chunk where it delivered it, else that of the lowest-index member that did, else zeros. For a tried run this
+ *              replaces the row described under "per run"; the rows of all other runs are that row, byte for byte. rmasks[r] with the
+ *              setting on is always a superset of rmasks[r] with it off. For a tried run the row equals gchunks / gmasks of
+ *              cimbar_hip_decode_batch_combined (or _scan_extract_decode_batch_combined_fmt) with groups_in = runs_out and the same
+ *              settings, provided no capture's decode depends on what was decoded before it (color_correction 0 or 1).
+ *              (CIMBAR_HIP_TAP_ONCE_RESCUE, CIMBAR_HIP_TAP_ONCE_RESCUE_CELLS)
+ *   unchanged  per-capture chunks / masks / status, runs_out, roles, *n_runs, the return value, the colour-correction carry afterwards and
+ *              the two mid-call read-backs: which runs are tried is decided on the device, nothing more is read back. With the setting
+ *              off no call launches, allocates or writes anything it did not before.
+ * The setting governs cimbar_hip_decode_batch_once and cimbar_hip_scan_extract_decode_batch_once_fmt only: the _once_stream calls below behave
+ * with it on exactly as with it off (their carry holds masks and a chunk row, no cells). Modes 4 and 8 refuse on != 0 (EINVAL), as they
+ * refuse the once-calls. Takes effect for once-calls issued after the call. The rescue uses the group scratch of the combined calls: a
+ * once-call with the setting on and a combined call on the same context at the same time on two streams is the caller's to order, as two
+ * combined calls are. get: writes 1 or 0 to *on and returns 0.
+ * Not covered: the once-stream calls, the colour vote (cimbar_hip_set_group_colour_vote is not consulted), stitching, the undistort path, the
+ * auto-detection objects, the C++ adapter and the receive shim. */
+int cimbar_hip_set_once_rescue(cimbar_hip_ctx* ctx, int on);
+int cimbar_hip_get_once_rescue(cimbar_hip_ctx* ctx, int* on);
 
 /* ---- repeat-capture skipping across calls: the open run is carried from call to call -------------------------------------------------------
  * A live receiver hands over one capture (or a few) per call, so a run of repeats spans calls. The two _once_stream calls are the calls above
@@ -932,7 +966,13 @@ enum {
 	CIMBAR_HIP_TAP_REPEAT_AGREE = 29,   /* (n - 1) u32         : agree(k, k + 1); after a once-stream call n u32 */
 	/* what the once-stream calls carry: the last capture of the last such call (CIMBAR_HIP_EINVAL while nothing is carried: after create and
 	 * after cimbar_hip_once_stream_reset); does not depend on the last batch */
-	CIMBAR_HIP_TAP_REPEAT_CARRY = 30    /* cells bytes + 3 u32 : the carried signature, then {usable, len, P}; len and P are 0 when usable is */
+	CIMBAR_HIP_TAP_REPEAT_CARRY = 30,   /* cells bytes + 3 u32 : the carried signature, then {usable, len, P}; len and P are 0 when usable is */
+	/* the run rescue of the last once-call (cimbar_hip_set_once_rescue; n = its captures). CIMBAR_HIP_EINVAL when that call ran with the
+	 * setting off or was a once-stream call. A call with the setting on that tried nothing (rchunks and rmasks both NULL included) reports
+	 * n times -1 and no cells. _CELLS reads the group scratch the combined calls share: ask before the next combined call on the context. */
+	CIMBAR_HIP_TAP_ONCE_RESCUE = 31,    /* n int32             : per run slot, -1 = the run was not tried, else the chunk bits the rescue added to the OR
+	                                       of the members' masks; slots at and above the run count are -1 */
+	CIMBAR_HIP_TAP_ONCE_RESCUE_CELLS = 32 /* tried * cells bytes : the combined cells of the tried runs, in run order, colour << 4 | symbol */
 };
 int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_bytes);
 

@@ -224,6 +224,18 @@ int cimbar_hip_get_group_colour_vote(cimbar_hip_ctx* ctx, int* on)
 	return CIMBAR_FWD(cimbar_hip_get_group_colour_vote, on);
 }
 
+int cimbar_hip_set_once_rescue(cimbar_hip_ctx* ctx, int on)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return CIMBAR_FWD(cimbar_hip_set_once_rescue, on);
+}
+
+int cimbar_hip_get_once_rescue(cimbar_hip_ctx* ctx, int* on)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return CIMBAR_FWD(cimbar_hip_get_once_rescue, on);
+}
+
 int cimbar_hip_set_stream_colour_vote(cimbar_hip_ctx* ctx, int on)
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;

@@ -144,33 +144,40 @@ struct CarryStore {
 	uint32_t* weights;   // the colour vote's weight of every cell of a member (cimbar_hip_set_stream_colour_vote); nullptr while the stream runs without it
 };
 
-// (CARRY = false is the plain calls' kernel as it always was: a member id is a batch index and `cs` is not read)
-template <bool CARRY>
+// (CARRY = false is the plain calls' kernel as it always was: a member id is a batch index and `cs` is not read. RESCUE, the once-calls' run
+// rescue -- k_group_cells_rescue at the end of this file: a member id is a capture index k and rmap[k] says where its cells are, ~slot of
+// the rescue store `cs` or, >= 0, a position in the batch pass 2 decoded)
+template <bool CARRY, bool RESCUE = false>
 __device__ __forceinline__ void group_cells_body(const uint32_t* __restrict__ plane, const Tables& tb, const uint8_t* __restrict__ symbols,
                                                  const uint8_t* __restrict__ colors, const int8_t* __restrict__ drift,
                                                  const uint32_t* __restrict__ flood_flag, const int* __restrict__ gmem,
                                                  const int* __restrict__ gcount, const int* __restrict__ ngroups, uint8_t* __restrict__ gsym,
                                                  uint8_t* __restrict__ gcol, uint16_t* __restrict__ gmargin, uint32_t* __restrict__ gdisp,
-                                                 const CarryStore& cs)
+                                                 const CarryStore& cs, const int* __restrict__ rmap = nullptr)
 {
 	auto sym_of = [&](int f) -> const uint8_t* {
-		if constexpr (CARRY) return f < CARRY_SLOTS ? cs.symbols + (size_t)f * CS_CELLS : symbols + (size_t)(f - CARRY_SLOTS) * NCELLS;
+		if constexpr (RESCUE) return f < 0 ? cs.symbols + (size_t)~f * CS_CELLS : symbols + (size_t)f * NCELLS;
+		else if constexpr (CARRY) return f < CARRY_SLOTS ? cs.symbols + (size_t)f * CS_CELLS : symbols + (size_t)(f - CARRY_SLOTS) * NCELLS;
 		else return symbols + (size_t)f * NCELLS;
 	};
 	auto col_of = [&](int f) -> const uint8_t* {
-		if constexpr (CARRY) return f < CARRY_SLOTS ? cs.colors + (size_t)f * CS_CELLS : colors + (size_t)(f - CARRY_SLOTS) * NCELLS;
+		if constexpr (RESCUE) return f < 0 ? cs.colors + (size_t)~f * CS_CELLS : colors + (size_t)f * NCELLS;
+		else if constexpr (CARRY) return f < CARRY_SLOTS ? cs.colors + (size_t)f * CS_CELLS : colors + (size_t)(f - CARRY_SLOTS) * NCELLS;
 		else return colors + (size_t)f * NCELLS;
 	};
 	auto drift_of = [&](int f) -> const int8_t* {
-		if constexpr (CARRY) return f < CARRY_SLOTS ? cs.drift + (size_t)f * CS_DRIFT : drift + (size_t)(f - CARRY_SLOTS) * NCELLS * 2;
+		if constexpr (RESCUE) return f < 0 ? cs.drift + (size_t)~f * CS_DRIFT : drift + (size_t)f * NCELLS * 2;
+		else if constexpr (CARRY) return f < CARRY_SLOTS ? cs.drift + (size_t)f * CS_DRIFT : drift + (size_t)(f - CARRY_SLOTS) * NCELLS * 2;
 		else return drift + (size_t)f * NCELLS * 2;
 	};
 	auto plane_of = [&](int f) -> const uint32_t* {
-		if constexpr (CARRY) return f < CARRY_SLOTS ? cs.plane + (size_t)f * CS_PLANE : plane + (size_t)(f - CARRY_SLOTS) * PLANE_WORDS;
+		if constexpr (RESCUE) return f < 0 ? cs.plane + (size_t)~f * CS_PLANE : plane + (size_t)f * PLANE_WORDS;
+		else if constexpr (CARRY) return f < CARRY_SLOTS ? cs.plane + (size_t)f * CS_PLANE : plane + (size_t)(f - CARRY_SLOTS) * PLANE_WORDS;
 		else return plane + (size_t)f * PLANE_WORDS;
 	};
 	auto flood_of = [&](int f) -> uint32_t {
-		if constexpr (CARRY) return f < CARRY_SLOTS ? cs.flood[f] : flood_flag[f - CARRY_SLOTS];
+		if constexpr (RESCUE) return f < 0 ? cs.flood[~f] : flood_flag[f];
+		else if constexpr (CARRY) return f < CARRY_SLOTS ? cs.flood[f] : flood_flag[f - CARRY_SLOTS];
 		else return flood_flag[f];
 	};
 	const int g = blockIdx.y;
@@ -180,7 +187,8 @@ __device__ __forceinline__ void group_cells_body(const uint32_t* __restrict__ pl
 	__shared__ uint16_t s_q[4][GC_CELLS / 4];
 	const int m = gcount[g];
 	if (threadIdx.x < GMAX) {
-		const int f = (int)threadIdx.x < m ? gmem[(size_t)g * GMAX + threadIdx.x] : 0;
+		int f = (int)threadIdx.x < m ? gmem[(size_t)g * GMAX + threadIdx.x] : 0;
+		if constexpr (RESCUE) f = (int)threadIdx.x < m ? rmap[f] : 0;
 		s_mem[threadIdx.x] = f;
 		s_flood[threadIdx.x] = (int)threadIdx.x < m ? flood_of(f) : 0u;
 	}
@@ -830,4 +838,48 @@ __global__ __launch_bounds__(256) void k_group_carry_weights(const uint8_t* __re
 		col[0] = mv & 0xFFu; col[1] = (mv >> 8) & 0xFFu; col[2] = (mv >> 16) & 0xFFu;
 	}
 	cs.weights[(size_t)r * CS_WEIGHTS + i] = color_fit<true>((float)col[0], (float)col[1], (float)col[2], s_m, s_m[9] != 0.0f).margin + 1u;
+}
+
+// ------------------------------------------------------------------------------------------------ run rescue (the once-calls, opt-in)
+// cimbar_hip_set_once_rescue: the group decode above over the runs of a plain once-call that stay incomplete after pass 2 (repeat.hip.inc,
+// "run rescue"). A rescue slot is one such run; its members are capture indices, in capture order. The representative's cells were saved
+// from pass 1's batch into a store laid out as the stream calls' carry store (k_rescue_save), the other members' cells are where pass 2
+// left them; rmap[capture] = ~slot or the position in pass 2's batch. Slots at or above *nslots, and slots whose run pass 2 completed
+// (gcount 0), return at once.
+__global__ __launch_bounds__(256) void k_group_cells_rescue(const uint32_t* __restrict__ plane, Tables tb, const uint8_t* __restrict__ symbols,
+                                                            const uint8_t* __restrict__ colors, const int8_t* __restrict__ drift,
+                                                            const uint32_t* __restrict__ flood_flag, const int* __restrict__ gmem,
+                                                            const int* __restrict__ gcount, const int* __restrict__ nslots, const int* __restrict__ rmap,
+                                                            uint8_t* __restrict__ gsym, uint8_t* __restrict__ gcol, uint16_t* __restrict__ gmargin,
+                                                            uint32_t* __restrict__ gdisp, CarryStore cs)
+{
+	if ((int)blockIdx.y >= *nslots || gcount[blockIdx.y] == 0) return;   // (uniform over the workgroup)
+	group_cells_body<false, true>(plane, tb, symbols, colors, drift, flood_flag, gmem, gcount, nslots, gsym, gcol, gmargin, gdisp, cs, rmap);
+}
+
+// G4 over the rescue slots. The members' chunks and masks are the call's per-capture outputs, by capture index: k_group_end's addressing, so
+// the body is the plain calls' instantiation, writing the slot's row of the staging the Reed-Solomon pass decoded into. Behind it the row
+// goes to the run's place: rchunks[run] / rmasks[run] (each may be nullptr) replace what k_repeat_end wrote there, and tap[run] = the bits
+// the rescue added to the OR of the members' masks.
+__global__ __launch_bounds__(256) void k_group_end_rescue(const uint8_t* __restrict__ gsym, const uint16_t* __restrict__ gmargin, Tables tb,
+                                                          const int* __restrict__ gmem, const int* __restrict__ gcount, const int* __restrict__ nslots,
+                                                          const uint8_t* __restrict__ grs_ok, const uint8_t* __restrict__ chunks,
+                                                          const uint32_t* __restrict__ masks, const uint32_t* __restrict__ gdisp,
+                                                          uint8_t* __restrict__ gchunks, uint32_t* __restrict__ gmasks, int e_on, int e_max,
+                                                          const int* __restrict__ slot_run, uint8_t* __restrict__ rchunks, uint32_t* __restrict__ rmasks,
+                                                          int32_t* __restrict__ tap)
+{
+	const int g = blockIdx.x;
+	if (g >= *nslots || gcount[g] == 0) return;                          // (uniform over the workgroup)
+	group_end_body<false>(gsym, gmargin, tb, gmem, gcount, nslots, grs_ok, chunks, masks, gdisp, gchunks, gmasks, e_on, e_max, CarryStore{}, nullptr);
+	__syncthreads();                                                      // (the row is whole, and visible to the whole workgroup)
+	const int run = slot_run[g];
+	if (rchunks) carry_copy(rchunks + (size_t)run * FRAME_BYTES, gchunks + (size_t)g * FRAME_BYTES, FRAME_BYTES);
+	if (threadIdx.x == 0) {
+		const uint32_t gm = gmasks[g];
+		uint32_t mm = 0;
+		for (int c = 0; c < gcount[g]; ++c) mm |= masks[gmem[(size_t)g * GMAX + c]];
+		if (rmasks) rmasks[run] = gm;
+		tap[run] = (int32_t)(gm & ~mm);
+	}
 }

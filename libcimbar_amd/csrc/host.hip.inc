@@ -89,6 +89,13 @@ struct cimbar_hip_ctx {
 	DevBuf<int> d_rp_words; PinnedBuf<int> h_rp_words;                                   // [0] runs = the length of list 1, [1] the length of list 2
 	DevBuf<uint8_t> d_rp_frames, d_rp_chunks; DevBuf<uint32_t> d_rp_masks;               // [list] gathered frames and what their decode delivered
 	DevBuf<uint8_t> d_rp_rchunks; DevBuf<uint32_t> d_rp_rmasks;                          // staging for host-memory run outputs
+	// run rescue (cimbar_hip_set_once_rescue, repeat.hip.inc "run rescue"): nothing of it exists until a plain once-call with the setting on needs it.
+	// The rescue's group scratch is the combined calls' (d_gsym .. d_gmasks above), sized by the rescue slots.
+	int rs_on = 0;                              // the setting
+	int rs_state = 0;                           // the last once-call: 0 = a stream call or the setting off, 1 = on and nothing launched, 2 = the rescue kernels ran
+	int rs_slots = 0;                           // ... over that many slots (the host's bound on the qualifying runs)
+	DevBuf<uint8_t> d_rs_symbols, d_rs_colors; DevBuf<int8_t> d_rs_drift; DevBuf<uint32_t> d_rs_plane, d_rs_flood;   // the store: [slots] x CS_CELLS, CS_CELLS, CS_DRIFT, CS_PLANE, 1
+	DevBuf<int> d_rs_run, d_rs_map, d_rs_count; DevBuf<int32_t> d_rs_tap;                // [slots] the slot's run, [n] where a member's cells are, 1 int, [n] CIMBAR_HIP_TAP_ONCE_RESCUE
 	int wave_adapt = 1;               // CIMBAR_HIP_FLOOD_WAVE_ADAPT=0: run k_flood_wave in front of every exact replay, whatever it achieved before
 	bool wave_ran = false;            // k_flood_wave ran in the batch h_flagged describes
 	int wave_skip_left = 0;           // batches that still go straight to the exact replay (see enqueue)
@@ -2105,6 +2112,30 @@ int ensure_once_list(cimbar_hip_ctx* ctx, int len)
 	return 0;
 }
 
+// the run rescue's buffers for a call of n captures and `slots` rescue slots: the store of the representatives' cells, the group scratch
+// (the combined calls': a slot is a group slot, d_gchunks / d_gmasks the slot staging) and the small maps
+int ensure_rescue_capacity(cimbar_hip_ctx* ctx, int n, int slots)
+{
+	const size_t S = (size_t)slots;
+	if (int r = ensure_group_capacity(ctx, slots)) return r;
+	HIPCHK(ctx->d_rs_symbols.reserve(S * CS_CELLS));
+	HIPCHK(ctx->d_rs_colors.reserve(S * CS_CELLS));
+	HIPCHK(ctx->d_rs_drift.reserve(S * CS_DRIFT));
+	HIPCHK(ctx->d_rs_plane.reserve(S * CS_PLANE));
+	HIPCHK(ctx->d_rs_flood.reserve(S));
+	HIPCHK(ctx->d_rs_run.reserve(S));
+	HIPCHK(ctx->d_rs_count.ensure(1));
+	HIPCHK(ctx->d_rs_map.reserve((size_t)n));
+	HIPCHK(ctx->d_rs_tap.reserve((size_t)n));
+	return 0;
+}
+
+// the store as the group kernels take it (what a rescue member has no use for stays null: its chunks and mask are the call's own outputs)
+CarryStore rescue_store(cimbar_hip_ctx* ctx)
+{
+	return CarryStore{ctx->d_rs_symbols, ctx->d_rs_colors, ctx->d_rs_plane, ctx->d_rs_drift, ctx->d_rs_flood, nullptr, nullptr, nullptr, nullptr};
+}
+
 // the 4-byte count d_words[which] (h_words: its page-locked mirror), read back behind everything enqueued on `st` so far
 int once_read_count(cimbar_hip_ctx* ctx, hipStream_t st, const int* d_words, int* h_words, int which, int* out)
 {
@@ -2169,6 +2200,10 @@ int64_t once_impl(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_frames, 
 	int* d_words = os ? os->cw.get() : ctx->d_rp_words.get();
 	int* h_words = os ? os->h_cw.get() : ctx->h_rp_words.get();
 	const int w_len1 = os ? (int)RPC_LEN1 : 0, w_len2 = os ? (int)RPC_LEN2 : 1;
+	// the run rescue (cimbar_hip_set_once_rescue): the plain once-calls only, and only where a run row is asked for
+	const bool rescue = ctx->rs_on != 0 && !os && (oa.rchunks || oa.rmasks);
+	int rs_slots = 0;
+	ctx->rs_state = 0;
 
 	hipLaunchKernelGGL(k_repeat_sums, dim3(DIM_Y, n), dim3(256), 0, st, d_frames, ctx->tb, ctx->d_rp_sums);
 	hipLaunchKernelGGL(k_repeat_sig, dim3(n), dim3(256), 0, st, ctx->d_rp_sums, ctx->d_rp_sig);
@@ -2217,11 +2252,23 @@ int64_t once_impl(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_frames, 
 			if (int r = pass(ctx->d_rp_list, len1)) return r;
 			if (os)
 				hipLaunchKernelGGL(k_repeat_lists2_stream, dim3(1), dim3(64), 0, st, ctx->d_rp_runs, ctx->d_rp_masks, n, cy, ctx->d_rp_roles, ctx->d_rp_list + n, d_words);
-			else
-				hipLaunchKernelGGL(k_repeat_lists2, dim3(1), dim3(64), 0, st, ctx->d_rp_runs, ctx->d_rp_masks, n, ctx->d_rp_roles, ctx->d_rp_list + n, ctx->d_rp_words + 1);
+			else {
+				if (rescue) HIPCHK(ctx->d_rs_map.reserve(N));
+				hipLaunchKernelGGL(k_repeat_lists2, dim3(1), dim3(64), 0, st, ctx->d_rp_runs, ctx->d_rp_masks, n, ctx->d_rp_roles, ctx->d_rp_list + n, ctx->d_rp_words + 1,
+				                   rescue ? ctx->d_rs_map.get() : (int*)nullptr);
+			}
 			HIPCHK(hipGetLastError());
 			if (int r = once_read_count(ctx, st, d_words, h_words, w_len2, &len2)) return r;
 			if (len2 < 0 || len2 > n - len1) { ctx->err = "decode_batch_once: the fallback count read back is out of range"; return CIMBAR_HIP_EHIP; }
+			if (rescue && len2 > 0) {
+				// pass 2 overwrites pass 1's scratch: the representatives of the runs that may need the rescue are saved first
+				rs_slots = len1 < len2 ? len1 : len2;
+				if (int r = ensure_rescue_capacity(ctx, n, rs_slots)) return r;
+				cimbar_hip_ctx::ScratchSet& p1 = ctx->cur();
+				hipLaunchKernelGGL(k_rescue_save, dim3(RS_ARRAYS * RS_PARTS, rs_slots), dim3(256), 0, st, p1.d_plane, p1.d_symbols, p1.d_colors, p1.d_drift, p1.d_flood,
+				                   ctx->d_rp_masks, ctx->d_rp_mem, ctx->d_rp_count, len1, rescue_store(ctx), ctx->d_rs_run, ctx->d_gmem, ctx->d_rs_map, ctx->d_rs_count);
+				HIPCHK(hipGetLastError());
+			}
 			if (len2 > 0) if (int r = pass(ctx->d_rp_list + n, len2)) return r;
 		}
 	}
@@ -2238,6 +2285,20 @@ int64_t once_impl(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_frames, 
 		hipLaunchKernelGGL(k_repeat_carry, dim3(1), dim3(256), 0, st, ctx->d_rp_sig, ctx->d_rp_runs, ctx->d_rp_mem, ctx->d_rp_count, d_words, d_chunks, d_masks, n, cy);
 	} else if (d_rchunks || d_rmasks)
 		hipLaunchKernelGGL(k_repeat_end, dim3(n), dim3(256), 0, st, ctx->d_rp_mem, ctx->d_rp_count, ctx->d_rp_words, d_chunks, d_masks, d_rchunks, d_rmasks);
+	if (rs_slots > 0) {
+		// the rescue: which slots are tried, their combined cells from the store and pass 2's scratch, the groups' Reed-Solomon pass into the
+		// slot staging, and the tried runs' rows over k_repeat_end's
+		cimbar_hip_ctx::ScratchSet& p2 = ctx->cur();
+		HIPCHK(hipMemsetAsync(ctx->d_rs_tap, 0xFF, sizeof(int32_t) * N, st));
+		hipLaunchKernelGGL(k_rescue_tried, dim3((rs_slots + 255) / 256), dim3(256), 0, st, ctx->d_rs_count, rs_slots, ctx->d_rs_run, ctx->d_gmem, ctx->d_rp_count, d_masks,
+		                   ctx->d_gcount, ctx->d_gdisp);
+		hipLaunchKernelGGL(k_group_cells_rescue, dim3(GC_BLOCKS, rs_slots), dim3(256), 0, st, p2.d_plane, ctx->tb, p2.d_symbols, p2.d_colors, p2.d_drift, p2.d_flood,
+		                   ctx->d_gmem, ctx->d_gcount, ctx->d_rs_count, ctx->d_rs_map, ctx->d_gsym, ctx->d_gcol, ctx->d_gmargin, ctx->d_gdisp, rescue_store(ctx));
+		launch_live_rs(ctx, st, rs_slots, ctx->d_gsym, ctx->d_gcol, ctx->d_grs_ok, ctx->d_rs_count, ctx->d_gdisp, ctx->d_gchunks);
+		hipLaunchKernelGGL(k_group_end_rescue, dim3(rs_slots), dim3(256), 0, st, ctx->d_gsym, ctx->d_gmargin, ctx->tb, ctx->d_gmem, ctx->d_gcount, ctx->d_rs_count,
+		                   ctx->d_grs_ok, d_chunks, d_masks, ctx->d_gdisp, ctx->d_gchunks, ctx->d_gmasks, (!LEGACY && ctx->er_sym > 0) ? 1 : 0, erasure_max(ctx),
+		                   ctx->d_rs_run, d_rchunks, d_rmasks, ctx->d_rs_tap);
+	}
 	HIPCHK(hipGetLastError());
 	const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
 	if (oa.runs_out) HIPCHK(hipMemcpyAsync(oa.runs_out, ctx->d_rp_runs, sizeof(int) * N, kind, st));
@@ -2245,6 +2306,8 @@ int64_t once_impl(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_frames, 
 	auto done = [&]() {
 		ctx->rp_n = n;
 		ctx->rp_stream = os != nullptr;
+		ctx->rs_state = (ctx->rs_on != 0 && !os) ? (rs_slots > 0 ? 2 : 1) : 0;
+		ctx->rs_slots = rs_slots;
 		if (os) { os->cur ^= 1; os->carried = true; }
 	};
 	if (dev) {
@@ -2527,6 +2590,22 @@ int cimbar_hip_get_group_colour_vote(cimbar_hip_ctx* ctx, int* on)
 	return 0;
 }
 
+int cimbar_hip_set_once_rescue(cimbar_hip_ctx* ctx, int on)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	if (LEGACY && on) { ctx->err = "set_once_rescue: modes 4 and 8 have no once-calls to govern; repeat-capture skipping covers modes 68 / 67 / 66"; return CIMBAR_HIP_EINVAL; }
+	// (read when a plain once-call is enqueued: calls already issued keep the setting they were issued with)
+	ctx->rs_on = on ? 1 : 0;
+	return 0;
+}
+
+int cimbar_hip_get_once_rescue(cimbar_hip_ctx* ctx, int* on)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	if (on) *on = ctx->rs_on;
+	return 0;
+}
+
 int cimbar_hip_set_stitch_strips(cimbar_hip_ctx* ctx, int strips)
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;
@@ -2656,6 +2735,38 @@ int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_byte
 		HIPCHK(hipDeviceSynchronize());
 		if (bytes) HIPCHK(hipMemcpy(out, what == CIMBAR_HIP_TAP_REPEAT_SIG ? (const void*)ctx->d_rp_sig.get() : (const void*)ctx->d_rp_agree.get(), bytes, hipMemcpyDeviceToHost));
 		return (int64_t)bytes;
+	}
+	if (what == CIMBAR_HIP_TAP_ONCE_RESCUE || what == CIMBAR_HIP_TAP_ONCE_RESCUE_CELLS) {
+		// the run rescue of the last plain once-call: per run slot what it added, and the combined cells of the tried runs, in run order
+		if (ctx->rp_n <= 0 || ctx->rs_state == 0) { ctx->err = "tap: the last once-call was not a plain one with the run rescue on (cimbar_hip_set_once_rescue)"; return CIMBAR_HIP_EINVAL; }
+		const size_t m = (size_t)ctx->rp_n, S = ctx->rs_state == 2 ? (size_t)ctx->rs_slots : 0;
+		HIPCHK(hipSetDevice(ctx->device));
+		HIPCHK(hipDeviceSynchronize());
+		if (what == CIMBAR_HIP_TAP_ONCE_RESCUE) {
+			if (out_bytes < m * sizeof(int32_t)) { ctx->err = "tap: buffer too small"; return CIMBAR_HIP_EINVAL; }
+			if (S) HIPCHK(hipMemcpy(out, ctx->d_rs_tap, m * sizeof(int32_t), hipMemcpyDeviceToHost));
+			else std::memset(out, 0xFF, m * sizeof(int32_t));
+			return (int64_t)(m * sizeof(int32_t));
+		}
+		std::vector<int> cnt(S);
+		int live = 0;
+		if (S) {
+			HIPCHK(hipMemcpy(&live, ctx->d_rs_count, sizeof(int), hipMemcpyDeviceToHost));
+			HIPCHK(hipMemcpy(cnt.data(), ctx->d_gcount, sizeof(int) * S, hipMemcpyDeviceToHost));
+		}
+		size_t tried = 0;
+		for (size_t s = 0; s < S && s < (size_t)live; ++s) tried += cnt[s] > 0 ? 1 : 0;
+		if (out_bytes < tried * NCELLS) { ctx->err = "tap: buffer too small"; return CIMBAR_HIP_EINVAL; }
+		std::vector<uint8_t> sym(NCELLS), col(NCELLS);
+		uint8_t* o = (uint8_t*)out;
+		for (size_t s = 0; s < S && s < (size_t)live; ++s) {
+			if (cnt[s] <= 0) continue;
+			HIPCHK(hipMemcpy(sym.data(), ctx->d_gsym + s * NCELLS, NCELLS, hipMemcpyDeviceToHost));
+			HIPCHK(hipMemcpy(col.data(), ctx->d_gcol + s * NCELLS, NCELLS, hipMemcpyDeviceToHost));
+			for (size_t k = 0; k < (size_t)NCELLS; ++k) o[k] = (uint8_t)((col[k] << 4) | (sym[k] & 15u));
+			o += NCELLS;
+		}
+		return (int64_t)(tried * NCELLS);
 	}
 	if (ctx->last_n <= 0) { ctx->err = "tap: no batch has been decoded on this context yet"; return CIMBAR_HIP_EINVAL; }
 	HIPCHK(hipSetDevice(ctx->device));

@@ -27,7 +27,8 @@
 //   R7 k_repeat_clear / k_repeat_scatter   zeroes for what no pass has decoded yet; a pass's chunks and masks back into capture slots
 //   R8 k_repeat_end      the per-run fill
 // The host reads the length of list 1, and then of list 2, back to size the decode launches (host.hip.inc, once_impl).
-// The once-stream calls carry the last capture's run from call to call: "runs across calls" at the end of this file.
+// The once-stream calls carry the last capture's run from call to call: "runs across calls" below. Opt-in, the plain once-calls decode a
+// run that stays incomplete after pass 2 once more from all its members' cells: "run rescue" at the end of this file.
 constexpr int RP_AGREE_DEFAULT = 900, RP_RUN_DEFAULT = 4;
 constexpr int RP_ROW0 = 2, RP_ROWS = 4;                                  // pixel rows y + 2 .. y + 5 of a cell
 constexpr int RP_ROW_BYTES = IMG_W * 3, RP_ROW_VEC = RP_ROW_BYTES / 16;   // 3072 | 2208 bytes: 192 | 138 16-byte loads
@@ -135,9 +136,10 @@ __global__ __launch_bounds__(256) void k_repeat_lists(const int* __restrict__ ru
 }
 
 // R5: one wavefront, 64 captures per step. A skipped capture whose run's representative came back with an incomplete mask (rep_masks[r]: pass
-// 1's masks, by run) takes role 2 and joins list 2, in capture order; *count2 = its length.
+// 1's masks, by run) takes role 2 and joins list 2, in capture order; *count2 = its length. map (the run rescue's, else nullptr): map[k] =
+// capture k's position in list 2.
 __global__ __launch_bounds__(64) void k_repeat_lists2(const int* __restrict__ runs, const uint32_t* __restrict__ rep_masks, int n, int* __restrict__ roles,
-                                                      int* __restrict__ list2, int* __restrict__ count2)
+                                                      int* __restrict__ list2, int* __restrict__ count2, int* __restrict__ map)
 {
 	const int lane = threadIdx.x;
 	const unsigned long long below = (1ull << lane) - 1ull;
@@ -148,7 +150,12 @@ __global__ __launch_bounds__(64) void k_repeat_lists2(const int* __restrict__ ru
 		bool take = false;
 		if (k < n && roles[k] == RP_ROLE_SKIPPED) take = (rep_masks[runs[k]] & FULL) != FULL;
 		const unsigned long long tb = __ballot(take);
-		if (take) { roles[k] = RP_ROLE_FALLBACK; list2[base + (int)__popcll(tb & below)] = k; }
+		if (take) {
+			const int pos = base + (int)__popcll(tb & below);
+			roles[k] = RP_ROLE_FALLBACK;
+			list2[pos] = k;
+			if (map) map[k] = pos;
+		}
 		base += (int)__popcll(tb);
 	}
 	if (lane == 0) *count2 = base;
@@ -466,4 +473,93 @@ __global__ __launch_bounds__(256) void k_repeat_carry(const uint8_t* __restrict_
 		w[RPW_LEN] = (uint32_t)(((r == 0 && cw[RPC_CONT]) ? (int)cy.words[cy.cur * RP_CARRY_WORDS + RPW_LEN] : 0) + rcount[r]);
 	}
 	repeat_fill_row(r, true, rmem, rcount, chunks, masks, cy, cw, cy.row + (size_t)to * RP_CARRY_ROW, w + RPW_P, s_src);
+}
+
+// ------------------------------------------------------------------------------------------------ run rescue (the plain once-calls, opt-in)
+// cimbar_hip_set_once_rescue. A run whose members have all been decoded and whose masks together are still not full is given up by the rule
+// above, although every member's cells were on the device a moment earlier. With the setting on such a run is decoded once more, as one
+// group of the combined call (combine.hip.inc G3, k_rs LIVE, G4), from the cells every member's own pass left:
+//   qualifies  a run of two or more members whose representative's mask is not full: pass 2 decodes its other members, so afterwards all of
+//              its members are decoded. At most min(|list 1|, |list 2|) runs qualify, each owning a member of list 2: the host sizes the
+//              store, the group scratch and every grid below from that bound and reads nothing back for it.
+//   slot       a qualifying run's rank among them, in run order
+//   tried      a qualifying run whose members' masks, after pass 2, are together still not full
+//   R10 k_rescue_save    in front of pass 2, which overwrites pass 1's scratch: the representative's symbols, colours, drift, bit plane and
+//                        flood word go from pass 1's batch (position = run) to the slot of a store laid out as the stream calls' carry store;
+//                        slot_run, the slot's member row, map[representative] = ~slot and the slot count are written too (k_repeat_lists2
+//                        wrote map[k] = the position in list 2 for the other members)
+//   R11 k_rescue_tried   behind pass 2's scatter: gcount[slot] = the run's members if it is tried, else 0; gdisp[slot] = 0
+//   G3r k_group_cells_rescue, k_rs LIVE, G4r k_group_end_rescue (combine.hip.inc), G4r behind R8: a tried run's row replaces R8's
+constexpr int RS_PARTS = 4, RS_ARRAYS = 4;
+
+// R10: workgroup (slice, slot). Wavefront 0 of every workgroup walks the runs, 64 per step with a carried base, to the run of its slot (none:
+// the slot is at or above the count and the workgroup returns); then one of RS_PARTS slices of one of the four arrays is copied, 16 bytes
+// per lane where the ends allow it (carry_copy).
+__global__ __launch_bounds__(256) void k_rescue_save(const uint32_t* __restrict__ plane, const uint8_t* __restrict__ symbols, const uint8_t* __restrict__ colors,
+                                                     const int8_t* __restrict__ drift, const uint32_t* __restrict__ flood_flag,
+                                                     const uint32_t* __restrict__ rep_masks, const int* __restrict__ rmem, const int* __restrict__ rcount,
+                                                     int nruns, CarryStore cs, int* __restrict__ slot_run, int* __restrict__ smem, int* __restrict__ map,
+                                                     int* __restrict__ nslots)
+{
+	const int slot = blockIdx.y;
+	__shared__ int s_run;
+	if (threadIdx.x < 64) {
+		const int lane = threadIdx.x;
+		const unsigned long long below = (1ull << lane) - 1ull;
+		int base = 0, mine = -1;
+		for (int r0 = 0; r0 < nruns; r0 += 64) {
+			const int r = r0 + lane;
+			const bool q = r < nruns && rcount[r] >= 2 && (rep_masks[r] & RP_FULL) != RP_FULL;
+			const unsigned long long qb = __ballot(q);
+			if (q && base + (int)__popcll(qb & below) == slot) mine = r;
+			base += (int)__popcll(qb);
+		}
+		for (int o = 32; o >= 1; o >>= 1) { const int t = __shfl_xor(mine, o); mine = t > mine ? t : mine; }
+		if (lane == 0) {
+			s_run = mine;
+			if (blockIdx.x == 0 && slot == 0) *nslots = base;
+		}
+	}
+	__syncthreads();
+	const int r = s_run;
+	if (r < 0) return;                                                   // (uniform over the workgroup)
+	if (blockIdx.x == 0) {
+		const int cnt = rcount[r];
+		if (threadIdx.x < GMAX) smem[(size_t)slot * GMAX + threadIdx.x] = (int)threadIdx.x < cnt ? rmem[(size_t)r * GMAX + threadIdx.x] : 0;
+		if (threadIdx.x == 0) {
+			slot_run[slot] = r;
+			map[repeat_rep(rmem, rcount, r)] = ~slot;
+			cs.flood[slot] = flood_flag[r];
+		}
+	}
+	const int arr = blockIdx.x / RS_PARTS, part = blockIdx.x % RS_PARTS;
+	const size_t k = (size_t)r;
+	const uint8_t* src; uint8_t* dst; size_t bytes;
+	switch (arr) {
+		case 0: src = symbols + k * NCELLS; dst = cs.symbols + (size_t)slot * CS_CELLS; bytes = NCELLS; break;
+		case 1: src = colors + k * NCELLS; dst = cs.colors + (size_t)slot * CS_CELLS; bytes = NCELLS; break;
+		case 2: src = reinterpret_cast<const uint8_t*>(drift + k * NCELLS * 2); dst = reinterpret_cast<uint8_t*>(cs.drift + (size_t)slot * CS_DRIFT); bytes = (size_t)NCELLS * 2; break;
+		default: src = reinterpret_cast<const uint8_t*>(plane + k * PLANE_WORDS); dst = reinterpret_cast<uint8_t*>(cs.plane + (size_t)slot * CS_PLANE); bytes = (size_t)PLANE_WORDS * 4; break;
+	}
+	// this workgroup's slice: whole 16-byte units, the last slice takes the rest
+	const size_t per = (bytes / RS_PARTS) & ~(size_t)15, lo = per * part, hi = part == RS_PARTS - 1 ? bytes : lo + per;
+	carry_copy(dst + lo, src + lo, hi - lo);
+}
+
+// R11: one lane per slot of the `slots` the host sized for. masks: the call's per-capture masks, pass 2's included.
+__global__ __launch_bounds__(256) void k_rescue_tried(const int* __restrict__ nslots, int slots, const int* __restrict__ slot_run, const int* __restrict__ smem,
+                                                      const int* __restrict__ rcount, const uint32_t* __restrict__ masks, int* __restrict__ gcount,
+                                                      uint32_t* __restrict__ gdisp)
+{
+	const int s = blockIdx.x * 256 + threadIdx.x;
+	if (s >= slots) return;
+	int m = 0;
+	if (s < *nslots) {
+		const int cnt = rcount[slot_run[s]];
+		uint32_t all = 0;
+		for (int j = 0; j < cnt; ++j) all |= masks[smem[(size_t)s * GMAX + j]];
+		m = (all & RP_FULL) != RP_FULL ? cnt : 0;
+	}
+	gcount[s] = m;
+	gdisp[s] = 0u;
 }

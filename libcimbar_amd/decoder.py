@@ -36,6 +36,7 @@ TAP_FLOOD_ROUNDS = 27   # the relaxed flood of the last batch (set_relaxed_flood
 RELAXED_FLOOD_SUGGESTED = 12
 TAP_REPEAT_SIG, TAP_REPEAT_AGREE = 28, 29   # the grouping of the last once-call (decode_batch_once): tap_repeat_sig / tap_repeat_agree
 TAP_REPEAT_CARRY = 30   # what the once-stream calls carry (decode_batch_once_stream): tap_repeat_carry
+TAP_ONCE_RESCUE, TAP_ONCE_RESCUE_CELLS = 31, 32   # the run rescue of the last plain once-call (set_once_rescue): tap_once_rescue / tap_once_rescue_cells
 # CIMBAR_HIP_ONCE_*: a capture's role in a once-call
 ONCE_UNUSABLE, ONCE_SKIPPED, ONCE_REPRESENTATIVE, ONCE_FALLBACK = -1, 0, 1, 2
 
@@ -69,6 +70,7 @@ EXPORTS = (
     "cimbar_hip_set_relaxed_flood", "cimbar_hip_get_relaxed_flood", "cimbar_hip_relaxed_flood_stats",
     "cimbar_hip_decode_batch_once", "cimbar_hip_scan_extract_decode_batch_once_fmt",
     "cimbar_hip_decode_batch_once_stream", "cimbar_hip_scan_extract_decode_batch_once_stream_fmt", "cimbar_hip_once_stream_reset",
+    "cimbar_hip_set_once_rescue", "cimbar_hip_get_once_rescue",
 )
 # cimbar_hip_deliver_chunks' flags
 DELIVER_DEDUP, DELIVER_REMEMBER, DELIVER_DROP_EMPTY = 1, 2, 4
@@ -263,6 +265,11 @@ def load_library(path=None):
         lib.cimbar_hip_set_stream_colour_vote.restype = i32
         lib.cimbar_hip_get_stream_colour_vote.argtypes = [vp, ctypes.POINTER(i32)]
         lib.cimbar_hip_get_stream_colour_vote.restype = i32
+    if hasattr(lib, "cimbar_hip_set_once_rescue"):   # (the same: tools/once_rescue_bench.py --parent-lib)
+        lib.cimbar_hip_set_once_rescue.argtypes = [vp, i32]
+        lib.cimbar_hip_set_once_rescue.restype = i32
+        lib.cimbar_hip_get_once_rescue.argtypes = [vp, ctypes.POINTER(i32)]
+        lib.cimbar_hip_get_once_rescue.restype = i32
     lib.cimbar_hip_mode_bufsize.argtypes = [i32]
     lib.cimbar_hip_mode_bufsize.restype = i32
     lib.cimbar_hip_ctx_bufsize.argtypes = [vp]
@@ -1132,6 +1139,16 @@ class HipDecoder:
         self._check(self._lib.cimbar_hip_get_group_colour_vote(self._ctx, ctypes.byref(a)), "cimbar_hip_get_group_colour_vote")
         return bool(a.value)
 
+    def set_once_rescue(self, on=True):
+        """cimbar_hip_set_once_rescue: decode_batch_once / scan_extract_decode_batch_once decode a run that stays incomplete after pass 2
+        once more from all its members' cells, as decode_batch_combined decodes a group (off after create; the once-stream calls ignore it)"""
+        self._check(self._lib.cimbar_hip_set_once_rescue(self._ctx, int(bool(on))), "cimbar_hip_set_once_rescue")
+
+    def get_once_rescue(self):
+        a = ctypes.c_int(0)
+        self._check(self._lib.cimbar_hip_get_once_rescue(self._ctx, ctypes.byref(a)), "cimbar_hip_get_once_rescue")
+        return bool(a.value)
+
     def set_stream_colour_vote(self, on=True):
         """cimbar_hip_set_stream_colour_vote: the colour vote (and, with set_colour_erasure_decode on, the group colour retry) in the stream
         calls; set_group_colour_vote governs the plain combined calls only. A stream samples it in its first call after create /
@@ -1267,6 +1284,20 @@ class HipDecoder:
         if out.size:
             self._check(self._lib.cimbar_hip_tap(self._ctx, TAP_REPEAT_AGREE, out.ctypes.data, out.nbytes), "cimbar_hip_tap")
         return out
+
+    def tap_once_rescue(self, n):
+        """TAP_ONCE_RESCUE of the last plain once-call of n captures with set_once_rescue on: (n,) int32 per run slot, -1 = not tried, else
+        the chunk bits the rescue added to the OR of the members' masks"""
+        out = np.zeros(n, dtype=np.int32)
+        self._check(self._lib.cimbar_hip_tap(self._ctx, TAP_ONCE_RESCUE, out.ctypes.data, out.nbytes), "cimbar_hip_tap")
+        return out
+
+    def tap_once_rescue_cells(self, n_tried):
+        """TAP_ONCE_RESCUE_CELLS of that call: (n_tried, NCELLS) uint8, the combined cells of the tried runs in run order, colour << 4 | symbol"""
+        out = np.zeros((max(n_tried, 1), self.geo.NCELLS), dtype=np.uint8)   # (never a null pointer; a call that tried nothing writes nothing)
+        got = self._check(self._lib.cimbar_hip_tap(self._ctx, TAP_ONCE_RESCUE_CELLS, out.ctypes.data, n_tried * self.geo.NCELLS), "cimbar_hip_tap")
+        assert got == n_tried * self.geo.NCELLS, (got, n_tried)
+        return out[:n_tried]
 
     def enable_timing(self, on=True):
         self._lib.cimbar_hip_enable_timing(self._ctx, int(bool(on)))
