@@ -490,13 +490,16 @@ int cimbar_hip_get_stitch_strips(cimbar_hip_ctx* ctx, int* strips);
  * Buffers, stream and errors otherwise as for cimbar_hip_decode_batch / cimbar_hip_scan_extract_decode_batch_fmt; a null chunks or masks,
  * n <= 0 or a parameter out of range is CIMBAR_HIP_EINVAL, checked before anything is enqueued. Runs across calls: the _once_stream calls
  * below. A run that stays incomplete after pass 2 is given up here; cimbar_hip_set_once_rescue (below) decodes it once more from all its
- * members' cells, as the combined calls decode a group. Not covered: the pipelined and frame-async entry points, the combined calls' colour
- * vote and stream forms, the stitched calls, the undistort path and the auto-detection objects. */
+ * members' cells, as the combined calls decode a group. A torn capture between two runs is a run of one and is decoded in pass 1;
+ * cimbar_hip_set_once_tear_skip (below) leaves it undecoded where both neighbour runs are complete. Not covered: the pipelined and
+ * frame-async entry points, the combined calls' colour vote and stream forms, stitching a frame out of torn captures (the stitched calls),
+ * the undistort path and the auto-detection objects. */
 enum {
 	CIMBAR_HIP_ONCE_UNUSABLE = -1,
 	CIMBAR_HIP_ONCE_SKIPPED = 0,
 	CIMBAR_HIP_ONCE_REPRESENTATIVE = 1,
-	CIMBAR_HIP_ONCE_FALLBACK = 2
+	CIMBAR_HIP_ONCE_FALLBACK = 2,
+	CIMBAR_HIP_ONCE_TORN = 3        /* only with cimbar_hip_set_once_tear_skip on: a torn boundary capture that was left undecoded */
 };
 int64_t cimbar_hip_decode_batch_once(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rgb_mem, int should_preprocess, int color_correction,
                                      int min_agree_permille, int max_run, uint8_t* chunks, uint32_t* masks, int* runs_out, int* roles,
@@ -538,6 +541,46 @@ int64_t cimbar_hip_scan_extract_decode_batch_once_fmt(cimbar_hip_ctx* ctx, const
  * auto-detection objects, the C++ adapter and the receive shim. */
 int cimbar_hip_set_once_rescue(cimbar_hip_ctx* ctx, int on);
 int cimbar_hip_get_once_rescue(cimbar_hip_ctx* ctx, int* on);
+
+/* Tear skipping (off after cimbar_hip_create): the two once-calls above leave a torn boundary capture undecoded. A camera that films faster
+ * than the display changes catches a frame switch in about one capture of four: frame P on one side of a line, frame N on the other. Its
+ * signature agrees with each neighbour on about 600 permille of the cells, so it is a run of one, its own representative, and is decoded in
+ * pass 1 -- through the flood path, for chunks its neighbour runs already have. With the setting on, runs, runs_out, *n_runs, the return
+ * value and the number of mid-call read-backs are what they are with it off; only who is decoded changes:
+ *   lines      line(i), L and width(l) are those of the stitched calls: axis 0 the grid rows, axis 1 the grid columns. axis 2 evaluates both:
+ *              a capture is torn if either axis says so, and axis 0's tear is reported when both do.
+ *   eligible   capture k is eligible when 1 <= k <= n - 2, captures k - 1, k and k + 1 are usable, and k's run has one member
+ *   per line   cntP(l) = the cells on line l whose sig equals capture k - 1's, cntN(l) the same against capture k + 1's;
+ *              flagP(l) = cntP(l) * 1000 >= line_permille * width(l), flagN(l) likewise; p(l) = flagP & !flagN, q(l) = flagN & !flagP
+ *   orientation and split  o = 0: P's frame is on the low lines, (a, b) = (p, q); o = 1: (a, b) = (q, p). For a split s with
+ *              min_side <= s <= L - min_side: first = #{l < s : a(l)}, last = #{l >= s : b(l)}; (o, s) is admissible when
+ *              8 first >= 7 s and 8 last >= 7 (L - s). The 7/8 per side tolerates the line the tear crosses and a few damaged lines; the
+ *              guard below bounds what a wrong "torn" can cost. It is a rule constant, not a measurement.
+ *   candidate  an eligible capture with an admissible (o, s). Its tear is the admissible pair with the largest first + last; ties go to
+ *              the lower o, then the lower s. (CIMBAR_HIP_TAP_ONCE_TEAR)
+ *   pass 1     list 1 = the representatives without the candidates, in capture order
+ *   guard      after pass 1, a candidate whose two neighbour runs' representatives both came back with full masks is torn: role
+ *              CIMBAR_HIP_ONCE_TORN, mask 0 and a zeroed slot, its run's row zero and rmask 0, never decoded. A neighbour that is itself a
+ *              candidate has not come back at all, so of two candidates in a row neither is torn.
+ *   pass 2     every other candidate joins list 2 in capture order, with role _FALLBACK, and is decoded there exactly as a plain call
+ *              decodes it: wherever a neighbour run is not complete, nothing is withheld that the setting-off call would have decoded
+ *   contract   as above: the per-capture results of list 1, then of list 2, are the results of two consecutive plain calls on a context
+ *              in the same state
+ *   run rescue composes unchanged: a candidate is a run of one and is never tried
+ *   synchronisation  as above: the length of list 1, then of list 2, 4 bytes each. The length of list 1 is no longer the run count once
+ *              a candidate exists; a host-output call takes the run count from its last copy. Nothing further is read back. With the
+ *              setting off no call launches, allocates or writes anything it did not before.
+ * set: axis -1 = off (the other two arguments are then not looked at; get reports -1, 750, 2), 0, 1 or 2; anything else is
+ * CIMBAR_HIP_EINVAL. line_permille <= 0 resolves to 750, above 1000 is CIMBAR_HIP_EINVAL. min_side <= 0 resolves to 2; 2 * min_side > L of
+ * the mode on the chosen axis (axis 2: on either) is CIMBAR_HIP_EINVAL. A refused call changes nothing. get reports the resolved values (each
+ * pointer may be NULL). Modes 4 and 8 refuse any axis other than -1 (EINVAL), as they refuse the once-calls. Takes effect for once-calls
+ * issued after the call. The once-stream calls behave with the setting on exactly as with it off: a torn capture's successor is not known
+ * when its call has to decide.
+ * Not covered: the once-stream calls; stitching a frame out of a torn capture's good side when a neighbour run is incomplete; slanted tears
+ * (the strip-by-strip form); two torn captures in a row, which agree with each other, form a run of two and are decoded as before; the
+ * undistort path, the auto-detection objects, the C++ adapter and the receive shim. */
+int cimbar_hip_set_once_tear_skip(cimbar_hip_ctx* ctx, int axis, int line_permille, int min_side);
+int cimbar_hip_get_once_tear_skip(cimbar_hip_ctx* ctx, int* axis, int* line_permille, int* min_side);
 
 /* ---- repeat-capture skipping across calls: the open run is carried from call to call -------------------------------------------------------
  * A live receiver hands over one capture (or a few) per call, so a run of repeats spans calls. The two _once_stream calls are the calls above
@@ -972,7 +1015,10 @@ enum {
 	 * n times -1 and no cells. _CELLS reads the group scratch the combined calls share: ask before the next combined call on the context. */
 	CIMBAR_HIP_TAP_ONCE_RESCUE = 31,    /* n int32             : per run slot, -1 = the run was not tried, else the chunk bits the rescue added to the OR
 	                                       of the members' masks; slots at and above the run count are -1 */
-	CIMBAR_HIP_TAP_ONCE_RESCUE_CELLS = 32 /* tried * cells bytes : the combined cells of the tried runs, in run order, colour << 4 | symbol */
+	CIMBAR_HIP_TAP_ONCE_RESCUE_CELLS = 32, /* tried * cells bytes : the combined cells of the tried runs, in run order, colour << 4 | symbol */
+	/* tear skipping in the last once-call (cimbar_hip_set_once_tear_skip; n = its captures). CIMBAR_HIP_EINVAL when that call ran with the
+	 * setting off or was a once-stream call */
+	CIMBAR_HIP_TAP_ONCE_TEAR = 33       /* n x 4 int32         : per capture {axis * 2 + o, s, first, last}; {-1, -1, 0, 0} for a capture that is no candidate */
 };
 int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_bytes);
 

@@ -236,6 +236,18 @@ int cimbar_hip_get_once_rescue(cimbar_hip_ctx* ctx, int* on)
 	return CIMBAR_FWD(cimbar_hip_get_once_rescue, on);
 }
 
+int cimbar_hip_set_once_tear_skip(cimbar_hip_ctx* ctx, int axis, int line_permille, int min_side)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return CIMBAR_FWD(cimbar_hip_set_once_tear_skip, axis, line_permille, min_side);
+}
+
+int cimbar_hip_get_once_tear_skip(cimbar_hip_ctx* ctx, int* axis, int* line_permille, int* min_side)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return CIMBAR_FWD(cimbar_hip_get_once_tear_skip, axis, line_permille, min_side);
+}
+
 int cimbar_hip_set_stream_colour_vote(cimbar_hip_ctx* ctx, int on)
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;

@@ -96,6 +96,10 @@ struct cimbar_hip_ctx {
 	int rs_slots = 0;                           // ... over that many slots (the host's bound on the qualifying runs)
 	DevBuf<uint8_t> d_rs_symbols, d_rs_colors; DevBuf<int8_t> d_rs_drift; DevBuf<uint32_t> d_rs_plane, d_rs_flood;   // the store: [slots] x CS_CELLS, CS_CELLS, CS_DRIFT, CS_PLANE, 1
 	DevBuf<int> d_rs_run, d_rs_map, d_rs_count; DevBuf<int32_t> d_rs_tap;                // [slots] the slot's run, [n] where a member's cells are, 1 int, [n] CIMBAR_HIP_TAP_ONCE_RESCUE
+	// tear skipping (cimbar_hip_set_once_tear_skip, repeat.hip.inc "tear skipping"): nothing of it exists until a plain once-call with the setting on
+	int rt_axis = -1, rt_line = RT_LINE_DEFAULT, rt_side = RT_SIDE_DEFAULT;   // the setting, resolved; axis -1 = off
+	bool rt_state = false;                      // the last once-call was a plain one with the setting on (CIMBAR_HIP_TAP_ONCE_TEAR describes it)
+	DevBuf<int32_t> d_rt_tap; DevBuf<int> d_rt_pos, d_rt_words; PinnedBuf<int> h_rt_words;   // [n][4] the records, [n] a run's place in list 1, {|list 1|, |list 2|} and their mirror
 	int wave_adapt = 1;               // CIMBAR_HIP_FLOOD_WAVE_ADAPT=0: run k_flood_wave in front of every exact replay, whatever it achieved before
 	bool wave_ran = false;            // k_flood_wave ran in the batch h_flagged describes
 	int wave_skip_left = 0;           // batches that still go straight to the exact replay (see enqueue)
@@ -2204,6 +2208,16 @@ int64_t once_impl(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_frames, 
 	const bool rescue = ctx->rs_on != 0 && !os && (oa.rchunks || oa.rmasks);
 	int rs_slots = 0;
 	ctx->rs_state = 0;
+	// tear skipping (cimbar_hip_set_once_tear_skip): the plain once-calls only. List 1 is then no longer "one per run": its length and list
+	// 2's come from the setting's own words, and pass 1's results are addressed through d_rt_pos.
+	const bool tear = ctx->rt_axis >= 0 && !os;
+	ctx->rt_state = false;
+	if (tear) {
+		HIPCHK(ctx->d_rt_tap.reserve(N * 4));
+		HIPCHK(ctx->d_rt_pos.reserve(N));
+		HIPCHK(ctx->d_rt_words.ensure(RT_WORDS));
+		HIPCHK(ctx->h_rt_words.ensure(RT_WORDS));
+	}
 
 	hipLaunchKernelGGL(k_repeat_sums, dim3(DIM_Y, n), dim3(256), 0, st, d_frames, ctx->tb, ctx->d_rp_sums);
 	hipLaunchKernelGGL(k_repeat_sig, dim3(n), dim3(256), 0, st, ctx->d_rp_sums, ctx->d_rp_sig);
@@ -2219,11 +2233,20 @@ int64_t once_impl(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_frames, 
 		HIPCHK(hipMemsetAsync(ctx->d_rp_words, 0, sizeof(int) * 2, st));
 		hipLaunchKernelGGL(k_group_walk, dim3(1), dim3(64), 0, st, ctx->d_rp_agree, n, d_status, stride, (const int*)nullptr, oa.min_agree, oa.max_run,
 		                   ctx->d_rp_runs, ctx->d_rp_mem, ctx->d_rp_count, ctx->d_rp_words);
-		hipLaunchKernelGGL(k_repeat_lists, dim3((n + 255) / 256), dim3(256), 0, st, ctx->d_rp_runs, ctx->d_rp_mem, ctx->d_rp_count, n, ctx->d_rp_roles, ctx->d_rp_list);
+		if (tear) {
+			hipLaunchKernelGGL(k_repeat_tear, dim3(n), dim3(256), 0, st, ctx->d_rp_sig, ctx->d_rp_runs, ctx->d_rp_count, n, ctx->tb_stitch_line, ctx->rt_axis, ctx->rt_line,
+			                   ctx->rt_side, ctx->d_rt_tap);
+			hipLaunchKernelGGL(k_repeat_lists_tear, dim3(1), dim3(64), 0, st, ctx->d_rp_runs, ctx->d_rp_mem, ctx->d_rp_count, n, ctx->d_rt_tap, ctx->d_rp_roles,
+			                   ctx->d_rp_list, ctx->d_rt_pos, ctx->d_rt_words);
+		} else
+			hipLaunchKernelGGL(k_repeat_lists, dim3((n + 255) / 256), dim3(256), 0, st, ctx->d_rp_runs, ctx->d_rp_mem, ctx->d_rp_count, n, ctx->d_rp_roles, ctx->d_rp_list);
 	}
 	HIPCHK(hipGetLastError());
 	int len1 = 0, len2 = 0;
-	if (int r = once_read_count(ctx, st, d_words, h_words, w_len1, &len1)) return r;
+	// (tear skipping: the same read-back, of the length of list 1 -- the run count less the candidates; the run count itself is needed by
+	// the device alone until the call's last copy)
+	if (tear) { if (int r = once_read_count(ctx, st, ctx->d_rt_words, ctx->h_rt_words, RTW_LEN1, &len1)) return r; }
+	else if (int r = once_read_count(ctx, st, d_words, h_words, w_len1, &len1)) return r;
 	if (len1 < 0 || len1 > n) { ctx->err = "decode_batch_once: the run count read back is out of range"; return CIMBAR_HIP_EHIP; }
 
 	// one decode pass over `len` listed captures: gather, enqueue() as one plain batch of the entry point's kind, scatter
@@ -2254,19 +2277,29 @@ int64_t once_impl(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_frames, 
 				hipLaunchKernelGGL(k_repeat_lists2_stream, dim3(1), dim3(64), 0, st, ctx->d_rp_runs, ctx->d_rp_masks, n, cy, ctx->d_rp_roles, ctx->d_rp_list + n, d_words);
 			else {
 				if (rescue) HIPCHK(ctx->d_rs_map.reserve(N));
-				hipLaunchKernelGGL(k_repeat_lists2, dim3(1), dim3(64), 0, st, ctx->d_rp_runs, ctx->d_rp_masks, n, ctx->d_rp_roles, ctx->d_rp_list + n, ctx->d_rp_words + 1,
-				                   rescue ? ctx->d_rs_map.get() : (int*)nullptr);
+				if (tear)
+					hipLaunchKernelGGL(k_repeat_lists2_tear, dim3(1), dim3(64), 0, st, ctx->d_rp_runs, ctx->d_rp_masks, ctx->d_rt_pos, n, ctx->d_rp_roles, ctx->d_rp_list + n,
+					                   ctx->d_rt_words + RTW_LEN2, rescue ? ctx->d_rs_map.get() : (int*)nullptr);
+				else
+					hipLaunchKernelGGL(k_repeat_lists2, dim3(1), dim3(64), 0, st, ctx->d_rp_runs, ctx->d_rp_masks, n, ctx->d_rp_roles, ctx->d_rp_list + n, ctx->d_rp_words + 1,
+					                   rescue ? ctx->d_rs_map.get() : (int*)nullptr);
 			}
 			HIPCHK(hipGetLastError());
-			if (int r = once_read_count(ctx, st, d_words, h_words, w_len2, &len2)) return r;
+			if (tear) { if (int r = once_read_count(ctx, st, ctx->d_rt_words, ctx->h_rt_words, RTW_LEN2, &len2)) return r; }
+			else if (int r = once_read_count(ctx, st, d_words, h_words, w_len2, &len2)) return r;
 			if (len2 < 0 || len2 > n - len1) { ctx->err = "decode_batch_once: the fallback count read back is out of range"; return CIMBAR_HIP_EHIP; }
 			if (rescue && len2 > 0) {
 				// pass 2 overwrites pass 1's scratch: the representatives of the runs that may need the rescue are saved first
 				rs_slots = len1 < len2 ? len1 : len2;
 				if (int r = ensure_rescue_capacity(ctx, n, rs_slots)) return r;
 				cimbar_hip_ctx::ScratchSet& p1 = ctx->cur();
-				hipLaunchKernelGGL(k_rescue_save, dim3(RS_ARRAYS * RS_PARTS, rs_slots), dim3(256), 0, st, p1.d_plane, p1.d_symbols, p1.d_colors, p1.d_drift, p1.d_flood,
-				                   ctx->d_rp_masks, ctx->d_rp_mem, ctx->d_rp_count, len1, rescue_store(ctx), ctx->d_rs_run, ctx->d_gmem, ctx->d_rs_map, ctx->d_rs_count);
+				if (tear)
+					hipLaunchKernelGGL(k_rescue_save_tear, dim3(RS_ARRAYS * RS_PARTS, rs_slots), dim3(256), 0, st, p1.d_plane, p1.d_symbols, p1.d_colors, p1.d_drift, p1.d_flood,
+					                   ctx->d_rp_masks, ctx->d_rp_mem, ctx->d_rp_count, n, rescue_store(ctx), ctx->d_rs_run, ctx->d_gmem, ctx->d_rs_map, ctx->d_rs_count,
+					                   ctx->d_rt_pos);
+				else
+					hipLaunchKernelGGL(k_rescue_save, dim3(RS_ARRAYS * RS_PARTS, rs_slots), dim3(256), 0, st, p1.d_plane, p1.d_symbols, p1.d_colors, p1.d_drift, p1.d_flood,
+					                   ctx->d_rp_masks, ctx->d_rp_mem, ctx->d_rp_count, len1, rescue_store(ctx), ctx->d_rs_run, ctx->d_gmem, ctx->d_rs_map, ctx->d_rs_count);
 				HIPCHK(hipGetLastError());
 			}
 			if (len2 > 0) if (int r = pass(ctx->d_rp_list + n, len2)) return r;
@@ -2308,6 +2341,7 @@ int64_t once_impl(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_frames, 
 		ctx->rp_stream = os != nullptr;
 		ctx->rs_state = (ctx->rs_on != 0 && !os) ? (rs_slots > 0 ? 2 : 1) : 0;
 		ctx->rs_slots = rs_slots;
+		ctx->rt_state = tear;
 		if (os) { os->cur ^= 1; os->carried = true; }
 	};
 	if (dev) {
@@ -2321,9 +2355,10 @@ int64_t once_impl(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_frames, 
 	if (oa.rchunks) HIPCHK(hipMemcpyAsync(oa.rchunks, d_rchunks, N * FRAME_BYTES, hipMemcpyDeviceToHost, st));
 	if (oa.rmasks) HIPCHK(hipMemcpyAsync(oa.rmasks, d_rmasks, sizeof(uint32_t) * N, hipMemcpyDeviceToHost, st));
 	if (os) HIPCHK(hipMemcpyAsync(h_words, d_words, sizeof(int) * RP_CALL_WORDS, hipMemcpyDeviceToHost, st));
+	if (tear) HIPCHK(hipMemcpyAsync(h_words, d_words, sizeof(int), hipMemcpyDeviceToHost, st));   // the run count: list 1 no longer tells it
 	HIPCHK(hipStreamSynchronize(st));
 	done();
-	const int n_runs = os ? ((volatile int*)h_words)[RPC_RUNS] : len1;
+	const int n_runs = (os || tear) ? ((volatile int*)h_words)[os ? (int)RPC_RUNS : 0] : len1;
 	if (oa.n_runs) *oa.n_runs = n_runs;
 	if (os && oa.continued) *oa.continued = ((volatile int*)h_words)[RPC_CONT];
 	return n_runs;
@@ -2606,6 +2641,31 @@ int cimbar_hip_get_once_rescue(cimbar_hip_ctx* ctx, int* on)
 	return 0;
 }
 
+int cimbar_hip_set_once_tear_skip(cimbar_hip_ctx* ctx, int axis, int line_permille, int min_side)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	if (axis < -1 || axis > 2) { ctx->err = "set_once_tear_skip: axis must be -1 (off), 0, 1 or 2"; return CIMBAR_HIP_EINVAL; }
+	if (axis == -1) { ctx->rt_axis = -1; ctx->rt_line = RT_LINE_DEFAULT; ctx->rt_side = RT_SIDE_DEFAULT; return 0; }
+	if (LEGACY) { ctx->err = "set_once_tear_skip: modes 4 and 8 have no once-calls to govern; repeat-capture skipping covers modes 68 / 67 / 66"; return CIMBAR_HIP_EINVAL; }
+	if (line_permille > 1000) { ctx->err = "set_once_tear_skip: line_permille above 1000"; return CIMBAR_HIP_EINVAL; }
+	if (line_permille <= 0) line_permille = RT_LINE_DEFAULT;
+	if (min_side <= 0) min_side = RT_SIDE_DEFAULT;
+	const int L = axis == 2 ? (stitch_lines(0) < stitch_lines(1) ? stitch_lines(0) : stitch_lines(1)) : stitch_lines(axis);
+	if (min_side > L / 2) { ctx->err = "set_once_tear_skip: 2 * min_side above the lines of the axis"; return CIMBAR_HIP_EINVAL; }
+	// (read when a plain once-call is enqueued: calls already issued keep the setting they were issued with)
+	ctx->rt_axis = axis; ctx->rt_line = line_permille; ctx->rt_side = min_side;
+	return 0;
+}
+
+int cimbar_hip_get_once_tear_skip(cimbar_hip_ctx* ctx, int* axis, int* line_permille, int* min_side)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	if (axis) *axis = ctx->rt_axis;
+	if (line_permille) *line_permille = ctx->rt_line;
+	if (min_side) *min_side = ctx->rt_side;
+	return 0;
+}
+
 int cimbar_hip_set_stitch_strips(cimbar_hip_ctx* ctx, int strips)
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;
@@ -2734,6 +2794,16 @@ int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_byte
 		HIPCHK(hipSetDevice(ctx->device));
 		HIPCHK(hipDeviceSynchronize());
 		if (bytes) HIPCHK(hipMemcpy(out, what == CIMBAR_HIP_TAP_REPEAT_SIG ? (const void*)ctx->d_rp_sig.get() : (const void*)ctx->d_rp_agree.get(), bytes, hipMemcpyDeviceToHost));
+		return (int64_t)bytes;
+	}
+	if (what == CIMBAR_HIP_TAP_ONCE_TEAR) {
+		// tear skipping in the last plain once-call: one record per capture
+		if (ctx->rp_n <= 0 || !ctx->rt_state) { ctx->err = "tap: the last once-call was not a plain one with tear skipping on (cimbar_hip_set_once_tear_skip)"; return CIMBAR_HIP_EINVAL; }
+		const size_t bytes = (size_t)ctx->rp_n * 4 * sizeof(int32_t);
+		if (out_bytes < bytes) { ctx->err = "tap: buffer too small"; return CIMBAR_HIP_EINVAL; }
+		HIPCHK(hipSetDevice(ctx->device));
+		HIPCHK(hipDeviceSynchronize());
+		HIPCHK(hipMemcpy(out, ctx->d_rt_tap, bytes, hipMemcpyDeviceToHost));
 		return (int64_t)bytes;
 	}
 	if (what == CIMBAR_HIP_TAP_ONCE_RESCUE || what == CIMBAR_HIP_TAP_ONCE_RESCUE_CELLS) {

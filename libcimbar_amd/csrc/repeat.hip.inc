@@ -495,11 +495,13 @@ constexpr int RS_PARTS = 4, RS_ARRAYS = 4;
 // R10: workgroup (slice, slot). Wavefront 0 of every workgroup walks the runs, 64 per step with a carried base, to the run of its slot (none:
 // the slot is at or above the count and the workgroup returns); then one of RS_PARTS slices of one of the four arrays is copied, 16 bytes
 // per lane where the ends allow it (carry_copy).
-__global__ __launch_bounds__(256) void k_rescue_save(const uint32_t* __restrict__ plane, const uint8_t* __restrict__ symbols, const uint8_t* __restrict__ colors,
-                                                     const int8_t* __restrict__ drift, const uint32_t* __restrict__ flood_flag,
-                                                     const uint32_t* __restrict__ rep_masks, const int* __restrict__ rmem, const int* __restrict__ rcount,
-                                                     int nruns, CarryStore cs, int* __restrict__ slot_run, int* __restrict__ smem, int* __restrict__ map,
-                                                     int* __restrict__ nslots)
+// (POS: tear skipping's form, where run r's representative stands at pos[r] in pass 1's batch instead of at r; see the end of this file)
+template <bool POS>
+__device__ __forceinline__ void rescue_save_body(const uint32_t* __restrict__ plane, const uint8_t* __restrict__ symbols, const uint8_t* __restrict__ colors,
+                                                 const int8_t* __restrict__ drift, const uint32_t* __restrict__ flood_flag,
+                                                 const uint32_t* __restrict__ rep_masks, const int* __restrict__ rmem, const int* __restrict__ rcount,
+                                                 int nruns, CarryStore cs, int* __restrict__ slot_run, int* __restrict__ smem, int* __restrict__ map,
+                                                 int* __restrict__ nslots, const int* __restrict__ pos)
 {
 	const int slot = blockIdx.y;
 	__shared__ int s_run;
@@ -509,7 +511,7 @@ __global__ __launch_bounds__(256) void k_rescue_save(const uint32_t* __restrict_
 		int base = 0, mine = -1;
 		for (int r0 = 0; r0 < nruns; r0 += 64) {
 			const int r = r0 + lane;
-			const bool q = r < nruns && rcount[r] >= 2 && (rep_masks[r] & RP_FULL) != RP_FULL;
+			const bool q = r < nruns && rcount[r] >= 2 && (rep_masks[POS ? pos[r] : r] & RP_FULL) != RP_FULL;
 			const unsigned long long qb = __ballot(q);
 			if (q && base + (int)__popcll(qb & below) == slot) mine = r;
 			base += (int)__popcll(qb);
@@ -529,11 +531,11 @@ __global__ __launch_bounds__(256) void k_rescue_save(const uint32_t* __restrict_
 		if (threadIdx.x == 0) {
 			slot_run[slot] = r;
 			map[repeat_rep(rmem, rcount, r)] = ~slot;
-			cs.flood[slot] = flood_flag[r];
+			cs.flood[slot] = flood_flag[POS ? pos[r] : r];
 		}
 	}
 	const int arr = blockIdx.x / RS_PARTS, part = blockIdx.x % RS_PARTS;
-	const size_t k = (size_t)r;
+	const size_t k = (size_t)(POS ? pos[r] : r);
 	const uint8_t* src; uint8_t* dst; size_t bytes;
 	switch (arr) {
 		case 0: src = symbols + k * NCELLS; dst = cs.symbols + (size_t)slot * CS_CELLS; bytes = NCELLS; break;
@@ -544,6 +546,15 @@ __global__ __launch_bounds__(256) void k_rescue_save(const uint32_t* __restrict_
 	// this workgroup's slice: whole 16-byte units, the last slice takes the rest
 	const size_t per = (bytes / RS_PARTS) & ~(size_t)15, lo = per * part, hi = part == RS_PARTS - 1 ? bytes : lo + per;
 	carry_copy(dst + lo, src + lo, hi - lo);
+}
+
+__global__ __launch_bounds__(256) void k_rescue_save(const uint32_t* __restrict__ plane, const uint8_t* __restrict__ symbols, const uint8_t* __restrict__ colors,
+                                                     const int8_t* __restrict__ drift, const uint32_t* __restrict__ flood_flag,
+                                                     const uint32_t* __restrict__ rep_masks, const int* __restrict__ rmem, const int* __restrict__ rcount,
+                                                     int nruns, CarryStore cs, int* __restrict__ slot_run, int* __restrict__ smem, int* __restrict__ map,
+                                                     int* __restrict__ nslots)
+{
+	rescue_save_body<false>(plane, symbols, colors, drift, flood_flag, rep_masks, rmem, rcount, nruns, cs, slot_run, smem, map, nslots, nullptr);
 }
 
 // R11: one lane per slot of the `slots` the host sized for. masks: the call's per-capture masks, pass 2's included.
@@ -562,4 +573,201 @@ __global__ __launch_bounds__(256) void k_rescue_tried(const int* __restrict__ ns
 	}
 	gcount[s] = m;
 	gdisp[s] = 0u;
+}
+
+// ------------------------------------------------------------------------------------------------ tear skipping (the plain once-calls, opt-in)
+// cimbar_hip_set_once_tear_skip. A camera that films faster than the display changes catches a frame switch in about one capture of four:
+// frame P on one side of a line, frame N on the other. Such a capture agrees with each neighbour on about 600 permille of its cells, so by
+// the rule above it is a run of one, its own representative, and decoded in pass 1 -- through the flood path, for chunks its neighbour runs
+// already have. With the setting on it is recognised from the signatures and left undecoded where both neighbour runs come back complete:
+//   eligible   capture k, 1 <= k <= n - 2, captures k - 1, k, k + 1 usable, k's run has one member
+//   lines      line(i), L and width(l) of stitch.hip.inc: axis 0 the grid rows, axis 1 the grid columns; axis 2 evaluates both
+//   per line   cntP(l) = the cells of line l whose sig equals capture k - 1's, cntN(l) the same against capture k + 1's;
+//              flagP(l) = cntP(l) * 1000 >= line_permille * width(l), flagN(l) likewise; p(l) = flagP & !flagN, q(l) = flagN & !flagP
+//   (o, s)     orientation o = 0: P's frame is on the low lines, (a, b) = (p, q); o = 1: (a, b) = (q, p). For a split s,
+//              min_side <= s <= L - min_side: first = #{l < s : a(l)}, last = #{l >= s : b(l)}; admissible iff 8 first >= 7 s and
+//              8 last >= 7 (L - s) (the 7/8 tolerates the line the tear crosses and a few damaged ones; a rule constant)
+//   candidate  some (o, s) is admissible; the tear is the admissible pair with the largest first + last, ties to the lower o, then the
+//              lower s. Axis 2: axis 0's tear where it has one, else axis 1's. The record is {axis * 2 + o, s, first, last}, a capture that is
+//              no candidate {-1, -1, 0, 0} (CIMBAR_HIP_TAP_ONCE_TEAR)
+//   pass 1     list 1 = the representatives without the candidates, in capture order
+//   guard      a candidate whose two neighbour runs' representatives both came back with full masks is TORN (role 3): never decoded,
+//              mask 0, a zeroed slot, its run's row zero. Every other candidate joins list 2, in capture order, as a fallback.
+//   R12 k_repeat_tear         one workgroup per capture, behind the walk: the record
+//   R4t k_repeat_lists_tear   R4 without the candidates: list 1 is no longer "by run", so one wavefront compacts it and writes pos[run] =
+//                             the representative's place in list 1 (-1: a candidate's run) and the call's words {|list 1|, 0}
+//   R5t k_repeat_lists2_tear  R5 through pos, with the guard
+//   R10t k_rescue_save_tear   R10 through pos (pass 1's scratch is by list position)
+// Everything else of the call is the kernels above, unchanged: a torn capture's mask is 0 and its slot zero by R7, its run's row by R8.
+constexpr int RT_LINE_DEFAULT = 750, RT_SIDE_DEFAULT = 2;
+constexpr int RT_LSTRIDE = 128;                                            // STITCH_LMAX <= 128
+enum { RP_ROLE_TORN = CIMBAR_HIP_ONCE_TORN };
+enum { RTW_LEN1 = 0, RTW_LEN2 = 1, RT_WORDS = 2 };                         // a call's words with the setting on: |list 1|, |list 2| (the run count stays where the walk wrote it)
+
+// R12: workgroup k. Integer arithmetic only. The per-line counts are LDS atomics: a dword of four cells lies on one grid row (one add of
+// 0..4 per side), and on four consecutive grid columns (one add per equal cell).
+__global__ __launch_bounds__(256) void k_repeat_tear(const uint8_t* __restrict__ sig, const int* __restrict__ runs, const int* __restrict__ rcount, int n,
+                                                     const uint8_t* __restrict__ line_tab, int axis, int line_permille, int min_side,
+                                                     int32_t* __restrict__ tap)
+{
+	const int k = blockIdx.x, t = threadIdx.x;
+	bool eligible = k >= 1 && k + 1 < n;
+	if (eligible) {
+		const int r = runs[k];
+		eligible = runs[k - 1] >= 0 && r >= 0 && runs[k + 1] >= 0 && rcount[r] == 1;
+	}
+	if (!eligible) {                                                     // (uniform over the workgroup)
+		if (t < 4) tap[(size_t)k * 4 + t] = t < 2 ? -1 : 0;
+		return;
+	}
+	__shared__ uint32_t s_cnt[2][2][RT_LSTRIDE];                         // [axis][P | N][line]
+	__shared__ uint16_t s_pre[2][2][RT_LSTRIDE + 2];                     // [axis][p | q][s] = the flagged lines below s, s = 0 .. L
+	__shared__ uint8_t s_pq[2][2][RT_LSTRIDE];
+	__shared__ uint32_t s_best;
+	for (int e = t; e < 2 * 2 * RT_LSTRIDE; e += 256) (&s_cnt[0][0][0])[e] = 0u;
+	if (t == 0) s_best = 0u;
+	__syncthreads();
+	const bool ax0 = axis != 1, ax1 = axis != 0;
+	constexpr int W = NCELLS / 4;
+	const uint32_t* c = reinterpret_cast<const uint32_t*>(sig + (size_t)k * NCELLS);
+	const uint32_t* row_tab = reinterpret_cast<const uint32_t*>(line_tab);
+	const uint32_t* col_tab = reinterpret_cast<const uint32_t*>(line_tab + NCELLS);
+	for (int w = t; w < W; w += 256) {
+		const uint32_t me = c[w], x = me ^ c[w - W], y = me ^ c[w + W];
+		const uint32_t eP[4] = {(x & 0xFFu) == 0u, (x & 0xFF00u) == 0u, (x & 0xFF0000u) == 0u, (x >> 24) == 0u};
+		const uint32_t eN[4] = {(y & 0xFFu) == 0u, (y & 0xFF00u) == 0u, (y & 0xFF0000u) == 0u, (y >> 24) == 0u};
+		if (ax0) {
+			const int row = (int)(row_tab[w] & 0xFFu);
+			const uint32_t cp = eP[0] + eP[1] + eP[2] + eP[3], cn = eN[0] + eN[1] + eN[2] + eN[3];
+			if (cp) atomicAdd(&s_cnt[0][0][row], cp);
+			if (cn) atomicAdd(&s_cnt[0][1][row], cn);
+		}
+		if (ax1) {
+			const uint32_t cols = col_tab[w];
+#pragma unroll
+			for (int j = 0; j < 4; ++j) {
+				const int col = (int)((cols >> (8 * j)) & 0xFFu);
+				if (eP[j]) atomicAdd(&s_cnt[1][0][col], 1u);
+				if (eN[j]) atomicAdd(&s_cnt[1][1][col], 1u);
+			}
+		}
+	}
+	__syncthreads();
+	{
+		const int ax = t >> 7, l = t & 127;
+		bool p = false, q = false;
+		if (l < stitch_lines(ax)) {
+			const uint32_t need = (uint32_t)line_permille * (uint32_t)stitch_width(ax, l);
+			const bool fP = s_cnt[ax][0][l] * 1000u >= need, fN = s_cnt[ax][1][l] * 1000u >= need;
+			p = fP && !fN;
+			q = fN && !fP;
+		}
+		s_pq[ax][0][l] = p ? 1 : 0;
+		s_pq[ax][1][l] = q ? 1 : 0;
+	}
+	__syncthreads();
+	if (t < 4) {
+		const int ax = t >> 1, which = t & 1, L = stitch_lines(ax);
+		uint32_t acc = 0;
+		for (int s = 0; s <= L; ++s) {
+			s_pre[ax][which][s] = (uint16_t)acc;
+			if (s < L) acc += s_pq[ax][which][s];
+		}
+	}
+	__syncthreads();
+	// first / last of (ax, o, s): o = 0 takes p below the split and q from it on, o = 1 the reverse
+	auto sides = [&](int ax, int o, int s, int& first, int& last) {
+		const int L = stitch_lines(ax);
+		first = s_pre[ax][o][s];
+		last = s_pre[ax][o ^ 1][L] - s_pre[ax][o ^ 1][s];
+	};
+	for (int e = t; e < 2 * 2 * (RT_LSTRIDE + 1); e += 256) {
+		const int ax = e / (2 * (RT_LSTRIDE + 1)), o = (e / (RT_LSTRIDE + 1)) & 1, s = e % (RT_LSTRIDE + 1);
+		const int L = stitch_lines(ax);
+		if (!(ax == 0 ? ax0 : ax1) || s < min_side || s > L - min_side) continue;
+		int first, last;
+		sides(ax, o, s, first, last);
+		if (8 * first >= 7 * s && 8 * last >= 7 * (L - s))
+			atomicMax(&s_best, 1u << 24 | (uint32_t)(1 - ax) << 23 | (uint32_t)(first + last) << 9 | (uint32_t)(1 - o) << 8 | (uint32_t)(255 - s));
+	}
+	__syncthreads();
+	if (t == 0) {
+		const uint32_t best = s_best;
+		int32_t* row = tap + (size_t)k * 4;
+		if (!best) { row[0] = -1; row[1] = -1; row[2] = 0; row[3] = 0; }
+		else {
+			const int ax = 1 - (int)((best >> 23) & 1u), o = 1 - (int)((best >> 8) & 1u), s = 255 - (int)(best & 255u);
+			int first, last;
+			sides(ax, o, s, first, last);
+			row[0] = ax * 2 + o; row[1] = s; row[2] = first; row[3] = last;
+		}
+	}
+}
+
+// R4t: one wavefront, 64 captures per step. A candidate (tap row k, word 0 >= 0: a run of one) takes RP_ROLE_TORN for now and stays off
+// list 1; pos[r] = where run r's representative stands in list 1, -1 for a candidate's run.
+__global__ __launch_bounds__(64) void k_repeat_lists_tear(const int* __restrict__ runs, const int* __restrict__ rmem, const int* __restrict__ rcount, int n,
+                                                          const int32_t* __restrict__ tap, int* __restrict__ roles, int* __restrict__ list1,
+                                                          int* __restrict__ pos, int* __restrict__ words)
+{
+	const int lane = threadIdx.x;
+	const unsigned long long below = (1ull << lane) - 1ull;
+	int base = 0;
+	for (int k0 = 0; k0 < n; k0 += 64) {
+		const int k = k0 + lane;
+		const int r = k < n ? runs[k] : -1;
+		const bool rep = r >= 0 && repeat_rep(rmem, rcount, r) == k;
+		const bool cand = rep && tap[(size_t)k * 4] >= 0;
+		const bool take = rep && !cand;
+		const unsigned long long tb = __ballot(take);
+		if (k < n) roles[k] = r < 0 ? RP_ROLE_UNUSABLE : take ? RP_ROLE_REP : cand ? RP_ROLE_TORN : RP_ROLE_SKIPPED;
+		if (take) {
+			const int at = base + (int)__popcll(tb & below);
+			list1[at] = k;
+			pos[r] = at;
+		}
+		if (cand) pos[r] = -1;
+		base += (int)__popcll(tb);
+	}
+	if (lane == 0) { words[RTW_LEN1] = base; words[RTW_LEN2] = 0; }
+}
+
+// R5t: as R5, with rep_masks by list position. A candidate is torn for good when the representatives of its two neighbours' runs both came
+// back with full masks; otherwise it joins list 2 as a fallback, in capture order among the others (map as in R5).
+__global__ __launch_bounds__(64) void k_repeat_lists2_tear(const int* __restrict__ runs, const uint32_t* __restrict__ rep_masks, const int* __restrict__ pos, int n,
+                                                           int* __restrict__ roles, int* __restrict__ list2, int* __restrict__ count2, int* __restrict__ map)
+{
+	const int lane = threadIdx.x;
+	const unsigned long long below = (1ull << lane) - 1ull;
+	auto full = [&](int k) { const int at = pos[runs[k]]; return at >= 0 && (rep_masks[at] & RP_FULL) == RP_FULL; };
+	int base = 0;
+	for (int k0 = 0; k0 < n; k0 += 64) {
+		const int k = k0 + lane;
+		bool take = false;
+		if (k < n) {
+			const int role = roles[k];
+			if (role == RP_ROLE_SKIPPED) take = !full(k);
+			else if (role == RP_ROLE_TORN) take = !(full(k - 1) && full(k + 1));   // (a candidate has both neighbours, and both are in runs)
+		}
+		const unsigned long long tb = __ballot(take);
+		if (take) {
+			const int at = base + (int)__popcll(tb & below);
+			roles[k] = RP_ROLE_FALLBACK;
+			list2[at] = k;
+			if (map) map[k] = at;
+		}
+		base += (int)__popcll(tb);
+	}
+	if (lane == 0) *count2 = base;
+}
+
+// R10t: R10 where run r's representative stands at pos[r] in pass 1's batch (a qualifying run has two members or more, so pos[r] >= 0).
+// nruns may be any bound on the run count up to n: the member counts at and above it are zero (the host zeroes all n before the walk).
+__global__ __launch_bounds__(256) void k_rescue_save_tear(const uint32_t* __restrict__ plane, const uint8_t* __restrict__ symbols, const uint8_t* __restrict__ colors,
+                                                          const int8_t* __restrict__ drift, const uint32_t* __restrict__ flood_flag,
+                                                          const uint32_t* __restrict__ rep_masks, const int* __restrict__ rmem, const int* __restrict__ rcount,
+                                                          int nruns, CarryStore cs, int* __restrict__ slot_run, int* __restrict__ smem, int* __restrict__ map,
+                                                          int* __restrict__ nslots, const int* __restrict__ pos)
+{
+	rescue_save_body<true>(plane, symbols, colors, drift, flood_flag, rep_masks, rmem, rcount, nruns, cs, slot_run, smem, map, nslots, pos);
 }

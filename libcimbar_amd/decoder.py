@@ -39,6 +39,8 @@ TAP_REPEAT_CARRY = 30   # what the once-stream calls carry (decode_batch_once_st
 TAP_ONCE_RESCUE, TAP_ONCE_RESCUE_CELLS = 31, 32   # the run rescue of the last plain once-call (set_once_rescue): tap_once_rescue / tap_once_rescue_cells
 # CIMBAR_HIP_ONCE_*: a capture's role in a once-call
 ONCE_UNUSABLE, ONCE_SKIPPED, ONCE_REPRESENTATIVE, ONCE_FALLBACK = -1, 0, 1, 2
+ONCE_TORN = 3           # ... with set_once_tear_skip on: a torn boundary capture that was left undecoded
+TAP_ONCE_TEAR = 33      # tear skipping in the last plain once-call (set_once_tear_skip): tap_once_tear
 
 # every symbol include/cimbar_hip.h declares (tests/test_capi_symbols.py checks the header against this list and the .so)
 EXPORTS = (
@@ -71,6 +73,7 @@ EXPORTS = (
     "cimbar_hip_decode_batch_once", "cimbar_hip_scan_extract_decode_batch_once_fmt",
     "cimbar_hip_decode_batch_once_stream", "cimbar_hip_scan_extract_decode_batch_once_stream_fmt", "cimbar_hip_once_stream_reset",
     "cimbar_hip_set_once_rescue", "cimbar_hip_get_once_rescue",
+    "cimbar_hip_set_once_tear_skip", "cimbar_hip_get_once_tear_skip",
 )
 # cimbar_hip_deliver_chunks' flags
 DELIVER_DEDUP, DELIVER_REMEMBER, DELIVER_DROP_EMPTY = 1, 2, 4
@@ -270,6 +273,11 @@ def load_library(path=None):
         lib.cimbar_hip_set_once_rescue.restype = i32
         lib.cimbar_hip_get_once_rescue.argtypes = [vp, ctypes.POINTER(i32)]
         lib.cimbar_hip_get_once_rescue.restype = i32
+    if hasattr(lib, "cimbar_hip_set_once_tear_skip"):   # (the same: tools/once_tear_bench.py --parent-lib)
+        lib.cimbar_hip_set_once_tear_skip.argtypes = [vp, i32, i32, i32]
+        lib.cimbar_hip_set_once_tear_skip.restype = i32
+        lib.cimbar_hip_get_once_tear_skip.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32)]
+        lib.cimbar_hip_get_once_tear_skip.restype = i32
     lib.cimbar_hip_mode_bufsize.argtypes = [i32]
     lib.cimbar_hip_mode_bufsize.restype = i32
     lib.cimbar_hip_ctx_bufsize.argtypes = [vp]
@@ -1149,6 +1157,18 @@ class HipDecoder:
         self._check(self._lib.cimbar_hip_get_once_rescue(self._ctx, ctypes.byref(a)), "cimbar_hip_get_once_rescue")
         return bool(a.value)
 
+    def set_once_tear_skip(self, axis, line_permille=0, min_side=0):
+        """cimbar_hip_set_once_tear_skip: decode_batch_once / scan_extract_decode_batch_once leave a torn capture between two complete runs
+        undecoded (role ONCE_TORN). axis -1 = off (the state after create), 0 = the tear runs along grid rows, 1 = along grid columns, 2 =
+        either; line_permille <= 0: 750, min_side <= 0: 2. The once-stream calls ignore it; modes 4 / 8 refuse anything but -1."""
+        self._check(self._lib.cimbar_hip_set_once_tear_skip(self._ctx, int(axis), int(line_permille), int(min_side)), "cimbar_hip_set_once_tear_skip")
+
+    def get_once_tear_skip(self):
+        """(axis, line_permille, min_side) as resolved"""
+        a, b, c = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        self._check(self._lib.cimbar_hip_get_once_tear_skip(self._ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "cimbar_hip_get_once_tear_skip")
+        return a.value, b.value, c.value
+
     def set_stream_colour_vote(self, on=True):
         """cimbar_hip_set_stream_colour_vote: the colour vote (and, with set_colour_erasure_decode on, the group colour retry) in the stream
         calls; set_group_colour_vote governs the plain combined calls only. A stream samples it in its first call after create /
@@ -1290,6 +1310,13 @@ class HipDecoder:
         the chunk bits the rescue added to the OR of the members' masks"""
         out = np.zeros(n, dtype=np.int32)
         self._check(self._lib.cimbar_hip_tap(self._ctx, TAP_ONCE_RESCUE, out.ctypes.data, out.nbytes), "cimbar_hip_tap")
+        return out
+
+    def tap_once_tear(self, n):
+        """TAP_ONCE_TEAR of the last plain once-call of n captures with set_once_tear_skip on: (n, 4) int32 {axis * 2 + o, s, first, last},
+        {-1, -1, 0, 0} for a capture that is no candidate"""
+        out = np.zeros((n, 4), dtype=np.int32)
+        self._check(self._lib.cimbar_hip_tap(self._ctx, TAP_ONCE_TEAR, out.ctypes.data, out.nbytes), "cimbar_hip_tap")
         return out
 
     def tap_once_rescue_cells(self, n_tried):
