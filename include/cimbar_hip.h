@@ -1018,7 +1018,15 @@ enum {
 	CIMBAR_HIP_TAP_ONCE_RESCUE_CELLS = 32, /* tried * cells bytes : the combined cells of the tried runs, in run order, colour << 4 | symbol */
 	/* tear skipping in the last once-call (cimbar_hip_set_once_tear_skip; n = its captures). CIMBAR_HIP_EINVAL when that call ran with the
 	 * setting off or was a once-stream call */
-	CIMBAR_HIP_TAP_ONCE_TEAR = 33       /* n x 4 int32         : per capture {axis * 2 + o, s, first, last}; {-1, -1, 0, 0} for a capture that is no candidate */
+	CIMBAR_HIP_TAP_ONCE_TEAR = 33,      /* n x 4 int32         : per capture {axis * 2 + o, s, first, last}; {-1, -1, 0, 0} for a capture that is no candidate */
+	/* which launches of the exact flood replay (k_flood3) the last batch of any kind made on the host side: bookkeeping only, answered without
+	 * waiting for the device, so it may be asked while pipelined batches are in flight. It describes the batch issued last (each batch starts
+	 * its own list). Record 0 is a header {areas asked for, areas held, launches, 0, 0, 0, 0}: the spill areas that batch needed [0, asked)
+	 * and the areas the context holds now (>= asked; it only grows). One record per launch follows, in issue order, at most 16 (later ones are
+	 * dropped): instance = 3, 4 or 8 frames per CU (heap slots in LDS: 10 240, 7 080, 4 095); a launch with grid < frames hands the frames from
+	 * `grid` on out through counter pair `counter`; workgroup b spills into area area0 + b; flags says which frames the launch was for. */
+	CIMBAR_HIP_TAP_FLOOD_LAUNCH = 34    /* (1 + launches) x 7 int32: {instance, grid, frames, first frame, area0, counter, flags: 0 = the batch's flags,
+	                                       1 = the verify replay (CIMBAR_HIP_FLOOD_VERIFY), 2 = the relaxed flood's fallback replay}; returns the bytes written */
 };
 int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_bytes);
 

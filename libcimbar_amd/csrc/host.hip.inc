@@ -197,7 +197,13 @@ struct cimbar_hip_ctx {
 	size_t ud_scratch = (size_t)256 << 20;   // CIMBAR_HIP_UNDISTORT_SCRATCH_MB
 	FloodScratch flood{};             // by value into the flood kernels: filled by ensure_flood_areas from the owners beside it
 	DevBuf<uint32_t> flood_heap, flood_next; DevBuf<uint8_t> flood_prio;
-	int flood_cap = 0;                // spill areas allocated in flood.heap (grown to what the launches use: one frame -> 0.6 MB, a full batch -> 610 MB)
+	int flood_cap = 0;                // spill areas allocated in flood.heap and flood.prio, 0.61 MB of device memory each, grown to what the launches index: one frame -> 0.6 MB,
+	                                  // 1 024 frames as one chain -> 620 MB, split or pipelined batches up to 2 048 areas = 1.25 GB (flood_area_scale)
+	// CIMBAR_HIP_TAP_FLOOD_LAUNCH: the exact-replay launches of the last enqueue(), {instance, grid, frames, first frame, area0, counter, flags}
+	// each, and the spill areas that enqueue() asked ensure_flood_areas for (host bookkeeping: nothing on the device knows of it)
+	static constexpr int FLOOD_LAUNCH_MAX = 16;
+	int32_t flood_launch[FLOOD_LAUNCH_MAX][7] = {};
+	int flood_launch_n = 0, flood_launch_top = 0;
 	DevBuf<uint32_t> d_fw_queue;      // k_flood_wave: one work queue of NCELLS entries per resident workgroup
 	int flood_verify = 0;             // CIMBAR_HIP_FLOOD_VERIFY=1: every frame k_flood_wave certified is replayed exactly as well and compared (see enqueue)
 	DevBuf<uint8_t> d_vsym; DevBuf<int8_t> d_vdrift; DevBuf<uint32_t> d_vflag; int vcap = 0;   // its buffers: saved batch results, [n] flags + [n] differing cells
@@ -545,9 +551,20 @@ int drain_pipeline_into(cimbar_hip_ctx* ctx, hipStream_t st)
 // the next batch (or frame) takes the next set
 void rotate_scratch_sets(cimbar_hip_ctx* ctx) { ctx->pipe_set = (ctx->pipe_set + 1) % ctx->pipe_depth; }
 
+// The ranges of spill areas that launches in flight together get (the sets of the pipeline, the two streams of a split batch) are spaced for
+// the largest launch the context can make: FLOOD_DENSE_PER areas per ordinary one wherever the dense replay may run (CIMBAR_HIP_FLOOD_DENSE
+// unset or 1). ONE spacing for both instances: a pipelined set's dense launch (more than `areas` frames) and another set's ordinary one used
+// to take theirs from two different partitions of the same buffer, which overlap (depth 4: [0, 300) dense on set 0, [256, 456) on set 1).
+// It costs device memory where the batches stay small: a pipelined set's batch of n <= areas frames asks for 2 (depth - 1) areas + n, not
+// (depth - 1) areas + n (depth 3: 682 areas = 415 MB more), a split batch of up to 512 frames for 1024 + n, not 512 + n (310 MB more); larger
+// batches were sized in these units already. (Split batches need it too: eight parts of 4 101 frames put 513 on stream 0 beside 512 on stream 1.)
+inline int flood_area_scale(const cimbar_hip_ctx* ctx) { return ctx->flood_dense != 0 ? FLOOD_DENSE_PER : 1; }
+
 // enqueue the whole pipeline for n device-resident frames on stream `st`
-// one spill area (HEAP_CAP words) per flood workgroup a launch may start, [0, count): grown on demand -- a context that only ever decodes single
-// frames keeps 0.6 MB, not the 610 MB a 1024-frame batch wants. Growing replaces the buffer, so everything in flight is waited for first.
+// one spill area (HEAP_CAP words, and PRIO_STRIDE bytes for the dense instance: 0.61 MB) per flood workgroup a launch may start, [0, count): grown on
+// demand -- a context that only ever decodes single frames through the plain calls keeps 0.6 MB (through the pipelined ones, whose last set starts at
+// 2 (depth - 1) areas: 830 MB at depth 3), not the 620 MB .. 1.25 GB a 1024-frame batch wants. Growing replaces the buffer, so everything in flight is
+// waited for first.
 int ensure_flood_areas(cimbar_hip_ctx* ctx, int count)
 {
 	if (count <= ctx->flood_cap) return 0;
@@ -576,6 +593,7 @@ int enqueue(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_rgb, int n, in
 	ctx->stitch_n = 0;        // (... and the stitch taps a stitched one)
 	ctx->gcv_valid = false;
 	ctx->gcv_stream_n = -1;
+	ctx->flood_launch_n = 0;
 	// the colour retry (erasure.hip.inc) runs behind every chain that reports chunks; the set in use holds its margins
 	const bool colour_retry = !LEGACY && !plain && !symbols_only && ctx->ec_margin > 0;
 	if (colour_retry) { if (int r = ensure_margin_capacity(ctx, cur)) return r; }
@@ -596,11 +614,14 @@ int enqueue(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_rgb, int n, in
 	{
 		// spill areas the flood launches below will index: the pipeline's sets and the two halves of a split batch use disjoint ranges
 		const int areas_ = pipe ? FLOOD_GRID / ctx->pipe_depth : (split ? FLOOD_GRID / 2 : FLOOD_GRID);
-		const int off_ = pipe ? (ctx->pipe_depth - 1) * areas_ : (split ? FLOOD_GRID / 2 : 0);
+		// (the dense replay runs FLOOD_DENSE_PER workgroups where the others run one; a context that may launch it -- flood_area_scale -- spaces
+		// every range by that factor, whichever instance a launch takes: a dense launch of one pipelined set and an ordinary one of another may
+		// be in flight together)
+		const int off_ = flood_area_scale(ctx) * (pipe ? (ctx->pipe_depth - 1) * areas_ : (split ? FLOOD_GRID / 2 : 0));
 		int top = off_ + (n < areas_ ? n : areas_);
-		// (the dense replay runs FLOOD_DENSE_PER workgroups where the others run one, over the same partition of the areas)
-		if (ctx->flood_dense > 0 || (ctx->flood_dense < 0 && n > areas_)) top = FLOOD_DENSE_PER * off_ + (n < FLOOD_DENSE_PER * areas_ ? n : FLOOD_DENSE_PER * areas_);
+		if (ctx->flood_dense > 0 || (ctx->flood_dense < 0 && n > areas_)) top = off_ + (n < FLOOD_DENSE_PER * areas_ ? n : FLOOD_DENSE_PER * areas_);
 		if (int r = ensure_flood_areas(ctx, top)) return r;
+		ctx->flood_launch_top = top;
 		if (ctx->flood_verify) if (int r = ensure_verify_capacity(ctx, n)) return r;
 	}
 	HIPCHK(mark());
@@ -658,7 +679,7 @@ int enqueue(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_rgb, int n, in
 			if (hipError_t e = (s == st ? mark() : hipSuccess)) return e;
 			// the two halves of a split batch may run their flood kernels at the same time: each gets its own half of the spill areas
 			const int areas = pipe ? FLOOD_GRID / ctx->pipe_depth : (split ? FLOOD_GRID / 2 : FLOOD_GRID);
-			const int area0 = pipe ? ctx->pipe_set * areas : ((split && s != st) ? FLOOD_GRID / 2 : 0);
+			const int area0 = flood_area_scale(ctx) * (pipe ? ctx->pipe_set * areas : ((split && s != st) ? FLOOD_GRID / 2 : 0));
 			if (run_wave && !(ctx->dbg_skip & 2)) {
 				// first the batch-parallel pass for frames whose flood provably does not depend on the tie order (it clears their flag to 2)
 				const int wareas = pipe ? FW_GRID / ctx->pipe_depth : (split ? FW_GRID / 2 : FW_GRID);
@@ -670,23 +691,32 @@ int enqueue(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_rgb, int n, in
 				if (hipError_t e = hipMemsetAsync(cur.d_flood + cur.cap + fa, 0xFF, sizeof(uint32_t) * (size_t)m, s)) return e;
 			}
 			const int counter = pipe ? ctx->pipe_set : ((split && s != st) ? 1 : 0);          // (launches that may overlap use different frame counters)
-			auto exact_flood = [&](const uint32_t* flags) {
+			auto exact_flood = [&](const uint32_t* flags, int kind) {
 				// three frames per CU while the batch fits, four (smaller LDS heap) beyond that
 				const int areas3 = areas * FLOOD_GRID3 / FLOOD_GRID;
 				// a launch with fewer workgroups than frames hands the rest out through the counter pair sc.next[2 * counter ..]: zeroed HERE, in stream
 				// order in front of the launch, so that a launch that faulted or was aborted cannot leave the pair non-zero for the ones after it
 				auto hand_out = [&](int grid) { if (grid < m) (void)hipMemsetAsync(ctx->flood.next + 2 * counter, 0, 2 * sizeof(uint32_t), s); return dim3(grid); };
+				auto note = [&](int instance, int grid) {
+					if (ctx->flood_launch_n >= cimbar_hip_ctx::FLOOD_LAUNCH_MAX) return;
+					const int32_t rec[7] = {instance, grid, m, fa, area0, counter, kind};
+					std::memcpy(ctx->flood_launch[ctx->flood_launch_n++], rec, sizeof rec);
+				};
 				if (ctx->dbg_skip & 2) {}
 				else if (ctx->flood_dense > 0 || (ctx->flood_dense < 0 && m > areas)) {
 					// more frames than four per CU hold: eight per CU (per-cell state as bits in LDS + bytes in global memory, a 4 160-slot LDS heap)
 					// (CIMBAR_HIP_FLOOD_DENSE_GRID: fewer workgroups than that, e.g. 1 792 = seven per CU, leave LDS for another stream's kernels while they run)
 					const int areas8 = FLOOD_DENSE_PER * areas * ctx->flood_dense_grid / (FLOOD_DENSE_PER * FLOOD_GRID);
+					note(8, m < areas8 ? m : areas8);
 					hipLaunchKernelGGL((k_flood3<HEAP_LDS8, true>), hand_out(m < areas8 ? m : areas8), dim3(128), 0, s, cur.d_plane, ctx->tb, ctx->flood, flags, cur.d_symbols, cur.d_drift, fa, m,
-					                   FLOOD_DENSE_PER * area0, counter);
-				} else if (m <= areas3)
+					                   area0, counter);
+				} else if (m <= areas3) {
+					note(3, m);
 					hipLaunchKernelGGL((k_flood3<HEAP_LDS, false>), dim3(m), dim3(128), 0, s, cur.d_plane, ctx->tb, ctx->flood, flags, cur.d_symbols, cur.d_drift, fa, m, area0, counter);
-				else
+				} else {
+					note(4, m < areas ? m : areas);
 					hipLaunchKernelGGL((k_flood3<HEAP_LDS4, false>), hand_out(m < areas ? m : areas), dim3(128), 0, s, cur.d_plane, ctx->tb, ctx->flood, flags, cur.d_symbols, cur.d_drift, fa, m, area0, counter);
+				}
 			};
 			// The relaxed flood (cimbar_hip_set_relaxed_flood): the frames still flagged 1 are flooded in threshold rounds (flag 3) instead of
 			// replayed; what the symbol streams' RS pass makes of them decides below whether they stay that way.
@@ -694,13 +724,13 @@ int enqueue(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_rgb, int n, in
 				if (hipError_t e = hipMemsetAsync(cur.d_flood + 2 * cur.cap + fa, 0, sizeof(uint32_t) * (size_t)m, s)) return e;
 				hipLaunchKernelGGL(k_flood_rounds, dim3(m < ctx->rf_grid ? m : ctx->rf_grid), dim3(FR_THREADS), 0, s, cur.d_plane, ctx->tb, cur.d_flood, cur.d_symbols,
 				                   cur.d_drift, fa, m, (uint32_t)ctx->rf_threshold, cur.d_flood + 2 * cur.cap);
-			} else exact_flood(cur.d_flood);
+			} else exact_flood(cur.d_flood, 0);
 			if (ctx->flood_verify && ctx->flood_wave && !(ctx->dbg_skip & 2)) {
 				// CIMBAR_HIP_FLOOD_VERIFY: what k_flood_wave certified (flag 2) is set aside, the same frames are replayed exactly, and the two
 				// results are compared cell by cell (symbol and drifted position). The exact result is what stays -- a wrong certificate would be
 				// counted (cimbar_hip_flood_verify_totals, CIMBAR_HIP_TAP_FLOOD_VERIFY) AND repaired.
 				hipLaunchKernelGGL(k_verify_begin, dim3(m), dim3(256), 0, s, cur.d_flood, cur.d_symbols, cur.d_drift, ctx->d_vflag, ctx->d_vsym, ctx->d_vdrift, fa, ctx->vcap);
-				exact_flood(ctx->d_vflag);
+				exact_flood(ctx->d_vflag, 1);
 				hipLaunchKernelGGL(k_verify_end, dim3(m), dim3(256), 0, s, cur.d_symbols, cur.d_drift, ctx->d_vflag, ctx->d_vsym, ctx->d_vdrift, fa, ctx->vcap, ctx->d_vtotals);
 			}
 			if (hipError_t e = (s == st ? mark() : hipSuccess)) return e;
@@ -716,7 +746,7 @@ int enqueue(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_rgb, int n, in
 				// more over the part (it rewrites the same bytes for the frames that did not change: 40 blocks per frame of clean-path work).
 				hipLaunchKernelGGL(k_rounds_check, dim3((m + 255) / 256), dim3(256), 0, s, cur.d_flood, cur.d_rs_ok, cur.d_flood + 2 * cur.cap, fa, m, ctx->rf_fallback, ctx->d_rf_stats);
 				if (ctx->rf_fallback) {
-					exact_flood(cur.d_flood);
+					exact_flood(cur.d_flood, 2);
 					hipLaunchKernelGGL((k_rs<4>), dim3((m * SYM_BLOCKS + 3) / 4), dim3(256), 0, s, cur.d_symbols, ctx->tb, fa, m, 0, d_chunks, cur.d_rs_ok, 0);
 				}
 			}
@@ -2737,6 +2767,16 @@ int cimbar_hip_rs_decode_erasures(cimbar_hip_ctx* ctx, const uint8_t* blocks, in
 int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_bytes)
 {
 	if (!ctx || !out) return CIMBAR_HIP_EINVAL;
+	if (what == CIMBAR_HIP_TAP_FLOOD_LAUNCH) {
+		// which exact-replay launches the last enqueue() made: host bookkeeping, no device work and no wait (batches may still be in flight)
+		if (ctx->last_n <= 0) { ctx->err = "tap: no batch has been decoded on this context yet"; return CIMBAR_HIP_EINVAL; }
+		const size_t bytes = sizeof(int32_t) * 7 * (size_t)(1 + ctx->flood_launch_n);
+		if (out_bytes < bytes) { ctx->err = "tap: buffer too small"; return CIMBAR_HIP_EINVAL; }
+		const int32_t head[7] = {ctx->flood_launch_top, ctx->flood_cap, ctx->flood_launch_n, 0, 0, 0, 0};
+		std::memcpy(out, head, sizeof head);
+		std::memcpy((int32_t*)out + 7, ctx->flood_launch, bytes - sizeof head);
+		return (int64_t)bytes;
+	}
 	if (what == CIMBAR_HIP_TAP_SCAN_PATH) {
 		// which kernels answered the last anchor search, per capture: the fast kernels' overflow flag and the status the slow path left
 		if (ctx->scan_n <= 0) { ctx->err = "tap: no capture has been searched for anchors on this context yet"; return CIMBAR_HIP_EINVAL; }

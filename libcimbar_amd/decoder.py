@@ -41,6 +41,9 @@ TAP_ONCE_RESCUE, TAP_ONCE_RESCUE_CELLS = 31, 32   # the run rescue of the last p
 ONCE_UNUSABLE, ONCE_SKIPPED, ONCE_REPRESENTATIVE, ONCE_FALLBACK = -1, 0, 1, 2
 ONCE_TORN = 3           # ... with set_once_tear_skip on: a torn boundary capture that was left undecoded
 TAP_ONCE_TEAR = 33      # tear skipping in the last plain once-call (set_once_tear_skip): tap_once_tear
+TAP_FLOOD_LAUNCH = 34   # the exact-replay launches the last batch made (host bookkeeping, no device wait): tap_flood_launches
+FLOOD_LAUNCH_FIELDS = ("instance", "grid", "frames", "first_frame", "area0", "counter", "flags")
+FLOOD_LAUNCH_MAX = 16
 
 # every symbol include/cimbar_hip.h declares (tests/test_capi_symbols.py checks the header against this list and the .so)
 EXPORTS = (
@@ -1272,6 +1275,8 @@ class HipDecoder:
             # (n = the captures of the stitched batch; the lines tap has DIM_Y entries per pair on axis 0 and DIM_X on axis 1: tap_stitch_lines)
             TAP_STITCH_CELLS: ((2 * max(n - 1, 0), self.geo.NCELLS), np.uint8),
             TAP_CELL_MEANS: ((n, self.geo.DIM_Y, self.geo.DIM_X), np.uint32),
+            # (does not depend on n: a header record and up to FLOOD_LAUNCH_MAX launches; tap_flood_launches reads it as dicts)
+            TAP_FLOOD_LAUNCH: ((1 + FLOOD_LAUNCH_MAX, len(FLOOD_LAUNCH_FIELDS)), np.int32),
         }
         shape, dt = shapes[what]
         out = np.zeros(shape, dtype=dt)
@@ -1318,6 +1323,17 @@ class HipDecoder:
         out = np.zeros((n, 4), dtype=np.int32)
         self._check(self._lib.cimbar_hip_tap(self._ctx, TAP_ONCE_TEAR, out.ctypes.data, out.nbytes), "cimbar_hip_tap")
         return out
+
+    def tap_flood_launches(self):
+        """TAP_FLOOD_LAUNCH of the batch issued last: (launches, areas_reserved) -- one dict per exact-replay launch (k_flood3) in issue order
+        with the keys FLOOD_LAUNCH_FIELDS (instance 3 / 4 / 8 = frames per CU; workgroup b of `grid` spills into area area0 + b; frames from `grid`
+        on are handed out through counter pair `counter`; flags 0 = the batch's own, 1 = the verify replay, 2 = the relaxed flood's fallback), and
+        the spill areas the batch asked the context to hold. Host bookkeeping: answered at once, also while pipelined batches are in flight."""
+        out = np.zeros((1 + FLOOD_LAUNCH_MAX, len(FLOOD_LAUNCH_FIELDS)), dtype=np.int32)
+        got = self._check(self._lib.cimbar_hip_tap(self._ctx, TAP_FLOOD_LAUNCH, out.ctypes.data, out.nbytes), "cimbar_hip_tap")
+        asked, held, count = (int(v) for v in out[0, :3])
+        assert got == (1 + count) * out.shape[1] * 4 and held >= asked, (got, asked, held, count)
+        return [dict(zip(FLOOD_LAUNCH_FIELDS, (int(v) for v in row))) for row in out[1:1 + count]], asked
 
     def tap_once_rescue_cells(self, n_tried):
         """TAP_ONCE_RESCUE_CELLS of that call: (n_tried, NCELLS) uint8, the combined cells of the tried runs in run order, colour << 4 | symbol"""
