@@ -12,32 +12,14 @@ inline int ctx_mode(const cimbar_hip_ctx* ctx) { return *reinterpret_cast<const 
 	                       : m68::fn((m68::cimbar_hip_ctx*)ctx, ##__VA_ARGS__))
 
 // what comm.hip.inc needs of a context
-inline void ctx_view(cimbar_hip_ctx* ctx, int* device, std::string** err, int* frame_bytes)
-{
-	if (ctx_mode(ctx) == 67) m67::ctx_view((m67::cimbar_hip_ctx*)ctx, device, err, frame_bytes);
-	else if (ctx_mode(ctx) == 66) m66::ctx_view((m66::cimbar_hip_ctx*)ctx, device, err, frame_bytes);
-	else if (ctx_mode(ctx) == 4) m4::ctx_view((m4::cimbar_hip_ctx*)ctx, device, err, frame_bytes);
-	else if (ctx_mode(ctx) == 8) m8::ctx_view((m8::cimbar_hip_ctx*)ctx, device, err, frame_bytes);
-	else m68::ctx_view((m68::cimbar_hip_ctx*)ctx, device, err, frame_bytes);
-}
+inline void ctx_view(cimbar_hip_ctx* ctx, int* device, std::string** err, int* frame_bytes) { CIMBAR_FWD(ctx_view, device, err, frame_bytes); }
 
-inline bool ctx_pipe_view(cimbar_hip_ctx* ctx, hipStream_t* stream, hipEvent_t* done)
-{
-	if (ctx_mode(ctx) == 67) return m67::ctx_pipe_view((m67::cimbar_hip_ctx*)ctx, stream, done);
-	if (ctx_mode(ctx) == 66) return m66::ctx_pipe_view((m66::cimbar_hip_ctx*)ctx, stream, done);
-	if (ctx_mode(ctx) == 4) return m4::ctx_pipe_view((m4::cimbar_hip_ctx*)ctx, stream, done);
-	if (ctx_mode(ctx) == 8) return m8::ctx_pipe_view((m8::cimbar_hip_ctx*)ctx, stream, done);
-	return m68::ctx_pipe_view((m68::cimbar_hip_ctx*)ctx, stream, done);
-}
+inline bool ctx_pipe_view(cimbar_hip_ctx* ctx, hipStream_t* stream, hipEvent_t* done) { return CIMBAR_FWD(ctx_pipe_view, stream, done); }
 
 inline deliver::View delivery_view(cimbar_hip_ctx* ctx)
 {
 	deliver::View v;
-	if (ctx_mode(ctx) == 67) m67::delivery_view((m67::cimbar_hip_ctx*)ctx, &v);
-	else if (ctx_mode(ctx) == 66) m66::delivery_view((m66::cimbar_hip_ctx*)ctx, &v);
-	else if (ctx_mode(ctx) == 4) m4::delivery_view((m4::cimbar_hip_ctx*)ctx, &v);
-	else if (ctx_mode(ctx) == 8) m8::delivery_view((m8::cimbar_hip_ctx*)ctx, &v);
-	else m68::delivery_view((m68::cimbar_hip_ctx*)ctx, &v);
+	CIMBAR_FWD(delivery_view, &v);
 	return v;
 }
 

@@ -337,6 +337,8 @@ int64_t cimbar_hip_auto_scan_extract_decode_batch_fmt(cimbar_hip_auto* a, const 
 	if (!m68::capture_dims_ok(width, height, fmt)) { a->err = std::string(who) + m68::CAPTURE_DIMS_MSG; return CIMBAR_HIP_EDIM; }
 	const size_t cbytes = cimbar_hip_capture_bytes(width, height, format <= 0 ? 3 : format);
 	if ((uint64_t)width * height * 4 >= (1ull << 33) || cbytes >= ((size_t)1 << 31)) { a->err = std::string(who) + ": captures of 2 GiB or more are not supported"; return CIMBAR_HIP_EDIM; }
+	// (the prologue of host.hip.inc's begin_call restated, not called: the object here is no mode's context -- its own error text and default
+	// stream -- and nothing is drained here: each phase's auto_symbols waits for its own context's pipeline)
 	AUTOCHK(hipSetDevice(a->device));
 	const bool any_device = img_mem == CIMBAR_HIP_MEM_DEVICE || out_mem == CIMBAR_HIP_MEM_DEVICE;
 	hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (any_device ? (hipStream_t)nullptr : a->stream);

@@ -66,26 +66,24 @@ const float* auto_ccm_frames(cimbar_hip_ctx* ctx) { return ctx->cur().d_ccm_fram
 int auto_symbols(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_in, unsigned width, unsigned height, int fmt, int m, const void* src_scan,
                  const int* list, int preprocess, int cc, uint8_t* d_chunks, uint32_t* d_masks)
 {
+	// (not begin_call: the stream and the mem flags are the auto context's business, automode.hip.inc)
 	HIPCHK(hipSetDevice(ctx->device));
 	if (int r = drain_pipeline_into(ctx, st)) return r;
-	if (int r = extract_state(ctx, m)) return r;
 	if (int r = ensure_capacity(ctx, m)) return r;
-	HIPCHK(ctx->d_ex_frames.reserve((size_t)m * FRAME_RGB));
-	if (!src_scan) {
-		if (int r = enqueue_scan(ctx, st, d_in, width, height, fmt, m)) return r;
-	} else {
+	// the capture front end with the anchor search swapped for a gather in the later phases (the captures are device-resident: nothing is staged)
+	auto scan = [&](const uint8_t* d) -> int {
+		if (!src_scan) return enqueue_scan(ctx, st, d, width, height, fmt, m);
 		hipLaunchKernelGGL(k_auto_scan_gather, dim3((m + 63) / 64), dim3(64), 0, st, (const ScanResult*)src_scan, list, m, ctx->d_scan_res);
 		hipLaunchKernelGGL(k_warp_matrices, dim3((m + 63) / 64), dim3(64), 0, st, ctx->d_scan_res[0].corners, sizeof(ScanResult) / sizeof(float),
 		                   &ctx->d_scan_res[0].status, sizeof(ScanResult) / sizeof(int), m, ctx->d_ex_minv);
-	}
-	if (int r = launch_warp_ctx(ctx, st, fmt, d_in, width, height, m, ctx->d_ex_minv, ctx->d_ex_frames)) return r;
-	const bool guess = preprocess != 0 && preprocess != 1;   // (as scan_extract_decode_impl: cimbar.cpp:131,147-154)
-	const int stride = (int)(sizeof(ScanResult) / sizeof(int));
-	ctx->no_split_once = true;                                // one chain on `st`: the colour half is issued later, by auto_colours
-	const int er = enqueue(ctx, st, ctx->d_ex_frames, m, preprocess == 1 ? 1 : 0, cc, d_chunks, d_masks, 0, false,
-	                       guess ? &ctx->d_scan_res[0].status : nullptr, stride, true);
-	ctx->no_split_once = false;
-	return er;
+		return 0;
+	};
+	if (int r = capture_front(ctx, st, d_in, width, height, fmt, 0, m, CIMBAR_HIP_MEM_DEVICE, nullptr, nullptr, CIMBAR_HIP_MEM_DEVICE, scan)) return r;
+	int stride;
+	const int* status = auto_status(ctx, &stride);
+	ChainArgs ca = chain_args(deskewed_source(ctx, status, stride, preprocess), m, cc, d_chunks, d_masks);   // (no_split: one chain on `st`)
+	ca.symbols_only = true;                                   // the colour half is issued later, by auto_colours
+	return enqueue(ctx, st, ca);
 }
 
 // the next phase's list from this one's m attempts (see k_auto_select); list == nullptr: this phase's list is 0 .. m-1

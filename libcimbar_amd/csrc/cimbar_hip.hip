@@ -6,7 +6,9 @@
 //
 // Pipeline (a batch of F frames per launch; nothing here is GEMM-shaped, so no MFMA). One call = K1, then the chain of short
 // kernels, on the caller's stream (large batches: the chain as two half-batches on two streams); the pipelined entry point
-// alternates whole batches between two context-owned streams. See enqueue() and DESIGN.md "Launch structure".
+// alternates whole batches between two context-owned streams. Every launch of the chain is enqueue(ctx, stream, ChainArgs) in host.hip.inc;
+// the batch entry points reach it through one driver per tail (decode_impl, once_call) over a FrameSource -- the caller's frames, or the
+// capture front end's deskewed ones. See DESIGN.md "Launch structure".
 //   K1 k_threshold      RGB -> gray -> (sharpen) -> 5x5|7x7 box-mean threshold -> bitplane   [HBM-read bound]
 //   K2 k_symbols        every cell at drift (0,0): 10x10 bit window -> 5|9 shifted 8x8 hashes -> popcount match;
 //                       flags the frame if any cell prefers a shifted window (order then matters -> K2b)

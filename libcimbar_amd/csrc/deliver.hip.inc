@@ -280,6 +280,8 @@ int64_t deliver_chunks(const View& v, const uint8_t* chunks, const uint32_t* mas
 	if (int r = ensure_state(v)) return r;
 	State* s = v.state->get();
 	// the stream rules of cimbar_hip_decode_batch: NULL is the null stream when a device buffer is involved, the context's own stream otherwise
+	// (host.hip.inc's begin_call restated, not called: this code is shared by every mode and sees a context through a View only; it touches no
+	// scratch set, so it waits for no pipelined batch)
 	const bool any_device = in_mem == CIMBAR_HIP_MEM_DEVICE || out_mem == CIMBAR_HIP_MEM_DEVICE;
 	hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (any_device ? (hipStream_t)nullptr : v.stream);
 

@@ -104,8 +104,6 @@ struct cimbar_hip_ctx {
 	bool wave_ran = false;            // k_flood_wave ran in the batch h_flagged describes
 	int wave_skip_left = 0;           // batches that still go straight to the exact replay (see enqueue)
 	                                  // The NEXT ordinary call reads it without waiting (a stale value only costs the heuristic): a stream of distorted frames runs un-split too
-	bool no_split_once = false;       // set by the capture path around its enqueue(): deskewed captures all take the exact flood, and two half-batch flood
-	                                  // launches on two queues run one after the other in effect (1024 captures: 62 ms split, 42 ms as one launch)
 	std::string err;
 	Tables tb{};                      // what the kernels take by value: filled by build_tables from the owners beside it
 	DevBuf<ushort2> tb_cell_xy; DevBuf<uint16_t> tb_stream_cell, tb_cell_grid, tb_ccm_grid; DevBuf<int16_t> tb_grid_cell, tb_cand;
@@ -178,8 +176,6 @@ struct cimbar_hip_ctx {
 	DevBuf<uint32_t> d_masks;
 	// extractor stage (scan_preprocess / deskew_batch): staging + small per-frame state
 	DevBuf<uint8_t> d_ex_in;
-	// set by decode_frame around ONE decode of an image larger than the frame (CimbReader's _gridPadding case): enqueue() then runs K1p on it
-	const uint8_t* pad_src = nullptr; int pad_w = 0, pad_h = 0, pad_off = 0;
 	DevBuf<uint8_t> d_ex_out;
 	DevBuf<uint32_t> d_ex_hist; DevBuf<int> d_ex_thr; DevBuf<double> d_ex_minv;
 	DevBuf<uint8_t> d_ex_gray;        // blurred gray captures (what the anchor search reads)
@@ -548,6 +544,27 @@ int drain_pipeline_into(cimbar_hip_ctx* ctx, hipStream_t st)
 	return 0;
 }
 
+// a call's mem flags, named in the message as the entry point's own arguments are (in_name == nullptr: the call has the one flag, out_name's)
+int check_mem_flags(cimbar_hip_ctx* ctx, const char* who, const char* in_name, int in_mem, const char* out_name, int out_mem)
+{
+	if ((!in_name || in_mem == CIMBAR_HIP_MEM_HOST || in_mem == CIMBAR_HIP_MEM_DEVICE) && (out_mem == CIMBAR_HIP_MEM_HOST || out_mem == CIMBAR_HIP_MEM_DEVICE)) return 0;
+	ctx->err = std::string(who) + ": " + (in_name ? std::string(in_name) + " / " : std::string()) + out_name + " must be CIMBAR_HIP_MEM_HOST or CIMBAR_HIP_MEM_DEVICE";
+	return CIMBAR_HIP_EINVAL;
+}
+
+// The prologue of every batch call, behind its own null / n checks: the mem flags, the device, the stream the call runs on (*st) and the
+// wait for the pipelined batches in flight. A NULL hip_stream means what it means for any HIP launch -- the (legacy) null stream -- whenever
+// a device buffer is involved, so the work is ordered after whatever produced the input there; the all-host path synchronises anyway and
+// uses the context's own stream.
+int begin_call(cimbar_hip_ctx* ctx, const char* who, const char* in_name, int in_mem, const char* out_name, int out_mem, void* hip_stream, hipStream_t* st)
+{
+	if (int r = check_mem_flags(ctx, who, in_name, in_mem, out_name, out_mem)) return r;
+	HIPCHK(hipSetDevice(ctx->device));
+	const bool any_device = (in_name && in_mem == CIMBAR_HIP_MEM_DEVICE) || out_mem == CIMBAR_HIP_MEM_DEVICE;
+	*st = hip_stream ? (hipStream_t)hip_stream : (any_device ? (hipStream_t)nullptr : ctx->stream);
+	return drain_pipeline_into(ctx, *st);
+}
+
 // the next batch (or frame) takes the next set
 void rotate_scratch_sets(cimbar_hip_ctx* ctx) { ctx->pipe_set = (ctx->pipe_set + 1) % ctx->pipe_depth; }
 
@@ -585,9 +602,28 @@ constexpr int ERASURE_MAX_DEFAULT = RS_PARITY - 8;
 inline int erasure_max(const cimbar_hip_ctx* ctx) { return ctx->er_max < 0 ? ERASURE_MAX_DEFAULT : ctx->er_max; }
 inline int colour_erasure_max(const cimbar_hip_ctx* ctx) { return ctx->ec_max < 0 ? ERASURE_MAX_DEFAULT : ctx->ec_max; }
 
-int enqueue(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_rgb, int n, int pre, int cc, uint8_t* d_chunks, uint32_t* d_masks, int plain = 0,
-            bool pipe = false, const int* d_sel = nullptr, int sel_stride = 0, bool symbols_only = false)
+// an image larger than the frame (CimbReader's _gridPadding case, decode_frame): K1p cuts the grid's window out of it while it thresholds it
+struct PadSource { const uint8_t* pad_src = nullptr; int pad_w = 0, pad_h = 0, pad_off = 0; };
+
+// one batch as enqueue() takes it
+struct ChainArgs {
+	const uint8_t* d_rgb = nullptr; int n = 0;      // n device-resident frames
+	int pre = 0, cc = 0;                            // sharpen every frame; the colour-correction setting
+	uint8_t* d_chunks = nullptr; uint32_t* d_masks = nullptr;   // device-visible outputs
+	int plain = 0;                                  // the plain stream (decode_plain_batch)
+	bool pipe = false;                              // one set of the pipeline: the whole chain on `st`, the carry from the set before
+	const int* d_sel = nullptr; int sel_stride = 0; // not null: sharpen where the extractor's verdict says so, per frame (`pre` is then not read)
+	bool symbols_only = false;                      // stop behind k_frame_mid (auto_symbols: the colour half is issued later)
+	bool no_split = false;                          // one chain, never two half-batches: deskewed captures all take the exact flood, and two half-batch flood
+	                                                // launches on two queues run one after the other in effect (1024 captures: 62 ms split, 42 ms as one launch)
+	PadSource pad{};                                // n == 1 only; d_rgb is then where K1p leaves the window
+};
+
+int enqueue(cimbar_hip_ctx* ctx, hipStream_t st, const ChainArgs& a)
 {
+	const uint8_t* const d_rgb = a.d_rgb; uint8_t* const d_chunks = a.d_chunks; uint32_t* const d_masks = a.d_masks; const int* const d_sel = a.d_sel;
+	const int n = a.n, pre = a.pre, cc = a.cc, plain = a.plain, sel_stride = a.sel_stride;
+	const bool pipe = a.pipe, symbols_only = a.symbols_only;
 	cimbar_hip_ctx::ScratchSet& cur = ctx->cur();
 	ctx->grp_valid = false;   // (the group taps describe a combined batch only until the next batch of any kind)
 	ctx->stitch_n = 0;        // (... and the stitch taps a stitched one)
@@ -610,7 +646,7 @@ int enqueue(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_rgb, int n, in
 	uint32_t flagged[3] = {0, 0, 0};
 	if (ctx->h_flagged) for (int k = 0; k < 3; ++k) flagged[k] = ((volatile uint32_t*)ctx->h_flagged)[k];
 	const bool mostly_flood = flagged[1] != 0 && 4u * flagged[0] > flagged[1];   // the batch before: more than a quarter took a flood kernel
-	const bool split = !tm && !pipe && ctx->tail_split && !ctx->no_split_once && !mostly_flood && n >= 64 * ctx->tail_parts;
+	const bool split = !tm && !pipe && ctx->tail_split && !a.no_split && !mostly_flood && n >= 64 * ctx->tail_parts;
 	{
 		// spill areas the flood launches below will index: the pipeline's sets and the two halves of a split batch use disjoint ranges
 		const int areas_ = pipe ? FLOOD_GRID / ctx->pipe_depth : (split ? FLOOD_GRID / 2 : FLOOD_GRID);
@@ -630,12 +666,13 @@ int enqueue(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_rgb, int n, in
 		// the sharpening variant is bound by its vector instructions (96 % of its cycles), not by the memory system: tall strips (69 row steps for 63
 		// rows instead of 24 for 18) shorten the launch itself, pipelined or not, once the batch fills the chip with them
 		const bool pre_tall = ctx->k1_tall > 0 || (ctx->k1_tall < 0 && n >= K1_TALL_MIN);
-		if (ctx->pad_src && n == 1) {
+		if (a.pad.pad_src && n == 1) {
 			// the frame buffer d_rgb is OUTPUT here: K1p cuts the grid's window out of the larger image while it thresholds it
 			uint8_t* frame = const_cast<uint8_t*>(d_rgb);
 			const dim3 gp((IMG_W + 63) / 64, (IMG_H + 3) / 4);
-			if (pre) hipLaunchKernelGGL((k_threshold_padded<3, true>), gp, dim3(256), 0, st, ctx->pad_src, ctx->pad_w, ctx->pad_h, ctx->pad_off, cur.d_plane, frame, cur.d_flood);
-			else hipLaunchKernelGGL((k_threshold_padded<2, false>), gp, dim3(256), 0, st, ctx->pad_src, ctx->pad_w, ctx->pad_h, ctx->pad_off, cur.d_plane, frame, cur.d_flood);
+			const PadSource& p = a.pad;
+			if (pre) hipLaunchKernelGGL((k_threshold_padded<3, true>), gp, dim3(256), 0, st, p.pad_src, p.pad_w, p.pad_h, p.pad_off, cur.d_plane, frame, cur.d_flood);
+			else hipLaunchKernelGGL((k_threshold_padded<2, false>), gp, dim3(256), 0, st, p.pad_src, p.pad_w, p.pad_h, p.pad_off, cur.d_plane, frame, cur.d_flood);
 			hipLaunchKernelGGL(k_cellmean_padded, dim3((GRID_CELLS + 255) / 256), dim3(256), 0, st, frame, cur.d_cellmean);
 		} else if (d_sel) {
 			// pre == -1 ("guess", cimbar.cpp:190): the extractor's verdict decides per frame; each variant returns at once for the other's frames
@@ -1202,6 +1239,13 @@ int64_t finish_stream(cimbar_hip_ctx* ctx, hipStream_t st, int n, uint8_t* chunk
 	return ng;
 }
 
+// the stage timers of the last enqueue() with timing on, once its events are complete
+int read_stage_times(cimbar_hip_ctx* ctx)
+{
+	for (int k = 0; k < cimbar_hip_ctx::NSTAGE; ++k) HIPCHK(hipEventElapsedTime(&ctx->stage_ms[k], ctx->ev[k], ctx->ev[k + 1]));
+	return 0;
+}
+
 // the end of a batch call: device outputs are enqueued (group ids and count included) and 0 returned; host outputs are copied back, then
 // the call synchronises and returns the good bytes over the batch, or with `cb` the group count
 int64_t finish_batch(cimbar_hip_ctx* ctx, hipStream_t st, int n, uint8_t* chunks, uint32_t* masks, const uint8_t* d_chunks, const uint32_t* d_masks,
@@ -1228,8 +1272,6 @@ int64_t finish_batch(cimbar_hip_ctx* ctx, hipStream_t st, int n, uint8_t* chunks
 		if (cb->n_groups) *cb->n_groups = ng;
 		return ng;
 	}
-	if (ctx->timing)
-		for (int k = 0; k < cimbar_hip_ctx::NSTAGE; ++k) HIPCHK(hipEventElapsedTime(&ctx->stage_ms[k], ctx->ev[k], ctx->ev[k + 1]));
 	// aligned_stream::tellp() summed over the batch: 625 bytes per delivered chunk (aligned_stream.h:29-32)
 	unsigned long long total = 0;
 	for (int f = 0; f < n; ++f) total += (unsigned long long)CHUNK * (unsigned)__builtin_popcount(masks[f] & ((1u << CHUNKS) - 1u));
@@ -1359,50 +1401,14 @@ int64_t finish_stitched(cimbar_hip_ctx* ctx, hipStream_t st, int n, uint8_t* chu
 	return cand;
 }
 
-int64_t decode_batch_impl(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rgb_mem, int should_preprocess, int color_correction, uint8_t* chunks,
-                          uint32_t* masks, int out_mem, void* hip_stream, CombineArgs* cb, StitchArgs* sa = nullptr)
-{
-	const bool strm = cb && cb->stream;
-	const char* who = sa ? (sa->stream ? "decode_batch_stitched_stream" : "decode_batch_stitched") : strm ? "decode_batch_combined_stream" : cb ? "decode_batch_combined" : "decode_batch";
-	// (a stream call may bring no capture at all: n == 0 with a flush closes the open group)
-	if (strm ? (n < 0 || (n > 0 && (!rgb || !chunks || !masks))) : (!rgb || !chunks || !masks || n <= 0)) { ctx->err = std::string(who) + ": null buffer or n <= 0"; return CIMBAR_HIP_EINVAL; }
-	if ((rgb_mem != CIMBAR_HIP_MEM_HOST && rgb_mem != CIMBAR_HIP_MEM_DEVICE) || (out_mem != CIMBAR_HIP_MEM_HOST && out_mem != CIMBAR_HIP_MEM_DEVICE)) {
-		ctx->err = std::string(who) + ": rgb_mem / out_mem must be CIMBAR_HIP_MEM_HOST or CIMBAR_HIP_MEM_DEVICE";
-		return CIMBAR_HIP_EINVAL;
-	}
-	if (cb) if (int r = check_combine(ctx, who, n, *cb)) return r;
-	if (sa) if (int r = check_stitch(ctx, who, n, *sa)) return r;
-	HIPCHK(hipSetDevice(ctx->device));
-	// NULL means what it means for any HIP launch -- the (legacy) null stream -- whenever a device buffer is involved, so the
-	// work is ordered after whatever produced the frames there; the all-host path synchronises anyway and uses its own stream
-	const bool any_device = rgb_mem == CIMBAR_HIP_MEM_DEVICE || out_mem == CIMBAR_HIP_MEM_DEVICE;
-	hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (any_device ? (hipStream_t)nullptr : ctx->stream);
-	if (int r = drain_pipeline_into(ctx, st)) return r;
-	if (strm && n == 0) {
-		if (int r = enqueue_combine_stream(ctx, st, 0, nullptr, nullptr, nullptr, nullptr, 0, *cb, out_mem)) return r;
-		return finish_stream(ctx, st, 0, chunks, masks, nullptr, nullptr, out_mem, *cb);
-	}
-	if (sa && sa->stream) if (int r = begin_stitch_stream(ctx, st)) return r;
-	if (int r = ensure_capacity(ctx, n)) return r;
+// what a capture entry point has and a frame one has not: the captures' size and format as the caller gave them, where their extraction
+// status goes (may be nullptr), and -- resolved by begin_decode -- the format the kernels take and a capture's bytes
+struct CaptureIn { unsigned width, height; int format; int* status; int fmt = 0; size_t cbytes = 0; };
 
-	const uint8_t* d_rgb = nullptr;
-	if (int r = stage_input(ctx, st, ctx->d_rgb, rgb, (size_t)n * FRAME_RGB, rgb_mem, &d_rgb)) return r;
-	uint8_t* d_chunks = out_mem == CIMBAR_HIP_MEM_DEVICE ? chunks : ctx->d_chunks;
-	uint32_t* d_masks = out_mem == CIMBAR_HIP_MEM_DEVICE ? masks : ctx->d_masks;
-
-	if (int r = enqueue(ctx, st, d_rgb, n, should_preprocess, color_correction, d_chunks, d_masks)) return r;
-	if (strm) {
-		if (int r = enqueue_combine_stream(ctx, st, n, d_rgb, d_chunks, d_masks, nullptr, 0, *cb, out_mem)) return r;
-		return finish_stream(ctx, st, n, chunks, masks, d_chunks, d_masks, out_mem, *cb);
-	}
-	if (cb)
-		if (int r = enqueue_combine(ctx, st, n, d_rgb, d_chunks, d_masks, nullptr, 0, *cb, out_mem)) return r;
-	if (sa) {
-		if (sa->rows(n) > 0) if (int r = enqueue_stitch(ctx, st, n, nullptr, 0, *sa, out_mem)) return r;
-		return finish_stitched(ctx, st, n, chunks, masks, d_chunks, d_masks, out_mem, *sa);
-	}
-	return finish_batch(ctx, st, n, chunks, masks, d_chunks, d_masks, out_mem, cb);
-}
+// The one driver of the plain / combined / combined-stream / stitched / stitched-stream calls, over frames (cap == nullptr: `img` is n frames)
+// or captures; defined behind the capture front end it drives. `pad`: decode_frame's image larger than the frame.
+int64_t decode_impl(cimbar_hip_ctx* ctx, CaptureIn* cap, const uint8_t* img, int n, int img_mem, int preprocess, int color_correction, uint8_t* chunks,
+                    uint32_t* masks, int out_mem, void* hip_stream, CombineArgs* cb, StitchArgs* sa = nullptr, const PadSource* pad = nullptr);
 
 }  // namespace
 
@@ -1410,7 +1416,7 @@ int64_t cimbar_hip_decode_batch(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, 
                                 int color_correction, uint8_t* chunks, uint32_t* masks, int out_mem, void* hip_stream)
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;
-	return decode_batch_impl(ctx, rgb, n, rgb_mem, should_preprocess, color_correction, chunks, masks, out_mem, hip_stream, nullptr);
+	return decode_impl(ctx, nullptr, rgb, n, rgb_mem, should_preprocess, color_correction, chunks, masks, out_mem, hip_stream, nullptr);
 }
 
 int64_t cimbar_hip_decode_batch_combined(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rgb_mem, int should_preprocess, int color_correction,
@@ -1419,7 +1425,7 @@ int64_t cimbar_hip_decode_batch_combined(cimbar_hip_ctx* ctx, const uint8_t* rgb
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;
 	CombineArgs cb{groups_in, min_agree_permille, max_group, groups_out, gchunks, gmasks, n_groups};
-	return decode_batch_impl(ctx, rgb, n, rgb_mem, should_preprocess, color_correction, chunks, masks, out_mem, hip_stream, &cb);
+	return decode_impl(ctx, nullptr, rgb, n, rgb_mem, should_preprocess, color_correction, chunks, masks, out_mem, hip_stream, &cb);
 }
 
 int64_t cimbar_hip_decode_batch_combined_stream(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rgb_mem, int should_preprocess, int color_correction,
@@ -1428,7 +1434,7 @@ int64_t cimbar_hip_decode_batch_combined_stream(cimbar_hip_ctx* ctx, const uint8
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;
 	CombineArgs cb{nullptr, min_agree_permille, max_group, groups_out, gchunks, gmasks, n_groups, true, flush, gsizes};
-	return decode_batch_impl(ctx, rgb, n, rgb_mem, should_preprocess, color_correction, chunks, masks, out_mem, hip_stream, &cb);
+	return decode_impl(ctx, nullptr, rgb, n, rgb_mem, should_preprocess, color_correction, chunks, masks, out_mem, hip_stream, &cb);
 }
 
 int64_t cimbar_hip_decode_batch_stitched(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rgb_mem, int should_preprocess, int color_correction,
@@ -1437,7 +1443,7 @@ int64_t cimbar_hip_decode_batch_stitched(cimbar_hip_ctx* ctx, const uint8_t* rgb
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;
 	StitchArgs sa{axis, min_agree_permille, min_band, schunks, smasks, tears, {}};
-	return decode_batch_impl(ctx, rgb, n, rgb_mem, should_preprocess, color_correction, chunks, masks, out_mem, hip_stream, nullptr, &sa);
+	return decode_impl(ctx, nullptr, rgb, n, rgb_mem, should_preprocess, color_correction, chunks, masks, out_mem, hip_stream, nullptr, &sa);
 }
 
 int64_t cimbar_hip_decode_batch_stitched_stream(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rgb_mem, int should_preprocess, int color_correction,
@@ -1446,7 +1452,7 @@ int64_t cimbar_hip_decode_batch_stitched_stream(cimbar_hip_ctx* ctx, const uint8
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;
 	StitchArgs sa{axis, min_agree_permille, min_band, schunks, smasks, tears, {}, true};
-	return decode_batch_impl(ctx, rgb, n, rgb_mem, should_preprocess, color_correction, chunks, masks, out_mem, hip_stream, nullptr, &sa);
+	return decode_impl(ctx, nullptr, rgb, n, rgb_mem, should_preprocess, color_correction, chunks, masks, out_mem, hip_stream, nullptr, &sa);
 }
 
 // wait for the stitched-stream calls issued so far and forget the carry: the next one's row 0 has no partner
@@ -1491,7 +1497,11 @@ int cimbar_hip_decode_batch_pipelined(cimbar_hip_ctx* ctx, const uint8_t* rgb, i
 	HIPCHK(hipStreamWaitEvent(own, ctx->ev_pk1[set], 0));
 	// (this set's intermediates belong to the batch issued pipe_depth calls ago on the same stream: stream order keeps them apart)
 	if (int r = ensure_capacity(ctx, n)) return r;
-	return enqueue(ctx, own, rgb, n, should_preprocess, color_correction, chunks, masks, 0, true);
+	ChainArgs ca;
+	ca.d_rgb = rgb; ca.n = n; ca.pre = should_preprocess; ca.cc = color_correction;
+	ca.d_chunks = chunks; ca.d_masks = masks;
+	ca.pipe = true;
+	return enqueue(ctx, own, ca);
 }
 
 int cimbar_hip_pipeline_depth(const cimbar_hip_ctx* ctx) { return ctx ? ctx->pipe_depth : CIMBAR_HIP_EINVAL; }
@@ -1521,19 +1531,16 @@ int64_t cimbar_hip_decode_plain_batch(cimbar_hip_ctx* ctx, const uint8_t* rgb, i
 	if (!rgb || !bytes || n <= 0) { ctx->err = "decode_plain_batch: null buffer or n <= 0"; return CIMBAR_HIP_EINVAL; }
 	if (ctx->er_sym > 0) { ctx->err = "decode_plain_batch: erasure decoding is on (cimbar_hip_set_erasure_decode); the plain stream has no chunk mask to extend"; return CIMBAR_HIP_EINVAL; }
 	if (ctx->ec_margin > 0) { ctx->err = "decode_plain_batch: colour erasure decoding is on (cimbar_hip_set_colour_erasure_decode); the plain stream has no chunk mask to extend"; return CIMBAR_HIP_EINVAL; }
-	if ((rgb_mem != CIMBAR_HIP_MEM_HOST && rgb_mem != CIMBAR_HIP_MEM_DEVICE) || (out_mem != CIMBAR_HIP_MEM_HOST && out_mem != CIMBAR_HIP_MEM_DEVICE)) {
-		ctx->err = "decode_plain_batch: rgb_mem / out_mem must be CIMBAR_HIP_MEM_HOST or CIMBAR_HIP_MEM_DEVICE";
-		return CIMBAR_HIP_EINVAL;
-	}
-	HIPCHK(hipSetDevice(ctx->device));
-	const bool any_device = rgb_mem == CIMBAR_HIP_MEM_DEVICE || out_mem == CIMBAR_HIP_MEM_DEVICE;
-	hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (any_device ? (hipStream_t)nullptr : ctx->stream);
-	if (int r = drain_pipeline_into(ctx, st)) return r;
+	hipStream_t st;
+	if (int r = begin_call(ctx, "decode_plain_batch", "rgb_mem", rgb_mem, "out_mem", out_mem, hip_stream, &st)) return r;
 	if (int r = ensure_capacity(ctx, n)) return r;
-	const uint8_t* d_rgb = nullptr;
-	if (int r = stage_input(ctx, st, ctx->d_rgb, rgb, (size_t)n * FRAME_RGB, rgb_mem, &d_rgb)) return r;
+	ChainArgs ca;
+	if (int r = stage_input(ctx, st, ctx->d_rgb, rgb, (size_t)n * FRAME_RGB, rgb_mem, &ca.d_rgb)) return r;
 	uint8_t* d_bytes = out_mem == CIMBAR_HIP_MEM_DEVICE ? bytes : ctx->d_chunks;
-	if (int r = enqueue(ctx, st, d_rgb, n, should_preprocess, color_correction, d_bytes, ctx->d_masks, 1)) return r;
+	ca.n = n; ca.pre = should_preprocess; ca.cc = color_correction;
+	ca.d_chunks = d_bytes; ca.d_masks = ctx->d_masks;
+	ca.plain = 1;
+	if (int r = enqueue(ctx, st, ca)) return r;
 	if (block_ok)
 		HIPCHK(hipMemcpyAsync(block_ok, ctx->cur().d_rs_ok, (size_t)n * ALL_BLOCKS, out_mem == CIMBAR_HIP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
 	if (out_mem == CIMBAR_HIP_MEM_DEVICE) return 0;
@@ -1567,10 +1574,9 @@ int cimbar_hip_decode_frame_sync(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsign
 		HIPCHK(hipDeviceSynchronize());   // (single-image edge path: nothing of an earlier call may still be reading the scratch)
 		HIPCHK(hipMemcpy2D(ctx->d_ex_in, row, rgb, stride ? stride : row, row, height, hipMemcpyHostToDevice));
 		const unsigned ex = width - (unsigned)IMG_W, ey = height - (unsigned)IMG_H;
-		ctx->pad_src = ctx->d_ex_in; ctx->pad_w = (int)width; ctx->pad_h = (int)height; ctx->pad_off = (int)((ex < ey ? ex : ey) / 2);
-		const int64_t r = cimbar_hip_decode_batch(ctx, ctx->d_rgb, 1, CIMBAR_HIP_MEM_DEVICE, should_preprocess, color_correction, chunks, good_mask, CIMBAR_HIP_MEM_HOST, nullptr);
-		ctx->pad_src = nullptr;
-		return (int)r;
+		const PadSource pad{ctx->d_ex_in, (int)width, (int)height, (int)((ex < ey ? ex : ey) / 2)};
+		return (int)decode_impl(ctx, nullptr, ctx->d_rgb, 1, CIMBAR_HIP_MEM_DEVICE, should_preprocess, color_correction, chunks, good_mask, CIMBAR_HIP_MEM_HOST,
+		                        nullptr, nullptr, nullptr, &pad);
 	}
 	if (stride == (size_t)IMG_W * 3 || stride == 0)
 		return (int)cimbar_hip_decode_batch(ctx, rgb, 1, CIMBAR_HIP_MEM_HOST, should_preprocess, color_correction, chunks, good_mask, CIMBAR_HIP_MEM_HOST, nullptr);
@@ -1666,7 +1672,11 @@ long long cimbar_hip_decode_frame_async(cimbar_hip_ctx* ctx, const uint8_t* rgb,
 	// the chunks and the mask are written where the host reads them: page-locked host memory is device-visible, the Reed-Solomon kernels store 7.5 KB
 	// into it over the link and no copy back (one more DMA packet with its latency) is queued behind the frame
 	uint8_t* const out = ctx->frame_zerocopy ? fs.h_out.get() : fs.d_out.get();
-	if (int r = enqueue(ctx, own, fs.d_rgb, 1, should_preprocess, color_correction, out, reinterpret_cast<uint32_t*>(out + FRAME_OUT_STRIDE), 0, true)) return r;
+	ChainArgs ca;
+	ca.d_rgb = fs.d_rgb; ca.n = 1; ca.pre = should_preprocess; ca.cc = color_correction;
+	ca.d_chunks = out; ca.d_masks = reinterpret_cast<uint32_t*>(out + FRAME_OUT_STRIDE);
+	ca.pipe = true;
+	if (int r = enqueue(ctx, own, ca)) return r;
 	if (!ctx->frame_zerocopy) HIPCHK(hipMemcpyAsync(fs.h_out, fs.d_out, FRAME_OUT_STRIDE + sizeof(uint32_t), hipMemcpyDeviceToHost, own));
 	HIPCHK(hipEventRecord(fs.done, own));
 	fs.user_chunks = chunks;
@@ -1798,6 +1808,14 @@ int check_capture(cimbar_hip_ctx* ctx, const char* who, unsigned width, unsigned
 	return 0;
 }
 
+// Scanner's blur unit (Scanner.h:157-159): max(3, nextPowerOfTwo(min(w, h) * 0.002) + 1)
+unsigned scan_blur_unit(unsigned width, unsigned height)
+{
+	unsigned unit = (unsigned)((width < height ? width : height) * 0.002);
+	unit--; unit |= unit >> 1; unit |= unit >> 2; unit |= unit >> 4; unit |= unit >> 8; unit |= unit >> 16;
+	return unit + 2 > 3u ? unit + 2 : 3u;
+}
+
 int extract_state(cimbar_hip_ctx* ctx, int n)
 {
 	HIPCHK(ctx->d_ex_hist.reserve((size_t)n * 256));
@@ -1823,21 +1841,12 @@ int cimbar_hip_scan_preprocess_fmt(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsi
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;
 	if (!rgb || !binary || n <= 0 || width < 8 || height < 8) { ctx->err = "scan_preprocess: null buffer, n <= 0 or a frame smaller than 8x8"; return CIMBAR_HIP_EINVAL; }
-	if ((rgb_mem != CIMBAR_HIP_MEM_HOST && rgb_mem != CIMBAR_HIP_MEM_DEVICE) || (out_mem != CIMBAR_HIP_MEM_HOST && out_mem != CIMBAR_HIP_MEM_DEVICE)) {
-		ctx->err = "scan_preprocess: rgb_mem / out_mem must be CIMBAR_HIP_MEM_HOST or CIMBAR_HIP_MEM_DEVICE";
-		return CIMBAR_HIP_EINVAL;
-	}
-	// Scanner.h:157-159: unit = max(3, nextPowerOfTwo(min(w, h) * 0.002) + 1)
-	unsigned unit = (unsigned)((width < height ? width : height) * 0.002);
-	unit--; unit |= unit >> 1; unit |= unit >> 2; unit |= unit >> 4; unit |= unit >> 8; unit |= unit >> 16;
-	unit = unit + 2 > 3u ? unit + 2 : 3u;
+	hipStream_t st;
+	if (int r = begin_call(ctx, "scan_preprocess", "rgb_mem", rgb_mem, "out_mem", out_mem, hip_stream, &st)) return r;
+	const unsigned unit = scan_blur_unit(width, height);
 	if (unit != 3 && unit != 5 && unit != 9 && unit != 17) { ctx->err = "scan_preprocess: captures of 8500 px or more on the short side need a 33x33 blur, not implemented"; return CIMBAR_HIP_EDIM; }
 	int fmt; size_t cbytes;
 	if (int r = check_capture(ctx, "scan_preprocess", width, height, format, &fmt, &cbytes)) return r;
-	HIPCHK(hipSetDevice(ctx->device));
-	const bool any_device = rgb_mem == CIMBAR_HIP_MEM_DEVICE || out_mem == CIMBAR_HIP_MEM_DEVICE;
-	hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (any_device ? (hipStream_t)nullptr : ctx->stream);
-	if (int r = drain_pipeline_into(ctx, st)) return r;
 	if (int r = extract_state(ctx, n)) return r;
 	const size_t px = (size_t)width * height;
 	const uint8_t* d_in = nullptr;
@@ -1867,16 +1876,10 @@ int cimbar_hip_deskew_batch_fmt(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsigne
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;
 	if (!rgb || !corners || !frames || n <= 0 || width < 2 || height < 2) { ctx->err = "deskew_batch: null buffer, n <= 0 or an empty frame"; return CIMBAR_HIP_EINVAL; }
-	if ((rgb_mem != CIMBAR_HIP_MEM_HOST && rgb_mem != CIMBAR_HIP_MEM_DEVICE) || (out_mem != CIMBAR_HIP_MEM_HOST && out_mem != CIMBAR_HIP_MEM_DEVICE)) {
-		ctx->err = "deskew_batch: rgb_mem / out_mem must be CIMBAR_HIP_MEM_HOST or CIMBAR_HIP_MEM_DEVICE";
-		return CIMBAR_HIP_EINVAL;
-	}
+	hipStream_t st;
+	if (int r = begin_call(ctx, "deskew_batch", "rgb_mem", rgb_mem, "out_mem", out_mem, hip_stream, &st)) return r;
 	int fmt; size_t cbytes;
 	if (int r = check_capture(ctx, "deskew_batch", width, height, format, &fmt, &cbytes)) return r;
-	HIPCHK(hipSetDevice(ctx->device));
-	const bool any_device = rgb_mem == CIMBAR_HIP_MEM_DEVICE || out_mem == CIMBAR_HIP_MEM_DEVICE;
-	hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (any_device ? (hipStream_t)nullptr : ctx->stream);
-	if (int r = drain_pipeline_into(ctx, st)) return r;
 	if (int r = extract_state(ctx, n)) return r;
 	// the matrices go through a context-owned pinned buffer: wait for the previous call's copy out of it (long done in practice)
 	HIPCHK(hipEventSynchronize(ctx->ev_ex_minv));
@@ -1902,14 +1905,6 @@ int cimbar_hip_deskew_batch(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsigned wi
 }
 
 namespace {
-
-// Scanner's blur unit (Scanner.h:157-159): max(3, nextPowerOfTwo(min(w, h) * 0.002) + 1)
-unsigned scan_blur_unit(unsigned width, unsigned height)
-{
-	unsigned unit = (unsigned)((width < height ? width : height) * 0.002);
-	unit--; unit |= unit >> 1; unit |= unit >> 2; unit |= unit >> 4; unit |= unit >> 8; unit |= unit >> 16;
-	return unit + 2 > 3u ? unit + 2 : 3u;
-}
 
 // X1 + X2 + S1 + S2 + S3 for n device-resident captures: blurred gray -> Otsu -> anchors -> corners / status -> warp matrices.
 // Leaves ScanResult[n] in ctx->d_scan_res and the matrices in ctx->d_ex_minv.
@@ -1952,6 +1947,146 @@ int enqueue_scan(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_in, unsig
 	return 0;
 }
 
+// The capture front end: n captures (host memory: staged through d_ex_in) searched -- `scan(d_in)` leaves ScanResult[n] in d_scan_res and the
+// warp matrices in d_ex_minv -- and warped into d_out (nullptr: d_ex_frames); `status` (may be nullptr) gets the strided copy of the status words.
+template <class Scan>
+int capture_front(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* img, unsigned width, unsigned height, int fmt, size_t cbytes, int n, int img_mem,
+                  uint8_t* d_out, int* status, int out_mem, Scan&& scan)
+{
+	if (int r = extract_state(ctx, n)) return r;
+	const uint8_t* d_in = nullptr;
+	if (int r = stage_input(ctx, st, ctx->d_ex_in, img, cbytes * n, img_mem, &d_in)) return r;
+	if (!d_out) { HIPCHK(ctx->d_ex_frames.reserve((size_t)n * FRAME_RGB)); d_out = ctx->d_ex_frames; }
+	if (int r = scan(d_in)) return r;
+	if (int r = launch_warp_ctx(ctx, st, fmt, d_in, width, height, n, ctx->d_ex_minv, d_out)) return r;
+	HIPCHK(hipGetLastError());
+	const hipMemcpyKind kind = out_mem == CIMBAR_HIP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+	if (status) HIPCHK(hipMemcpy2DAsync(status, sizeof(int), &ctx->d_scan_res[0].status, sizeof(ScanResult), sizeof(int), (size_t)n, kind, st));
+	return 0;
+}
+// ... with the anchor search itself (X1 + X2 + S1-S3, enqueue_scan)
+int capture_front(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* img, unsigned width, unsigned height, int fmt, size_t cbytes, int n, int img_mem,
+                  uint8_t* d_out, int* status, int out_mem)
+{
+	return capture_front(ctx, st, img, width, height, fmt, cbytes, n, img_mem, d_out, status, out_mem,
+	                     [&](const uint8_t* d_in) { return enqueue_scan(ctx, st, d_in, width, height, fmt, n); });
+}
+
+// what a decode tail reads: n device-resident frames and what came with them
+struct FrameSource {
+	const uint8_t* d_frames = nullptr;
+	const int* d_status = nullptr; int stride = 0;   // the extraction status per frame, `stride` ints apart (nullptr: frame input, every frame usable)
+	int pre = 0; bool guess = false;                 // sharpen every frame / where the extractor said NEEDS_SHARPEN (d_status)
+	bool captures = false;                           // deskewed captures: one chain (ChainArgs::no_split), and what the extractor gave up on is masked
+	PadSource pad{};
+};
+
+// the caller's frames (host memory: staged through d_rgb)
+int frames_source(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* rgb, int n, int rgb_mem, int should_preprocess, FrameSource* fs)
+{
+	fs->pre = should_preprocess;
+	return stage_input(ctx, st, ctx->d_rgb, rgb, (size_t)n * FRAME_RGB, rgb_mem, &fs->d_frames);
+}
+
+// the frames a capture front end left in d_ex_frames, with their status words. cimbar.cpp:131,147-154: preprocess 1 = sharpen every frame,
+// 0 = none, anything else = where the extractor said NEEDS_SHARPEN
+FrameSource deskewed_source(cimbar_hip_ctx* ctx, const int* d_status, int stride, int preprocess)
+{
+	FrameSource fs;
+	fs.d_frames = ctx->d_ex_frames; fs.d_status = d_status; fs.stride = stride;
+	fs.pre = preprocess == 1 ? 1 : 0; fs.guess = preprocess != 0 && preprocess != 1;
+	fs.captures = true;
+	return fs;
+}
+
+// the caller's captures through the front end (extraction runs for every capture: the once-calls find their runs on the deskewed frames)
+int captures_source(cimbar_hip_ctx* ctx, hipStream_t st, const CaptureIn& cap, const uint8_t* img, int n, int img_mem, int preprocess, int out_mem, FrameSource* fs)
+{
+	if (int r = capture_front(ctx, st, img, cap.width, cap.height, cap.fmt, cap.cbytes, n, img_mem, nullptr, cap.status, out_mem)) return r;
+	*fs = deskewed_source(ctx, &ctx->d_scan_res[0].status, (int)(sizeof(ScanResult) / sizeof(int)), preprocess);
+	return 0;
+}
+
+// enqueue()'s arguments for n frames of a source
+ChainArgs chain_args(const FrameSource& fs, int n, int cc, uint8_t* d_chunks, uint32_t* d_masks)
+{
+	ChainArgs ca;
+	ca.d_rgb = fs.d_frames; ca.n = n; ca.pre = fs.pre; ca.cc = cc;
+	ca.d_chunks = d_chunks; ca.d_masks = d_masks;
+	if (fs.guess) { ca.d_sel = fs.d_status; ca.sel_stride = fs.stride; }
+	ca.no_split = fs.captures;
+	ca.pad = fs.pad;
+	return ca;
+}
+
+// the decode chain over a source and, behind it and in front of any combine / stitch, the masking of the captures the extractor gave up on:
+// the reference skips them (cimbar.cpp:141-146), nothing of them reaches the sink, a group or a stitched pair
+int enqueue_source(cimbar_hip_ctx* ctx, hipStream_t st, const FrameSource& fs, int n, int cc, uint8_t* d_chunks, uint32_t* d_masks)
+{
+	if (int r = enqueue(ctx, st, chain_args(fs, n, cc, d_chunks, d_masks))) return r;
+	if (fs.captures) {
+		hipLaunchKernelGGL(k_mask_failed, dim3(n), dim3(256), 0, st, fs.d_status, fs.stride, n, d_masks, d_chunks);
+		HIPCHK(hipGetLastError());
+	}
+	return 0;
+}
+
+// "decode_batch" + tail for frames, "scan_extract_decode_batch" + tail for captures: what the messages call an entry point
+std::string call_name(const CaptureIn* cap, const char* tail) { return std::string(cap ? "scan_extract_decode_batch" : "decode_batch") + tail; }
+
+// What the decode entry points check of their input, in this order: null buffers / n (captures: / 8x8), then the call prologue with its mem
+// flags (begin_call), then -- captures -- what the format can hold (EDIM; cap->fmt and cap->cbytes are resolved here). `flush`: a
+// combined-stream call with n == 0, which reads no image argument.
+int begin_decode(cimbar_hip_ctx* ctx, const char* who, CaptureIn* cap, const void* img, int n, const char* in_name, int img_mem, bool outputs, int out_mem,
+                 void* hip_stream, bool flush, hipStream_t* st)
+{
+	if (!flush && (!img || !outputs || n <= 0 || (cap && (cap->width < 8 || cap->height < 8)))) {
+		ctx->err = std::string(who) + (cap ? ": null buffer, n <= 0 or a capture smaller than 8x8" : ": null buffer or n <= 0");
+		return CIMBAR_HIP_EINVAL;
+	}
+	// (a quirk, kept: the flush of the capture call checks out_mem alone and accepts any img_mem; that of the frame call checks both flags)
+	if (int r = begin_call(ctx, who, (flush && cap) ? nullptr : in_name, img_mem, "out_mem", out_mem, hip_stream, st)) return r;
+	if (cap && !flush) return check_capture(ctx, who, cap->width, cap->height, cap->format, &cap->fmt, &cap->cbytes);
+	return 0;
+}
+
+int64_t decode_impl(cimbar_hip_ctx* ctx, CaptureIn* cap, const uint8_t* img, int n, int img_mem, int preprocess, int color_correction, uint8_t* chunks,
+                    uint32_t* masks, int out_mem, void* hip_stream, CombineArgs* cb, StitchArgs* sa, const PadSource* pad)
+{
+	const bool strm = cb && cb->stream;
+	const std::string name = call_name(cap, sa ? (sa->stream ? "_stitched_stream" : "_stitched") : strm ? "_combined_stream" : cb ? "_combined" : "");
+	const char* who = name.c_str();
+	// (a stream call may bring no capture at all: n == 0 with a flush closes the open group)
+	const bool flush = strm && n == 0;
+	hipStream_t st;
+	if (int r = begin_decode(ctx, who, cap, img, n, "rgb_mem", img_mem, chunks && masks, out_mem, hip_stream, flush, &st)) return r;
+	if (cb) if (int r = check_combine(ctx, who, n, *cb)) return r;
+	if (sa) if (int r = check_stitch(ctx, who, n, *sa)) return r;
+	if (flush) {
+		if (int r = enqueue_combine_stream(ctx, st, 0, nullptr, nullptr, nullptr, nullptr, 0, *cb, out_mem)) return r;
+		return finish_stream(ctx, st, 0, chunks, masks, nullptr, nullptr, out_mem, *cb);
+	}
+	// (a stitched-stream call waits for the one before in front of every reservation and staging copy)
+	if (sa && sa->stream) if (int r = begin_stitch_stream(ctx, st)) return r;
+	if (int r = ensure_capacity(ctx, n)) return r;
+	FrameSource fs;
+	if (int r = cap ? captures_source(ctx, st, *cap, img, n, img_mem, preprocess, out_mem, &fs) : frames_source(ctx, st, img, n, img_mem, preprocess, &fs)) return r;
+	if (pad) fs.pad = *pad;
+	uint8_t* d_chunks = out_mem == CIMBAR_HIP_MEM_DEVICE ? chunks : ctx->d_chunks;
+	uint32_t* d_masks = out_mem == CIMBAR_HIP_MEM_DEVICE ? masks : ctx->d_masks;
+	if (int r = enqueue_source(ctx, st, fs, n, color_correction, d_chunks, d_masks)) return r;
+	if (strm) {
+		if (int r = enqueue_combine_stream(ctx, st, n, fs.d_frames, d_chunks, d_masks, fs.d_status, fs.stride, *cb, out_mem)) return r;
+		return finish_stream(ctx, st, n, chunks, masks, d_chunks, d_masks, out_mem, *cb);
+	}
+	if (cb) if (int r = enqueue_combine(ctx, st, n, fs.d_frames, d_chunks, d_masks, fs.d_status, fs.stride, *cb, out_mem)) return r;
+	if (sa && sa->rows(n) > 0) if (int r = enqueue_stitch(ctx, st, n, fs.d_status, fs.stride, *sa, out_mem)) return r;
+	const int64_t rc = sa ? finish_stitched(ctx, st, n, chunks, masks, d_chunks, d_masks, out_mem, *sa) : finish_batch(ctx, st, n, chunks, masks, d_chunks, d_masks, out_mem, cb);
+	// (host outputs of a plain or stitched call: it has synchronised, so the stage timers of its chain can be read)
+	if (rc >= 0 && !cb && out_mem == CIMBAR_HIP_MEM_HOST && ctx->timing) if (int r = read_stage_times(ctx)) return r;
+	return rc;
+}
+
 }  // namespace
 
 int cimbar_hip_extract_batch_fmt(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsigned width, unsigned height, int format, int n, int rgb_mem, uint8_t* frames,
@@ -1959,26 +2094,14 @@ int cimbar_hip_extract_batch_fmt(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsign
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;
 	if (!rgb || !frames || !status || n <= 0 || width < 8 || height < 8) { ctx->err = "extract_batch: null buffer, n <= 0 or a capture smaller than 8x8"; return CIMBAR_HIP_EINVAL; }
-	if ((rgb_mem != CIMBAR_HIP_MEM_HOST && rgb_mem != CIMBAR_HIP_MEM_DEVICE) || (out_mem != CIMBAR_HIP_MEM_HOST && out_mem != CIMBAR_HIP_MEM_DEVICE)) {
-		ctx->err = "extract_batch: rgb_mem / out_mem must be CIMBAR_HIP_MEM_HOST or CIMBAR_HIP_MEM_DEVICE";
-		return CIMBAR_HIP_EINVAL;
-	}
+	hipStream_t st;
+	if (int r = begin_call(ctx, "extract_batch", "rgb_mem", rgb_mem, "out_mem", out_mem, hip_stream, &st)) return r;
 	int fmt; size_t cbytes;
 	if (int r = check_capture(ctx, "extract_batch", width, height, format, &fmt, &cbytes)) return r;
-	HIPCHK(hipSetDevice(ctx->device));
-	const bool any_device = rgb_mem == CIMBAR_HIP_MEM_DEVICE || out_mem == CIMBAR_HIP_MEM_DEVICE;
-	hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (any_device ? (hipStream_t)nullptr : ctx->stream);
-	if (int r = drain_pipeline_into(ctx, st)) return r;
-	if (int r = extract_state(ctx, n)) return r;
-	const uint8_t* d_in = nullptr;
-	if (int r = stage_input(ctx, st, ctx->d_ex_in, rgb, cbytes * n, rgb_mem, &d_in)) return r;
 	uint8_t* d_out = nullptr;
 	if (int r = stage_output(ctx, ctx->d_ex_out, frames, (size_t)n * FRAME_RGB, out_mem, &d_out)) return r;
-	if (int r = enqueue_scan(ctx, st, d_in, width, height, fmt, n)) return r;
-	if (int r = launch_warp_ctx(ctx, st, fmt, d_in, width, height, n, ctx->d_ex_minv, d_out)) return r;
-	HIPCHK(hipGetLastError());
+	if (int r = capture_front(ctx, st, rgb, width, height, fmt, cbytes, n, rgb_mem, d_out, status, out_mem)) return r;
 	const hipMemcpyKind kind = out_mem == CIMBAR_HIP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-	HIPCHK(hipMemcpy2DAsync(status, sizeof(int), &ctx->d_scan_res[0].status, sizeof(ScanResult), sizeof(int), (size_t)n, kind, st));
 	if (corners) HIPCHK(hipMemcpy2DAsync(corners, sizeof(float) * 8, ctx->d_scan_res[0].corners, sizeof(ScanResult), sizeof(float) * 8, (size_t)n, kind, st));
 	if (out_mem == CIMBAR_HIP_MEM_DEVICE) return 0;
 	HIPCHK(hipMemcpyAsync(frames, d_out, (size_t)n * FRAME_RGB, hipMemcpyDeviceToHost, st));
@@ -1992,79 +2115,13 @@ int cimbar_hip_extract_batch(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsigned w
 	return cimbar_hip_extract_batch_fmt(ctx, rgb, width, height, FMT_RGB, n, rgb_mem, frames, status, corners, out_mem, hip_stream);
 }
 
-namespace {
-
-int64_t scan_extract_decode_impl(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsigned width, unsigned height, int format, int n, int rgb_mem,
-                                 int preprocess, int color_correction, uint8_t* chunks, uint32_t* masks, int* status, int out_mem,
-                                 void* hip_stream, CombineArgs* cb, StitchArgs* sa = nullptr)
-{
-	const bool strm = cb && cb->stream;
-	const char* who = sa ? (sa->stream ? "scan_extract_decode_batch_stitched_stream" : "scan_extract_decode_batch_stitched") : strm ? "scan_extract_decode_batch_combined_stream" : cb ? "scan_extract_decode_batch_combined" : "scan_extract_decode_batch";
-	if (strm && n == 0) {   // (no capture: a flush closes the open group; no image argument is read)
-		if (out_mem != CIMBAR_HIP_MEM_HOST && out_mem != CIMBAR_HIP_MEM_DEVICE) { ctx->err = std::string(who) + ": out_mem must be CIMBAR_HIP_MEM_HOST or CIMBAR_HIP_MEM_DEVICE"; return CIMBAR_HIP_EINVAL; }
-		if (int r = check_combine(ctx, who, n, *cb)) return r;
-		HIPCHK(hipSetDevice(ctx->device));
-		hipStream_t st0 = hip_stream ? (hipStream_t)hip_stream : (out_mem == CIMBAR_HIP_MEM_DEVICE ? (hipStream_t)nullptr : ctx->stream);
-		if (int r = drain_pipeline_into(ctx, st0)) return r;
-		if (int r = enqueue_combine_stream(ctx, st0, 0, nullptr, nullptr, nullptr, nullptr, 0, *cb, out_mem)) return r;
-		return finish_stream(ctx, st0, 0, chunks, masks, nullptr, nullptr, out_mem, *cb);
-	}
-	if (!rgb || !chunks || !masks || n <= 0 || width < 8 || height < 8) { ctx->err = std::string(who) + ": null buffer, n <= 0 or a capture smaller than 8x8"; return CIMBAR_HIP_EINVAL; }
-	if ((rgb_mem != CIMBAR_HIP_MEM_HOST && rgb_mem != CIMBAR_HIP_MEM_DEVICE) || (out_mem != CIMBAR_HIP_MEM_HOST && out_mem != CIMBAR_HIP_MEM_DEVICE)) {
-		ctx->err = std::string(who) + ": rgb_mem / out_mem must be CIMBAR_HIP_MEM_HOST or CIMBAR_HIP_MEM_DEVICE";
-		return CIMBAR_HIP_EINVAL;
-	}
-	int fmt; size_t cbytes;
-	if (int r = check_capture(ctx, who, width, height, format, &fmt, &cbytes)) return r;
-	if (cb) if (int r = check_combine(ctx, who, n, *cb)) return r;
-	if (sa) if (int r = check_stitch(ctx, who, n, *sa)) return r;
-	HIPCHK(hipSetDevice(ctx->device));
-	const bool any_device = rgb_mem == CIMBAR_HIP_MEM_DEVICE || out_mem == CIMBAR_HIP_MEM_DEVICE;
-	hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (any_device ? (hipStream_t)nullptr : ctx->stream);
-	if (int r = drain_pipeline_into(ctx, st)) return r;
-	if (sa && sa->stream) if (int r = begin_stitch_stream(ctx, st)) return r;
-	if (int r = extract_state(ctx, n)) return r;
-	if (int r = ensure_capacity(ctx, n)) return r;
-	const uint8_t* d_in = nullptr;
-	if (int r = stage_input(ctx, st, ctx->d_ex_in, rgb, cbytes * n, rgb_mem, &d_in)) return r;
-	HIPCHK(ctx->d_ex_frames.reserve((size_t)n * FRAME_RGB));
-	if (int r = enqueue_scan(ctx, st, d_in, width, height, fmt, n)) return r;
-	if (int r = launch_warp_ctx(ctx, st, fmt, d_in, width, height, n, ctx->d_ex_minv, ctx->d_ex_frames)) return r;
-	uint8_t* d_chunks = out_mem == CIMBAR_HIP_MEM_DEVICE ? chunks : ctx->d_chunks;
-	uint32_t* d_masks = out_mem == CIMBAR_HIP_MEM_DEVICE ? masks : ctx->d_masks;
-	// cimbar.cpp:131,147-154: preprocess 1 = sharpen every frame, 0 = none, anything else = where the extractor said NEEDS_SHARPEN
-	const bool guess = preprocess != 0 && preprocess != 1;
-	const int stride = (int)(sizeof(ScanResult) / sizeof(int));
-	ctx->no_split_once = true;
-	const int er = enqueue(ctx, st, ctx->d_ex_frames, n, preprocess == 1 ? 1 : 0, color_correction, d_chunks, d_masks, 0, false,
-	                       guess ? &ctx->d_scan_res[0].status : nullptr, stride);
-	ctx->no_split_once = false;
-	if (er) return er;
-	// a capture the extractor gave up on is skipped by the reference (cimbar.cpp:141-146): nothing of it reaches the sink
-	hipLaunchKernelGGL(k_mask_failed, dim3(n), dim3(256), 0, st, &ctx->d_scan_res[0].status, stride, n, d_masks, d_chunks);
-	HIPCHK(hipGetLastError());
-	// ... nor any group (it is in none)
-	if (strm) { if (int r = enqueue_combine_stream(ctx, st, n, ctx->d_ex_frames, d_chunks, d_masks, &ctx->d_scan_res[0].status, stride, *cb, out_mem)) return r; }
-	else if (cb)
-		if (int r = enqueue_combine(ctx, st, n, ctx->d_ex_frames, d_chunks, d_masks, &ctx->d_scan_res[0].status, stride, *cb, out_mem)) return r;
-	// ... nor any stitched pair
-	if (sa && sa->rows(n) > 0)
-		if (int r = enqueue_stitch(ctx, st, n, &ctx->d_scan_res[0].status, stride, *sa, out_mem)) return r;
-	const hipMemcpyKind kind = out_mem == CIMBAR_HIP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-	if (status) HIPCHK(hipMemcpy2DAsync(status, sizeof(int), &ctx->d_scan_res[0].status, sizeof(ScanResult), sizeof(int), (size_t)n, kind, st));
-	if (strm) return finish_stream(ctx, st, n, chunks, masks, d_chunks, d_masks, out_mem, *cb);
-	if (sa) return finish_stitched(ctx, st, n, chunks, masks, d_chunks, d_masks, out_mem, *sa);
-	return finish_batch(ctx, st, n, chunks, masks, d_chunks, d_masks, out_mem, cb);
-}
-
-}  // namespace
-
 int64_t cimbar_hip_scan_extract_decode_batch_fmt(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsigned width, unsigned height, int format, int n, int rgb_mem,
                                                  int preprocess, int color_correction, uint8_t* chunks, uint32_t* masks, int* status, int out_mem,
                                                  void* hip_stream)
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;
-	return scan_extract_decode_impl(ctx, rgb, width, height, format, n, rgb_mem, preprocess, color_correction, chunks, masks, status, out_mem, hip_stream, nullptr);
+	CaptureIn cap{width, height, format, status};
+	return decode_impl(ctx, &cap, rgb, n, rgb_mem, preprocess, color_correction, chunks, masks, out_mem, hip_stream, nullptr);
 }
 
 int64_t cimbar_hip_scan_extract_decode_batch_combined_fmt(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsigned width, unsigned height, int format, int n,
@@ -2074,7 +2131,8 @@ int64_t cimbar_hip_scan_extract_decode_batch_combined_fmt(cimbar_hip_ctx* ctx, c
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;
 	CombineArgs cb{groups_in, min_agree_permille, max_group, groups_out, gchunks, gmasks, n_groups};
-	return scan_extract_decode_impl(ctx, rgb, width, height, format, n, rgb_mem, preprocess, color_correction, chunks, masks, status, out_mem, hip_stream, &cb);
+	CaptureIn cap{width, height, format, status};
+	return decode_impl(ctx, &cap, rgb, n, rgb_mem, preprocess, color_correction, chunks, masks, out_mem, hip_stream, &cb);
 }
 
 int64_t cimbar_hip_scan_extract_decode_batch_stitched_fmt(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsigned width, unsigned height, int format, int n,
@@ -2084,7 +2142,8 @@ int64_t cimbar_hip_scan_extract_decode_batch_stitched_fmt(cimbar_hip_ctx* ctx, c
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;
 	StitchArgs sa{axis, min_agree_permille, min_band, schunks, smasks, tears, {}};
-	return scan_extract_decode_impl(ctx, rgb, width, height, format, n, rgb_mem, preprocess, color_correction, chunks, masks, status, out_mem, hip_stream, nullptr, &sa);
+	CaptureIn cap{width, height, format, status};
+	return decode_impl(ctx, &cap, rgb, n, rgb_mem, preprocess, color_correction, chunks, masks, out_mem, hip_stream, nullptr, &sa);
 }
 
 int64_t cimbar_hip_scan_extract_decode_batch_stitched_stream_fmt(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsigned width, unsigned height, int format,
@@ -2094,7 +2153,8 @@ int64_t cimbar_hip_scan_extract_decode_batch_stitched_stream_fmt(cimbar_hip_ctx*
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;
 	StitchArgs sa{axis, min_agree_permille, min_band, schunks, smasks, tears, {}, true};
-	return scan_extract_decode_impl(ctx, rgb, width, height, format, n, rgb_mem, preprocess, color_correction, chunks, masks, status, out_mem, hip_stream, nullptr, &sa);
+	CaptureIn cap{width, height, format, status};
+	return decode_impl(ctx, &cap, rgb, n, rgb_mem, preprocess, color_correction, chunks, masks, out_mem, hip_stream, nullptr, &sa);
 }
 
 int64_t cimbar_hip_scan_extract_decode_batch_combined_stream_fmt(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsigned width, unsigned height, int format,
@@ -2105,7 +2165,8 @@ int64_t cimbar_hip_scan_extract_decode_batch_combined_stream_fmt(cimbar_hip_ctx*
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;
 	CombineArgs cb{nullptr, min_agree_permille, max_group, groups_out, gchunks, gmasks, n_groups, true, flush, gsizes};
-	return scan_extract_decode_impl(ctx, rgb, width, height, format, n, rgb_mem, preprocess, color_correction, chunks, masks, status, out_mem, hip_stream, &cb);
+	CaptureIn cap{width, height, format, status};
+	return decode_impl(ctx, &cap, rgb, n, rgb_mem, preprocess, color_correction, chunks, masks, out_mem, hip_stream, &cb);
 }
 
 int64_t cimbar_hip_scan_extract_decode_batch(cimbar_hip_ctx* ctx, const uint8_t* rgb, unsigned width, unsigned height, int n, int rgb_mem,
@@ -2204,14 +2265,13 @@ int64_t end_once_stream(cimbar_hip_ctx* ctx, hipStream_t st, int64_t rc)
 	return rc;
 }
 
-// Everything behind the input: n device-resident frames d_frames (the caller's, or the warp's), d_status = the capture path's extraction status
-// (stride ints apart; nullptr: every frame usable, sharpening by `pre`). R1-R5 and G2, the read-back of the run count, pass 1, the read-back
-// of list 2's length, pass 2, R8 and the outputs. pre / guess as scan_extract_decode_impl resolves them.
-int64_t once_impl(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_frames, int n, const int* d_status, int stride, int pre, bool guess, int cc,
-                  uint8_t* chunks, uint32_t* masks, const OnceArgs& oa, int out_mem)
+// Everything behind the input: the n device-resident frames of `src` (the caller's, or the warp's, with the capture path's extraction status).
+// R1-R5 and G2, the read-back of the run count, pass 1, the read-back of list 2's length, pass 2, R8 and the outputs.
+int64_t once_impl(cimbar_hip_ctx* ctx, hipStream_t st, const FrameSource& src, int n, int cc, uint8_t* chunks, uint32_t* masks, const OnceArgs& oa, int out_mem)
 {
 	const size_t N = (size_t)n;
-	const bool dev = out_mem == CIMBAR_HIP_MEM_DEVICE, capture = d_status != nullptr;
+	const bool dev = out_mem == CIMBAR_HIP_MEM_DEVICE, guess = src.guess;
+	const uint8_t* const d_frames = src.d_frames; const int* const d_status = src.d_status; const int stride = src.stride;
 	HIPCHK(ctx->d_rp_sums.reserve(N * NCELLS));
 	HIPCHK(ctx->d_rp_sig.reserve(N * NCELLS));
 	HIPCHK(ctx->d_rp_agree.reserve(N));
@@ -2284,10 +2344,9 @@ int64_t once_impl(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_frames, 
 		if (int r = ensure_once_list(ctx, len)) return r;
 		if (int r = ensure_capacity(ctx, len)) return r;
 		hipLaunchKernelGGL(k_repeat_gather, dim3(96, len), dim3(256), 0, st, d_frames, d_list, ctx->d_rp_frames, guess ? d_status : (const int*)nullptr, stride, ctx->d_rp_sel);
-		ctx->no_split_once = capture;
-		const int er = enqueue(ctx, st, ctx->d_rp_frames, len, pre, cc, ctx->d_rp_chunks, ctx->d_rp_masks, 0, false, guess ? ctx->d_rp_sel.get() : nullptr, 1);
-		ctx->no_split_once = false;
-		if (er) return er;
+		FrameSource gathered = src;
+		gathered.d_frames = ctx->d_rp_frames; gathered.d_status = ctx->d_rp_sel; gathered.stride = 1;
+		if (int r = enqueue(ctx, st, chain_args(gathered, len, cc, ctx->d_rp_chunks, ctx->d_rp_masks))) return r;
 		hipLaunchKernelGGL(k_repeat_scatter, dim3(len), dim3(256), 0, st, d_list, ctx->d_rp_chunks, ctx->d_rp_masks, d_chunks, d_masks);
 		HIPCHK(hipGetLastError());
 		return 0;
@@ -2295,10 +2354,7 @@ int64_t once_impl(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_frames, 
 	if (len1 == n) {
 		// every capture is its own run: pass 1 decodes the input in place, and there is nobody for a pass 2
 		if (int r = ensure_capacity(ctx, n)) return r;
-		ctx->no_split_once = capture;
-		const int er = enqueue(ctx, st, d_frames, n, pre, cc, d_chunks, d_masks, 0, false, guess ? d_status : nullptr, stride);
-		ctx->no_split_once = false;
-		if (er) return er;
+		if (int r = enqueue(ctx, st, chain_args(src, n, cc, d_chunks, d_masks))) return r;
 	} else {
 		hipLaunchKernelGGL(k_repeat_clear, dim3(n), dim3(256), 0, st, ctx->d_rp_roles, d_chunks, d_masks);
 		if (len1 > 0) {
@@ -2394,63 +2450,22 @@ int64_t once_impl(cimbar_hip_ctx* ctx, hipStream_t st, const uint8_t* d_frames, 
 	return n_runs;
 }
 
-// the frame entry points: oa as the caller gave it (check_once resolves the two parameters)
-int64_t decode_batch_once_impl(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rgb_mem, int should_preprocess, int color_correction, uint8_t* chunks,
-                               uint32_t* masks, OnceArgs oa, int out_mem, void* hip_stream)
+// the once entry points, over frames (cap == nullptr) or captures: oa as the caller gave it (check_once, first of all checks, resolves the two parameters)
+int64_t once_call(cimbar_hip_ctx* ctx, CaptureIn* cap, const uint8_t* img, int n, int img_mem, int preprocess, int color_correction, uint8_t* chunks,
+                  uint32_t* masks, OnceArgs oa, int out_mem, void* hip_stream)
 {
-	const char* who = oa.stream ? "decode_batch_once_stream" : "decode_batch_once";
+	const std::string name = call_name(cap, oa.stream ? "_once_stream" : "_once");
+	const char* who = name.c_str();
 	if (int r = check_once(ctx, who, oa)) return r;
-	if (!rgb || !chunks || !masks || n <= 0) { ctx->err = std::string(who) + ": null buffer or n <= 0"; return CIMBAR_HIP_EINVAL; }
-	if ((rgb_mem != CIMBAR_HIP_MEM_HOST && rgb_mem != CIMBAR_HIP_MEM_DEVICE) || (out_mem != CIMBAR_HIP_MEM_HOST && out_mem != CIMBAR_HIP_MEM_DEVICE)) {
-		ctx->err = std::string(who) + ": rgb_mem / out_mem must be CIMBAR_HIP_MEM_HOST or CIMBAR_HIP_MEM_DEVICE";
-		return CIMBAR_HIP_EINVAL;
-	}
-	HIPCHK(hipSetDevice(ctx->device));
-	const bool any_device = rgb_mem == CIMBAR_HIP_MEM_DEVICE || out_mem == CIMBAR_HIP_MEM_DEVICE;
-	hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (any_device ? (hipStream_t)nullptr : ctx->stream);
-	if (int r = drain_pipeline_into(ctx, st)) return r;
+	hipStream_t st;
+	if (int r = begin_decode(ctx, who, cap, img, n, cap ? "img_mem" : "rgb_mem", img_mem, chunks && masks, out_mem, hip_stream, false, &st)) return r;
 	// (a stream call waits for the one before in front of the staging copy: the call before may still be decoding out of d_rgb)
 	if (oa.stream) if (int r = begin_once_stream(ctx, st)) return r;
+	// (... and every exit from here on, failed or not, goes through end_once_stream)
 	const int64_t rc = [&]() -> int64_t {
-		const uint8_t* d_rgb = nullptr;
-		if (int r = stage_input(ctx, st, ctx->d_rgb, rgb, (size_t)n * FRAME_RGB, rgb_mem, &d_rgb)) return r;
-		return once_impl(ctx, st, d_rgb, n, nullptr, 0, should_preprocess, false, color_correction, chunks, masks, oa, out_mem);
-	}();
-	return oa.stream ? end_once_stream(ctx, st, rc) : rc;
-}
-
-// ... and the capture entry points
-int64_t scan_extract_decode_batch_once_impl(cimbar_hip_ctx* ctx, const uint8_t* img, unsigned width, unsigned height, int format, int n, int img_mem,
-                                            int preprocess, int color_correction, uint8_t* chunks, uint32_t* masks, int* status, OnceArgs oa, int out_mem,
-                                            void* hip_stream)
-{
-	const char* who = oa.stream ? "scan_extract_decode_batch_once_stream" : "scan_extract_decode_batch_once";
-	if (int r = check_once(ctx, who, oa)) return r;
-	if (!img || !chunks || !masks || n <= 0 || width < 8 || height < 8) { ctx->err = std::string(who) + ": null buffer, n <= 0 or a capture smaller than 8x8"; return CIMBAR_HIP_EINVAL; }
-	if ((img_mem != CIMBAR_HIP_MEM_HOST && img_mem != CIMBAR_HIP_MEM_DEVICE) || (out_mem != CIMBAR_HIP_MEM_HOST && out_mem != CIMBAR_HIP_MEM_DEVICE)) {
-		ctx->err = std::string(who) + ": img_mem / out_mem must be CIMBAR_HIP_MEM_HOST or CIMBAR_HIP_MEM_DEVICE";
-		return CIMBAR_HIP_EINVAL;
-	}
-	int fmt; size_t cbytes;
-	if (int r = check_capture(ctx, who, width, height, format, &fmt, &cbytes)) return r;
-	HIPCHK(hipSetDevice(ctx->device));
-	const bool any_device = img_mem == CIMBAR_HIP_MEM_DEVICE || out_mem == CIMBAR_HIP_MEM_DEVICE;
-	hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (any_device ? (hipStream_t)nullptr : ctx->stream);
-	if (int r = drain_pipeline_into(ctx, st)) return r;
-	if (oa.stream) if (int r = begin_once_stream(ctx, st)) return r;
-	const int64_t rc = [&]() -> int64_t {
-		if (int r = extract_state(ctx, n)) return r;
-		const uint8_t* d_in = nullptr;
-		if (int r = stage_input(ctx, st, ctx->d_ex_in, img, cbytes * n, img_mem, &d_in)) return r;
-		HIPCHK(ctx->d_ex_frames.reserve((size_t)n * FRAME_RGB));
-		// extraction runs for every capture, repeats included: the runs are found on the deskewed frames
-		if (int r = enqueue_scan(ctx, st, d_in, width, height, fmt, n)) return r;
-		if (int r = launch_warp_ctx(ctx, st, fmt, d_in, width, height, n, ctx->d_ex_minv, ctx->d_ex_frames)) return r;
-		const hipMemcpyKind kind = out_mem == CIMBAR_HIP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-		if (status) HIPCHK(hipMemcpy2DAsync(status, sizeof(int), &ctx->d_scan_res[0].status, sizeof(ScanResult), sizeof(int), (size_t)n, kind, st));
-		const bool guess = preprocess != 0 && preprocess != 1;
-		return once_impl(ctx, st, ctx->d_ex_frames, n, &ctx->d_scan_res[0].status, (int)(sizeof(ScanResult) / sizeof(int)), preprocess == 1 ? 1 : 0, guess,
-		                 color_correction, chunks, masks, oa, out_mem);
+		FrameSource fs;
+		if (int r = cap ? captures_source(ctx, st, *cap, img, n, img_mem, preprocess, out_mem, &fs) : frames_source(ctx, st, img, n, img_mem, preprocess, &fs)) return r;
+		return once_impl(ctx, st, fs, n, color_correction, chunks, masks, oa, out_mem);
 	}();
 	return oa.stream ? end_once_stream(ctx, st, rc) : rc;
 }
@@ -2462,8 +2477,8 @@ int64_t cimbar_hip_decode_batch_once(cimbar_hip_ctx* ctx, const uint8_t* rgb, in
                                      uint8_t* rchunks, uint32_t* rmasks, int* n_runs, int out_mem, void* hip_stream)
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;
-	return decode_batch_once_impl(ctx, rgb, n, rgb_mem, should_preprocess, color_correction, chunks, masks,
-	                              OnceArgs{min_agree_permille, max_run, runs_out, roles, rchunks, rmasks, n_runs}, out_mem, hip_stream);
+	return once_call(ctx, nullptr, rgb, n, rgb_mem, should_preprocess, color_correction, chunks, masks,
+	                 OnceArgs{min_agree_permille, max_run, runs_out, roles, rchunks, rmasks, n_runs}, out_mem, hip_stream);
 }
 
 int64_t cimbar_hip_scan_extract_decode_batch_once_fmt(cimbar_hip_ctx* ctx, const uint8_t* img, unsigned width, unsigned height, int format, int n,
@@ -2472,8 +2487,9 @@ int64_t cimbar_hip_scan_extract_decode_batch_once_fmt(cimbar_hip_ctx* ctx, const
                                                       uint32_t* rmasks, int* n_runs, int out_mem, void* hip_stream)
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;
-	return scan_extract_decode_batch_once_impl(ctx, img, width, height, format, n, img_mem, preprocess, color_correction, chunks, masks, status,
-	                                           OnceArgs{min_agree_permille, max_run, runs_out, roles, rchunks, rmasks, n_runs}, out_mem, hip_stream);
+	CaptureIn cap{width, height, format, status};
+	return once_call(ctx, &cap, img, n, img_mem, preprocess, color_correction, chunks, masks,
+	                 OnceArgs{min_agree_permille, max_run, runs_out, roles, rchunks, rmasks, n_runs}, out_mem, hip_stream);
 }
 
 int64_t cimbar_hip_decode_batch_once_stream(cimbar_hip_ctx* ctx, const uint8_t* rgb, int n, int rgb_mem, int should_preprocess, int color_correction,
@@ -2481,8 +2497,8 @@ int64_t cimbar_hip_decode_batch_once_stream(cimbar_hip_ctx* ctx, const uint8_t* 
                                             uint8_t* rchunks, uint32_t* rmasks, int* n_runs, int* continued, int out_mem, void* hip_stream)
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;
-	return decode_batch_once_impl(ctx, rgb, n, rgb_mem, should_preprocess, color_correction, chunks, masks,
-	                              OnceArgs{min_agree_permille, max_run, runs_out, roles, rchunks, rmasks, n_runs, true, continued}, out_mem, hip_stream);
+	return once_call(ctx, nullptr, rgb, n, rgb_mem, should_preprocess, color_correction, chunks, masks,
+	                 OnceArgs{min_agree_permille, max_run, runs_out, roles, rchunks, rmasks, n_runs, true, continued}, out_mem, hip_stream);
 }
 
 int64_t cimbar_hip_scan_extract_decode_batch_once_stream_fmt(cimbar_hip_ctx* ctx, const uint8_t* img, unsigned width, unsigned height, int format, int n,
@@ -2492,9 +2508,9 @@ int64_t cimbar_hip_scan_extract_decode_batch_once_stream_fmt(cimbar_hip_ctx* ctx
                                                              void* hip_stream)
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;
-	return scan_extract_decode_batch_once_impl(ctx, img, width, height, format, n, img_mem, preprocess, color_correction, chunks, masks, status,
-	                                           OnceArgs{min_agree_permille, max_run, runs_out, roles, rchunks, rmasks, n_runs, true, continued}, out_mem,
-	                                           hip_stream);
+	CaptureIn cap{width, height, format, status};
+	return once_call(ctx, &cap, img, n, img_mem, preprocess, color_correction, chunks, masks,
+	                 OnceArgs{min_agree_permille, max_run, runs_out, roles, rchunks, rmasks, n_runs, true, continued}, out_mem, hip_stream);
 }
 
 // wait for the once-stream calls issued so far and forget the carry: the next one's capture 0 starts a run
@@ -2525,14 +2541,8 @@ int cimbar_hip_encode_batch(cimbar_hip_ctx* ctx, const uint8_t* payload, int n, 
 	if (!ctx) return CIMBAR_HIP_EINVAL;
 	if (!payload || !rgb_out || n <= 0) { ctx->err = "encode_batch: null buffer or n <= 0"; return CIMBAR_HIP_EINVAL; }
 	if (!ctx->d_template) { ctx->err = "encode_batch: call cimbar_hip_set_template first"; return CIMBAR_HIP_EINVAL; }
-	if ((payload_mem != CIMBAR_HIP_MEM_HOST && payload_mem != CIMBAR_HIP_MEM_DEVICE) || (rgb_mem != CIMBAR_HIP_MEM_HOST && rgb_mem != CIMBAR_HIP_MEM_DEVICE)) {
-		ctx->err = "encode_batch: payload_mem / rgb_mem must be CIMBAR_HIP_MEM_HOST or CIMBAR_HIP_MEM_DEVICE";
-		return CIMBAR_HIP_EINVAL;
-	}
-	HIPCHK(hipSetDevice(ctx->device));
-	const bool any_device = payload_mem == CIMBAR_HIP_MEM_DEVICE || rgb_mem == CIMBAR_HIP_MEM_DEVICE;
-	hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (any_device ? (hipStream_t)nullptr : ctx->stream);
-	if (int r = drain_pipeline_into(ctx, st)) return r;
+	hipStream_t st;
+	if (int r = begin_call(ctx, "encode_batch", "payload_mem", payload_mem, "rgb_mem", rgb_mem, hip_stream, &st)) return r;
 	if (int r = ensure_capacity(ctx, n)) return r;
 	const uint8_t* d_payload = nullptr;
 	if (int r = stage_input(ctx, st, ctx->d_payload, payload, (size_t)n * FRAME_BYTES, payload_mem, &d_payload)) return r;
@@ -2733,7 +2743,8 @@ int cimbar_hip_rs_decode_erasures(cimbar_hip_ctx* ctx, const uint8_t* blocks, in
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;
 	if (!blocks || !erasures || !counts || !msgs || !status || n <= 0) { ctx->err = "rs_decode_erasures: null buffer or n <= 0"; return CIMBAR_HIP_EINVAL; }
-	if (mem != CIMBAR_HIP_MEM_HOST && mem != CIMBAR_HIP_MEM_DEVICE) { ctx->err = "rs_decode_erasures: mem must be CIMBAR_HIP_MEM_HOST or CIMBAR_HIP_MEM_DEVICE"; return CIMBAR_HIP_EINVAL; }
+	// (not begin_call: the call touches no scratch set, so it does not wait for the pipelined batches in flight, and its streams are its own -- below)
+	if (int r = check_mem_flags(ctx, "rs_decode_erasures", nullptr, 0, "mem", mem)) return r;
 	HIPCHK(hipSetDevice(ctx->device));
 	const unsigned grid = (unsigned)((n + 3) / 4);
 	if (mem == CIMBAR_HIP_MEM_DEVICE) {   // stream-ordered on the caller's stream (the null stream by default); nothing waits
@@ -3070,7 +3081,7 @@ int cimbar_hip_stage_times(cimbar_hip_ctx* ctx, const char** names, float* ms, i
 	if (ctx->timing && ctx->last_n > 0) {
 		// device-output batches do not synchronise inside decode_batch; resolve the events here
 		HIPCHK(hipEventSynchronize(ctx->ev[cimbar_hip_ctx::NSTAGE]));
-		for (int k = 0; k < cimbar_hip_ctx::NSTAGE; ++k) HIPCHK(hipEventElapsedTime(&ctx->stage_ms[k], ctx->ev[k], ctx->ev[k + 1]));
+		if (int r = read_stage_times(ctx)) return r;
 	}
 	int k = 0;
 	for (; k < cimbar_hip_ctx::NSTAGE && k < max; ++k) {
@@ -3187,22 +3198,6 @@ void launch_undistort(hipStream_t st, int fmt, const uint8_t* d_in, unsigned wid
 	for_capture_format(fmt, [&](auto F) { hipLaunchKernelGGL((k_undistort<decltype(F)::value>), g, dim3(256), 0, st, d_in, W, H, d_xt, P, d_k1, d_ok, d_out, xcd_order); });
 }
 
-// the argument checks the three entry points share; *st = the stream the call runs on
-int undistort_args(cimbar_hip_ctx* ctx, const char* who, const uint8_t* img, unsigned width, unsigned height, int format, int n, int img_mem, int out_mem,
-                   void* hip_stream, int* fmt, size_t* cbytes, hipStream_t* st)
-{
-	if (!img || n <= 0 || width < 8 || height < 8) { ctx->err = std::string(who) + ": null buffer, n <= 0 or a capture smaller than 8x8"; return CIMBAR_HIP_EINVAL; }
-	if ((img_mem != CIMBAR_HIP_MEM_HOST && img_mem != CIMBAR_HIP_MEM_DEVICE) || (out_mem != CIMBAR_HIP_MEM_HOST && out_mem != CIMBAR_HIP_MEM_DEVICE)) {
-		ctx->err = std::string(who) + ": img_mem / out_mem must be CIMBAR_HIP_MEM_HOST or CIMBAR_HIP_MEM_DEVICE";
-		return CIMBAR_HIP_EINVAL;
-	}
-	if (int r = check_capture(ctx, who, width, height, format, fmt, cbytes)) return r;
-	HIPCHK(hipSetDevice(ctx->device));
-	const bool any_device = img_mem == CIMBAR_HIP_MEM_DEVICE || out_mem == CIMBAR_HIP_MEM_DEVICE;
-	*st = hip_stream ? (hipStream_t)hip_stream : (any_device ? (hipStream_t)nullptr : ctx->stream);
-	return drain_pipeline_into(ctx, *st);
-}
-
 }  // namespace
 
 int cimbar_hip_undistort_calibrate_fmt(cimbar_hip_ctx* ctx, const uint8_t* img, unsigned width, unsigned height, int format, int n, int img_mem,
@@ -3210,8 +3205,9 @@ int cimbar_hip_undistort_calibrate_fmt(cimbar_hip_ctx* ctx, const uint8_t* img, 
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;
 	if (!ok || !k1) { ctx->err = "undistort_calibrate: null ok / k1"; return CIMBAR_HIP_EINVAL; }
-	int fmt; size_t cbytes; hipStream_t st;
-	if (int r = undistort_args(ctx, "undistort_calibrate", img, width, height, format, n, img_mem, CIMBAR_HIP_MEM_HOST, hip_stream, &fmt, &cbytes, &st)) return r;
+	CaptureIn cap{width, height, format, nullptr}; hipStream_t st;
+	if (int r = begin_decode(ctx, "undistort_calibrate", &cap, img, n, "img_mem", img_mem, true, CIMBAR_HIP_MEM_HOST, hip_stream, false, &st)) return r;
+	const int fmt = cap.fmt; const size_t cbytes = cap.cbytes;
 	UndistortParams P; double ir[9];
 	if (int r = undistort_setup(ctx, "undistort_calibrate", nullptr, width, height, &P, ir)) return r;
 	const int group = undistort_group(ctx, width, height, n);
@@ -3233,8 +3229,9 @@ int cimbar_hip_undistort_batch_fmt(cimbar_hip_ctx* ctx, const uint8_t* img, unsi
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;
 	if (!out_rgb) { ctx->err = "undistort_batch: null out_rgb"; return CIMBAR_HIP_EINVAL; }
-	int fmt; size_t cbytes; hipStream_t st;
-	if (int r = undistort_args(ctx, "undistort_batch", img, width, height, format, n, img_mem, out_mem, hip_stream, &fmt, &cbytes, &st)) return r;
+	CaptureIn cap{width, height, format, nullptr}; hipStream_t st;
+	if (int r = begin_decode(ctx, "undistort_batch", &cap, img, n, "img_mem", img_mem, true, out_mem, hip_stream, false, &st)) return r;
+	const int fmt = cap.fmt; const size_t cbytes = cap.cbytes;
 	UndistortParams P; double ir[9];
 	if (int r = undistort_setup(ctx, "undistort_batch", params, width, height, &P, ir)) return r;
 	const int group = undistort_group(ctx, width, height, n);
@@ -3268,8 +3265,9 @@ int64_t cimbar_hip_scan_undistort_extract_decode_batch_fmt(cimbar_hip_ctx* ctx, 
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;
 	if (!chunks || !masks) { ctx->err = "scan_undistort_extract_decode_batch: null chunks / masks"; return CIMBAR_HIP_EINVAL; }
-	int fmt; size_t cbytes; hipStream_t st;
-	if (int r = undistort_args(ctx, "scan_undistort_extract_decode_batch", img, width, height, format, n, img_mem, out_mem, hip_stream, &fmt, &cbytes, &st)) return r;
+	CaptureIn cap{width, height, format, nullptr}; hipStream_t st;
+	if (int r = begin_decode(ctx, "scan_undistort_extract_decode_batch", &cap, img, n, "img_mem", img_mem, true, out_mem, hip_stream, false, &st)) return r;
+	const int fmt = cap.fmt; const size_t cbytes = cap.cbytes;
 	UndistortParams P; double ir[9];
 	if (int r = undistort_setup(ctx, "scan_undistort_extract_decode_batch", nullptr, width, height, &P, ir)) return r;
 	if (int r = ensure_capacity(ctx, n)) return r;
@@ -3290,21 +3288,10 @@ int64_t cimbar_hip_scan_undistort_extract_decode_batch_fmt(cimbar_hip_ctx* ctx, 
 	}
 	uint8_t* d_chunks = out_mem == CIMBAR_HIP_MEM_DEVICE ? chunks : ctx->d_chunks;
 	uint32_t* d_masks = out_mem == CIMBAR_HIP_MEM_DEVICE ? masks : ctx->d_masks;
-	const bool guess = preprocess != 0 && preprocess != 1;
-	ctx->no_split_once = true;
-	const int er = enqueue(ctx, st, ctx->d_ex_frames, n, preprocess == 1 ? 1 : 0, color_correction, d_chunks, d_masks, 0, false, guess ? ctx->d_ud_status : nullptr, 1);
-	ctx->no_split_once = false;
-	if (er) return er;
-	hipLaunchKernelGGL(k_mask_failed, dim3(n), dim3(256), 0, st, ctx->d_ud_status, 1, n, d_masks, d_chunks);
-	HIPCHK(hipGetLastError());
+	if (int r = enqueue_source(ctx, st, deskewed_source(ctx, ctx->d_ud_status, 1, preprocess), n, color_correction, d_chunks, d_masks)) return r;
 	const hipMemcpyKind kind = out_mem == CIMBAR_HIP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
 	if (status) HIPCHK(hipMemcpyAsync(status, ctx->d_ud_status, sizeof(int) * (size_t)n, kind, st));
 	if (undistort_ok) HIPCHK(hipMemcpyAsync(undistort_ok, ctx->d_ud_ok, sizeof(int) * (size_t)n, kind, st));
-	if (out_mem == CIMBAR_HIP_MEM_DEVICE) return 0;
-	HIPCHK(hipMemcpyAsync(chunks, d_chunks, (size_t)n * FRAME_BYTES, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipMemcpyAsync(masks, d_masks, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipStreamSynchronize(st));
-	unsigned long long total = 0;
-	for (int f = 0; f < n; ++f) total += (unsigned long long)CHUNK * (unsigned)__builtin_popcount(masks[f] & ((1u << CHUNKS) - 1u));
-	return (int64_t)total;
+	// (finish_batch alone: unlike decode_impl, this call has never read the stage timers, and still does not)
+	return finish_batch(ctx, st, n, chunks, masks, d_chunks, d_masks, out_mem, nullptr);
 }

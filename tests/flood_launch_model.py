@@ -27,7 +27,7 @@ BATCH_FLAGS, VERIFY_REPLAY, FALLBACK_REPLAY = 0, 1, 2
 def splits(n, entry="plain", tail_split=1, tail_parts=2, mostly_flood=False, timed=False):
     """does the chain behind the threshold pass run as tail_parts parts on two streams? Only the plain entry points split: a pipelined
     batch is one chain on its set's stream, the capture path (`capture`: scan + extract + decode, and every other caller that sets
-    no_split_once) asks for one chain, a timed batch is measured stage by stage; `mostly_flood` = more than a quarter of the batch
+    ChainArgs::no_split) asks for one chain, a timed batch is measured stage by stage; `mostly_flood` = more than a quarter of the batch
     before took a flood kernel (two half-size exact replays cost more than one)."""
     assert entry in ("plain", "pipelined", "capture")
     return entry == "plain" and not timed and bool(tail_split) and not mostly_flood and n >= 64 * tail_parts
