@@ -537,8 +537,9 @@ int64_t cimbar_hip_scan_extract_decode_batch_once_fmt(cimbar_hip_ctx* ctx, const
  * refuse the once-calls. Takes effect for once-calls issued after the call. The rescue uses the group scratch of the combined calls: a
  * once-call with the setting on and a combined call on the same context at the same time on two streams is the caller's to order, as two
  * combined calls are. get: writes 1 or 0 to *on and returns 0.
- * Not covered: the once-stream calls, the colour vote (cimbar_hip_set_group_colour_vote is not consulted), stitching, the undistort path, the
- * auto-detection objects, the C++ adapter and the receive shim. */
+ * Not covered: the once-stream calls, the colour vote (cimbar_hip_set_group_colour_vote is not consulted), stitching (but see tear salvage
+ * below: a torn capture's good side can join a tried run's vote), the undistort path, the auto-detection objects, the C++ adapter and the
+ * receive shim. */
 int cimbar_hip_set_once_rescue(cimbar_hip_ctx* ctx, int on);
 int cimbar_hip_get_once_rescue(cimbar_hip_ctx* ctx, int* on);
 
@@ -576,11 +577,58 @@ int cimbar_hip_get_once_rescue(cimbar_hip_ctx* ctx, int* on);
  * pointer may be NULL). Modes 4 and 8 refuse any axis other than -1 (EINVAL), as they refuse the once-calls. Takes effect for once-calls
  * issued after the call. The once-stream calls behave with the setting on exactly as with it off: a torn capture's successor is not known
  * when its call has to decide.
- * Not covered: the once-stream calls; stitching a frame out of a torn capture's good side when a neighbour run is incomplete; slanted tears
- * (the strip-by-strip form); two torn captures in a row, which agree with each other, form a run of two and are decoded as before; the
- * undistort path, the auto-detection objects, the C++ adapter and the receive shim. */
+ * Not covered: the once-stream calls; slanted tears (the strip-by-strip form); two torn captures in a row, which agree with each other, form
+ * a run of two and are decoded as before; the undistort path, the auto-detection objects, the C++ adapter and the receive shim. Using a
+ * torn capture's good side when a neighbour run is incomplete is tear salvage, below. */
 int cimbar_hip_set_once_tear_skip(cimbar_hip_ctx* ctx, int axis, int line_permille, int min_side);
 int cimbar_hip_get_once_tear_skip(cimbar_hip_ctx* ctx, int* axis, int* line_permille, int* min_side);
+
+/* Tear salvage (off after cimbar_hip_create): a torn capture's sides join the run rescue of its neighbour runs. A candidate of tear skipping
+ * that stands beside an incomplete run is decoded whole in pass 2. It is half frame P and half frame N, so it delivers next to nothing, but
+ * on every line on P's side of the tear its cells are correctly decoded cells of P, and likewise for N. With the setting EFFECTIVE those
+ * cells vote in the group decode of the neighbour run. The setting is effective in a plain once-call only when all three hold: run rescue
+ * is on, tear skipping's axis is not -1, and rchunks or rmasks is asked for. Otherwise the call behaves, byte for byte and launch for
+ * launch, as with the setting off. Everything below applies after pass 2, with the setting effective:
+ *   sides      a candidate k has the record {w, s, first, last} (CIMBAR_HIP_TAP_ONCE_TEAR), axis = w >> 1, o = w & 1, and L lines on that
+ *              axis. With the guard g: low = [0, s - g) and high = [s + g, L). Its P side is low when o = 0 and high when o = 1; its N side
+ *              is the other one. The P side is the side on which the candidate agreed with capture k - 1, the N side the one on which it
+ *              agreed with capture k + 1. A side whose range is empty gives no partial.
+ *   partials   let run r be a run that is no candidate's run, with first member f and last member e. Its following partial is capture
+ *              e + 1, if that capture is a candidate with role _FALLBACK, taken with its P side. Its preceding partial is capture f - 1, if
+ *              that capture is such a candidate, taken with its N side. A candidate beside a run whose representative is incomplete is
+ *              always in list 2, by tear skipping's guard. One candidate can serve both of its neighbours. A candidate's own run is never
+ *              tried, as before.
+ *   qualifies  (decided in front of pass 2, when the representative's cells must be kept) the representative's mask is not full, and the
+ *              run has at least two members or at least one partial
+ *   tried      the run qualifies, and the OR of the full members' masks after pass 2 is not full. A run that qualifies only through its
+ *              partial is a run of one: it has no pass-2 member, so all its members are decoded.
+ *   group order  the full members first, in capture order; then the preceding partial, then the following partial. A partial joins only
+ *              while the group has fewer than 8 members. "Lowest member index" in the combined cells' tie-breaks means the position in this
+ *              order. Member 0 is always a full member.
+ *   participation  a full member takes part in every cell. A partial takes part in cell i if and only if lo <= line_axis(i) < hi, with
+ *              line_axis(i) the stitched calls' line of cell i on the partial's axis.
+ *   combined cells  the rule of the combined calls, unchanged, but per cell over that cell's participants: the symbol vote over
+ *              2 d_c(t) - [t == s_c], the colour plurality with its two tie-breaks, and the margin. A cell with one participant takes that
+ *              participant's symbol and colour, and its symbol counts as undisputed. A group counts as disputed where the participants of
+ *              any cell differ.
+ *   decode and row  as the run rescue: Reed-Solomon over the combined cells, the chunk bookkeeping, and the symbol-erasure retry when it
+ *              is on. Only the FULL members' masks and chunks enter the row; a partial contributes cells and nothing else, because its own
+ *              decode can hold chunks of the other frame when the tear is near an edge, and those must never reach this run's row.
+ *              rmasks[r] is a superset of the OR of the full members' masks. For a run the rescue alone would also try, NO superset of
+ *              the rescue-alone row is promised: the partial's cells change the vote, and a vote can lose a chunk as well as gain one.
+ *              CIMBAR_HIP_TAP_ONCE_RESCUE and _RESCUE_CELLS keep their meaning; their "members" are the full members.
+ *              (CIMBAR_HIP_TAP_ONCE_SALVAGE)
+ *   unchanged  per-capture chunks, masks and status; runs_out, roles and *n_runs; the return value and the colour-correction carry; the
+ *              rows of every run that is not tried; the two 4-byte read-backs, with nothing further read back. The rescue's store and
+ *              scratch are sized for min(|list 1|, 2 |list 2|) runs instead of min(|list 1|, |list 2|). With the setting off no call
+ *              launches, allocates or writes anything it did not before.
+ * set: guard_lines -1 resolves to 1; 0 .. 16 are legal; anything else is CIMBAR_HIP_EINVAL. Modes 4 and 8 refuse on != 0 (EINVAL). A refused
+ * call changes nothing. get reports the resolved values (each pointer may be NULL). Takes effect for once-calls issued after the call. The
+ * once-stream calls ignore the setting.
+ * Not covered: the once-stream calls; slanted tears (the strip-by-strip form); two torn captures in a row; the colour vote in the salvage
+ * group; the undistort path, the auto-detection objects, the C++ adapter and the receive shim. */
+int cimbar_hip_set_once_tear_salvage(cimbar_hip_ctx* ctx, int on, int guard_lines);
+int cimbar_hip_get_once_tear_salvage(cimbar_hip_ctx* ctx, int* on, int* guard_lines);
 
 /* ---- repeat-capture skipping across calls: the open run is carried from call to call -------------------------------------------------------
  * A live receiver hands over one capture (or a few) per call, so a run of repeats spans calls. The two _once_stream calls are the calls above
@@ -1025,8 +1073,13 @@ enum {
 	 * and the areas the context holds now (>= asked; it only grows). One record per launch follows, in issue order, at most 16 (later ones are
 	 * dropped): instance = 3, 4 or 8 frames per CU (heap slots in LDS: 10 240, 7 080, 4 095); a launch with grid < frames hands the frames from
 	 * `grid` on out through counter pair `counter`; workgroup b spills into area area0 + b; flags says which frames the launch was for. */
-	CIMBAR_HIP_TAP_FLOOD_LAUNCH = 34    /* (1 + launches) x 7 int32: {instance, grid, frames, first frame, area0, counter, flags: 0 = the batch's flags,
+	CIMBAR_HIP_TAP_FLOOD_LAUNCH = 34,   /* (1 + launches) x 7 int32: {instance, grid, frames, first frame, area0, counter, flags: 0 = the batch's flags,
 	                                       1 = the verify replay (CIMBAR_HIP_FLOOD_VERIFY), 2 = the relaxed flood's fallback replay}; returns the bytes written */
+	/* tear salvage in the last once-call (cimbar_hip_set_once_tear_salvage; n = its captures). CIMBAR_HIP_EINVAL when the setting was not
+	 * effective in that call, or it was a once-stream call */
+	CIMBAR_HIP_TAP_ONCE_SALVAGE = 35    /* n x 8 int32         : per run slot {kp, axis_p, lo_p, hi_p, kf, axis_f, lo_f, hi_f}, the preceding and the following
+	                                       partial of the run with their line ranges; {-1, -1, 0, 0} for a partial the run does not have, and for
+	                                       both partials of a run that was not tried */
 };
 int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_bytes);
 

@@ -230,6 +230,18 @@ int cimbar_hip_get_once_tear_skip(cimbar_hip_ctx* ctx, int* axis, int* line_perm
 	return CIMBAR_FWD(cimbar_hip_get_once_tear_skip, axis, line_permille, min_side);
 }
 
+int cimbar_hip_set_once_tear_salvage(cimbar_hip_ctx* ctx, int on, int guard_lines)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return CIMBAR_FWD(cimbar_hip_set_once_tear_salvage, on, guard_lines);
+}
+
+int cimbar_hip_get_once_tear_salvage(cimbar_hip_ctx* ctx, int* on, int* guard_lines)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return CIMBAR_FWD(cimbar_hip_get_once_tear_salvage, on, guard_lines);
+}
+
 int cimbar_hip_set_stream_colour_vote(cimbar_hip_ctx* ctx, int on)
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;

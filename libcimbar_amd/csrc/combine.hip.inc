@@ -146,14 +146,16 @@ struct CarryStore {
 
 // (CARRY = false is the plain calls' kernel as it always was: a member id is a batch index and `cs` is not read. RESCUE, the once-calls' run
 // rescue -- k_group_cells_rescue at the end of this file: a member id is a capture index k and rmap[k] says where its cells are, ~slot of
-// the rescue store `cs` or, >= 0, a position in the batch pass 2 decoded)
-template <bool CARRY, bool RESCUE = false>
+// the rescue store `cs` or, >= 0, a position in the batch pass 2 decoded. SALVAGE, tear salvage -- k_group_cells_salvage at the end of this
+// file: RESCUE where a member may take part in some cells only; `in(c)` is "member c takes part in this cell", without SALVAGE c < m)
+template <bool CARRY, bool RESCUE = false, bool SALVAGE = false>
 __device__ __forceinline__ void group_cells_body(const uint32_t* __restrict__ plane, const Tables& tb, const uint8_t* __restrict__ symbols,
                                                  const uint8_t* __restrict__ colors, const int8_t* __restrict__ drift,
                                                  const uint32_t* __restrict__ flood_flag, const int* __restrict__ gmem,
                                                  const int* __restrict__ gcount, const int* __restrict__ ngroups, uint8_t* __restrict__ gsym,
                                                  uint8_t* __restrict__ gcol, uint16_t* __restrict__ gmargin, uint32_t* __restrict__ gdisp,
-                                                 const CarryStore& cs, const int* __restrict__ rmap = nullptr)
+                                                 const CarryStore& cs, const int* __restrict__ rmap = nullptr, const int* __restrict__ gfull = nullptr,
+                                                 const int32_t* __restrict__ part = nullptr, const uint8_t* __restrict__ line_tab = nullptr)
 {
 	auto sym_of = [&](int f) -> const uint8_t* {
 		if constexpr (RESCUE) return f < 0 ? cs.symbols + (size_t)~f * CS_CELLS : symbols + (size_t)f * NCELLS;
@@ -192,6 +194,33 @@ __device__ __forceinline__ void group_cells_body(const uint32_t* __restrict__ pl
 		s_mem[threadIdx.x] = f;
 		s_flood[threadIdx.x] = (int)threadIdx.x < m ? flood_of(f) : 0u;
 	}
+	// (SALVAGE: the members' line ranges, in LDS only. Members 0 .. gfull[g] - 1 are full; the partials behind them come from the slot's row
+	// of `part`, the preceding one first where the group took it)
+	__shared__ uint8_t s_rng[SALVAGE ? GMAX : 1][4];                     // {axis, lo, hi, 0}
+	if constexpr (SALVAGE) {
+		if (threadIdx.x < GMAX) {
+			const int c = (int)threadIdx.x - gfull[g];
+			const int32_t* row = part + (size_t)g * 8;
+			const int32_t* p = (c == 0 && row[0] >= 0) ? row : row + 4;
+			const bool full = c < 0 || (int)threadIdx.x >= m;
+			s_rng[threadIdx.x][0] = full ? 0 : (uint8_t)p[1];
+			s_rng[threadIdx.x][1] = full ? 0 : (uint8_t)p[2];
+			s_rng[threadIdx.x][2] = full ? 255 : (uint8_t)p[3];
+		}
+	}
+	// member c takes part in cell i (bit c of `who`, SALVAGE only)
+	auto who_of = [&](int i) -> uint32_t {
+		uint32_t who = 0;
+		if constexpr (SALVAGE) {
+			const uint32_t ln[2] = {line_tab[i], line_tab[NCELLS + i]};
+#pragma unroll
+			for (int c = 0; c < GMAX; ++c) {
+				const uint32_t l = ln[s_rng[c][0] & 1];
+				who |= (c < m && s_rng[c][1] <= l && l < s_rng[c][2]) ? 1u << c : 0u;
+			}
+		}
+		return who;
+	};
 	__syncthreads();
 	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 	uint8_t* os = gsym + (size_t)g * NCELLS;
@@ -207,11 +236,17 @@ __device__ __forceinline__ void group_cells_body(const uint32_t* __restrict__ pl
 		if (i < NCELLS) {
 			uint32_t sy[GMAX], co[GMAX];
 			bool sym_eq = true;
+			const uint32_t who = who_of(i);
+			auto in = [&](int c) -> bool {
+				if constexpr (SALVAGE) return ((who >> c) & 1u) != 0;
+				else return c < m;
+			};
+			const int np = SALVAGE ? (int)__popc(who) : m;                  // the cell's participants
 #pragma unroll
 			for (int c = 0; c < GMAX; ++c) {
-				sy[c] = c < m ? sym_of(s_mem[c])[i] & 15u : 0u;
-				co[c] = c < m ? col_of(s_mem[c])[i] : 0u;
-				sym_eq = sym_eq && (c >= m || sy[c] == sy[0]);
+				sy[c] = in(c) ? sym_of(s_mem[c])[i] & 15u : 0u;
+				co[c] = in(c) ? col_of(s_mem[c])[i] : 0u;
+				sym_eq = sym_eq && (!in(c) || sy[c] == sy[0]);
 			}
 			// plurality: the first member's colour among those with the most votes, and whether another colour has as many
 			int best = 0;
@@ -221,14 +256,14 @@ __device__ __forceinline__ void group_cells_body(const uint32_t* __restrict__ pl
 			for (int c = 0; c < GMAX; ++c) {
 				int v = 0;
 #pragma unroll
-				for (int q = 0; q < GMAX; ++q) v += (c < m && q < m && co[q] == co[c]) ? 1 : 0;
-				if (c < m) {
+				for (int q = 0; q < GMAX; ++q) v += (in(c) && in(q) && co[q] == co[c]) ? 1 : 0;
+				if (in(c)) {
 					if (v > best) { best = v; win = co[c]; tie = false; }
 					else if (v == best && co[c] != win) tie = true;
 				}
 			}
-			need = m > 1 && (!sym_eq || tie);
-			differ = differ || !sym_eq || best != m;
+			need = np > 1 && (!sym_eq || tie);
+			differ = differ || !sym_eq || best != np;
 			if (!need) {
 				os[i] = (uint8_t)sy[0];
 				oc[i] = (uint8_t)win;
@@ -252,11 +287,16 @@ __device__ __forceinline__ void group_cells_body(const uint32_t* __restrict__ pl
 #pragma unroll
 		for (int t = 0; t < 16; ++t) score[t] = 0;
 		bool sym_eq = true;
+		const uint32_t who = who_of(i);
+		auto in = [&](int c) -> bool {
+			if constexpr (SALVAGE) return ((who >> c) & 1u) != 0;
+			else return c < m;
+		};
 #pragma unroll
 		for (int c = 0; c < GMAX; ++c) {
 			H[c] = 0;
 			sy[c] = co[c] = 0;
-			if (c < m) {
+			if (in(c)) {
 				const int f = s_mem[c];
 				sy[c] = sym_of(f)[i] & 15u;
 				co[c] = col_of(f)[i];
@@ -291,9 +331,9 @@ __device__ __forceinline__ void group_cells_body(const uint32_t* __restrict__ pl
 		for (int c = 0; c < GMAX; ++c) {
 			int v = 0;
 #pragma unroll
-			for (int q2 = 0; q2 < GMAX; ++q2) v += (c < m && q2 < m && co[q2] == co[c]) ? 1 : 0;
+			for (int q2 = 0; q2 < GMAX; ++q2) v += (in(c) && in(q2) && co[q2] == co[c]) ? 1 : 0;
 			votes[c] = v;
-			if (c < m) {
+			if (in(c)) {
 				if (v > best) { best = v; win = co[c]; tie = false; }
 				else if (v == best && co[c] != win) tie = true;
 			}
@@ -302,7 +342,7 @@ __device__ __forceinline__ void group_cells_body(const uint32_t* __restrict__ pl
 #pragma unroll
 			for (int c = 0; c < GMAX; ++c) {
 				const int d = (int)__popcll(H[c] ^ c_tile[s_hat]);
-				if (c < m && votes[c] == best && d < bd) { bd = d; win = co[c]; }
+				if (in(c) && votes[c] == best && d < bd) { bd = d; win = co[c]; }
 			}
 		}
 		os[i] = (uint8_t)s_hat;
@@ -882,4 +922,23 @@ __global__ __launch_bounds__(256) void k_group_end_rescue(const uint8_t* __restr
 		if (rmasks) rmasks[run] = gm;
 		tap[run] = (int32_t)(gm & ~mm);
 	}
+}
+
+// ------------------------------------------------------------------------------------------------ tear salvage (the once-calls, opt-in)
+// cimbar_hip_set_once_tear_salvage: the rescue's group decode where a torn capture beside the run joins the vote on its good side
+// (repeat.hip.inc, "tear salvage"). gcount[slot] counts the full members and the partials, gfull[slot] the full members alone; the slot's
+// row of `part` is {kp, axis_p, lo_p, hi_p, kf, axis_f, lo_f, hi_f} and gmem holds the partials behind the full members, in that order. A
+// partial takes part in cell i iff lo <= line_axis(i) < hi, line_tab being the stitched calls' table; member 0 is always a full member.
+__global__ __launch_bounds__(256) void k_group_cells_salvage(const uint32_t* __restrict__ plane, Tables tb, const uint8_t* __restrict__ symbols,
+                                                             const uint8_t* __restrict__ colors, const int8_t* __restrict__ drift,
+                                                             const uint32_t* __restrict__ flood_flag, const int* __restrict__ gmem,
+                                                             const int* __restrict__ gcount, const int* __restrict__ gfull,
+                                                             const int32_t* __restrict__ part, const uint8_t* __restrict__ line_tab,
+                                                             const int* __restrict__ nslots, const int* __restrict__ rmap, uint8_t* __restrict__ gsym,
+                                                             uint8_t* __restrict__ gcol, uint16_t* __restrict__ gmargin, uint32_t* __restrict__ gdisp,
+                                                             CarryStore cs)
+{
+	if ((int)blockIdx.y >= *nslots || gcount[blockIdx.y] == 0) return;   // (uniform over the workgroup)
+	group_cells_body<false, true, true>(plane, tb, symbols, colors, drift, flood_flag, gmem, gcount, nslots, gsym, gcol, gmargin, gdisp, cs, rmap, gfull, part,
+	                                    line_tab);
 }

@@ -100,6 +100,10 @@ struct cimbar_hip_ctx {
 	int rt_axis = -1, rt_line = RT_LINE_DEFAULT, rt_side = RT_SIDE_DEFAULT;   // the setting, resolved; axis -1 = off
 	bool rt_state = false;                      // the last once-call was a plain one with the setting on (CIMBAR_HIP_TAP_ONCE_TEAR describes it)
 	DevBuf<int32_t> d_rt_tap; DevBuf<int> d_rt_pos, d_rt_words; PinnedBuf<int> h_rt_words;   // [n][4] the records, [n] a run's place in list 1, {|list 1|, |list 2|} and their mirror
+	// tear salvage (cimbar_hip_set_once_tear_salvage, repeat.hip.inc "tear salvage"): nothing of it exists until a plain once-call in which it is effective
+	int sv_on = 0, sv_guard = RV_GUARD_DEFAULT; // the setting, resolved
+	bool sv_state = false;                      // the last once-call was a plain one in which the setting was effective (CIMBAR_HIP_TAP_ONCE_SALVAGE describes it)
+	DevBuf<int32_t> d_sv_part; DevBuf<int> d_sv_full;   // [slots][8] the slots' partials, [slots] the full members of a tried slot
 	int wave_adapt = 1;               // CIMBAR_HIP_FLOOD_WAVE_ADAPT=0: run k_flood_wave in front of every exact replay, whatever it achieved before
 	bool wave_ran = false;            // k_flood_wave ran in the batch h_flagged describes
 	int wave_skip_left = 0;           // batches that still go straight to the exact replay (see enqueue)
@@ -2302,6 +2306,9 @@ int64_t once_impl(cimbar_hip_ctx* ctx, hipStream_t st, const FrameSource& src, i
 	// 2's come from the setting's own words, and pass 1's results are addressed through d_rt_pos.
 	const bool tear = ctx->rt_axis >= 0 && !os;
 	ctx->rt_state = false;
+	// tear salvage (cimbar_hip_set_once_tear_salvage): effective only where the rescue and tear skipping both are
+	const bool salvage = ctx->sv_on != 0 && rescue && tear;
+	ctx->sv_state = false;
 	if (tear) {
 		HIPCHK(ctx->d_rt_tap.reserve(N * 4));
 		HIPCHK(ctx->d_rt_pos.reserve(N));
@@ -2376,10 +2383,17 @@ int64_t once_impl(cimbar_hip_ctx* ctx, hipStream_t st, const FrameSource& src, i
 			if (len2 < 0 || len2 > n - len1) { ctx->err = "decode_batch_once: the fallback count read back is out of range"; return CIMBAR_HIP_EHIP; }
 			if (rescue && len2 > 0) {
 				// pass 2 overwrites pass 1's scratch: the representatives of the runs that may need the rescue are saved first
-				rs_slots = len1 < len2 ? len1 : len2;
+				// (tear salvage: a capture of list 2 may be the partial of the runs on both its sides)
+				rs_slots = salvage ? (len1 < 2 * len2 ? len1 : 2 * len2) : (len1 < len2 ? len1 : len2);
 				if (int r = ensure_rescue_capacity(ctx, n, rs_slots)) return r;
 				cimbar_hip_ctx::ScratchSet& p1 = ctx->cur();
-				if (tear)
+				if (salvage) {
+					HIPCHK(ctx->d_sv_part.reserve((size_t)rs_slots * 8));
+					HIPCHK(ctx->d_sv_full.reserve((size_t)rs_slots));
+					hipLaunchKernelGGL(k_rescue_save_salvage, dim3(RS_ARRAYS * RS_PARTS, rs_slots), dim3(256), 0, st, p1.d_plane, p1.d_symbols, p1.d_colors, p1.d_drift,
+					                   p1.d_flood, ctx->d_rp_masks, ctx->d_rp_mem, ctx->d_rp_count, n, rescue_store(ctx), ctx->d_rs_run, ctx->d_gmem, ctx->d_rs_map,
+					                   ctx->d_rs_count, ctx->d_rt_pos, ctx->d_rp_roles, ctx->d_rt_tap, n, ctx->sv_guard, ctx->d_sv_part);
+				} else if (tear)
 					hipLaunchKernelGGL(k_rescue_save_tear, dim3(RS_ARRAYS * RS_PARTS, rs_slots), dim3(256), 0, st, p1.d_plane, p1.d_symbols, p1.d_colors, p1.d_drift, p1.d_flood,
 					                   ctx->d_rp_masks, ctx->d_rp_mem, ctx->d_rp_count, n, rescue_store(ctx), ctx->d_rs_run, ctx->d_gmem, ctx->d_rs_map, ctx->d_rs_count,
 					                   ctx->d_rt_pos);
@@ -2409,12 +2423,21 @@ int64_t once_impl(cimbar_hip_ctx* ctx, hipStream_t st, const FrameSource& src, i
 		// slot staging, and the tried runs' rows over k_repeat_end's
 		cimbar_hip_ctx::ScratchSet& p2 = ctx->cur();
 		HIPCHK(hipMemsetAsync(ctx->d_rs_tap, 0xFF, sizeof(int32_t) * N, st));
-		hipLaunchKernelGGL(k_rescue_tried, dim3((rs_slots + 255) / 256), dim3(256), 0, st, ctx->d_rs_count, rs_slots, ctx->d_rs_run, ctx->d_gmem, ctx->d_rp_count, d_masks,
-		                   ctx->d_gcount, ctx->d_gdisp);
-		hipLaunchKernelGGL(k_group_cells_rescue, dim3(GC_BLOCKS, rs_slots), dim3(256), 0, st, p2.d_plane, ctx->tb, p2.d_symbols, p2.d_colors, p2.d_drift, p2.d_flood,
-		                   ctx->d_gmem, ctx->d_gcount, ctx->d_rs_count, ctx->d_rs_map, ctx->d_gsym, ctx->d_gcol, ctx->d_gmargin, ctx->d_gdisp, rescue_store(ctx));
+		if (salvage) {
+			// (d_gcount counts the partials too, for the cells kernel and the taps; the row is made from the full members: d_sv_full)
+			hipLaunchKernelGGL(k_rescue_tried_salvage, dim3((rs_slots + 255) / 256), dim3(256), 0, st, ctx->d_rs_count, rs_slots, ctx->d_rs_run, ctx->d_gmem, ctx->d_rp_count,
+			                   d_masks, ctx->d_sv_part, ctx->d_gcount, ctx->d_sv_full, ctx->d_gdisp);
+			hipLaunchKernelGGL(k_group_cells_salvage, dim3(GC_BLOCKS, rs_slots), dim3(256), 0, st, p2.d_plane, ctx->tb, p2.d_symbols, p2.d_colors, p2.d_drift, p2.d_flood,
+			                   ctx->d_gmem, ctx->d_gcount, ctx->d_sv_full, ctx->d_sv_part, ctx->tb_stitch_line, ctx->d_rs_count, ctx->d_rs_map, ctx->d_gsym, ctx->d_gcol,
+			                   ctx->d_gmargin, ctx->d_gdisp, rescue_store(ctx));
+		} else {
+			hipLaunchKernelGGL(k_rescue_tried, dim3((rs_slots + 255) / 256), dim3(256), 0, st, ctx->d_rs_count, rs_slots, ctx->d_rs_run, ctx->d_gmem, ctx->d_rp_count, d_masks,
+			                   ctx->d_gcount, ctx->d_gdisp);
+			hipLaunchKernelGGL(k_group_cells_rescue, dim3(GC_BLOCKS, rs_slots), dim3(256), 0, st, p2.d_plane, ctx->tb, p2.d_symbols, p2.d_colors, p2.d_drift, p2.d_flood,
+			                   ctx->d_gmem, ctx->d_gcount, ctx->d_rs_count, ctx->d_rs_map, ctx->d_gsym, ctx->d_gcol, ctx->d_gmargin, ctx->d_gdisp, rescue_store(ctx));
+		}
 		launch_live_rs(ctx, st, rs_slots, ctx->d_gsym, ctx->d_gcol, ctx->d_grs_ok, ctx->d_rs_count, ctx->d_gdisp, ctx->d_gchunks);
-		hipLaunchKernelGGL(k_group_end_rescue, dim3(rs_slots), dim3(256), 0, st, ctx->d_gsym, ctx->d_gmargin, ctx->tb, ctx->d_gmem, ctx->d_gcount, ctx->d_rs_count,
+		hipLaunchKernelGGL(k_group_end_rescue, dim3(rs_slots), dim3(256), 0, st, ctx->d_gsym, ctx->d_gmargin, ctx->tb, ctx->d_gmem, salvage ? ctx->d_sv_full.get() : ctx->d_gcount.get(), ctx->d_rs_count,
 		                   ctx->d_grs_ok, d_chunks, d_masks, ctx->d_gdisp, ctx->d_gchunks, ctx->d_gmasks, (!LEGACY && ctx->er_sym > 0) ? 1 : 0, erasure_max(ctx),
 		                   ctx->d_rs_run, d_rchunks, d_rmasks, ctx->d_rs_tap);
 	}
@@ -2428,6 +2451,7 @@ int64_t once_impl(cimbar_hip_ctx* ctx, hipStream_t st, const FrameSource& src, i
 		ctx->rs_state = (ctx->rs_on != 0 && !os) ? (rs_slots > 0 ? 2 : 1) : 0;
 		ctx->rs_slots = rs_slots;
 		ctx->rt_state = tear;
+		ctx->sv_state = salvage;
 		if (os) { os->cur ^= 1; os->carried = true; }
 	};
 	if (dev) {
@@ -2706,6 +2730,25 @@ int cimbar_hip_get_once_tear_skip(cimbar_hip_ctx* ctx, int* axis, int* line_perm
 	return 0;
 }
 
+int cimbar_hip_set_once_tear_salvage(cimbar_hip_ctx* ctx, int on, int guard_lines)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	if (guard_lines < -1 || guard_lines > RV_GUARD_MAX) { ctx->err = "set_once_tear_salvage: guard_lines must be -1 (the default, 1) or 0 .. 16"; return CIMBAR_HIP_EINVAL; }
+	if (LEGACY && on) { ctx->err = "set_once_tear_salvage: modes 4 and 8 have no once-calls to govern; repeat-capture skipping covers modes 68 / 67 / 66"; return CIMBAR_HIP_EINVAL; }
+	// (read when a plain once-call is enqueued: calls already issued keep the setting they were issued with)
+	ctx->sv_on = on ? 1 : 0;
+	ctx->sv_guard = guard_lines < 0 ? RV_GUARD_DEFAULT : guard_lines;
+	return 0;
+}
+
+int cimbar_hip_get_once_tear_salvage(cimbar_hip_ctx* ctx, int* on, int* guard_lines)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	if (on) *on = ctx->sv_on;
+	if (guard_lines) *guard_lines = ctx->sv_guard;
+	return 0;
+}
+
 int cimbar_hip_set_stitch_strips(cimbar_hip_ctx* ctx, int strips)
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;
@@ -2856,6 +2899,28 @@ int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_byte
 		HIPCHK(hipDeviceSynchronize());
 		HIPCHK(hipMemcpy(out, ctx->d_rt_tap, bytes, hipMemcpyDeviceToHost));
 		return (int64_t)bytes;
+	}
+	if (what == CIMBAR_HIP_TAP_ONCE_SALVAGE) {
+		// tear salvage in the last plain once-call: per run slot the partials of a tried run, composed from the slots' rows
+		if (ctx->rp_n <= 0 || !ctx->sv_state) { ctx->err = "tap: the last once-call was not a plain one in which tear salvage was effective (cimbar_hip_set_once_tear_salvage)"; return CIMBAR_HIP_EINVAL; }
+		const size_t m = (size_t)ctx->rp_n, S = ctx->rs_state == 2 ? (size_t)ctx->rs_slots : 0;
+		if (out_bytes < m * 8 * sizeof(int32_t)) { ctx->err = "tap: buffer too small"; return CIMBAR_HIP_EINVAL; }
+		HIPCHK(hipSetDevice(ctx->device));
+		HIPCHK(hipDeviceSynchronize());
+		int32_t* o = (int32_t*)out;
+		for (size_t r = 0; r < m; ++r) for (int h = 0; h < 2; ++h) { o[r * 8 + 4 * h] = o[r * 8 + 4 * h + 1] = -1; o[r * 8 + 4 * h + 2] = o[r * 8 + 4 * h + 3] = 0; }
+		if (S) {
+			int live = 0;
+			std::vector<int> cnt(S), run(S);
+			std::vector<int32_t> part(S * 8);
+			HIPCHK(hipMemcpy(&live, ctx->d_rs_count, sizeof(int), hipMemcpyDeviceToHost));
+			HIPCHK(hipMemcpy(cnt.data(), ctx->d_gcount, sizeof(int) * S, hipMemcpyDeviceToHost));
+			HIPCHK(hipMemcpy(run.data(), ctx->d_rs_run, sizeof(int) * S, hipMemcpyDeviceToHost));
+			HIPCHK(hipMemcpy(part.data(), ctx->d_sv_part, sizeof(int32_t) * 8 * S, hipMemcpyDeviceToHost));
+			for (size_t s = 0; s < S && s < (size_t)live; ++s)
+				if (cnt[s] > 0 && run[s] >= 0 && (size_t)run[s] < m) std::memcpy(o + (size_t)run[s] * 8, &part[s * 8], 8 * sizeof(int32_t));
+		}
+		return (int64_t)(m * 8 * sizeof(int32_t));
 	}
 	if (what == CIMBAR_HIP_TAP_ONCE_RESCUE || what == CIMBAR_HIP_TAP_ONCE_RESCUE_CELLS) {
 		// the run rescue of the last plain once-call: per run slot what it added, and the combined cells of the tried runs, in run order

@@ -28,7 +28,8 @@
 //   R8 k_repeat_end      the per-run fill
 // The host reads the length of list 1, and then of list 2, back to size the decode launches (host.hip.inc, once_impl).
 // The once-stream calls carry the last capture's run from call to call: "runs across calls" below. Opt-in, the plain once-calls decode a
-// run that stays incomplete after pass 2 once more from all its members' cells: "run rescue" at the end of this file.
+// run that stays incomplete after pass 2 once more from all its members' cells: "run rescue" below; "tear skipping" leaves torn boundary
+// captures undecoded, and "tear salvage", at the end of this file, lets the ones that are decoded vote in that rescue.
 constexpr int RP_AGREE_DEFAULT = 900, RP_RUN_DEFAULT = 4;
 constexpr int RP_ROW0 = 2, RP_ROWS = 4;                                  // pixel rows y + 2 .. y + 5 of a cell
 constexpr int RP_ROW_BYTES = IMG_W * 3, RP_ROW_VEC = RP_ROW_BYTES / 16;   // 3072 | 2208 bytes: 192 | 138 16-byte loads
@@ -495,13 +496,17 @@ constexpr int RS_PARTS = 4, RS_ARRAYS = 4;
 // R10: workgroup (slice, slot). Wavefront 0 of every workgroup walks the runs, 64 per step with a carried base, to the run of its slot (none:
 // the slot is at or above the count and the workgroup returns); then one of RS_PARTS slices of one of the four arrays is copied, 16 bytes
 // per lane where the ends allow it (carry_copy).
-// (POS: tear skipping's form, where run r's representative stands at pos[r] in pass 1's batch instead of at r; see the end of this file)
-template <bool POS>
+// (POS: tear skipping's form, where run r's representative stands at pos[r] in pass 1's batch instead of at r; SALVAGE: tear salvage's form of
+// that, where a torn capture beside the run lets it qualify and joins its member row; see the end of this file, salvage_side included)
+__device__ __forceinline__ bool salvage_side(const int32_t* __restrict__ tap, const int* __restrict__ roles, int k, int n, bool p_side, int guard, int& axis,
+                                             int& lo, int& hi);
+template <bool POS, bool SALVAGE = false>
 __device__ __forceinline__ void rescue_save_body(const uint32_t* __restrict__ plane, const uint8_t* __restrict__ symbols, const uint8_t* __restrict__ colors,
                                                  const int8_t* __restrict__ drift, const uint32_t* __restrict__ flood_flag,
                                                  const uint32_t* __restrict__ rep_masks, const int* __restrict__ rmem, const int* __restrict__ rcount,
                                                  int nruns, CarryStore cs, int* __restrict__ slot_run, int* __restrict__ smem, int* __restrict__ map,
-                                                 int* __restrict__ nslots, const int* __restrict__ pos)
+                                                 int* __restrict__ nslots, const int* __restrict__ pos, const int* __restrict__ roles = nullptr,
+                                                 const int32_t* __restrict__ tap = nullptr, int n = 0, int guard = 0, int32_t* __restrict__ parts = nullptr)
 {
 	const int slot = blockIdx.y;
 	__shared__ int s_run;
@@ -511,7 +516,17 @@ __device__ __forceinline__ void rescue_save_body(const uint32_t* __restrict__ pl
 		int base = 0, mine = -1;
 		for (int r0 = 0; r0 < nruns; r0 += 64) {
 			const int r = r0 + lane;
-			const bool q = r < nruns && rcount[r] >= 2 && (rep_masks[POS ? pos[r] : r] & RP_FULL) != RP_FULL;
+			bool q;
+			if constexpr (SALVAGE) {
+				// (a run slot at or above the run count has no members and no pos; a candidate's run has pos -1 and is never tried)
+				const int cnt = r < nruns ? rcount[r] : 0, at = cnt >= 1 ? pos[r] : -1;
+				q = at >= 0 && (rep_masks[at] & RP_FULL) != RP_FULL;
+				if (q && cnt < 2) {
+					int ax, lo, hi;
+					const int f = rmem[(size_t)r * GMAX];
+					q = salvage_side(tap, roles, f - 1, n, false, guard, ax, lo, hi) || salvage_side(tap, roles, f + 1, n, true, guard, ax, lo, hi);
+				}
+			} else q = r < nruns && rcount[r] >= 2 && (rep_masks[POS ? pos[r] : r] & RP_FULL) != RP_FULL;
 			const unsigned long long qb = __ballot(q);
 			if (q && base + (int)__popcll(qb & below) == slot) mine = r;
 			base += (int)__popcll(qb);
@@ -527,7 +542,28 @@ __device__ __forceinline__ void rescue_save_body(const uint32_t* __restrict__ pl
 	if (r < 0) return;                                                   // (uniform over the workgroup)
 	if (blockIdx.x == 0) {
 		const int cnt = rcount[r];
-		if (threadIdx.x < GMAX) smem[(size_t)slot * GMAX + threadIdx.x] = (int)threadIdx.x < cnt ? rmem[(size_t)r * GMAX + threadIdx.x] : 0;
+		if constexpr (SALVAGE) {
+			// the member row: the full members, then the preceding partial, then the following one, each only while the row has room
+			if (threadIdx.x < GMAX) {
+				const int t = threadIdx.x, f = rmem[(size_t)r * GMAX], e = rmem[(size_t)r * GMAX + cnt - 1];
+				int pa[2], pl[2], ph[2];
+				const bool hp = cnt < GMAX && salvage_side(tap, roles, f - 1, n, false, guard, pa[0], pl[0], ph[0]);
+				const bool hf = cnt + (hp ? 1 : 0) < GMAX && salvage_side(tap, roles, e + 1, n, true, guard, pa[1], pl[1], ph[1]);
+				int k = 0;
+				if (t < cnt) k = rmem[(size_t)r * GMAX + t];
+				else if (hp && t == cnt) k = f - 1;
+				else if (hf && t == cnt + (hp ? 1 : 0)) k = e + 1;
+				smem[(size_t)slot * GMAX + t] = k;
+				if (t < 2) {
+					int32_t* row = parts + (size_t)slot * 8 + 4 * t;
+					const bool have = t == 0 ? hp : hf;
+					row[0] = have ? (t == 0 ? f - 1 : e + 1) : -1;
+					row[1] = have ? pa[t] : -1;
+					row[2] = have ? pl[t] : 0;
+					row[3] = have ? ph[t] : 0;
+				}
+			}
+		} else if (threadIdx.x < GMAX) smem[(size_t)slot * GMAX + threadIdx.x] = (int)threadIdx.x < cnt ? rmem[(size_t)r * GMAX + threadIdx.x] : 0;
 		if (threadIdx.x == 0) {
 			slot_run[slot] = r;
 			map[repeat_rep(rmem, rcount, r)] = ~slot;
@@ -770,4 +806,70 @@ __global__ __launch_bounds__(256) void k_rescue_save_tear(const uint32_t* __rest
                                                           int* __restrict__ nslots, const int* __restrict__ pos)
 {
 	rescue_save_body<true>(plane, symbols, colors, drift, flood_flag, rep_masks, rmem, rcount, nruns, cs, slot_run, smem, map, nslots, pos);
+}
+
+// ------------------------------------------------------------------------------------------------ tear salvage (the plain once-calls, opt-in)
+// cimbar_hip_set_once_tear_salvage, effective with the run rescue and tear skipping both on. A torn candidate beside an incomplete run is
+// decoded whole in pass 2 and delivers next to nothing, yet on every line on that run's side of the tear its cells are cells of the run's
+// frame. With the setting effective such a candidate joins the rescue's group decode of the run as a PARTIAL member:
+//   sides      candidate k, record {w, s, first, last}, axis = w >> 1, o = w & 1, L lines, guard g: low = [0, s - g), high = [s + g, L); its
+//              P side (towards capture k - 1) is low when o = 0, high when o = 1, its N side the other. An empty side gives no partial.
+//   partials   run r (no candidate's run), members f .. e: the following partial is capture e + 1 with its P side, the preceding partial
+//              capture f - 1 with its N side, each if that capture is a candidate with role FALLBACK
+//   qualifies  the representative's mask is not full and the run has two members or a partial: at most min(|list 1|, 2 |list 2|) runs, as
+//              each has its representative in list 1 and a member or an adjacent candidate in list 2, which serves two runs at most
+//   order      the full members, the preceding partial, the following partial; a partial joins only while the row has fewer than GMAX members
+//   tried      a qualifying run whose full members' masks, after pass 2, are together still not full
+//   R10s k_rescue_save_salvage   R10t with that rule; the slot's row of `part` = {kp, axis_p, lo_p, hi_p, kf, axis_f, lo_f, hi_f}
+//   R11s k_rescue_tried_salvage  gcount[slot] = the full members plus the partials of a tried run, gfull[slot] = the full members alone
+//   G3p k_group_cells_salvage (combine.hip.inc) over gcount; k_rs LIVE and G4r k_group_end_rescue as they are, G4r over gfull: only the full
+//   members' chunks and masks enter the row
+constexpr int RV_GUARD_DEFAULT = 1, RV_GUARD_MAX = 16;
+
+// a torn candidate k's side towards capture k - 1 (p_side) or towards k + 1 as a partial: {axis, lo, hi}. false: k is outside the call, is no
+// candidate that pass 2 decodes, or the side is empty. tap: tear skipping's records; roles: as k_repeat_lists2_tear left them.
+__device__ __forceinline__ bool salvage_side(const int32_t* __restrict__ tap, const int* __restrict__ roles, int k, int n, bool p_side, int guard, int& axis,
+                                             int& lo, int& hi)
+{
+	axis = 0; lo = 0; hi = 0;
+	if (k < 0 || k >= n || roles[k] != RP_ROLE_FALLBACK) return false;
+	const int w = tap[(size_t)k * 4];
+	if (w < 0) return false;                                             // (a fallback that is no candidate: a member of some run)
+	const int s = tap[(size_t)k * 4 + 1], o = w & 1;
+	axis = w >> 1;
+	const bool low = p_side == (o == 0);
+	lo = low ? 0 : s + guard;
+	hi = low ? s - guard : stitch_lines(axis);
+	return lo < hi;
+}
+
+__global__ __launch_bounds__(256) void k_rescue_save_salvage(const uint32_t* __restrict__ plane, const uint8_t* __restrict__ symbols, const uint8_t* __restrict__ colors,
+                                                             const int8_t* __restrict__ drift, const uint32_t* __restrict__ flood_flag,
+                                                             const uint32_t* __restrict__ rep_masks, const int* __restrict__ rmem, const int* __restrict__ rcount,
+                                                             int nruns, CarryStore cs, int* __restrict__ slot_run, int* __restrict__ smem, int* __restrict__ map,
+                                                             int* __restrict__ nslots, const int* __restrict__ pos, const int* __restrict__ roles,
+                                                             const int32_t* __restrict__ tap, int n, int guard, int32_t* __restrict__ part)
+{
+	rescue_save_body<true, true>(plane, symbols, colors, drift, flood_flag, rep_masks, rmem, rcount, nruns, cs, slot_run, smem, map, nslots, pos, roles, tap, n, guard,
+	                             part);
+}
+
+// R11s: R11 over the full members, with the second count
+__global__ __launch_bounds__(256) void k_rescue_tried_salvage(const int* __restrict__ nslots, int slots, const int* __restrict__ slot_run, const int* __restrict__ smem,
+                                                              const int* __restrict__ rcount, const uint32_t* __restrict__ masks, const int32_t* __restrict__ part,
+                                                              int* __restrict__ gcount, int* __restrict__ gfull, uint32_t* __restrict__ gdisp)
+{
+	const int s = blockIdx.x * 256 + threadIdx.x;
+	if (s >= slots) return;
+	int m = 0, all_m = 0;
+	if (s < *nslots) {
+		const int cnt = rcount[slot_run[s]];
+		uint32_t all = 0;
+		for (int j = 0; j < cnt; ++j) all |= masks[smem[(size_t)s * GMAX + j]];
+		m = (all & RP_FULL) != RP_FULL ? cnt : 0;
+		all_m = m ? m + (part[(size_t)s * 8] >= 0 ? 1 : 0) + (part[(size_t)s * 8 + 4] >= 0 ? 1 : 0) : 0;
+	}
+	gcount[s] = all_m;
+	gfull[s] = m;
+	gdisp[s] = 0u;
 }

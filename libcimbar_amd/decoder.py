@@ -41,6 +41,7 @@ TAP_ONCE_RESCUE, TAP_ONCE_RESCUE_CELLS = 31, 32   # the run rescue of the last p
 ONCE_UNUSABLE, ONCE_SKIPPED, ONCE_REPRESENTATIVE, ONCE_FALLBACK = -1, 0, 1, 2
 ONCE_TORN = 3           # ... with set_once_tear_skip on: a torn boundary capture that was left undecoded
 TAP_ONCE_TEAR = 33      # tear skipping in the last plain once-call (set_once_tear_skip): tap_once_tear
+TAP_ONCE_SALVAGE = 35   # tear salvage in the last plain once-call (set_once_tear_salvage): tap_once_salvage
 TAP_FLOOD_LAUNCH = 34   # the exact-replay launches the last batch made (host bookkeeping, no device wait): tap_flood_launches
 FLOOD_LAUNCH_FIELDS = ("instance", "grid", "frames", "first_frame", "area0", "counter", "flags")
 FLOOD_LAUNCH_MAX = 16
@@ -77,6 +78,7 @@ EXPORTS = (
     "cimbar_hip_decode_batch_once_stream", "cimbar_hip_scan_extract_decode_batch_once_stream_fmt", "cimbar_hip_once_stream_reset",
     "cimbar_hip_set_once_rescue", "cimbar_hip_get_once_rescue",
     "cimbar_hip_set_once_tear_skip", "cimbar_hip_get_once_tear_skip",
+    "cimbar_hip_set_once_tear_salvage", "cimbar_hip_get_once_tear_salvage",
 )
 # cimbar_hip_deliver_chunks' flags
 DELIVER_DEDUP, DELIVER_REMEMBER, DELIVER_DROP_EMPTY = 1, 2, 4
@@ -281,6 +283,11 @@ def load_library(path=None):
         lib.cimbar_hip_set_once_tear_skip.restype = i32
         lib.cimbar_hip_get_once_tear_skip.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32)]
         lib.cimbar_hip_get_once_tear_skip.restype = i32
+    if hasattr(lib, "cimbar_hip_set_once_tear_salvage"):   # (the same: tools/once_salvage_bench.py --parent-lib)
+        lib.cimbar_hip_set_once_tear_salvage.argtypes = [vp, i32, i32]
+        lib.cimbar_hip_set_once_tear_salvage.restype = i32
+        lib.cimbar_hip_get_once_tear_salvage.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]
+        lib.cimbar_hip_get_once_tear_salvage.restype = i32
     lib.cimbar_hip_mode_bufsize.argtypes = [i32]
     lib.cimbar_hip_mode_bufsize.restype = i32
     lib.cimbar_hip_ctx_bufsize.argtypes = [vp]
@@ -1172,6 +1179,18 @@ class HipDecoder:
         self._check(self._lib.cimbar_hip_get_once_tear_skip(self._ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "cimbar_hip_get_once_tear_skip")
         return a.value, b.value, c.value
 
+    def set_once_tear_salvage(self, on=True, guard_lines=-1):
+        """cimbar_hip_set_once_tear_salvage: with set_once_rescue and set_once_tear_skip both on, a torn capture decoded in pass 2 joins the
+        rescue's vote of its neighbour runs on its good side, guard_lines lines away from the tear (-1: 1; 0 .. 16). Off after create; the
+        once-stream calls ignore it; modes 4 / 8 refuse on."""
+        self._check(self._lib.cimbar_hip_set_once_tear_salvage(self._ctx, int(bool(on)), int(guard_lines)), "cimbar_hip_set_once_tear_salvage")
+
+    def get_once_tear_salvage(self):
+        """(on, guard_lines) as resolved"""
+        a, b = ctypes.c_int(0), ctypes.c_int(0)
+        self._check(self._lib.cimbar_hip_get_once_tear_salvage(self._ctx, ctypes.byref(a), ctypes.byref(b)), "cimbar_hip_get_once_tear_salvage")
+        return bool(a.value), b.value
+
     def set_stream_colour_vote(self, on=True):
         """cimbar_hip_set_stream_colour_vote: the colour vote (and, with set_colour_erasure_decode on, the group colour retry) in the stream
         calls; set_group_colour_vote governs the plain combined calls only. A stream samples it in its first call after create /
@@ -1322,6 +1341,13 @@ class HipDecoder:
         {-1, -1, 0, 0} for a capture that is no candidate"""
         out = np.zeros((n, 4), dtype=np.int32)
         self._check(self._lib.cimbar_hip_tap(self._ctx, TAP_ONCE_TEAR, out.ctypes.data, out.nbytes), "cimbar_hip_tap")
+        return out
+
+    def tap_once_salvage(self, n):
+        """TAP_ONCE_SALVAGE of the last plain once-call of n captures in which set_once_tear_salvage was effective: (n, 8) int32 per run slot
+        {kp, axis_p, lo_p, hi_p, kf, axis_f, lo_f, hi_f}; {-1, -1, 0, 0} for a partial the run lacks and for a run that was not tried"""
+        out = np.zeros((n, 8), dtype=np.int32)
+        self._check(self._lib.cimbar_hip_tap(self._ctx, TAP_ONCE_SALVAGE, out.ctypes.data, out.nbytes), "cimbar_hip_tap")
         return out
 
     def tap_flood_launches(self):
