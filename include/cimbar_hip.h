@@ -374,8 +374,8 @@ int cimbar_hip_get_stream_colour_vote(cimbar_hip_ctx* ctx, int* on);
  *              the later capture's low lines and the earlier capture's high lines show the shared frame. Direction 1 is the reverse, for a
  *              sensor read the other way round. Symbol and colour are taken from the chosen capture as it decided them.
  *   decode     both directions' cells go through the same Reed-Solomon decode and chunk bookkeeping as one frame (modes 4 / 8: the coupled
- *              stream). No colour-correction matrix is derived, read or carried; nothing is voted, retried (the erasure settings do not
- *              reach this decode) or filled in from the two captures, which show other frames.
+ *              stream). No colour-correction matrix is derived, read or carried; nothing is voted, retried (the erasure settings reach
+ *              this decode only through cimbar_hip_set_stitch_erasure, below) or filled in from the two captures, which show other frames.
  *   schunks / smasks  2 (n - 1) slots of cimbar_hip_ctx_bufsize bytes / one mask word; pair k, direction d is slot 2k + d. smask is the
  *              stitched decode's own mask, chunks outside it are zero, and so is everything of a pair that is no candidate. The wrong
  *              direction yields chunks of a neighbouring frame or nothing: every chunk in any mask is a genuine chunk, and a sink
@@ -405,7 +405,7 @@ int64_t cimbar_hip_scan_extract_decode_batch_stitched_fmt(cimbar_hip_ctx* ctx, c
  *   row 0 without a usable carry  (the first call after create or reset; capture path: the carried capture's extraction failed) is no
  *              candidate: tears {-1, -1, -1, 0}, both slots zero, both masks 0
  *   the rule   otherwise the one above, word for word: eq, flag, band, candidate, split, both directions, the decode and what smask means. No
- *              matrix is derived, read or carried; no vote, no erasure retry
+ *              matrix is derived, read or carried; no vote, no erasure retry (cimbar_hip_set_stitch_erasure does not reach these calls)
  *   chunks / masks / status and the colour-correction carry are the plain call's for the same input
  *   axis, min_agree_permille, min_band, should_preprocess, color_correction, n and the capture size may change from call to call: row 0 is
  *              judged with the parameters of the call that reports it. Only the carry is state
@@ -449,6 +449,34 @@ int cimbar_hip_stitch_stream_reset(cimbar_hip_ctx* ctx);
  * every mode accepts 1..8. get: writes the setting to *strips and returns 0. For a hand-held receiver 4 to 8 is the advice. */
 int cimbar_hip_set_stitch_strips(cimbar_hip_ctx* ctx, int strips);
 int cimbar_hip_get_stitch_strips(cimbar_hip_ctx* ctx, int* strips);
+
+/* Erasure retry in the stitched decode (off after cimbar_hip_create: everything above, byte for byte; nothing more is launched, allocated or
+ * written). A stitched frame is built from the worse-exposed edges of two captures, so a block that fails errors-only decoding by a few bytes
+ * is its usual failure. With the setting on, slot 2k + d of cimbar_hip_decode_batch_stitched / _scan_extract_decode_batch_stitched_fmt (host or
+ * device outputs, either axis, strips 1..8) is retried after the decode above:
+ *   source     cell i of the slot came from capture src(i), k or k + 1: the selection of "split" above (with strips, of "cells")
+ *   d_sym(i)   the symbol confidence of cimbar_hip_set_erasure_decode, evaluated in capture src(i): the popcount of the 8x8 hash of that
+ *              capture's bit plane at the cell's final position XOR the tile hash of the stitched symbol; the final position is the grid
+ *              position plus that capture's drift where that capture took a flood pass, the grid position otherwise
+ *   symbol retry  with cimbar_hip_set_erasure_decode on (its sym_distance and max_erasures), for a live slot whose smask lacks symbol chunks:
+ *              the blocks of the missing symbol chunks, a byte's score = max over its two cells of d_sym - sym_distance + 1
+ *   margin(i)  the colour confidence of cimbar_hip_set_colour_erasure_decode in capture src(i): second-smallest minus smallest squared
+ *              distance of the classifier, on that capture's cell mean where it took no flood pass, on the 6x6 mean at the drifted position
+ *              where it did, under the matrix that capture's colours were decided with (active flag included)
+ *   colour retry  with cimbar_hip_set_colour_erasure_decode on (its colour_margin and max_erasures), behind the symbol retry, for a live slot
+ *              whose smask lacks colour chunks: score = colour_margin - margin, max over a byte's four cells
+ *   unchanged  selection (the max_erasures highest scores, ties to the lower byte), acceptance (the codeword check, nothing located in the
+ *              padding, 2 errors <= parity - erasures - 6), a failed block with nothing flagged is not retried, a block errors-only decoding
+ *              accepted is decoded again with no erasure; a chunk whose blocks are all accepted joins smask with its bytes, the slots of
+ *              chunks still missing stay zero
+ *   never touched  chunks already in smask, the tear records, the line counts, the stitched cells (CIMBAR_HIP_TAP_STITCH_CELLS), the block
+ *              flags, the per-capture chunks / masks / status and the colour-correction carry
+ * smask with the setting on is always a superset of smask with it off. A slot that is not live, or whose chunks are complete, is left at its
+ * first test. With neither erasure setting on nothing runs. The stitched-stream calls behave with the setting on exactly as with it off: their
+ * carry holds cells, not bit planes or cell means (carrying confidences is a later change). The stitched calls read the setting when they are
+ * called. Modes 4 and 8 (one coupled stream): on != 0 is CIMBAR_HIP_EINVAL. get: writes the setting to *on and returns 0. */
+int cimbar_hip_set_stitch_erasure(cimbar_hip_ctx* ctx, int on);
+int cimbar_hip_get_stitch_erasure(cimbar_hip_ctx* ctx, int* on);
 
 /* ---- repeat-capture skipping: one decode per displayed frame ------------------------------------------------------------------------------
  * A camera films the display faster than it changes, so every frame arrives as a run of two to four near-identical captures, and the calls
@@ -1077,9 +1105,15 @@ enum {
 	                                       1 = the verify replay (CIMBAR_HIP_FLOOD_VERIFY), 2 = the relaxed flood's fallback replay}; returns the bytes written */
 	/* tear salvage in the last once-call (cimbar_hip_set_once_tear_salvage; n = its captures). CIMBAR_HIP_EINVAL when the setting was not
 	 * effective in that call, or it was a once-stream call */
-	CIMBAR_HIP_TAP_ONCE_SALVAGE = 35    /* n x 8 int32         : per run slot {kp, axis_p, lo_p, hi_p, kf, axis_f, lo_f, hi_f}, the preceding and the following
+	CIMBAR_HIP_TAP_ONCE_SALVAGE = 35,   /* n x 8 int32         : per run slot {kp, axis_p, lo_p, hi_p, kf, axis_f, lo_f, hi_f}, the preceding and the following
 	                                       partial of the run with their line ranges; {-1, -1, 0, 0} for a partial the run does not have, and for
 	                                       both partials of a run that was not tried */
+	/* the erasure retry of the last batch's stitched decode (cimbar_hip_set_stitch_erasure). CIMBAR_HIP_EINVAL when that batch was not a plain
+	 * stitched call that ran the respective retry (the setting off, its erasure setting off, a stitched-stream call, n == 1) */
+	CIMBAR_HIP_TAP_STITCH_DISTANCE = 36,      /* 2 (n - 1) * cells u8 : d_sym of every cell of slot 2k + d, by linear cell index; 0xFF for every
+	                                             cell of a slot the symbol retry skipped (not live, or no symbol chunk missing) */
+	CIMBAR_HIP_TAP_STITCH_COLOUR_MARGIN = 37  /* 2 (n - 1) * cells u32: margin of every cell of the slot; 0xFFFFFFFF for a slot the colour retry
+	                                             skipped */
 };
 int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_bytes);
 

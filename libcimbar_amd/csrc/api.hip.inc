@@ -402,6 +402,18 @@ int cimbar_hip_get_stitch_strips(cimbar_hip_ctx* ctx, int* strips)
 	return CIMBAR_FWD(cimbar_hip_get_stitch_strips, strips);
 }
 
+int cimbar_hip_set_stitch_erasure(cimbar_hip_ctx* ctx, int on)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return CIMBAR_FWD(cimbar_hip_set_stitch_erasure, on);
+}
+
+int cimbar_hip_get_stitch_erasure(cimbar_hip_ctx* ctx, int* on)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	return CIMBAR_FWD(cimbar_hip_get_stitch_erasure, on);
+}
+
 int cimbar_hip_combine_stream_reset(cimbar_hip_ctx* ctx)
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;

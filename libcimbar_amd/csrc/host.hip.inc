@@ -79,6 +79,10 @@ struct cimbar_hip_ctx {
 	int stitch_S = 1;                           // the strips of the last stitched batch (> 1: the strip taps describe it)
 	DevBuf<int32_t> d_sstrips; DevBuf<uint16_t> d_sstrip_lines;   // [rows][S][4], [rows][S][L]: allocated by the first stitched call with strips > 1
 	DevBuf<uint8_t> d_schunks; DevBuf<uint32_t> d_smasks;   // staging for host-memory stitch outputs
+	// the stitched decode's erasure retry (cimbar_hip_set_stitch_erasure, stitch.hip.inc S3 / S4): nothing of it exists until a plain stitched call runs with it on
+	int stitch_er = 0;                          // the setting
+	int stitch_er_ran = 0;                      // the last stitched batch: bit 0 = S3 ran, bit 1 = S4 ran (CIMBAR_HIP_TAP_STITCH_DISTANCE / _COLOUR_MARGIN describe it)
+	DevBuf<uint8_t> d_sdist; DevBuf<uint32_t> d_smargin, d_sworked;   // [2 rows][NCELLS] each; [2][2 rows] "worked on" words, S3's then S4's
 	// repeat-capture skipping (cimbar_hip_decode_batch_once / _scan_extract_decode_batch_once_fmt, repeat.hip.inc): per capture, grown on demand;
 	// the gathered frames and their results are sized by the longer of a call's two lists
 	int rp_n = 0;                               // the last once-call had that many captures (> 0: the repeat taps describe it)
@@ -1289,6 +1293,7 @@ struct StitchArgs {
 	std::vector<int32_t> h_tears;                         // host outputs: where the tear records land when the caller wants none
 	bool stream = false;                                  // a stream call: n rows, row 0 against the carried capture; else n - 1
 	int strips = 1;                                       // cimbar_hip_set_stitch_strips as the call found it (check_stitch)
+	int er_sym = 0, er_col = 0;                           // cimbar_hip_set_stitch_erasure as the call found it: the armed retries' thresholds (0: not run)
 	int rows(int n) const { return stream ? n : n - 1; }
 };
 
@@ -1301,12 +1306,19 @@ int check_stitch(cimbar_hip_ctx* ctx, const char* who, int n, StitchArgs& sa)
 	if (sa.min_agree <= 0) sa.min_agree = STITCH_AGREE_DEFAULT;
 	if (sa.min_band <= 0) sa.min_band = STITCH_BAND_DEFAULT;
 	sa.strips = ctx->stitch_strips;
+	// (the stream calls carry cells, not planes or means: the retry does not reach them)
+	const bool er = !LEGACY && ctx->stitch_er && !sa.stream;
+	sa.er_sym = er ? ctx->er_sym : 0;
+	sa.er_col = er ? ctx->ec_margin : 0;
 	return 0;
 }
 
-int ensure_stitch_capacity(cimbar_hip_ctx* ctx, int rows, int strips)
+int ensure_stitch_capacity(cimbar_hip_ctx* ctx, int rows, int strips, bool er_sym, bool er_col)
 {
 	const size_t P = (size_t)rows, S = 2 * P;
+	if (er_sym) HIPCHK(ctx->d_sdist.reserve(S * NCELLS));
+	if (er_col) HIPCHK(ctx->d_smargin.reserve(S * NCELLS));
+	if (er_sym || er_col) HIPCHK(ctx->d_sworked.reserve(2 * S));
 	if (strips > 1) {
 		HIPCHK(ctx->d_sstrips.reserve(P * STITCH_SMAX * 4));
 		HIPCHK(ctx->d_sstrip_lines.reserve(P * STITCH_SMAX * STITCH_LMAX));
@@ -1341,10 +1353,10 @@ int begin_stitch_stream(cimbar_hip_ctx* ctx, hipStream_t st)
 // a batch's per-capture decode on the same stream (rows > 0: n - 1 pairs, a stream call n rows). Reads that decode's symbols and colours; writes the
 // caller's buffers (device outputs) or the context's staging, whose copies back to the host are enqueued here as well. d_status as for enqueue_combine.
 // A stream call (after begin_stitch_stream): S1 reads the carried capture from one slot and leaves its last capture in the other.
-int enqueue_stitch(cimbar_hip_ctx* ctx, hipStream_t st, int n, const int* d_status, int stride, StitchArgs& sa, int out_mem)
+int enqueue_stitch(cimbar_hip_ctx* ctx, hipStream_t st, int n, const uint8_t* d_frames, const int* d_status, int stride, StitchArgs& sa, int out_mem)
 {
 	const int pairs = sa.rows(n), slots = 2 * pairs;
-	if (int r = ensure_stitch_capacity(ctx, pairs, sa.strips)) return r;
+	if (int r = ensure_stitch_capacity(ctx, pairs, sa.strips, sa.er_sym > 0, sa.er_col > 0)) return r;
 	cimbar_hip_ctx::ScratchSet& cur = ctx->cur();
 	const bool dev = out_mem == CIMBAR_HIP_MEM_DEVICE;
 	uint8_t* d_out = dev ? sa.schunks : ctx->d_schunks.get();
@@ -1372,6 +1384,16 @@ int enqueue_stitch(cimbar_hip_ctx* ctx, hipStream_t st, int n, const int* d_stat
 		                   sa.min_agree, sa.min_band, ctx->d_stears, ctx->d_slines, ctx->d_slive, ctx->d_sslots, ctx->d_ssym, ctx->d_scol);
 	launch_live_rs(ctx, st, slots, ctx->d_ssym, ctx->d_scol, ctx->d_srs_ok, ctx->d_sslots, ctx->d_slive, d_out);
 	hipLaunchKernelGGL(k_stitch_end, dim3(slots), dim3(256), 0, st, ctx->d_slive, ctx->d_srs_ok, d_out, d_om);
+	// opt-in erasure retry of the chunks a slot's mask lacks (cimbar_hip_set_stitch_erasure): the symbol retry, then the colour retry, each only
+	// where its own erasure setting is on; they read the two captures' intermediates of the per-capture decode and write the slot's chunks and mask
+	if (sa.er_sym > 0)
+		hipLaunchKernelGGL(k_stitch_erasure, dim3(slots), dim3(256), 0, st, cur.d_plane, ctx->tb, cur.d_drift, cur.d_flood, ctx->tb_stitch_line, sa.axis,
+		                   sa.strips, ctx->d_stears, ctx->d_sstrips, ctx->d_slive, ctx->d_ssym, ctx->d_srs_ok, d_out, d_om, ctx->d_sdist, ctx->d_sworked,
+		                   sa.er_sym, erasure_max(ctx));
+	if (sa.er_col > 0)
+		hipLaunchKernelGGL(k_stitch_colour_erasure, dim3(slots), dim3(256), 0, st, d_frames, cur.d_cellmean, ctx->tb, cur.d_drift, cur.d_flood,
+		                   cur.d_ccm_used, ctx->tb_stitch_line, sa.axis, sa.strips, ctx->d_stears, ctx->d_sstrips, ctx->d_slive, ctx->d_scol, ctx->d_srs_ok,
+		                   d_out, d_om, ctx->d_smargin, ctx->d_sworked + slots, sa.er_col, colour_erasure_max(ctx));
 	HIPCHK(hipGetLastError());
 	if (dev) {
 		if (sa.tears) HIPCHK(hipMemcpyAsync(sa.tears, ctx->d_stears, sizeof(int32_t) * 4 * (size_t)pairs, hipMemcpyDeviceToDevice, st));
@@ -1395,6 +1417,7 @@ int64_t finish_stitched(cimbar_hip_ctx* ctx, hipStream_t st, int n, uint8_t* chu
 	ctx->stitch_rows = sa.rows(n);
 	ctx->stitch_axis = sa.axis;
 	ctx->stitch_S = sa.strips;
+	ctx->stitch_er_ran = sa.rows(n) > 0 ? (sa.er_sym > 0 ? 1 : 0) | (sa.er_col > 0 ? 2 : 0) : 0;
 	if (sa.stream) {
 		HIPCHK(hipEventRecord(ctx->sstream->ev_last, st));
 		ctx->sstream->used = true;
@@ -2084,7 +2107,7 @@ int64_t decode_impl(cimbar_hip_ctx* ctx, CaptureIn* cap, const uint8_t* img, int
 		return finish_stream(ctx, st, n, chunks, masks, d_chunks, d_masks, out_mem, *cb);
 	}
 	if (cb) if (int r = enqueue_combine(ctx, st, n, fs.d_frames, d_chunks, d_masks, fs.d_status, fs.stride, *cb, out_mem)) return r;
-	if (sa && sa->rows(n) > 0) if (int r = enqueue_stitch(ctx, st, n, fs.d_status, fs.stride, *sa, out_mem)) return r;
+	if (sa && sa->rows(n) > 0) if (int r = enqueue_stitch(ctx, st, n, fs.d_frames, fs.d_status, fs.stride, *sa, out_mem)) return r;
 	const int64_t rc = sa ? finish_stitched(ctx, st, n, chunks, masks, d_chunks, d_masks, out_mem, *sa) : finish_batch(ctx, st, n, chunks, masks, d_chunks, d_masks, out_mem, cb);
 	// (host outputs of a plain or stitched call: it has synchronised, so the stage timers of its chain can be read)
 	if (rc >= 0 && !cb && out_mem == CIMBAR_HIP_MEM_HOST && ctx->timing) if (int r = read_stage_times(ctx)) return r;
@@ -2765,6 +2788,22 @@ int cimbar_hip_get_stitch_strips(cimbar_hip_ctx* ctx, int* strips)
 	return 0;
 }
 
+int cimbar_hip_set_stitch_erasure(cimbar_hip_ctx* ctx, int on)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	if (LEGACY && on) { ctx->err = "set_stitch_erasure: modes 4 and 8 carry one coupled stream; the erasure retries cover modes 68 / 67 / 66"; return CIMBAR_HIP_EINVAL; }
+	// (read when a stitched call is enqueued: calls already issued keep the setting they were issued with)
+	ctx->stitch_er = on ? 1 : 0;
+	return 0;
+}
+
+int cimbar_hip_get_stitch_erasure(cimbar_hip_ctx* ctx, int* on)
+{
+	if (!ctx) return CIMBAR_HIP_EINVAL;
+	if (on) *on = ctx->stitch_er;
+	return 0;
+}
+
 int cimbar_hip_set_stream_colour_vote(cimbar_hip_ctx* ctx, int on)
 {
 	if (!ctx) return CIMBAR_HIP_EINVAL;
@@ -3087,6 +3126,20 @@ int64_t cimbar_hip_tap(cimbar_hip_ctx* ctx, int what, void* out, size_t out_byte
 			HIPCHK(hipMemcpy(col.data(), ctx->d_scol, bytes, hipMemcpyDeviceToHost));
 			HIPCHK(hipMemcpy(lv.data(), ctx->d_slive, sizeof(uint32_t) * slots, hipMemcpyDeviceToHost));
 			for (size_t k = 0; k < bytes; ++k) ((uint8_t*)out)[k] = lv[k / NCELLS] ? (uint8_t)((col[k] << 4) | (((uint8_t*)out)[k] & 15u)) : (uint8_t)0;
+			return (int64_t)bytes;
+		}
+		case CIMBAR_HIP_TAP_STITCH_DISTANCE:
+		case CIMBAR_HIP_TAP_STITCH_COLOUR_MARGIN: {
+			const bool dist = what == CIMBAR_HIP_TAP_STITCH_DISTANCE;
+			if (ctx->stitch_n <= 0 || !(ctx->stitch_er_ran & (dist ? 1 : 2))) { ctx->err = "tap: the last batch was not a plain stitched one that ran this retry (cimbar_hip_set_stitch_erasure with the erasure setting on)"; return CIMBAR_HIP_EINVAL; }
+			const size_t slots = 2 * (size_t)ctx->stitch_rows, row = (size_t)NCELLS * (dist ? 1 : sizeof(uint32_t));
+			bytes = slots * row;
+			if (out_bytes < bytes) { ctx->err = "tap: buffer too small"; return CIMBAR_HIP_EINVAL; }
+			std::vector<uint32_t> worked(slots);
+			HIPCHK(hipMemcpy(out, dist ? (const void*)ctx->d_sdist.get() : (const void*)ctx->d_smargin.get(), bytes, hipMemcpyDeviceToHost));
+			HIPCHK(hipMemcpy(worked.data(), ctx->d_sworked + (dist ? 0 : slots), sizeof(uint32_t) * slots, hipMemcpyDeviceToHost));
+			// slots that are not live or lacked nothing: the retry returned at once and computed no confidence
+			for (size_t g = 0; g < slots; ++g) if (!worked[g]) std::memset((uint8_t*)out + g * row, 0xFF, row);
 			return (int64_t)bytes;
 		}
 		case CIMBAR_HIP_TAP_STITCH_STRIPS:

@@ -16,7 +16,8 @@
 //              reverse, for a sensor read the other way round. Symbol and colour are the chosen capture's own decisions.
 //   decode     slot 2k + d holds pair k, direction d. A candidate's two cell sets go through k_rs<.., LIVE> and the aligned_stream
 //              bookkeeping of one frame (group_end_body's cmask; modes 4 / 8: the coupled stream). No colour-correction matrix is
-//              derived, read or carried; nothing is filled in from the members (they show other frames); no vote, no erasure retry.
+//              derived, read or carried; nothing is filled in from the members (they show other frames); no vote; an erasure retry only with
+//              cimbar_hip_set_stitch_erasure on (S3 / S4 at the end of this file).
 //              smask = that decode's own mask; slots of chunks outside it are zero.
 // The wrong direction yields chunks of a neighbouring frame or nothing: every chunk in a mask is a genuine chunk, and a sink dedups.
 //   S1 k_stitch_pairs  one workgroup per pair: cnt, the tear record {a, b, s, f}, the two slots' live flags and, for a candidate, both
@@ -434,4 +435,135 @@ __global__ __launch_bounds__(256) void k_stitch_end(const uint32_t* __restrict__
 		for (int k = threadIdx.x; k < CHUNK; k += 256) dst[k] = 0;
 	}
 	if (threadIdx.x == 0) smasks[g] = mask;
+}
+
+// ------------------------------------------------------------------------------------------------ erasure retry (cimbar_hip_set_stitch_erasure)
+// Opt-in, plain stitched calls only (the stream calls carry cells, not planes or means), modes 68 / 67 / 66, behind S2 on the same stream:
+// the retries of erasure.hip.inc over a slot's stitched cells, each cell's confidence taken in the capture the cell came from.
+//   src(i)     the capture S1 took cell i of slot 2k + d from: k + 1 if (line(i) < s) != (d == 1), else k; s = the tear record's split, with
+//              strips above 1 the resolved split s_j of strip(i) (read back from d_stears / d_sstrips: S1's own decision, not a second one)
+//   d_sym(i)   k_erasure_frame's distance in capture src(i): popcount(the 8x8 hash of that capture's plane at the cell's final position ^ the
+//              tile hash of the STITCHED symbol); final position = grid position + that capture's drift where it took a flood pass
+//   margin(i)  k_colour_erasure_frame's margin in capture src(i): color_fit<true> on that capture's K1 cell mean, or on mean6x6 at its drifted
+//              position where it took a flood pass, under that capture's ccm_used row (active flag included)
+//   S3 k_stitch_erasure         a live slot whose smask lacks symbol chunks: d_sym of every cell into sdist[slot], then er_retry_blocks over
+//                               the missing symbol chunks (score = max over a byte's two cells of d_sym - t_sym + 1) and er_commit
+//   S4 k_stitch_colour_erasure  the same for the colour chunks, behind S3: margins into smargin[slot], score = c_margin - margin, max over a
+//                               byte's four cells. A kernel of its own: er_retry_blocks may be called once per kernel.
+// A slot that is not live, or lacks nothing, returns at its first test with worked[slot] = 0. Chunks already in smask, d_srs_ok, the tear
+// records, the line counts, the stitched cells, the per-capture outputs and the carried matrix are not touched.
+__device__ __forceinline__ int stitch_src(const uint8_t* __restrict__ line_tab, int axis, int S, const int32_t* __restrict__ tears,
+                                          const int32_t* __restrict__ strips, int k, int d, int i)
+{
+	const int line = line_tab[(size_t)axis * NCELLS + i];
+	int s;
+	if (S > 1) {
+		const uint32_t j = stitch_strip(axis, line_tab[(size_t)(axis ^ 1) * NCELLS + i], (uint32_t)S);
+		s = strips[((size_t)k * S + j) * 4 + 2];
+	} else s = tears[(size_t)k * 4 + 2];
+	return ((line < s) != (d == 1)) ? k + 1 : k;
+}
+
+__global__ __launch_bounds__(256) void k_stitch_erasure(const uint32_t* __restrict__ plane, Tables tb, const int8_t* __restrict__ drift,
+                                                        const uint32_t* __restrict__ flood_flag, const uint8_t* __restrict__ line_tab, int axis, int S,
+                                                        const int32_t* __restrict__ tears, const int32_t* __restrict__ strips,
+                                                        const uint32_t* __restrict__ live, const uint8_t* __restrict__ ssym,
+                                                        const uint8_t* __restrict__ rs_ok, uint8_t* __restrict__ schunks, uint32_t* __restrict__ smasks,
+                                                        uint8_t* sdist, uint32_t* __restrict__ worked, int t_sym, int e_max)
+{
+	if constexpr (LEGACY) return;                          // (one coupled stream: the setter refuses these modes; the host never launches it there)
+	constexpr uint32_t SYM_MASK = (1u << SYM_CHUNKS) - 1u;
+	const int g = blockIdx.x, k = g >> 1, d = g & 1;
+	const uint32_t mask = live[g] ? smasks[g] : SYM_MASK;
+	if ((mask & SYM_MASK) == SYM_MASK) {                   // (uniform over the workgroup)
+		if (threadIdx.x == 0) worked[g] = 0;
+		return;
+	}
+	const uint8_t* sym = ssym + (size_t)g * NCELLS;
+	uint8_t* ds = sdist + (size_t)g * NCELLS;
+	for (int i = threadIdx.x; i < NCELLS; i += 256) {
+		const int f = stitch_src(line_tab, axis, S, tears, strips, k, d, i);
+		const bool flooded = flood_flag[f] != 0;
+		const ushort2 xy = tb.cell_xy[i];
+		const int dx = flooded ? drift[((size_t)f * NCELLS + i) * 2] : 0, dy = flooded ? drift[((size_t)f * NCELLS + i) * 2 + 1] : 0;
+		uint32_t rows[10];
+		window_rows(plane + (size_t)f * PLANE_WORDS, (int)xy.x + dx - 1, (int)xy.y + dy - 1, rows);
+		ds[i] = (uint8_t)__popcll(window_hash(rows, 4) ^ c_tile[sym[i] & 15u]);
+	}
+	if (threadIdx.x == 0) worked[g] = 1;
+	__syncthreads();                                       // (the distances are read back below by other lanes of this workgroup)
+	uint8_t* fc = schunks + (size_t)g * FRAME_BYTES;
+	const uint32_t done = er_retry_blocks<int16_t, 0, SYM_BLOCKS>(SYM_MASK & ~mask, rs_ok + (size_t)g * ALL_BLOCKS, e_max, fc, [&](int b, int kb, bool ok) {
+		const int sidx = (RS_BLOCK * b + kb) * 2;
+		int best = -32768;
+		uint32_t v = 0;
+#pragma unroll
+		for (int q = 0; q < 2; ++q) {
+			const int cell = tb.stream_cell[sidx + q];
+			v = (v << 4) | (sym[cell] & 15u);
+			if (!ok) {
+				const int sc = (int)ds[cell] - t_sym + 1;
+				best = sc > best ? sc : best;
+			}
+		}
+		return ErByte{v, best};
+	});
+	er_commit(mask | done, smasks + g, fc, 0, SYM_CHUNKS);
+}
+
+__global__ __launch_bounds__(256) void k_stitch_colour_erasure(const uint8_t* __restrict__ rgb, const uint32_t* __restrict__ cellmean, Tables tb,
+                                                               const int8_t* __restrict__ drift, const uint32_t* __restrict__ flood_flag,
+                                                               const float* __restrict__ ccm_used, const uint8_t* __restrict__ line_tab, int axis, int S,
+                                                               const int32_t* __restrict__ tears, const int32_t* __restrict__ strips,
+                                                               const uint32_t* __restrict__ live, const uint8_t* __restrict__ scol,
+                                                               const uint8_t* __restrict__ rs_ok, uint8_t* __restrict__ schunks,
+                                                               uint32_t* __restrict__ smasks, uint32_t* smargin, uint32_t* __restrict__ worked,
+                                                               int c_margin, int e_max)
+{
+	if constexpr (LEGACY) return;                          // (as S3)
+	constexpr uint32_t COL_MASK = ((1u << COL_CHUNKS) - 1u) << SYM_CHUNKS;
+	const int g = blockIdx.x, k = g >> 1, d = g & 1;
+	const uint32_t mask = live[g] ? smasks[g] : COL_MASK;
+	if ((mask & COL_MASK) == COL_MASK) {                   // (uniform over the workgroup)
+		if (threadIdx.x == 0) worked[g] = 0;
+		return;
+	}
+	__shared__ float s_m[2][10];                           // ccm_used of captures k and k + 1
+	if (threadIdx.x < 20) s_m[threadIdx.x / 10][threadIdx.x % 10] = ccm_used[(size_t)k * 10 + threadIdx.x];
+	__syncthreads();
+	uint32_t* mg = smargin + (size_t)g * NCELLS;
+	for (int i = threadIdx.x; i < NCELLS; i += 256) {
+		const int f = stitch_src(line_tab, axis, S, tears, strips, k, d, i);
+		const float* m = s_m[f - k];
+		uint32_t col[3];
+		if (flood_flag[f] != 0) {
+			const ushort2 xy = tb.cell_xy[i];
+			const int x = (int)xy.x + drift[((size_t)f * NCELLS + i) * 2], y = (int)xy.y + drift[((size_t)f * NCELLS + i) * 2 + 1];
+			mean6x6(rgb + (size_t)f * FRAME_RGB, x + 1, y + 1, col);
+		} else {
+			const uint32_t mv = cellmean[(size_t)f * GRID_CELLS + tb.cell_grid[i]];
+			col[0] = mv & 0xFFu; col[1] = (mv >> 8) & 0xFFu; col[2] = (mv >> 16) & 0xFFu;
+		}
+		mg[i] = color_fit<true>((float)col[0], (float)col[1], (float)col[2], m, m[9] != 0.0f).margin;
+	}
+	if (threadIdx.x == 0) worked[g] = 1;
+	__syncthreads();                                       // (the margins are read back below by other lanes of this workgroup)
+	const uint8_t* cf = scol + (size_t)g * NCELLS;
+	uint8_t* fc = schunks + (size_t)g * FRAME_BYTES;
+	const uint32_t done = er_retry_blocks<int32_t, SYM_BLOCKS, COL_BLOCKS>(COL_MASK & ~mask, rs_ok + (size_t)g * ALL_BLOCKS, e_max, fc, [&](int b, int kb, bool ok) {
+		const int sidx = (RS_BLOCK * (b - SYM_BLOCKS) + kb) * 4;
+		int best = INT_MIN;
+		uint32_t v = 0;
+#pragma unroll
+		for (int q = 0; q < 4; ++q) {
+			const int cell = tb.stream_cell[sidx + q];
+			v = (v << 2) | (cf[cell] & 3u);
+			if (!ok) {
+				const int sc = c_margin - (int)mg[cell];
+				best = sc > best ? sc : best;
+			}
+		}
+		return ErByte{v, best};
+	});
+	er_commit(mask | done, smasks + g, fc, SYM_CHUNKS, CHUNKS);
 }

@@ -26,6 +26,7 @@ TAP_GROUP_COLOUR_MARGIN, TAP_GROUP_COLOUR_WEIGHTS = 15, 16   # the colour vote o
 TAP_STREAM_CARRY_WEIGHTS = 17   # the carried weights of the open group's members after a stream call with set_stream_colour_vote on
 TAP_STITCH_CELLS, TAP_STITCH_LINES = 18, 19   # the stitching of the last stitched batch (decode_batch_stitched): n = its captures
 TAP_STITCH_STRIPS, TAP_STITCH_STRIP_LINES = 22, 23   # the strips of the last stitched batch (set_stitch_strips above 1): tap_stitch_strips
+TAP_STITCH_DISTANCE, TAP_STITCH_COLOUR_MARGIN = 36, 37   # the erasure retry of the last plain stitched batch (set_stitch_erasure): tap_stitch_distance / tap_stitch_colour_margin
 TAP_STITCH_CARRY = 20   # the capture the stitched-stream calls carry (decode_batch_stitched_stream): tap_stitch_carry
 TAP_CELL_MEANS = 21   # the threshold kernel's undrifted cell means, r | g << 8 | b << 16 by grid slot (row * DIM_X + column)
 TAP_SCAN_GRAY, TAP_SCAN_HIST, TAP_SCAN_THRESHOLD = 24, 25, 26   # what the stage in front of the last anchor search produced: tap_scan
@@ -73,6 +74,7 @@ EXPORTS = (
     "cimbar_hip_decode_batch_stitched", "cimbar_hip_scan_extract_decode_batch_stitched_fmt",
     "cimbar_hip_decode_batch_stitched_stream", "cimbar_hip_scan_extract_decode_batch_stitched_stream_fmt", "cimbar_hip_stitch_stream_reset",
     "cimbar_hip_set_stitch_strips", "cimbar_hip_get_stitch_strips",
+    "cimbar_hip_set_stitch_erasure", "cimbar_hip_get_stitch_erasure",
     "cimbar_hip_set_relaxed_flood", "cimbar_hip_get_relaxed_flood", "cimbar_hip_relaxed_flood_stats",
     "cimbar_hip_decode_batch_once", "cimbar_hip_scan_extract_decode_batch_once_fmt",
     "cimbar_hip_decode_batch_once_stream", "cimbar_hip_scan_extract_decode_batch_once_stream_fmt", "cimbar_hip_once_stream_reset",
@@ -211,6 +213,11 @@ def load_library(path=None):
         lib.cimbar_hip_set_stitch_strips.restype = i32
         lib.cimbar_hip_get_stitch_strips.argtypes = [vp, ctypes.POINTER(i32)]
         lib.cimbar_hip_get_stitch_strips.restype = i32
+    if hasattr(lib, "cimbar_hip_set_stitch_erasure"):   # (likewise)
+        lib.cimbar_hip_set_stitch_erasure.argtypes = [vp, i32]
+        lib.cimbar_hip_set_stitch_erasure.restype = i32
+        lib.cimbar_hip_get_stitch_erasure.argtypes = [vp, ctypes.POINTER(i32)]
+        lib.cimbar_hip_get_stitch_erasure.restype = i32
     if hasattr(lib, "cimbar_hip_decode_batch_once"):   # (CIMBAR_HIP_LIB may name an older build for an A/B run)
         lib.cimbar_hip_decode_batch_once.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp]
         lib.cimbar_hip_decode_batch_once.restype = i64
@@ -868,6 +875,31 @@ class HipDecoder:
         stream=True: (n, strips, L)"""
         out = np.zeros((n if stream else max(n - 1, 0), int(strips), self.geo.DIM_Y if axis == 0 else self.geo.DIM_X), np.uint16)
         self._check(self._lib.cimbar_hip_tap(self._ctx, TAP_STITCH_STRIP_LINES, out.ctypes.data, out.nbytes), "cimbar_hip_tap")
+        return out
+
+    def set_stitch_erasure(self, on):
+        """cimbar_hip_set_stitch_erasure: the plain stitched calls retry the chunks a stitched slot lacks with low-confidence cells erased,
+        each cell's confidence taken in the capture it came from (the symbol retry where set_erasure_decode is on, the colour retry where
+        set_colour_erasure_decode is on). Off after create; the stitched-stream calls are not affected; modes 4 and 8 refuse it."""
+        self._check(self._lib.cimbar_hip_set_stitch_erasure(self._ctx, int(bool(on))), "cimbar_hip_set_stitch_erasure")
+
+    def get_stitch_erasure(self):
+        a = ctypes.c_int32(0)
+        self._check(self._lib.cimbar_hip_get_stitch_erasure(self._ctx, ctypes.byref(a)), "cimbar_hip_get_stitch_erasure")
+        return int(a.value)
+
+    def tap_stitch_distance(self, n):
+        """TAP_STITCH_DISTANCE of the last plain stitched batch of n captures, which ran the symbol retry: (2 (n - 1), NCELLS) uint8 d_sym of
+        every stitched cell, 0xFF for the slots the retry skipped; raises when that retry did not run"""
+        out = np.zeros((2 * max(n - 1, 0), self.geo.NCELLS), np.uint8)
+        self._check(self._lib.cimbar_hip_tap(self._ctx, TAP_STITCH_DISTANCE, out.ctypes.data, out.nbytes), "cimbar_hip_tap")
+        return out
+
+    def tap_stitch_colour_margin(self, n):
+        """TAP_STITCH_COLOUR_MARGIN of that batch, which ran the colour retry: (2 (n - 1), NCELLS) uint32, 0xFFFFFFFF for the slots the
+        retry skipped; raises when that retry did not run"""
+        out = np.zeros((2 * max(n - 1, 0), self.geo.NCELLS), np.uint32)
+        self._check(self._lib.cimbar_hip_tap(self._ctx, TAP_STITCH_COLOUR_MARGIN, out.ctypes.data, out.nbytes), "cimbar_hip_tap")
         return out
 
     def tap_stitch_carry(self):
