@@ -8,7 +8,9 @@
 // kernels, on the caller's stream (large batches: the chain as two half-batches on two streams); the pipelined entry point
 // alternates whole batches between two context-owned streams. Every launch of the chain is enqueue(ctx, stream, ChainArgs) in host.hip.inc;
 // the batch entry points reach it through one driver per tail (decode_impl, once_call) over a FrameSource -- the caller's frames, or the
-// capture front end's deskewed ones. See DESIGN.md "Launch structure".
+// capture front end's deskewed ones. What enqueue() launches is decided once per call by plan_chain() in chainplan.hip.inc (the chain's shape,
+// its parts, every lane's spill areas, queues and counter, the exact replay's instance and grid: plain C++ that a CPU test holds against
+// tests/flood_launch_model.py); enqueue() only issues it. See DESIGN.md "Launch structure".
 //   K1 k_threshold      RGB -> gray -> (sharpen) -> 5x5|7x7 box-mean threshold -> bitplane   [HBM-read bound]
 //   K2 k_symbols        every cell at drift (0,0): 10x10 bit window -> 5|9 shifted 8x8 hashes -> popcount match;
 //                       flags the frame if any cell prefers a shifted window (order then matters -> K2b)
@@ -46,6 +48,9 @@
 
 // chunk delivery: three integers of geometry, so one copy serves every mode (the contexts below own its state)
 #include "deliver.hip.inc"
+
+// the launch plan of a decode chain and the launch constants it is made of: plain arithmetic, no geometry in it (enqueue() in host.hip.inc issues it)
+#include "chainplan.hip.inc"
 
 // One copy of the geometry-dependent code per supported mode (Config.h:19-44), then the mode-independent C ABI on top.
 #define CIMBAR_MODE 68

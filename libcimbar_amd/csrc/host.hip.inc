@@ -48,7 +48,7 @@ struct cimbar_hip_ctx {
 	// Everything below that owns something (devbuf.hip.inc) frees it in its destructor, after the body of ~cimbar_hip_ctx() at the end of this struct.
 	Stream stream;
 	Stream stream2;                           // second half of a batch's tail kernels (see enqueue)
-	Event ev_k1, ev_join, ev_mid[8];
+	Event ev_k1, ev_join, ev_mid[CHAIN_PARTS_MAX];
 	int tail_split = 1, tail_parts = 2;
 	PinnedBuf<uint32_t> h_flagged;    // written by k_count_flagged at the end of every ordinary batch: [0] frames that left the parallel path, [1] frames of that batch,
 	                                  // [2] frames the exact replay (or, with the relaxed flood on, k_flood_rounds) had to take.
@@ -202,10 +202,9 @@ struct cimbar_hip_ctx {
 	FloodScratch flood{};             // by value into the flood kernels: filled by ensure_flood_areas from the owners beside it
 	DevBuf<uint32_t> flood_heap, flood_next; DevBuf<uint8_t> flood_prio;
 	int flood_cap = 0;                // spill areas allocated in flood.heap and flood.prio, 0.61 MB of device memory each, grown to what the launches index: one frame -> 0.6 MB,
-	                                  // 1 024 frames as one chain -> 620 MB, split or pipelined batches up to 2 048 areas = 1.25 GB (flood_area_scale)
+	                                  // 1 024 frames as one chain -> 620 MB, split or pipelined batches up to 2 048 areas = 1.25 GB (ChainPlan::flood_top)
 	// CIMBAR_HIP_TAP_FLOOD_LAUNCH: the exact-replay launches of the last enqueue(), {instance, grid, frames, first frame, area0, counter, flags}
 	// each, and the spill areas that enqueue() asked ensure_flood_areas for (host bookkeeping: nothing on the device knows of it)
-	static constexpr int FLOOD_LAUNCH_MAX = 16;
 	int32_t flood_launch[FLOOD_LAUNCH_MAX][7] = {};
 	int flood_launch_n = 0, flood_launch_top = 0;
 	DevBuf<uint32_t> d_fw_queue;      // k_flood_wave: one work queue of NCELLS entries per resident workgroup
@@ -576,20 +575,12 @@ int begin_call(cimbar_hip_ctx* ctx, const char* who, const char* in_name, int in
 // the next batch (or frame) takes the next set
 void rotate_scratch_sets(cimbar_hip_ctx* ctx) { ctx->pipe_set = (ctx->pipe_set + 1) % ctx->pipe_depth; }
 
-// The ranges of spill areas that launches in flight together get (the sets of the pipeline, the two streams of a split batch) are spaced for
-// the largest launch the context can make: FLOOD_DENSE_PER areas per ordinary one wherever the dense replay may run (CIMBAR_HIP_FLOOD_DENSE
-// unset or 1). ONE spacing for both instances: a pipelined set's dense launch (more than `areas` frames) and another set's ordinary one used
-// to take theirs from two different partitions of the same buffer, which overlap (depth 4: [0, 300) dense on set 0, [256, 456) on set 1).
-// It costs device memory where the batches stay small: a pipelined set's batch of n <= areas frames asks for 2 (depth - 1) areas + n, not
-// (depth - 1) areas + n (depth 3: 682 areas = 415 MB more), a split batch of up to 512 frames for 1024 + n, not 512 + n (310 MB more); larger
-// batches were sized in these units already. (Split batches need it too: eight parts of 4 101 frames put 513 on stream 0 beside 512 on stream 1.)
-inline int flood_area_scale(const cimbar_hip_ctx* ctx) { return ctx->flood_dense != 0 ? FLOOD_DENSE_PER : 1; }
-
-// enqueue the whole pipeline for n device-resident frames on stream `st`
 // one spill area (HEAP_CAP words, and PRIO_STRIDE bytes for the dense instance: 0.61 MB) per flood workgroup a launch may start, [0, count): grown on
 // demand -- a context that only ever decodes single frames through the plain calls keeps 0.6 MB (through the pipelined ones, whose last set starts at
 // 2 (depth - 1) areas: 830 MB at depth 3), not the 620 MB .. 1.25 GB a 1024-frame batch wants. Growing replaces the buffer, so everything in flight is
-// waited for first.
+// waited for first. `count` is ChainPlan::flood_top. Its one spacing for every instance (chainplan.hip.inc) costs device memory where the batches stay
+// small: a pipelined set's batch of n <= areas frames asks for 2 (depth - 1) areas + n, not (depth - 1) areas + n (depth 3: 682 areas = 415 MB more), a
+// split batch of up to 512 frames for 1024 + n, not 512 + n (310 MB more); larger batches were sized in these units already.
 int ensure_flood_areas(cimbar_hip_ctx* ctx, int count)
 {
 	if (count <= ctx->flood_cap) return 0;
@@ -613,7 +604,9 @@ inline int colour_erasure_max(const cimbar_hip_ctx* ctx) { return ctx->ec_max < 
 // an image larger than the frame (CimbReader's _gridPadding case, decode_frame): K1p cuts the grid's window out of it while it thresholds it
 struct PadSource { const uint8_t* pad_src = nullptr; int pad_w = 0, pad_h = 0, pad_off = 0; };
 
-// one batch as enqueue() takes it
+// One batch as enqueue() takes it. What the chain for it looks like -- one chain, a pipelined set's, or parts on two streams; each lane's spill
+// areas, wave queues and counter; the exact replay's instance and grid -- is not decided here or in enqueue(): plan_chain() in chainplan.hip.inc
+// states that rule once, from these arguments and the context's settings, and tests/test_chain_plan.py checks it without a GPU.
 struct ChainArgs {
 	const uint8_t* d_rgb = nullptr; int n = 0;      // n device-resident frames
 	int pre = 0, cc = 0;                            // sharpen every frame; the colour-correction setting
@@ -627,243 +620,244 @@ struct ChainArgs {
 	PadSource pad{};                                // n == 1 only; d_rgb is then where K1p leaves the window
 };
 
+// What the stages of one enqueue() share. The plan (chainplan.hip.inc) says what to launch; the stages below issue it and decide nothing.
+struct Chain {
+	cimbar_hip_ctx* ctx; cimbar_hip_ctx::ScratchSet& cur; const ChainArgs& a; const ChainPlan& plan;
+	hipStream_t st;        // the caller's stream (or the pipelined set's)
+	bool timed;            // stage timing: only ever a single chain on `st` (a timed batch is neither pipelined nor split)
+	bool relaxed;          // the relaxed flood (cimbar_hip_set_relaxed_flood) is on
+	bool colour_retry;     // the colour retry (erasure.hip.inc) runs behind every chain that reports chunks; the set in use holds its margins
+};
+static_assert(cimbar_hip_ctx::MAXP <= FLOOD_COUNTERS && 2 <= FLOOD_COUNTERS, "a counter pair per pipelined set and per stream of a split batch");
+
+// stage boundary k of a timed batch (STAGE_NAMES[k] lies between k and k + 1)
+inline hipError_t mark(const Chain& c, int k) { return c.timed ? hipEventRecord(c.ctx->ev[k], c.st) : hipSuccess; }
+
+template <int RAD, bool PRE, bool TALL>
+void launch_k1(const Chain& c, const int* d_sel, int sel_stride, int lds)
+{
+	hipLaunchKernelGGL((k_threshold<RAD, PRE, TALL ? K1_TALLROWS : K1_CELLROWS>), dim3(TALL ? K1_TALL_BLOCKS : K1_BLOCKS, c.a.n), dim3(256), (size_t)lds, c.st,
+	                   c.a.d_rgb, c.cur.d_plane, c.cur.d_cellmean, c.cur.d_flood, 0, d_sel, sel_stride);
+}
+
+// K1 for the whole batch, on the caller's stream
+void launch_threshold(const Chain& c)
+{
+	const cimbar_hip_ctx* ctx = c.ctx; const ChainArgs& a = c.a; cimbar_hip_ctx::ScratchSet& cur = c.cur;
+	if (a.pad.pad_src && a.n == 1) {
+		// the frame buffer d_rgb is OUTPUT here: K1p cuts the grid's window out of the larger image while it thresholds it
+		uint8_t* frame = const_cast<uint8_t*>(a.d_rgb);
+		const dim3 gp((IMG_W + 63) / 64, (IMG_H + 3) / 4);
+		const PadSource& p = a.pad;
+		if (a.pre) hipLaunchKernelGGL((k_threshold_padded<3, true>), gp, dim3(256), 0, c.st, p.pad_src, p.pad_w, p.pad_h, p.pad_off, cur.d_plane, frame, cur.d_flood);
+		else hipLaunchKernelGGL((k_threshold_padded<2, false>), gp, dim3(256), 0, c.st, p.pad_src, p.pad_w, p.pad_h, p.pad_off, cur.d_plane, frame, cur.d_flood);
+		hipLaunchKernelGGL(k_cellmean_padded, dim3((GRID_CELLS + 255) / 256), dim3(256), 0, c.st, frame, cur.d_cellmean);
+		return;
+	}
+	// the sharpening variant is bound by its vector instructions (96 % of its cycles), not by the memory system: tall strips (69 row steps for 63
+	// rows instead of 24 for 18) shorten the launch itself, pipelined or not, once the batch fills the chip with them; the plain one takes them
+	// inside the pipelined loop (fewer row steps and halo rows per frame; the uneven drain is covered by the other batches in flight)
+	const bool tall = ctx->k1_tall > 0 || (ctx->k1_tall < 0 && a.n >= K1_TALL_MIN);
+	const bool sharp_tall = tall, plain_tall = tall && (ctx->k1_tall > 0 || a.pipe);
+	// pre == -1 ("guess", cimbar.cpp:190): the extractor's verdict decides per frame; each variant returns at once for the other's frames.
+	// CIMBAR_HIP_K1_LDS_PAD caps the occupancy of the plain variant where it runs alone.
+	const int* sel = a.d_sel; const int stride = sel ? a.sel_stride : 0;
+	if (sel || a.pre) { if (sharp_tall) launch_k1<3, true, true>(c, sel, stride, 0); else launch_k1<3, true, false>(c, sel, stride, 0); }
+	if (sel) launch_k1<2, false, false>(c, sel, stride, 0);
+	else if (!a.pre) { if (plain_tall) launch_k1<2, false, true>(c, nullptr, 0, ctx->k1_lds_pad); else launch_k1<2, false, false>(c, nullptr, 0, ctx->k1_lds_pad); }
+}
+
+// One exact replay (k_flood3) of a part's frames flagged in `flags`: the instance and grid are the plan's, the spill areas and the counter pair
+// its lane's. kind: CIMBAR_HIP_TAP_FLOOD_LAUNCH's flags (0 the batch's own, 1 the verify replay, 2 the relaxed flood's fallback).
+void launch_exact_flood(const Chain& c, hipStream_t s, const ChainPart& p, const uint32_t* flags, int kind)
+{
+	cimbar_hip_ctx* ctx = c.ctx; cimbar_hip_ctx::ScratchSet& cur = c.cur;
+	if (ctx->dbg_skip & 2) return;
+	const ChainLane& L = c.plan.lane[p.lane];
+	const ExactLaunch x = exact_launch(c.plan, p.lane, p.count);
+	if (ctx->flood_launch_n < FLOOD_LAUNCH_MAX) {
+		const int32_t rec[7] = {x.instance, x.grid, p.count, p.first, L.area0, L.counter, kind};
+		std::memcpy(ctx->flood_launch[ctx->flood_launch_n++], rec, sizeof rec);
+	}
+	// a launch with fewer workgroups than frames hands the rest out through the counter pair sc.next[2 * counter ..]: zeroed HERE, in stream
+	// order in front of the launch, so that a launch that faulted or was aborted cannot leave the pair non-zero for the ones after it
+	if (x.hand_out) (void)hipMemsetAsync(ctx->flood.next + 2 * L.counter, 0, 2 * sizeof(uint32_t), s);
+	const dim3 grid(x.grid);
+	if (x.instance == 8) hipLaunchKernelGGL((k_flood3<HEAP_LDS8, true>), grid, dim3(128), 0, s, cur.d_plane, ctx->tb, ctx->flood, flags, cur.d_symbols, cur.d_drift, p.first, p.count, L.area0, L.counter);
+	else if (x.instance == 3) hipLaunchKernelGGL((k_flood3<HEAP_LDS, false>), grid, dim3(128), 0, s, cur.d_plane, ctx->tb, ctx->flood, flags, cur.d_symbols, cur.d_drift, p.first, p.count, L.area0, L.counter);
+	else hipLaunchKernelGGL((k_flood3<HEAP_LDS4, false>), grid, dim3(128), 0, s, cur.d_plane, ctx->tb, ctx->flood, flags, cur.d_symbols, cur.d_drift, p.first, p.count, L.area0, L.counter);
+}
+
+// The front half of the chain for one part, on stream s: symbols -> flood -> RS -> k_frame_mid (header / CCM)
+hipError_t chain_front(const Chain& c, hipStream_t s, const ChainPart& p)
+{
+	cimbar_hip_ctx* ctx = c.ctx; cimbar_hip_ctx::ScratchSet& cur = c.cur; const ChainArgs& a = c.a;
+	const ChainLane& L = c.plan.lane[p.lane];
+	const int fa = p.first, m = p.count;
+	if (!(ctx->dbg_skip & 1)) hipLaunchKernelGGL(k_symbols, dim3(K2_BLOCKS, m), dim3(256), 0, s, cur.d_plane, ctx->tb, cur.d_symbols, cur.d_flood, fa);
+	if (hipError_t e = mark(c, 2)) return e;
+	if (c.plan.run_wave && !(ctx->dbg_skip & 2)) {
+		// first the batch-parallel pass for frames whose flood provably does not depend on the tie order (it clears their flag to 2)
+		hipLaunchKernelGGL(k_flood_wave, dim3(m < L.wareas ? m : L.wareas), dim3(256), 0, s, cur.d_plane, ctx->tb, ctx->d_fw_queue, cur.d_flood,
+		                   cur.d_symbols, cur.d_drift, fa, m, L.warea0, cur.d_flood + cur.cap);
+	} else if (ctx->flood_wave && !(ctx->dbg_skip & 2)) {
+		// skipped by the scheduler: CIMBAR_HIP_TAP_FLOOD_INFO must not show what the pass said about some earlier batch
+		if (hipError_t e = hipMemsetAsync(cur.d_flood + cur.cap + fa, 0xFF, sizeof(uint32_t) * (size_t)m, s)) return e;
+	}
+	// The relaxed flood (cimbar_hip_set_relaxed_flood): the frames still flagged 1 are flooded in threshold rounds (flag 3) instead of
+	// replayed; what the symbol streams' RS pass makes of them decides below whether they stay that way.
+	if (c.relaxed) {
+		if (hipError_t e = hipMemsetAsync(cur.d_flood + 2 * cur.cap + fa, 0, sizeof(uint32_t) * (size_t)m, s)) return e;
+		hipLaunchKernelGGL(k_flood_rounds, dim3(m < ctx->rf_grid ? m : ctx->rf_grid), dim3(FR_THREADS), 0, s, cur.d_plane, ctx->tb, cur.d_flood, cur.d_symbols,
+		                   cur.d_drift, fa, m, (uint32_t)ctx->rf_threshold, cur.d_flood + 2 * cur.cap);
+	}
+	if (c.plan.exact_batch) launch_exact_flood(c, s, p, cur.d_flood, 0);
+	if (c.plan.exact_verify && !(ctx->dbg_skip & 2)) {
+		// CIMBAR_HIP_FLOOD_VERIFY: what k_flood_wave certified (flag 2) is set aside, the same frames are replayed exactly, and the two
+		// results are compared cell by cell (symbol and drifted position). The exact result is what stays -- a wrong certificate would be
+		// counted (cimbar_hip_flood_verify_totals, CIMBAR_HIP_TAP_FLOOD_VERIFY) AND repaired.
+		hipLaunchKernelGGL(k_verify_begin, dim3(m), dim3(256), 0, s, cur.d_flood, cur.d_symbols, cur.d_drift, ctx->d_vflag, ctx->d_vsym, ctx->d_vdrift, fa, ctx->vcap);
+		launch_exact_flood(c, s, p, ctx->d_vflag, 1);
+		hipLaunchKernelGGL(k_verify_end, dim3(m), dim3(256), 0, s, cur.d_symbols, cur.d_drift, ctx->d_vflag, ctx->d_vsym, ctx->d_vdrift, fa, ctx->vcap, ctx->d_vtotals);
+	}
+	if (hipError_t e = mark(c, 3)) return e;
+	// (legacy modes have ONE stream, decoded after the colour pass; the stage-time slot stays so that the names keep their meaning)
+#ifdef CIMBAR_PROBES
+	if (!LEGACY && (ctx->dbg_skip & 128)) hipLaunchKernelGGL((k_rs<4, true>), dim3((m * SYM_BLOCKS + 3) / 4), dim3(256), 0, s, cur.d_symbols, ctx->tb, fa, m, 0, a.d_chunks, cur.d_rs_ok, 0, (const uint8_t*)nullptr);
+	else
+#endif
+	if (!LEGACY && !(ctx->dbg_skip & 4)) hipLaunchKernelGGL((k_rs<4>), dim3((m * SYM_BLOCKS + 3) / 4), dim3(256), 0, s, cur.d_symbols, ctx->tb, fa, m, 0, a.d_chunks, cur.d_rs_ok, 0);
+	if (c.relaxed) {
+		// acceptance: a frame flooded in rounds keeps its result iff every symbol block decoded. With fallback on, the others go back to flag 1,
+		// the exact replay takes them -- inside this call, in front of everything that reads symbols, drift or flags -- and the RS pass runs once
+		// more over the part (it rewrites the same bytes for the frames that did not change: 40 blocks per frame of clean-path work).
+		hipLaunchKernelGGL(k_rounds_check, dim3((m + 255) / 256), dim3(256), 0, s, cur.d_flood, cur.d_rs_ok, cur.d_flood + 2 * cur.cap, fa, m, ctx->rf_fallback, ctx->d_rf_stats);
+		if (c.plan.exact_fallback) {
+			launch_exact_flood(c, s, p, cur.d_flood, 2);
+			hipLaunchKernelGGL((k_rs<4>), dim3((m * SYM_BLOCKS + 3) / 4), dim3(256), 0, s, cur.d_symbols, ctx->tb, fa, m, 0, a.d_chunks, cur.d_rs_ok, 0);
+		}
+	}
+	if (hipError_t e = mark(c, 4)) return e;
+	if (!(ctx->dbg_skip & 8)) hipLaunchKernelGGL(k_frame_mid, dim3(m), dim3(64), 0, s, a.d_rgb, cur.d_cellmean, ctx->tb, a.d_chunks, cur.d_rs_ok, a.cc, cur.d_states, cur.d_ccm_frames, fa, a.plain);
+	return mark(c, 5);
+}
+
+// The back half for one part, on stream s: colours -> RS -> k_frame_end (masks, carry), then the erasure retries
+hipError_t chain_back(const Chain& c, hipStream_t s, const ChainPart& p)
+{
+	cimbar_hip_ctx* ctx = c.ctx; cimbar_hip_ctx::ScratchSet& cur = c.cur; const ChainArgs& a = c.a;
+	const int fa = p.first, m = p.count;
+	if (!(ctx->dbg_skip & 16)) hipLaunchKernelGGL((k_colors<false>), dim3(K5_BLOCKS, m), dim3(256), 0, s, a.d_rgb, cur.d_cellmean, ctx->tb, cur.d_ccm_frames,
+	                   ctx->d_carry, cur.d_flood, cur.d_drift, cur.d_colors, cur.d_ccm_used, fa);
+	if (hipError_t e = mark(c, 6)) return e;
+	if (LEGACY) hipLaunchKernelGGL((k_rs<(LEGACY ? CELL_BITS : 6)>), dim3((m * ALL_BLOCKS + 3) / 4), dim3(256), 0, s, cur.d_symbols, ctx->tb, fa, m, 0, a.d_chunks, cur.d_rs_ok, 0, cur.d_colors);
+#ifdef CIMBAR_PROBES
+	else if (ctx->dbg_skip & 128) hipLaunchKernelGGL((k_rs<2, true>), dim3((m * COL_BLOCKS + 3) / 4), dim3(256), 0, s, cur.d_colors, ctx->tb, fa, m, SYM_CHUNKS, a.d_chunks, cur.d_rs_ok, SYM_BLOCKS, (const uint8_t*)nullptr);
+#endif
+	else if (!(ctx->dbg_skip & 32)) hipLaunchKernelGGL((k_rs<2>), dim3((m * COL_BLOCKS + 3) / 4), dim3(256), 0, s, cur.d_colors, ctx->tb, fa, m, SYM_CHUNKS, a.d_chunks, cur.d_rs_ok, SYM_BLOCKS);
+	if (hipError_t e = mark(c, 7)) return e;
+	// (split chain: the carry is written by k_carry_out after the join -- an earlier part's colour pass may still be reading the old one)
+	if (!(ctx->dbg_skip & 64)) hipLaunchKernelGGL(k_frame_end, dim3(m), dim3(64), 0, s, cur.d_rs_ok, cur.d_states, a.d_chunks, a.d_masks, cur.d_ccm_used, ctx->d_carry, fa,
+	                   (!c.plan.split && fa + m == a.n) ? 1 : 0, a.plain);
+	// opt-in erasure retry of the symbol chunks the mask lacks (erasure.hip.inc); reads the frame's own intermediates only, writes its
+	// chunks and mask: the same stream, after k_frame_end, in every chain shape (split halves, pipelined sets)
+	if (!LEGACY && !a.plain && ctx->er_sym > 0)
+		hipLaunchKernelGGL(k_erasure_frame, dim3(m), dim3(256), 0, s, cur.d_plane, ctx->tb, cur.d_symbols, cur.d_drift, cur.d_flood, cur.d_rs_ok,
+		                   a.d_chunks, a.d_masks, fa, ctx->er_sym, erasure_max(ctx));
+	// ... and of the colour chunks it lacks (cimbar_hip_set_colour_erasure_decode), independent of the symbol retry and behind it
+	if (c.colour_retry)
+		hipLaunchKernelGGL(k_colour_erasure_frame, dim3(m), dim3(256), 0, s, a.d_rgb, cur.d_cellmean, ctx->tb, cur.d_colors, cur.d_drift, cur.d_flood,
+		                   cur.d_ccm_used, cur.d_rs_ok, a.d_chunks, a.d_masks, cur.d_cmargin, cur.d_cmargin + (size_t)cur.cm_cap * NCELLS, fa,
+		                   ctx->ec_margin, colour_erasure_max(ctx));
+	return mark(c, 8);
+}
+
+// Enqueue the whole chain for a.n device-resident frames on stream `st`: plan it (plan_chain, from one snapshot of the context's settings and
+// of what the batch before reported), make room, note what the taps will be asked about, launch K1, then drive the parts of the plan.
+// Everything after K1 is a chain of small kernels per frame (symbols -> flood -> RS -> header/CCM -> colours -> RS -> masks), some of
+// them latency-bound (k_frame_mid is one serial wavefront per frame). For a large batch the chain runs as parts on two streams, so one
+// part's serial phases and launch gaps are covered by the other's kernels. The only cross-part dependency is the colour-correction carry:
+// a frame with no matrix of its own takes the newest one of the frames before it, so a part's colour pass waits for k_frame_mid of the
+// part before. Stage timing uses the single-stream order.
 int enqueue(cimbar_hip_ctx* ctx, hipStream_t st, const ChainArgs& a)
 {
-	const uint8_t* const d_rgb = a.d_rgb; uint8_t* const d_chunks = a.d_chunks; uint32_t* const d_masks = a.d_masks; const int* const d_sel = a.d_sel;
-	const int n = a.n, pre = a.pre, cc = a.cc, plain = a.plain, sel_stride = a.sel_stride;
-	const bool pipe = a.pipe, symbols_only = a.symbols_only;
+	const int n = a.n;
 	cimbar_hip_ctx::ScratchSet& cur = ctx->cur();
+	const bool colour_retry = !LEGACY && !a.plain && !a.symbols_only && ctx->ec_margin > 0;
+	if (colour_retry) { if (int r = ensure_margin_capacity(ctx, cur)) return r; }
+	const bool relaxed = !LEGACY && ctx->rf_threshold >= 0 && ctx->d_rf_stats && !(ctx->dbg_skip & 2);
+
+	ChainPlanIn in;
+	in.n = n; in.pipe = a.pipe; in.no_split = a.no_split; in.symbols_only = a.symbols_only;
+	in.timed = ctx->timing && !a.pipe;
+	// What the batch before reported (k_count_flagged writes these pinned words asynchronously -- a device-output call returns without a
+	// sync -- so they are read ONCE here; a stale value only costs the heuristic).
+	in.have_flagged = ctx->h_flagged != nullptr;
+	if (in.have_flagged) for (int k = 0; k < 3; ++k) in.flagged[k] = ((volatile uint32_t*)ctx->h_flagged)[k];
+	in.tail_split = ctx->tail_split; in.tail_parts = ctx->tail_parts; in.pipe_depth = ctx->pipe_depth; in.pipe_set = ctx->pipe_set;
+	in.flood_dense = ctx->flood_dense; in.flood_dense_grid = ctx->flood_dense_grid;
+	in.flood_wave = ctx->flood_wave; in.flood_verify = ctx->flood_verify; in.wave_adapt = ctx->wave_adapt;
+	in.wave_ran = ctx->wave_ran; in.wave_skip_left = ctx->wave_skip_left;
+	in.relaxed = relaxed; in.relaxed_fallback = ctx->rf_fallback != 0;
+	const ChainPlan plan = plan_chain(in);
+
+	if (int r = ensure_flood_areas(ctx, plan.flood_top)) return r;
+	if (ctx->flood_verify) if (int r = ensure_verify_capacity(ctx, n)) return r;
+
+	// the context's bookkeeping of this batch (a call that could not make room has left the last batch's in place)
 	ctx->grp_valid = false;   // (the group taps describe a combined batch only until the next batch of any kind)
 	ctx->stitch_n = 0;        // (... and the stitch taps a stitched one)
 	ctx->gcv_valid = false;
 	ctx->gcv_stream_n = -1;
-	ctx->flood_launch_n = 0;
-	// the colour retry (erasure.hip.inc) runs behind every chain that reports chunks; the set in use holds its margins
-	const bool colour_retry = !LEGACY && !plain && !symbols_only && ctx->ec_margin > 0;
-	if (colour_retry) { if (int r = ensure_margin_capacity(ctx, cur)) return r; }
 	ctx->cm_valid = colour_retry;
-	const bool tm = ctx->timing && !pipe;
-	int evi = 0;
-	auto mark = [&]() -> hipError_t { return tm ? hipEventRecord(ctx->ev[evi++], st) : hipSuccess; };
-	const dim3 cell_grid((NCELLS + 255) / 256, n);
-	const int f0 = 0;   // kernels index frames as f0 + block index, so a caller may also run a sub-range of a resident batch
-
-	// What the batch before reported (k_count_flagged writes these pinned words asynchronously -- a device-output call returns without a
-	// sync -- so they are read ONCE here: the split decision below sizes the spill areas AND picks the launches' area offsets, and the two
-	// must agree even if the words change under us; a stale value only costs the heuristic).
-	uint32_t flagged[3] = {0, 0, 0};
-	if (ctx->h_flagged) for (int k = 0; k < 3; ++k) flagged[k] = ((volatile uint32_t*)ctx->h_flagged)[k];
-	const bool mostly_flood = flagged[1] != 0 && 4u * flagged[0] > flagged[1];   // the batch before: more than a quarter took a flood kernel
-	const bool split = !tm && !pipe && ctx->tail_split && !a.no_split && !mostly_flood && n >= 64 * ctx->tail_parts;
-	{
-		// spill areas the flood launches below will index: the pipeline's sets and the two halves of a split batch use disjoint ranges
-		const int areas_ = pipe ? FLOOD_GRID / ctx->pipe_depth : (split ? FLOOD_GRID / 2 : FLOOD_GRID);
-		// (the dense replay runs FLOOD_DENSE_PER workgroups where the others run one; a context that may launch it -- flood_area_scale -- spaces
-		// every range by that factor, whichever instance a launch takes: a dense launch of one pipelined set and an ordinary one of another may
-		// be in flight together)
-		const int off_ = flood_area_scale(ctx) * (pipe ? (ctx->pipe_depth - 1) * areas_ : (split ? FLOOD_GRID / 2 : 0));
-		int top = off_ + (n < areas_ ? n : areas_);
-		if (ctx->flood_dense > 0 || (ctx->flood_dense < 0 && n > areas_)) top = off_ + (n < FLOOD_DENSE_PER * areas_ ? n : FLOOD_DENSE_PER * areas_);
-		if (int r = ensure_flood_areas(ctx, top)) return r;
-		ctx->flood_launch_top = top;
-		if (ctx->flood_verify) if (int r = ensure_verify_capacity(ctx, n)) return r;
-	}
-	HIPCHK(mark());
-	{
-		dim3 g(K1_BLOCKS, n), gt(K1_TALL_BLOCKS, n);
-		// the sharpening variant is bound by its vector instructions (96 % of its cycles), not by the memory system: tall strips (69 row steps for 63
-		// rows instead of 24 for 18) shorten the launch itself, pipelined or not, once the batch fills the chip with them
-		const bool pre_tall = ctx->k1_tall > 0 || (ctx->k1_tall < 0 && n >= K1_TALL_MIN);
-		if (a.pad.pad_src && n == 1) {
-			// the frame buffer d_rgb is OUTPUT here: K1p cuts the grid's window out of the larger image while it thresholds it
-			uint8_t* frame = const_cast<uint8_t*>(d_rgb);
-			const dim3 gp((IMG_W + 63) / 64, (IMG_H + 3) / 4);
-			const PadSource& p = a.pad;
-			if (pre) hipLaunchKernelGGL((k_threshold_padded<3, true>), gp, dim3(256), 0, st, p.pad_src, p.pad_w, p.pad_h, p.pad_off, cur.d_plane, frame, cur.d_flood);
-			else hipLaunchKernelGGL((k_threshold_padded<2, false>), gp, dim3(256), 0, st, p.pad_src, p.pad_w, p.pad_h, p.pad_off, cur.d_plane, frame, cur.d_flood);
-			hipLaunchKernelGGL(k_cellmean_padded, dim3((GRID_CELLS + 255) / 256), dim3(256), 0, st, frame, cur.d_cellmean);
-		} else if (d_sel) {
-			// pre == -1 ("guess", cimbar.cpp:190): the extractor's verdict decides per frame; each variant returns at once for the other's frames
-			if (pre_tall) hipLaunchKernelGGL((k_threshold<3, true, K1_TALLROWS>), gt, dim3(256), 0, st, d_rgb, cur.d_plane, cur.d_cellmean, cur.d_flood, f0, d_sel, sel_stride);
-			else hipLaunchKernelGGL((k_threshold<3, true>), g, dim3(256), 0, st, d_rgb, cur.d_plane, cur.d_cellmean, cur.d_flood, f0, d_sel, sel_stride);
-			hipLaunchKernelGGL((k_threshold<2, false>), g, dim3(256), 0, st, d_rgb, cur.d_plane, cur.d_cellmean, cur.d_flood, f0, d_sel, sel_stride);
-		} else if (pre) {
-			if (pre_tall) hipLaunchKernelGGL((k_threshold<3, true, K1_TALLROWS>), gt, dim3(256), 0, st, d_rgb, cur.d_plane, cur.d_cellmean, cur.d_flood, f0, (const int*)nullptr, 0);
-			else hipLaunchKernelGGL((k_threshold<3, true>), g, dim3(256), 0, st, d_rgb, cur.d_plane, cur.d_cellmean, cur.d_flood, f0, (const int*)nullptr, 0);
-		} else if (ctx->k1_tall > 0 || (ctx->k1_tall < 0 && pipe && n >= K1_TALL_MIN))
-			// inside the pipelined loop: tall strips (fewer row steps and halo rows per frame; the uneven drain is covered by the other batches in flight)
-			hipLaunchKernelGGL((k_threshold<2, false, K1_TALLROWS>), dim3(K1_TALL_BLOCKS, n), dim3(256), (size_t)ctx->k1_lds_pad, st, d_rgb, cur.d_plane, cur.d_cellmean, cur.d_flood, f0, (const int*)nullptr, 0);
-		else hipLaunchKernelGGL((k_threshold<2, false>), g, dim3(256), (size_t)ctx->k1_lds_pad, st, d_rgb, cur.d_plane, cur.d_cellmean, cur.d_flood, f0, (const int*)nullptr, 0);
-	}
-	HIPCHK(mark());
-	// Everything after K1 is a chain of small kernels per frame (symbols -> flood -> RS -> header/CCM -> colours -> RS -> masks), some of
-	// them latency-bound (k_frame_mid is one serial wavefront per frame). For a large batch the chain runs as two half-batches on two
-	// streams, so one half's serial phases and launch gaps are covered by the other half's kernels. The only cross-half dependency
-	// is the colour-correction carry: a frame with no matrix of its own takes the newest one of the frames before it, so the second
-	// half's colour pass waits for the first half's k_frame_mid. Stage timing uses the single-stream order.
-	// The certifying pass costs ~2.5 us per flagged frame even when it gives up in its first super-round, which is what it does on every
-	// deskewed camera frame (DESIGN.md, K2c). Where the batch before shows that it certified fewer than one in sixteen of the frames it was
-	// given, the next fifteen batches go straight to the exact replay and the one after probes again. The decoded bytes do not depend on
-	// this (both passes produce the reference's result); it only decides which kernel does the work.
-	const bool counted = !pipe && !tm && ctx->h_flagged && ctx->tail_split && n >= 64 * ctx->tail_parts;     // this batch ends with k_count_flagged
-	bool run_wave = ctx->flood_wave != 0;
-	if (run_wave && counted && ctx->wave_adapt && !ctx->flood_verify) {
-		if (ctx->wave_skip_left > 0) { --ctx->wave_skip_left; run_wave = false; }
-		else if (ctx->wave_ran && flagged[0] >= 16u && 16u * (flagged[0] - (flagged[2] <= flagged[0] ? flagged[2] : flagged[0])) < flagged[0]) {
-			run_wave = false;
-			ctx->wave_skip_left = 14;
-		}
-	}
-	if (counted) ctx->wave_ran = run_wave;
-	const bool relaxed = !LEGACY && ctx->rf_threshold >= 0 && ctx->d_rf_stats && !(ctx->dbg_skip & 2);
 	ctx->rf_valid = relaxed;
-	auto tail = [&](hipStream_t s, int fa, int m, int part) -> hipError_t {
-		// part 0: up to k_frame_mid, part 1: the rest
-		if (part == 0) {
-			if (!(ctx->dbg_skip & 1)) hipLaunchKernelGGL(k_symbols, dim3(K2_BLOCKS, m), dim3(256), 0, s, cur.d_plane, ctx->tb, cur.d_symbols, cur.d_flood, fa);
-			if (hipError_t e = (s == st ? mark() : hipSuccess)) return e;
-			// the two halves of a split batch may run their flood kernels at the same time: each gets its own half of the spill areas
-			const int areas = pipe ? FLOOD_GRID / ctx->pipe_depth : (split ? FLOOD_GRID / 2 : FLOOD_GRID);
-			const int area0 = flood_area_scale(ctx) * (pipe ? ctx->pipe_set * areas : ((split && s != st) ? FLOOD_GRID / 2 : 0));
-			if (run_wave && !(ctx->dbg_skip & 2)) {
-				// first the batch-parallel pass for frames whose flood provably does not depend on the tie order (it clears their flag to 2)
-				const int wareas = pipe ? FW_GRID / ctx->pipe_depth : (split ? FW_GRID / 2 : FW_GRID);
-				const int warea0 = pipe ? ctx->pipe_set * wareas : ((split && s != st) ? FW_GRID / 2 : 0);
-				hipLaunchKernelGGL(k_flood_wave, dim3(m < wareas ? m : wareas), dim3(256), 0, s, cur.d_plane, ctx->tb, ctx->d_fw_queue, cur.d_flood,
-				                   cur.d_symbols, cur.d_drift, fa, m, warea0, cur.d_flood + cur.cap);
-			} else if (ctx->flood_wave && !(ctx->dbg_skip & 2)) {
-				// skipped by the scheduler: CIMBAR_HIP_TAP_FLOOD_INFO must not show what the pass said about some earlier batch
-				if (hipError_t e = hipMemsetAsync(cur.d_flood + cur.cap + fa, 0xFF, sizeof(uint32_t) * (size_t)m, s)) return e;
-			}
-			const int counter = pipe ? ctx->pipe_set : ((split && s != st) ? 1 : 0);          // (launches that may overlap use different frame counters)
-			auto exact_flood = [&](const uint32_t* flags, int kind) {
-				// three frames per CU while the batch fits, four (smaller LDS heap) beyond that
-				const int areas3 = areas * FLOOD_GRID3 / FLOOD_GRID;
-				// a launch with fewer workgroups than frames hands the rest out through the counter pair sc.next[2 * counter ..]: zeroed HERE, in stream
-				// order in front of the launch, so that a launch that faulted or was aborted cannot leave the pair non-zero for the ones after it
-				auto hand_out = [&](int grid) { if (grid < m) (void)hipMemsetAsync(ctx->flood.next + 2 * counter, 0, 2 * sizeof(uint32_t), s); return dim3(grid); };
-				auto note = [&](int instance, int grid) {
-					if (ctx->flood_launch_n >= cimbar_hip_ctx::FLOOD_LAUNCH_MAX) return;
-					const int32_t rec[7] = {instance, grid, m, fa, area0, counter, kind};
-					std::memcpy(ctx->flood_launch[ctx->flood_launch_n++], rec, sizeof rec);
-				};
-				if (ctx->dbg_skip & 2) {}
-				else if (ctx->flood_dense > 0 || (ctx->flood_dense < 0 && m > areas)) {
-					// more frames than four per CU hold: eight per CU (per-cell state as bits in LDS + bytes in global memory, a 4 160-slot LDS heap)
-					// (CIMBAR_HIP_FLOOD_DENSE_GRID: fewer workgroups than that, e.g. 1 792 = seven per CU, leave LDS for another stream's kernels while they run)
-					const int areas8 = FLOOD_DENSE_PER * areas * ctx->flood_dense_grid / (FLOOD_DENSE_PER * FLOOD_GRID);
-					note(8, m < areas8 ? m : areas8);
-					hipLaunchKernelGGL((k_flood3<HEAP_LDS8, true>), hand_out(m < areas8 ? m : areas8), dim3(128), 0, s, cur.d_plane, ctx->tb, ctx->flood, flags, cur.d_symbols, cur.d_drift, fa, m,
-					                   area0, counter);
-				} else if (m <= areas3) {
-					note(3, m);
-					hipLaunchKernelGGL((k_flood3<HEAP_LDS, false>), dim3(m), dim3(128), 0, s, cur.d_plane, ctx->tb, ctx->flood, flags, cur.d_symbols, cur.d_drift, fa, m, area0, counter);
-				} else {
-					note(4, m < areas ? m : areas);
-					hipLaunchKernelGGL((k_flood3<HEAP_LDS4, false>), hand_out(m < areas ? m : areas), dim3(128), 0, s, cur.d_plane, ctx->tb, ctx->flood, flags, cur.d_symbols, cur.d_drift, fa, m, area0, counter);
-				}
-			};
-			// The relaxed flood (cimbar_hip_set_relaxed_flood): the frames still flagged 1 are flooded in threshold rounds (flag 3) instead of
-			// replayed; what the symbol streams' RS pass makes of them decides below whether they stay that way.
-			if (relaxed) {
-				if (hipError_t e = hipMemsetAsync(cur.d_flood + 2 * cur.cap + fa, 0, sizeof(uint32_t) * (size_t)m, s)) return e;
-				hipLaunchKernelGGL(k_flood_rounds, dim3(m < ctx->rf_grid ? m : ctx->rf_grid), dim3(FR_THREADS), 0, s, cur.d_plane, ctx->tb, cur.d_flood, cur.d_symbols,
-				                   cur.d_drift, fa, m, (uint32_t)ctx->rf_threshold, cur.d_flood + 2 * cur.cap);
-			} else exact_flood(cur.d_flood, 0);
-			if (ctx->flood_verify && ctx->flood_wave && !(ctx->dbg_skip & 2)) {
-				// CIMBAR_HIP_FLOOD_VERIFY: what k_flood_wave certified (flag 2) is set aside, the same frames are replayed exactly, and the two
-				// results are compared cell by cell (symbol and drifted position). The exact result is what stays -- a wrong certificate would be
-				// counted (cimbar_hip_flood_verify_totals, CIMBAR_HIP_TAP_FLOOD_VERIFY) AND repaired.
-				hipLaunchKernelGGL(k_verify_begin, dim3(m), dim3(256), 0, s, cur.d_flood, cur.d_symbols, cur.d_drift, ctx->d_vflag, ctx->d_vsym, ctx->d_vdrift, fa, ctx->vcap);
-				exact_flood(ctx->d_vflag, 1);
-				hipLaunchKernelGGL(k_verify_end, dim3(m), dim3(256), 0, s, cur.d_symbols, cur.d_drift, ctx->d_vflag, ctx->d_vsym, ctx->d_vdrift, fa, ctx->vcap, ctx->d_vtotals);
-			}
-			if (hipError_t e = (s == st ? mark() : hipSuccess)) return e;
-			// (legacy modes have ONE stream, decoded after the colour pass; the stage-time slot stays so that the names keep their meaning)
-#ifdef CIMBAR_PROBES
-			if (!LEGACY && (ctx->dbg_skip & 128)) hipLaunchKernelGGL((k_rs<4, true>), dim3((m * SYM_BLOCKS + 3) / 4), dim3(256), 0, s, cur.d_symbols, ctx->tb, fa, m, 0, d_chunks, cur.d_rs_ok, 0, (const uint8_t*)nullptr);
-			else
-#endif
-			if (!LEGACY && !(ctx->dbg_skip & 4)) hipLaunchKernelGGL((k_rs<4>), dim3((m * SYM_BLOCKS + 3) / 4), dim3(256), 0, s, cur.d_symbols, ctx->tb, fa, m, 0, d_chunks, cur.d_rs_ok, 0);
-			if (relaxed) {
-				// acceptance: a frame flooded in rounds keeps its result iff every symbol block decoded. With fallback on, the others go back to flag 1,
-				// the exact replay takes them -- inside this call, in front of everything that reads symbols, drift or flags -- and the RS pass runs once
-				// more over the part (it rewrites the same bytes for the frames that did not change: 40 blocks per frame of clean-path work).
-				hipLaunchKernelGGL(k_rounds_check, dim3((m + 255) / 256), dim3(256), 0, s, cur.d_flood, cur.d_rs_ok, cur.d_flood + 2 * cur.cap, fa, m, ctx->rf_fallback, ctx->d_rf_stats);
-				if (ctx->rf_fallback) {
-					exact_flood(cur.d_flood, 2);
-					hipLaunchKernelGGL((k_rs<4>), dim3((m * SYM_BLOCKS + 3) / 4), dim3(256), 0, s, cur.d_symbols, ctx->tb, fa, m, 0, d_chunks, cur.d_rs_ok, 0);
-				}
-			}
-			if (hipError_t e = (s == st ? mark() : hipSuccess)) return e;
-			if (!(ctx->dbg_skip & 8)) hipLaunchKernelGGL(k_frame_mid, dim3(m), dim3(64), 0, s, d_rgb, cur.d_cellmean, ctx->tb, d_chunks, cur.d_rs_ok, cc, cur.d_states, cur.d_ccm_frames, fa, plain);
-			return s == st ? mark() : hipSuccess;
-		}
-		if (!(ctx->dbg_skip & 16)) hipLaunchKernelGGL((k_colors<false>), dim3(K5_BLOCKS, m), dim3(256), 0, s, d_rgb, cur.d_cellmean, ctx->tb, cur.d_ccm_frames,
-		                   ctx->d_carry, cur.d_flood, cur.d_drift, cur.d_colors, cur.d_ccm_used, fa);
-		if (hipError_t e = (s == st ? mark() : hipSuccess)) return e;
-		if (LEGACY) hipLaunchKernelGGL((k_rs<(LEGACY ? CELL_BITS : 6)>), dim3((m * ALL_BLOCKS + 3) / 4), dim3(256), 0, s, cur.d_symbols, ctx->tb, fa, m, 0, d_chunks, cur.d_rs_ok, 0, cur.d_colors);
-#ifdef CIMBAR_PROBES
-		else if (ctx->dbg_skip & 128) hipLaunchKernelGGL((k_rs<2, true>), dim3((m * COL_BLOCKS + 3) / 4), dim3(256), 0, s, cur.d_colors, ctx->tb, fa, m, SYM_CHUNKS, d_chunks, cur.d_rs_ok, SYM_BLOCKS, (const uint8_t*)nullptr);
-#endif
-		else if (!(ctx->dbg_skip & 32)) hipLaunchKernelGGL((k_rs<2>), dim3((m * COL_BLOCKS + 3) / 4), dim3(256), 0, s, cur.d_colors, ctx->tb, fa, m, SYM_CHUNKS, d_chunks, cur.d_rs_ok, SYM_BLOCKS);
-		if (hipError_t e = (s == st ? mark() : hipSuccess)) return e;
-		// (split chain: the carry is written by k_carry_out after the join -- an earlier part's colour pass may still be reading the old one)
-		if (!(ctx->dbg_skip & 64)) hipLaunchKernelGGL(k_frame_end, dim3(m), dim3(64), 0, s, cur.d_rs_ok, cur.d_states, d_chunks, d_masks, cur.d_ccm_used, ctx->d_carry, fa,
-		                   (!split && fa + m == n) ? 1 : 0, plain);
-		// opt-in erasure retry of the symbol chunks the mask lacks (erasure.hip.inc); reads the frame's own intermediates only, writes its
-		// chunks and mask: the same stream, after k_frame_end, in every chain shape (split halves, pipelined sets)
-		if (!LEGACY && !plain && ctx->er_sym > 0)
-			hipLaunchKernelGGL(k_erasure_frame, dim3(m), dim3(256), 0, s, cur.d_plane, ctx->tb, cur.d_symbols, cur.d_drift, cur.d_flood, cur.d_rs_ok,
-			                   d_chunks, d_masks, fa, ctx->er_sym, erasure_max(ctx));
-		// ... and of the colour chunks it lacks (cimbar_hip_set_colour_erasure_decode), independent of the symbol retry and behind it
-		if (colour_retry)
-			hipLaunchKernelGGL(k_colour_erasure_frame, dim3(m), dim3(256), 0, s, d_rgb, cur.d_cellmean, ctx->tb, cur.d_colors, cur.d_drift, cur.d_flood,
-			                   cur.d_ccm_used, cur.d_rs_ok, d_chunks, d_masks, cur.d_cmargin, cur.d_cmargin + (size_t)cur.cm_cap * NCELLS, fa,
-			                   ctx->ec_margin, colour_erasure_max(ctx));
-		return s == st ? mark() : hipSuccess;
-	};
-	if (pipe) {
+	ctx->flood_launch_n = 0;  // (launch_exact_flood appends)
+	ctx->flood_launch_top = plan.flood_top;
+	ctx->wave_ran = plan.wave_ran;
+	ctx->wave_skip_left = plan.wave_skip_left;
+	ctx->last_n = n;
+
+	const Chain c{ctx, cur, a, plan, st, in.timed, relaxed, colour_retry};
+	HIPCHK(mark(c, 0));
+	launch_threshold(c);
+	HIPCHK(mark(c, 1));
+	const ChainPart* const part = plan.part;
+	if (a.pipe) {
 		// the whole batch runs on one of the context's pipeline streams (`st` here), the next batch on the next one: independent
 		// queues, so K1 of one batch overlaps the short kernels of the others. The one thing that crosses over is the colour-
 		// correction carry (and the order of the results): this batch's colour pass waits for the previous batch's end.
 		const int set = ctx->pipe_set, prev = (set + ctx->pipe_depth - 1) % ctx->pipe_depth;
-		HIPCHK(tail(st, f0, n, 0));
+		HIPCHK(chain_front(c, st, part[0]));
 		if (ctx->pipe_used[prev]) HIPCHK(hipStreamWaitEvent(st, ctx->ev_pdone[prev], 0));
-		HIPCHK(tail(st, f0, n, 1));
+		HIPCHK(chain_back(c, st, part[0]));
 		HIPCHK(hipEventRecord(ctx->ev_pdone[set], st));
 		ctx->pipe_used[set] = true;
 		ctx->pipe_gathered[set] = false;
-	} else if (!split) {
-		HIPCHK(tail(st, f0, n, 0));
+	} else if (!plan.split) {
+		HIPCHK(chain_front(c, st, part[0]));
 		// (symbols_only: the mode auto-detection runs the colour half itself, once the matrix in force is known per frame: automode_mode.hip.inc)
-		if (!symbols_only) HIPCHK(tail(st, f0, n, 1));
+		if (!plan.stop_at_mid) HIPCHK(chain_back(c, st, part[0]));
 	} else {
-		// parts alternate between the caller's stream and stream2; pairs are issued together so that both streams always have work
-		const int P = ctx->tail_parts;
-		hipStream_t sb = ctx->stream2;
-		auto lo = [&](int p) { return (int)((long long)n * p / P); };
+		// lane 0 is the caller's stream, lane 1 stream2; pairs of parts are issued together so that both streams always have work
+		const hipStream_t lane[2] = {st, ctx->stream2};
 		HIPCHK(hipEventRecord(ctx->ev_k1, st));
-		HIPCHK(hipStreamWaitEvent(sb, ctx->ev_k1, 0));
-		for (int p = 0; p < P; p += 2) {
+		HIPCHK(hipStreamWaitEvent(lane[1], ctx->ev_k1, 0));
+		for (int p = 0; p < plan.nparts; p += 2) {
 			for (int q = p; q < p + 2; ++q) {
-				hipStream_t sq = (q & 1) ? sb : st;
-				HIPCHK(tail(sq, f0 + lo(q), lo(q + 1) - lo(q), 0));
-				HIPCHK(hipEventRecord(ctx->ev_mid[q], sq));
+				HIPCHK(chain_front(c, lane[part[q].lane], part[q]));
+				HIPCHK(hipEventRecord(ctx->ev_mid[q], lane[part[q].lane]));
 			}
 			for (int q = p; q < p + 2; ++q) {
-				hipStream_t sq = (q & 1) ? sb : st;
-				if (q > 0) HIPCHK(hipStreamWaitEvent(sq, ctx->ev_mid[q - 1], 0));   // every k_frame_mid of the frames before this part is done
-				HIPCHK(tail(sq, f0 + lo(q), lo(q + 1) - lo(q), 1));
+				if (q > 0) HIPCHK(hipStreamWaitEvent(lane[part[q].lane], ctx->ev_mid[q - 1], 0));   // every k_frame_mid of the frames before this part is done
+				HIPCHK(chain_back(c, lane[part[q].lane], part[q]));
 			}
 		}
-		HIPCHK(hipEventRecord(ctx->ev_join, sb));
+		HIPCHK(hipEventRecord(ctx->ev_join, lane[1]));
 		HIPCHK(hipStreamWaitEvent(st, ctx->ev_join, 0));
-		hipLaunchKernelGGL(k_carry_out, dim3(1), dim3(64), 0, st, cur.d_ccm_used, ctx->d_carry, f0 + n - 1);
+		hipLaunchKernelGGL(k_carry_out, dim3(1), dim3(64), 0, st, cur.d_ccm_used, ctx->d_carry, n - 1);
 	}
-	if (counted) hipLaunchKernelGGL(k_count_flagged, dim3(1), dim3(256), 0, st, cur.d_flood, n, ctx->h_flagged);
+	if (plan.counted) hipLaunchKernelGGL(k_count_flagged, dim3(1), dim3(256), 0, st, cur.d_flood, n, ctx->h_flagged);
 	HIPCHK(hipGetLastError());
-	ctx->last_n = n;
 	return 0;
 }
 
@@ -960,7 +954,7 @@ int cimbar_hip_create(int device, int mode_val, cimbar_hip_ctx** out)
 	if (const char* v = std::getenv("CIMBAR_HIP_K1_LDS_PAD")) { int k = std::atoi(v); if (k >= 0 && k <= 100000) ctx->k1_lds_pad = k; }
 	if (const char* v = std::getenv("CIMBAR_HIP_FRAME_ZEROCOPY")) ctx->frame_zerocopy = std::atoi(v);
 	if (const char* v = std::getenv("CIMBAR_HIP_FRAME_COPYSTREAM")) ctx->frame_copystream = std::atoi(v);
-	if (const char* v = std::getenv("CIMBAR_HIP_TAIL_PARTS")) { int k = std::atoi(v); if (k >= 2 && k <= 8 && k % 2 == 0) ctx->tail_parts = k; }
+	if (const char* v = std::getenv("CIMBAR_HIP_TAIL_PARTS")) { int k = std::atoi(v); if (k >= 2 && k <= CHAIN_PARTS_MAX && k % 2 == 0) ctx->tail_parts = k; }
 	for (Event& e : ctx->ev) if (e.create(hipEventDefault) != hipSuccess) return fail(CIMBAR_HIP_EHIP);
 	if (ctx->d_carry.reserve(10) != hipSuccess) return fail(CIMBAR_HIP_ENOMEM);
 	if (hipMemset(ctx->d_carry, 0, sizeof(float) * 10) != hipSuccess) return fail(CIMBAR_HIP_EHIP);

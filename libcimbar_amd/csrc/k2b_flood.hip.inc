@@ -26,11 +26,11 @@ constexpr int HEAP_LDS = CIMBAR_HEAP_LDS;  // heap slots held in LDS (40 KiB; a 
                                  // CIMBAR_HEAP_LDS=1024 so that the spill path runs on ordinary frames)
 struct FloodScratch {
 	uint32_t* heap;      // [areas][HEAP_CAP] one spill area per workgroup; only indices >= HEAP_LDS are ever touched
-	uint32_t* next;      // [FLOOD_COUNTERS] one counter PAIR per launch that may be in flight (the host zeroes the pair in stream order in front of every launch that uses it, host.hip.inc `hand_out`): workgroups take frames as they finish
+	uint32_t* next;      // [FLOOD_COUNTERS] one counter PAIR per launch that may be in flight (the host zeroes the pair in stream order in front of every launch that uses it, host.hip.inc launch_exact_flood): workgroups take frames as they finish
 	uint8_t* prio;       // [areas][PRIO_STRIDE] k_flood3's dense instance: the per-cell "best offered priority + 1" bytes (everything else of s_state is in LDS bits)
 };
 constexpr int PRIO_STRIDE = (NCELLS + 16 + 255) / 256 * 256;
-constexpr int FLOOD_COUNTERS = 8;        // (pairs: frames handed out, workgroups that have left)
+// (FLOOD_COUNTERS: chainplan.hip.inc)
 
 __device__ __forceinline__ uint32_t cool_enc(uint32_t c) { return c == 0xFEu ? 0u : (c == 0xFFu ? 2u : c); }   // real values: 1,3,4,5,7
 __device__ __forceinline__ uint32_t cool_dec(uint32_t k) { return k == 0u ? 0xFEu : (k == 2u ? 0xFFu : k); }
@@ -428,8 +428,8 @@ __device__ __forceinline__ void flood_seed(HP& hp, int lane)
 
 // Two instances: HEAP_LDS slots in LDS (52 KiB with the state: three workgroups per CU, 768 frames resident) for batches that fit, and
 // HEAP_LDS4 slots (just under 40 KiB: four per CU, 1024 resident; a clean shifted frame then spends part of its life in the spill path) for larger
-// ones, where a second round of the 24 ms kernel would cost more than the spilling does.
-constexpr int FLOOD_GRID3 = 768, FLOOD_GRID = 1024;
+// ones, where a second round of the 24 ms kernel would cost more than the spilling does. (The launch sizes that go with them, FLOOD_GRID3, FLOOD_GRID
+// and the dense instance's FLOOD_DENSE_PER, are chainplan.hip.inc's.)
 #ifndef CIMBAR_HEAP_LDS4
 #define CIMBAR_HEAP_LDS4 7080
 #endif
@@ -440,7 +440,6 @@ constexpr int HEAP_LDS4 = HEAP_LDS < CIMBAR_HEAP_LDS4 ? HEAP_LDS : CIMBAR_HEAP_L
 #define CIMBAR_HEAP_LDS8 4095
 #endif
 constexpr int HEAP_LDS8 = HEAP_LDS < CIMBAR_HEAP_LDS8 ? 63 : CIMBAR_HEAP_LDS8;   // (the spill-test build: one block in LDS, every deeper access global)
-constexpr int FLOOD_DENSE_PER = 2;                       // dense workgroups (and spill areas) per ordinary one
 // flood_flag[f]: 0 = the parallel pass (k_symbols) was exact; 1 = needs the exact replay; 2 = settled by k_flood_wave; 3 = flooded in rounds by
 // k_flood_rounds (k2d_floodrounds.hip.inc; only with cimbar_hip_set_relaxed_flood on -- k_rounds_check may set it back to 1). Whoever reads the
 // flag to learn "does this frame have drift?" tests != 0.

@@ -24,7 +24,7 @@
 constexpr int FW_PREFIX = 64;            // cells decoded by the exact replay first
 constexpr int FW_HEAP = 1024;            // 8 seeds + 64 * 12 offers at most
 constexpr int FW_MAX_ROUNDS = 64;        // certified frames need a handful; a frame that fragments into many tiny rounds is K2b's
-constexpr int FW_GRID = 512;             // 75 KiB of LDS per workgroup: two per CU
+// (FW_GRID, the workgroups of a launch -- 75 KiB of LDS each, two per CU: chainplan.hip.inc)
 constexpr int FW_BITWORDS = (NCELLS + 31) / 32;
 static_assert(FW_HEAP >= 8 + 12 * FW_PREFIX + 16, "the prefix must never reach the spill half of the heap");
 

@@ -1,7 +1,7 @@
-"""Which launches of the exact flood replay (k_flood3) one decode call makes: a plain restatement of the host's rule (enqueue() in
-libcimbar_amd/csrc/host.hip.inc: the split decision, `exact_flood`, and the sizing in front of ensure_flood_areas), in the terms of
-CIMBAR_HIP_TAP_FLOOD_LAUNCH. No GPU, no library: tests/test_flood_launch_model.py checks its invariants, tests/test_gpu_flood_shapes.py holds
-HipDecoder.tap_flood_launches() against it.
+"""Which launches of the exact flood replay (k_flood3) one decode call makes: a plain restatement of the host's rule (plan_chain() and
+exact_launch() in libcimbar_amd/csrc/chainplan.hip.inc, which enqueue() in host.hip.inc issues), in the terms of
+CIMBAR_HIP_TAP_FLOOD_LAUNCH. No GPU, no library: tests/test_flood_launch_model.py checks its invariants, tests/test_chain_plan.py holds the
+host's plan against it on a CPU, tests/test_gpu_flood_shapes.py holds HipDecoder.tap_flood_launches() against it.
 
 The rule. A = the spill areas a launch may use: FLOOD_GRID = 1024 for a batch that runs as one chain, 512 per stream of a split batch,
 1024 / pipe_depth per pipelined set; A3 = A * 768 / 1024. A launch of m frames is
